@@ -12,7 +12,15 @@ The line's top-level fields are the reference-precision measurement in SURVEY.md
         `roofline` = that pass's dominant kernel, k_simbits_screen_mfma<4, 2, 64, true>, HIP events on its stream around
         every launch of the timed region, against the fp64 peak by 8d's 53 A + 600 flop per alignment.
 
-Extra blocks of the same line (each with its own device timing, outside the timed region):
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line:
+its top-level fields, `config` and the roofline of the timed launches.  `--dump-outputs DIR` also writes what the last
+timed step computed as DIR/<name>.npy: here the two (N, N) outputs at 16 384 seeded pairs (pair_i, pair_j, rmsd, maxdev),
+the survivor mask with --workload cfg4, the pass mask at 2^20 seeded poses with cfg5.  Everything else -- value_check,
+the blocks below, the CPU baselines, the N = 1 member of a multi-GPU family -- runs only with `--full`.
+
+value_check (--full): those sampled outputs against the oracle; a failure exits 3 after the line is out.
+
+Extra blocks of the same line (--full; each with its own device timing, outside the timed region):
 
   prune_path   the pruning step the reference's prune_by_rmsd performs on the same ensemble -- all-pairs
                similarity DECISIONS (split-half f16 screen, fp64-exact refine of the candidates) + k-ladder ->
@@ -166,6 +174,14 @@ def mask_checks(mask, assign):
     last[assign] = np.arange(len(assign))
     return {"survivors": int(mask.sum()), "survivors_expected": K, "survivor_count_ok": int(mask.sum()) == K,
             "survivors_are_last_cluster_members": bool(np.array_equal(np.flatnonzero(mask), np.sort(last)))}
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: name -> array, as <out_dir>/<name>.npy (float64 stays float64, anything else is written as float32)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
 
 
 def pmc_traffic(files, n_conf, n_atoms, world=1):
@@ -427,9 +443,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", choices=("auto", "cfg2", "cfg4", "cfg5"), default="auto",
                     help="auto = cfg2 (BASELINE configs[1]; conformers x sqrt(n_gpus)) with the cfg4 family as an extra block on several GPUs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: value_check, the extra blocks, the CPU baseline and, on several GPUs, the "
+                         "family's N = 1 member (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed region (profile runs): no prune_path / fp64_path / secondary / host-in legs")
+                    help="with --full: no prune_path / fp64_path / secondary / host-in legs")
     ap.add_argument("--cpu-baseline-configs", action="store_true",
                     help="only time the CPU oracle on samples of BASELINE configs 3 and 5 (no GPU needed) and exit")
     args = ap.parse_args()
@@ -573,7 +594,8 @@ def complete_roofline(kernel_ms, owned_pairs, n_conf, n_atoms, world):
 def value_check_pairs(n_conf, rank, world, fdist, n_pairs=2048, seed=1234):
     """Pairs (i < j) of the rows THIS rank owns (row blocks of 128 in snake order): random ones, plus the corners of the
     launch -- first / last owned rows, both sides of 16- / 128-row boundaries, the last (partial) column tile, the tip of
-    the triangle where the item table ends in half-row-block items."""
+    the triangle where the item table ends in half-row-block items.  The same seeded pairs in every run of a workload:
+    the elements value_check compares and --dump-outputs writes."""
     rng = np.random.default_rng(seed + rank)
     rows = np.flatnonzero(fdist.owner_of_rows(n_conf, world, 128) == rank)
     rows = rows[rows < n_conf - 1]
@@ -618,7 +640,7 @@ def run_alignments(ctx):
     ens = fc.DeviceEnsemble(coords, center=True)  # resident in HBM from here on
     pairs_total = n_conf * (n_conf - 1) // 2
 
-    chk_i, chk_j = value_check_pairs(n_conf, rank, world, ctx["fdist"])
+    chk_i, chk_j = value_check_pairs(n_conf, rank, world, ctx["fdist"], n_pairs=16384)
     sampled = [None, None]
 
     def run(n, sample=False):
@@ -645,11 +667,16 @@ def run_alignments(ctx):
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     owned = int(st[0])
-    check = value_check(coords, chk_i, chk_j, sampled[0], sampled[1])
-    ranks_failed = int(round(max_over_ranks(0.0 if check["ok"] else 1.0)))
-    if not check["ok"]:
-        sys.stderr.write(f"bench.py: rank {rank}: value_check FAILED: {json.dumps(check)}\n")
-    ctx["value_check_failed"] = bool(ranks_failed)
+    if args.dump_outputs and rank == 0:
+        # the two (N, N) fp64 outputs of the last timed pass at the seeded pairs of this rank's rows (value_check's)
+        write_outputs(args.dump_outputs, {"pair_i": chk_i.astype(np.float64), "pair_j": chk_j.astype(np.float64),
+                                          "rmsd": sampled[0], "maxdev": sampled[1]})
+    if args.full:
+        check = value_check(coords, chk_i, chk_j, sampled[0], sampled[1])
+        ranks_failed = int(round(max_over_ranks(0.0 if check["ok"] else 1.0)))
+        if not check["ok"]:
+            sys.stderr.write(f"bench.py: rank {rank}: value_check FAILED: {json.dumps(check)}\n")
+        ctx["value_check_failed"] = bool(ranks_failed)
 
     out = None
     if rank == 0:
@@ -679,8 +706,9 @@ def run_alignments(ctx):
                        "host_sync": "once per batch of <= 1024 stream-ordered steps",
                        "device_ms_per_step": dev_ms / steps},
             "fixup_pairs_last_step": int(st[1]),
-            "value_check": dict(check, all_ranks_ok=not ranks_failed),
         }
+        if args.full:
+            out["value_check"] = dict(check, all_ranks_ok=not ranks_failed)
         out["roofline"] = complete_roofline(k_ms, owned, n_conf, n_atoms, world)
         bytes_per_alignment = 2 * n_atoms * 24 + 16
         achieved = owned * bytes_per_alignment / (k_ms * 1e-3) / 1e9
@@ -692,7 +720,7 @@ def run_alignments(ctx):
                                        "staged tile of 64 conformers serves 128 partners; the compulsory traffic is the ensemble "
                                        "once + the two output matrices"}
 
-    if world > 1:
+    if args.full and world > 1:
         # the family's n_gpus = 1 member (same pairs per GPU), on rank 0 alone, outside the timed region
         if rank == 0:
             c1, _, _ = syn.synthetic_ensemble(int(round(10000 * rehearsal_scale())), n_atoms, seed=seed)
@@ -720,10 +748,11 @@ def run_alignments(ctx):
     elif world > 1 and rank == 0:
         out["ranks_seen"] = world  # (every rank answered the file rendezvous)
 
-    if not args.no_extras and world > 1 and not ctx["comm"]:
+    extras = args.full and not args.no_extras
+    if extras and world > 1 and not ctx["comm"]:
         if rank == 0:
             out["prune_path"] = {"skipped": "the sharded prune exchanges its similar-pair lists over RCCL; " + str(ctx["comm_error"])}
-    elif not args.no_extras and world > 1:
+    elif extras and world > 1:
         # the blocks that exchange data between the ranks: whatever goes wrong in them -- the same on every rank, the calls
         # are collective -- must not take the headline measurement above with it
         timer = ctx["guard_extras"](out if rank == 0 else {}, int(os.environ.get("FC_BENCH_EXTRAS_TIMEOUT_S", "300")))
@@ -741,13 +770,13 @@ def run_alignments(ctx):
                 out["extras_error"] = f"{type(exc).__name__}: {exc}"
         finally:
             timer.cancel()
-    elif not args.no_extras:
+    elif extras:
         blk = prune_block(ctx, "cfg2", ens, coords, atoms, assign, n_conf, n_atoms, steps_default=200, warmup_default=20)
         if rank == 0:
             out["prune_path"] = blk
             out["pruned_ensembles_per_s"] = blk["pruned_ensembles_per_s"]
             extras_single_gpu(args, out, fc, _lib, syn, ens, coords, atoms, n_conf, n_atoms, pairs_total)
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(coords)
         out["vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
     return out
@@ -756,8 +785,10 @@ def run_alignments(ctx):
 # ----------------------------------------------------------------------------------------------
 # cfg2 / cfg4: all-pairs RMSD prune (pair decisions + ladder -> survivor mask)
 # ----------------------------------------------------------------------------------------------
-def prune_block(ctx, workload, ens, coords, atoms, assign, n_conf, n_atoms, steps_default, warmup_default, steps=None, warmup=None):
-    """K stream-ordered prunes of the resident ensemble, bracketed like the main region -> dict (rank 0) / None."""
+def prune_block(ctx, workload, ens, coords, atoms, assign, n_conf, n_atoms, steps_default, warmup_default, steps=None, warmup=None,
+                dump=None):
+    """K stream-ordered prunes of the resident ensemble, bracketed like the main region -> dict (rank 0) / None; with `dump`
+    a directory, the last step's survivor mask goes there (--dump-outputs)."""
     _lib, rank, world = ctx["_lib"], ctx["rank"], ctx["world"]
     barrier, max_over_ranks = ctx["barrier"], ctx["max_over_ranks"]
     sharded = world > 1 or workload == "cfg4" or os.environ.get("FC_BENCH_FORCE_SHARDED") == "1"
@@ -779,6 +810,8 @@ def prune_block(ctx, workload, ens, coords, atoms, assign, n_conf, n_atoms, step
     t_kernel_ms = tk / steps
     if rank != 0:
         return None
+    if dump:
+        write_outputs(dump, {"survivor_mask": mask})
     roof = screen_roofline(_lib, t_kernel_ms, owned, n_atoms, world=world, stats=stats, n_conf=n_conf)
     roof["kernel_ms_source"] = ("HIP events on the kernel's stream around every %sth launch of the timed region "
                                 "(an event pair costs the stream ~14 us; FC_BENCH_EVENT_STRIDE=1 times all)"
@@ -818,10 +851,11 @@ def run_prune_line(ctx, workload, as_block=False):
             "this weak-scaling family: n_conf = 100 000 * sqrt(n_gpus / 8), 6.25e8 pairs per GPU)")
     coords, atoms, assign = syn.synthetic_ensemble(n_conf, n_atoms, seed=seed)
     with fc.DeviceEnsemble(coords, center=True) as ens:
-        blk = prune_block(ctx, "cfg4", ens, coords, atoms, assign, n_conf, n_atoms, 20, 3, steps=steps, warmup=warmup)
+        blk = prune_block(ctx, "cfg4", ens, coords, atoms, assign, n_conf, n_atoms, 20, 3, steps=steps, warmup=warmup,
+                          dump=None if as_block else args.dump_outputs)
     if rank == 0:
         blk["workload"] = what
-    if world > 1:
+    if args.full and world > 1:
         if rank == 0:
             # the family's n_gpus = 1 member (same pairs per GPU), on rank 0 alone
             n1 = int(round(100000 * np.sqrt(1 / 8.0) * rehearsal_scale()))
@@ -1023,6 +1057,10 @@ def run_cfg5(args, fc, _lib, fdist, syn, rank, world, barrier, max_over_ranks):
     if rank != 0:
         return None
     P = int(ok.size)
+    if args.dump_outputs:
+        # the gathered pass mask of the last step at 2^20 seeded poses (the whole mask is 1.6e7 poses and more)
+        pick = np.sort(np.random.default_rng(5).choice(P, min(P, 1 << 20), replace=False))
+        write_outputs(args.dump_outputs, {"pose_index": pick.astype(np.float64), "passed": np.ravel(ok)[pick]})
     k_ms = float(np.mean(kernel_ms))
     local_poses = P // world
     bytes_per_pose = (A + A) * 24 + 2 * 96 + 1
@@ -1039,7 +1077,7 @@ def run_cfg5(args, fc, _lib, fdist, syn, rank, world, barrier, max_over_ranks):
                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": local_poses * bytes_per_pose / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                         "traffic": None, "kernel_ms": k_ms, "algorithmic_bytes_per_pose": bytes_per_pose,
                         "note": "rank 0's kernel (HIP events); > 1 = the pre-transformed structures are reused from LDS / L2"}}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline_poses()
     return out
 

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -64,7 +65,7 @@ def _check_prune_block(p):
 @pytest.mark.gpu
 @pytest.mark.parametrize("sharded", [False, True])
 def test_bench_prints_one_contract_line(sharded):
-    d = _run({"FC_BENCH_FORCE_SHARDED": "1"} if sharded else {}, ["--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    d = _run({"FC_BENCH_FORCE_SHARDED": "1"} if sharded else {}, ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])
     _check_headline(d, 2, 1)
     _check_prune_block(d["prune_path"])
     assert d["pruned_ensembles_per_s"] == d["prune_path"]["pruned_ensembles_per_s"]
@@ -80,19 +81,55 @@ def test_bench_prints_one_contract_line(sharded):
 
 @pytest.mark.gpu
 def test_bench_cpu_baseline_block():
-    d = _run({"FC_BENCH_CPU_SECONDS": "3"}, ["--steps", "1", "--warmup", "0", "--no-extras"])
+    d = _run({"FC_BENCH_CPU_SECONDS": "3"}, ["--steps", "1", "--warmup", "0", "--full", "--no-extras"])
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["unit"] == "alignments/s" and c["value"] > 0 and c["sample"]
     assert abs(d["vs_cpu_baseline"] - d["value"] / c["value"]) < 1e-6 * d["vs_cpu_baseline"] and "prune_path" not in d
 
 
 @pytest.mark.gpu
-def test_bench_cfg4_and_cfg5_workloads_run_on_one_rank():
-    d = _run({}, ["--workload", "cfg4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` as the driver runs it: the timed steps and the line, nothing that --full adds;
+    --dump-outputs writes the last timed pass's two outputs at value_check's seeded pairs -- the same pairs in a --full run,
+    whose value_check passes, and the same values"""
+    d = _run({}, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "plain")])
+    _check_headline(d, 3, 1)
+    for k in ("value_check", "prune_path", "fp64_path", "rmsd_values_per_s", "cpu_baseline", "scaling_family_n1"):
+        assert k not in d, k
+    names = ("pair_i", "pair_j", "rmsd", "maxdev")
+    assert sorted(os.listdir(tmp_path / "plain")) == sorted(n + ".npy" for n in names)
+    a = {n: np.load(tmp_path / "plain" / (n + ".npy")) for n in names}
+    assert all(x.dtype == np.float64 and x.shape == (16384,) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    i, j = a["pair_i"].astype(np.int64), a["pair_j"].astype(np.int64)
+    assert np.array_equal(i, a["pair_i"]) and np.all(i >= 0) and np.all(i < j) and np.all(j < 10000)
+    assert np.all(np.isfinite(a["rmsd"])) and np.all(a["maxdev"] >= a["rmsd"] - 1e-9)
+
+    f = _run({}, ["--steps", "2", "--warmup", "0", "--full", "--no-extras", "--no-cpu-baseline",
+                  "--dump-outputs", str(tmp_path / "full")])
+    assert f["value_check"]["ok"] is True and f["value_check"]["pairs"] == 16384
+    b = {n: np.load(tmp_path / "full" / (n + ".npy")) for n in names}
+    assert np.array_equal(a["pair_i"], b["pair_i"]) and np.array_equal(a["pair_j"], b["pair_j"])
+    assert np.max(np.abs(a["rmsd"] - b["rmsd"])) < 1e-12 and np.max(np.abs(a["maxdev"] - b["maxdev"])) < 1e-12
+
+
+def test_bench_help_names_full_and_dump_outputs():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+@pytest.mark.gpu
+def test_bench_cfg4_and_cfg5_workloads_run_on_one_rank(tmp_path):
+    d = _run({}, ["--workload", "cfg4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "cfg4")])
     assert d["config"]["baseline_config"] == "configs[3]" and d["config"]["n_atoms"] == 80 and d["unit"] == "pair decisions/s"
     _check_prune_block(dict(d["prune_path"], roofline=d["roofline"]))
-    d = _run({}, ["--workload", "cfg5", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
+    m = np.load(tmp_path / "cfg4" / "survivor_mask.npy")
+    assert m.dtype == np.float32 and m.shape == (d["config"]["n_conformers"],) and m.sum() == d["prune_path"]["survivors"]
+    d = _run({}, ["--workload", "cfg5", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "cfg5")])
     assert d["config"]["baseline_config"] == "configs[4]" and d["unit"] == "poses/s" and d["value"] > 0
+    idx, ok = np.load(tmp_path / "cfg5" / "pose_index.npy"), np.load(tmp_path / "cfg5" / "passed.npy")
+    assert idx.shape == ok.shape == (min(d["config"]["poses_per_step"], 1 << 20),) and ok.dtype == np.float32
+    assert np.all(np.diff(idx) > 0) and set(np.unique(ok)) <= {0.0, 1.0}
 
 
 @pytest.mark.gpu
@@ -123,7 +160,7 @@ def test_bench_two_ranks_on_one_device_agree_through_files(tmp_path):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533",
                    FC_COMM_ID_FILE=idfile, FC_COMM_TIMEOUT_S="120", HSA_ENABLE_IPC_MODE_LEGACY="0")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                                       "--no-cpu-baseline", "--no-extras"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                                       "--full", "--no-cpu-baseline", "--no-extras"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     assert [p.returncode for p in procs] == [0, 0], outs[0][1][-1500:] + outs[1][1][-1500:]
@@ -141,7 +178,7 @@ def test_bench_gpus_3_as_typed_on_one_device():
     """`python bench.py --gpus 3` as the driver types it, rehearsed on one device (FC_BENCH_SAME_DEVICE=1): the parent starts
     three rank processes, relays rank 0's single line, exits 0; the ranks agree through files (RCCL refuses a duplicate device)"""
     d = _run({"FC_BENCH_SAME_DEVICE": "1", "FC_COMM_TIMEOUT_S": "120"},
-             ["--gpus", "3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"])
+             ["--gpus", "3", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras"])
     assert d["n_gpus"] == 3 and d["ranks_seen"] == 3 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["n_conformers"] == 17321 and 0 < d["efficiency"] < 1.2
     assert "scaling_family_n1" in d and d["rank_coordination"].startswith("barrier / max over ranks through files")

@@ -167,7 +167,7 @@ def test_bench_two_ranks_with_a_working_communicator(stub_lib):
 
     env = dict(os.environ, FC_BENCH_SAME_DEVICE="1", FC_RCCL_LIB=stub_lib, FC_BENCH_EXTRAS_TIMEOUT_S="600",
                FC_BENCH_SETTLE_S="0.01")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -188,7 +188,7 @@ def test_bench_four_ranks_rehearsal_and_failing_ranks(stub_lib):
 
     env = dict(os.environ, FC_BENCH_SAME_DEVICE="1", FC_RCCL_LIB=stub_lib, FC_BENCH_EXTRAS_TIMEOUT_S="600",
                FC_BENCH_SETTLE_S="0.01", FC_BENCH_REHEARSAL_SCALE="0.3")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

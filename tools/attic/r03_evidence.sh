@@ -11,8 +11,8 @@ say() { echo "[r03] $*"; }
 parts="${*:-pmc secondary cfg4 bench workloads variants extra}"
 for part in $parts; do case $part in
 bench)
-  say "bench default"; python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
-  say "bench driver form"; python bench.py --steps 20 --warmup 5 > $O/bench_n1_k20.json 2> $O/bench_n1_k20.err
+  say "bench default"; python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
+  say "bench driver form"; python bench.py --steps 20 --warmup 5 --full > $O/bench_n1_k20.json 2> $O/bench_n1_k20.err
   say "bench under rocprof (kernel trace + stats; the timed region only)"
   rocprofv3 --kernel-trace --stats -d $O/prof_bench --output-format csv -- python3 bench.py --no-cpu-baseline --no-extras > $O/bench_n1_under_rocprof.json 2> $O/prof_bench.err
   find $O/prof_bench -name "*kernel_stats.csv" -exec cp {} $O/bench_n1_kernel_stats.csv \;
@@ -45,8 +45,8 @@ workloads)
   ;;
 variants)
   say "bench: self-spawn with one rank, forced sharded, cfg4 line, cfg5 line"
-  FC_BENCH_FORCE_SPAWN=1 python bench.py --gpus 1 --no-cpu-baseline > $O/bench_spawned_1rank.json 2> $O/bench_spawned_1rank.err
-  FC_BENCH_FORCE_SHARDED=1 python bench.py --no-cpu-baseline > $O/bench_forced_sharded_1rank.json 2> $O/bench_forced_sharded_1rank.err
+  FC_BENCH_FORCE_SPAWN=1 python bench.py --gpus 1 --full --no-cpu-baseline > $O/bench_spawned_1rank.json 2> $O/bench_spawned_1rank.err
+  FC_BENCH_FORCE_SHARDED=1 python bench.py --full --no-cpu-baseline > $O/bench_forced_sharded_1rank.json 2> $O/bench_forced_sharded_1rank.err
   python bench.py --workload cfg4 --no-cpu-baseline > $O/bench_cfg4_n1.json 2> $O/bench_cfg4_n1.err
   python bench.py --workload cfg5 --no-cpu-baseline > $O/bench_cfg5_n1.json 2> $O/bench_cfg5_n1.err
   ;;
@@ -62,7 +62,7 @@ extra)
   timeout -k 10 400 bash tools/attic/two_ranks_one_device.sh --no-extras > $O/two_ranks_one_device.txt 2>&1
   cp gpurun_out/two_r0.out $O/two_ranks_one_device_rank0.json 2>/dev/null
   say "the driver's launch form, two ranks on one device"
-  FC_BENCH_SAME_DEVICE=1 FC_COMM_TIMEOUT_S=120 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/torchrun_2ranks_one_device.json 2> $O/torchrun_2ranks_one_device.err
+  FC_BENCH_SAME_DEVICE=1 FC_COMM_TIMEOUT_S=120 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 2 --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras > $O/torchrun_2ranks_one_device.json 2> $O/torchrun_2ranks_one_device.err
   say "timeline of steady-state prune steps"
   rocprofv3 --kernel-trace -d $O/prof_timeline --output-format csv -- python3 tools/attic/prune_probe.py 10000 50 2 100 > $O/timeline_probe.json 2> $O/timeline.err
   python3 tools/step_timeline.py $(find $O/prof_timeline -name "*kernel_trace.csv" | head -1) 60 3 > $O/prune_step_timeline.txt 2>&1

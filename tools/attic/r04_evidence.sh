@@ -31,8 +31,8 @@ refine)
   FC_LADDER_MANY=0 python3 tools/attic/ladder_many_probe.py > $O/ladder_one_workgroup.json 2>/dev/null
   ;;
 bench)
-  say "bench default"; python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
-  say "bench driver form"; python bench.py --steps 20 --warmup 5 > $O/bench_n1_k20.json 2> $O/bench_n1_k20.err
+  say "bench default"; python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
+  say "bench driver form"; python bench.py --steps 20 --warmup 5 --full > $O/bench_n1_k20.json 2> $O/bench_n1_k20.err
   say "bench under rocprof (kernel trace + stats; the timed region only)"
   rocprofv3 --kernel-trace --stats -d $O/prof_bench --output-format csv -- python3 bench.py --no-cpu-baseline --no-extras > $O/bench_n1_under_rocprof.json 2> $O/prof_bench.err
   find $O/prof_bench -name "*kernel_stats.csv" -exec cp {} $O/bench_n1_kernel_stats.csv \;
@@ -67,7 +67,7 @@ hostin)
 ranks)
   say "two ranks on one device with the stand-in collective (tests/stubs/rccl_stub.cpp): the N > 1 code path, not a scaling measurement"
   hipcc -O2 -std=c++17 -fPIC -shared -x hip --offload-arch=gfx950 tests/stubs/rccl_stub.cpp -o /tmp/librccl_stub.so -lrt -lpthread 2> $O/stub_build.err
-  FC_BENCH_SAME_DEVICE=1 FC_RCCL_LIB=/tmp/librccl_stub.so python bench.py --gpus 2 --steps 10 --warmup 2 > $O/bench_two_ranks_one_device_stub_collective.json 2> $O/bench_two_ranks_one_device_stub_collective.err
+  FC_BENCH_SAME_DEVICE=1 FC_RCCL_LIB=/tmp/librccl_stub.so python bench.py --gpus 2 --steps 10 --warmup 2 --full > $O/bench_two_ranks_one_device_stub_collective.json 2> $O/bench_two_ranks_one_device_stub_collective.err
   ;;
 esac; done
 say done

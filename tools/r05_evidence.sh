@@ -33,7 +33,7 @@ tests)
   ;;
 bench)
   say "bench as the driver runs it"
-  python bench.py --steps 20 --warmup 5 > $O/bench_n1_k20.json 2> $O/bench_n1_k20.err
+  python bench.py --steps 20 --warmup 5 --full > $O/bench_n1_k20.json 2> $O/bench_n1_k20.err
   tail -c 600 $O/bench_n1_k20.json
   ;;
 atoms)
