@@ -316,6 +316,57 @@ def test_cfg3_full_scan_samples_and_tfd(fc):
         assert d.min() < 10
 
 
+def test_catalyst_whole_grid_samples_and_tfd(fc, golden):
+    """cfg3 on a real molecule: the reference's csearch input (catalyst.xyz, 85 atoms) with its 13 perceived torsions
+    (twelve 3-fold, one 4-fold: 2 125 764 angle-sets) -- interleaved, branched rotation masks; counts and fingerprints
+    of every set without the 4.3 GB of coordinates, sampled sets against the oracle scan"""
+    from firecode_amd import torsion_perception as tp
+    from firecode_amd.pruner import rotation_mask
+
+    atoms = np.array([str(a) for a in golden["fx_catalyst_atoms"]])
+    base = np.asarray(golden["fx_catalyst_coords"], dtype=np.float64)[0]
+    graph = tp.graphize(atoms, base)
+    torsions = tp.get_torsions(graph, double_bonds=tp.get_double_bonds_indices(base, atoms), mode="csearch")
+    quads = np.array([t.torsion for t in torsions], dtype=np.int64)
+    masks = np.array([rotation_mask(graph, q, len(atoms)) for q in quads])
+    values = [fc.torsion_module.N_FOLD_ANGLES[int(t.n_fold)] for t in torsions]
+    assert len(torsions) == 13 and sorted(int(t.n_fold) for t in torsions) == [3] * 12 + [4]
+    angles = fc.utils.cartesian_product(*values)
+    assert angles.shape == (2125764, 13)
+    tf, rot = fc.torsion_module.torsion_scan_fingerprints(base, quads, masks, angles, quads, thresh=1.5)
+    del angles
+    rng = np.random.default_rng(13)
+    pick = rng.choice(len(rot), 300, replace=False)
+    rows = fc.utils.cartesian_rows_at(values, pick)
+    out, rot_s = fc.torsion_module.torsion_scan(base, quads, masks, rows, thresh=1.5)
+    ref_c, ref_r = o.torsion_scan(base, quads, masks, rows, thresh=1.5)
+    assert np.array_equal(rot[pick], ref_r) and np.array_equal(rot_s, ref_r)
+    assert np.abs(out - ref_c).max() < TOL
+    assert np.abs(tf[pick] - o.get_tf_mat(ref_c, quads)).max() < TOL
+    # (at the reference's 1.5 A no sampled set clashes: every non-zero angle is a rotated bond -- the back-off loops
+    # on this molecule are tested at 2.2 A on torsion groups, tests/test_gpu_molecules.py)
+    assert np.array_equal(ref_r, (rows != 0).sum(axis=1)) and ref_r.min() >= 4
+    keep = np.concatenate([[0], 1 + np.flatnonzero(rot != 0)])
+    tf_all = np.concatenate([fc.torsion_module.get_torsion_fingerprint(base, quads)[None], tf[rot != 0]])
+    del tf
+    mask = fc.torsion_module.prune_tfd_from_tf_mat(tf_all, 10)
+    assert 0 < mask.sum() < len(mask)
+    # the csearch driver's fused call (grid generated on the device, fingerprints kept there) == the two calls
+    rot_g, keep_g = fc.torsion_module.torsion_scan_tfd_grid(base, quads, masks, values, quads, thresh=1.5, tfd_thresh=10)
+    assert np.array_equal(rot_g, rot)
+    expect = np.zeros(len(rot) + 1, dtype=bool)
+    expect[keep] = mask
+    assert np.array_equal(keep_g, expect)
+    sl = tf_all[200000:200700]
+    assert np.array_equal(fc.torsion_module.prune_tfd_from_tf_mat(sl, 10), o.prune_tfd_from_tf_mat(sl, 10))
+    removed = np.flatnonzero(~mask)
+    for i in rng.choice(removed, 15, replace=False):
+        d = np.abs(tf_all - tf_all[i])
+        d = np.abs(d - (d > 180) * 360).sum(axis=1)
+        d[i] = 1e9
+        assert d.min() < 10
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_bench_multi_gpu_sizes_with_logical_ranks(fc, world):
