@@ -146,6 +146,8 @@ _SIGNATURES = {
     "fc_debug_comm_loopback": [_i64, _i64],
     "fc_prune_rmsd_sharded": [_ens, _f64, _f64, _i64, _i64, _p_u8, _p_i64],
     "fc_bench_prune_rmsd_sharded": [_ens, _f64, _f64, _i64, C.c_int, _p_f64, _p_f64, _p_u8, _p_i64],
+    "fc_ensemble_select_diverse": [_ens, _i64, _i64, _f64, _p_i64, _p_f64, C.POINTER(C.c_int32), _p_f64, _p_i64],
+    "fc_bench_select_diverse": [_ens, _i64, _i64, _f64, _i64, _p_f64, _p_f64, _p_i64, _p_i64, _p_i64],
     "fc_prune_rmsd_many": [C.POINTER(_ens), _i64, _f64, _f64, _i64, C.POINTER(_p_u8), _p_i64],
 }
 
@@ -417,6 +419,31 @@ class DeviceEnsemble:
         r, m = np.empty(P), np.empty(P)
         call("fc_ensemble_rmsd_pairs", self.handle, pi(pi_), pi(pj_), P, pf(r), pf(m))
         return r, m
+
+    def select_diverse(self, n_max, start=0, stop_rmsd=None):
+        """Greedy max-min selection under this ensemble's RMSD (fc_ensemble_select_diverse; the contract is in
+        include/fc_hip.h) -> ``(indices (K,) int64 in selection order, labels (N,) int32 = position in ``indices``
+        of each conformer's representative, distances (N,) to it, radii (K,) nonincreasing, radii[0] = inf)``."""
+        n_max, start = int(n_max), int(start)
+        stop = -1.0 if stop_rmsd is None else float(stop_rmsd)
+        if stop_rmsd is not None and not stop >= 0.0:
+            raise FirecodeHipInputError(FC_E_INVALID, f"stop_rmsd={stop_rmsd!r} must be >= 0")
+        cap = max(1, min(n_max, self.N))
+        idx, rad = np.empty(cap, dtype=np.int64), np.empty(cap)
+        lab, dist = np.empty(self.N, dtype=np.int32), np.empty(self.N)
+        k = C.c_int64(0)
+        call("fc_ensemble_select_diverse", self.handle, n_max, start, stop, pi(idx), pf(rad),
+             ptr(lab, C.c_int32), pf(dist), C.byref(k))
+        return idx[:k.value], lab, dist, rad[:k.value]
+
+    def bench_select_diverse(self, n_max, start=0, stop_rmsd=None, reps=3):
+        """``reps`` selections -> (mean device ms, mean host ms, indices of the last, lanes per conformer used)."""
+        stop = -1.0 if stop_rmsd is None else float(stop_rmsd)
+        idx = np.empty(max(1, min(int(n_max), self.N)), dtype=np.int64)
+        dev, host, k, lanes = C.c_double(0), C.c_double(0), C.c_int64(0), C.c_int64(0)
+        call("fc_bench_select_diverse", self.handle, int(n_max), int(start), stop, int(reps), C.byref(dev),
+             C.byref(host), pi(idx), C.byref(k), C.byref(lanes))
+        return dev.value, host.value, idx[:k.value], lanes.value
 
     def rmsd_matrix(self):
         r = np.zeros((self.N, self.N))

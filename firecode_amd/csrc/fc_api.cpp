@@ -113,6 +113,9 @@ int warm_prune();
 int warm_h2_check();
 int warm_kabsch();
 int warm_tfd_ladder();
+int warm_diverse();
+int select_diverse(fc_ensemble *, int64_t, int64_t, double, int64_t *, double *, int32_t *, double *, int64_t *, double *);
+int diverse_lanes(int64_t);
 int tfd_ladder_emulate_device(const int64_t *, int64_t, uint8_t *);
 int xyz_write(const char *, const char *const *, int64_t, const double *, int64_t, const char *, int);
 int xyz_read(const char *, int64_t *, int64_t *, char *, double *);
@@ -983,6 +986,7 @@ int fc_warmup(void) {
   FC_TRY(warm_h2_check());
   FC_TRY(warm_kabsch());
   FC_TRY(warm_tfd_ladder());
+  FC_TRY(warm_diverse());
   FC_TRY(side_streams());  // the pipelines' streams and ordering events
   // the buffers a first large call would otherwise take from the runtime one by one (0.2 - 1 ms each): through the pool once
   {
@@ -1262,6 +1266,49 @@ static int bench_rmsd_and_max_all(fc_ensemble *ens, int64_t reps, double *ms_ker
     FC_TRY(d2h(sample_maxdev, sm.p, (size_t)P * sizeof(double)));
     FC_TRY(sync());
   }
+  return FC_OK;
+}
+
+// ---- RMSD-diverse selection (greedy max-min; the contract: include/fc_hip.h, fc_diverse.hip) ----------------------
+static int select_diverse_checked(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
+                                  double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected,
+                                  double *ms_device) {
+  FC_REQUIRE(ens != nullptr, "ens is NULL");
+  FC_REQUIRE(indices_out != nullptr && n_selected != nullptr, "indices_out / n_selected is NULL");
+  FC_REQUIRE(n_max >= 1, "n_max=%lld < 1", (long long)n_max);
+  FC_REQUIRE(!(stop_rmsd != stop_rmsd), "stop_rmsd is NaN");
+  FC_REQUIRE(ens->epoch == ctx().epoch, "this ensemble was created before fc_shutdown / a device switch: create it again");
+  *n_selected = 0;
+  if (ens->N == 0) return FC_OK;
+  FC_REQUIRE(start >= 0 && start < ens->N, "start=%lld outside [0, %lld)", (long long)start, (long long)ens->N);
+  FC_REQUIRE(ens->N <= (int64_t)INT32_MAX - 256, "N=%lld: the selection indexes conformers with 32 bits", (long long)ens->N);
+  FC_TRY(ensure_init());
+  return select_diverse(ens, n_max, start, stop_rmsd, indices_out, radii_out, labels_out, dist_out, n_selected, ms_device);
+}
+
+int fc_ensemble_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
+                               double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected) {
+  FC_API_LOCK;
+  return select_diverse_checked(ens, n_max, start, stop_rmsd, indices_out, radii_out, labels_out, dist_out, n_selected,
+                                nullptr);
+}
+
+int fc_bench_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd, int64_t reps,
+                            double *ms_device_mean, double *ms_host_mean, int64_t *indices_out, int64_t *n_selected,
+                            int64_t *lanes_out) {
+  FC_API_LOCK;
+  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
+  double dev = 0.0, host = 0.0;
+  for (int64_t r = 0; r < reps; ++r) {
+    double ms = 0.0;
+    const auto t0 = std::chrono::steady_clock::now();
+    FC_TRY(select_diverse_checked(ens, n_max, start, stop_rmsd, indices_out, nullptr, nullptr, nullptr, n_selected, &ms));
+    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    dev += ms;
+  }
+  *ms_device_mean = dev / (double)reps;
+  *ms_host_mean = host / (double)reps;
+  if (lanes_out) *lanes_out = diverse_lanes(ens->N);
   return FC_OK;
 }
 

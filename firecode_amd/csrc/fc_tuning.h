@@ -27,3 +27,13 @@
      defined(FC_RB_AHEAD) || defined(FC_RB_CHUNK) || defined(FC_H2_WGS) || defined(FC_F32_WGS) || defined(FC_REFINE_ROUNDS) || defined(FC_V2_ALIGN) || defined(FC_STAGE_PAIRS_F32) || defined(FC_TS_WGS) || defined(FC_TS_TURN))
 #error "a tuning switch (FC_*TIMELINE / FC_*ABLATE* / FC_RB_* / FC_TFD_STAMPS ...) without -DFC_TUNING_BUILD: see fc_tuning.h"
 #endif
+
+#ifdef __cplusplus
+namespace fc {
+// fc_diverse.hip: up to this many conformers a selection step gives each conformer 8 lanes (the atom loops split, the
+// sums meet through shuffles: 8 x the wavefronts), above it 1 lane.  Measured at 50 atoms (tools/bench_diverse.py --lanes,
+// us per step 1 lane / 8 lanes): 1 000: 14.9 / 10.7, 3 000: 15.2 / 11.1, 10 000: 15.5 / 15.4, 30 000: 22.9 / 24.9,
+// 100 000: 38.9 / 83.3.  FC_DIVERSE_LANES=1 / 8 forces either form at run time.
+constexpr int64_t kDiverseLanes8MaxN = 10000;
+}  // namespace fc
+#endif

@@ -107,6 +107,28 @@ class Ensemble:
         self.energies = self.energies[order]
         self.coords = self.coords[order]
 
+    def diversity_selection(self, n=None, stop_rmsd=None, heavy_atoms_only=True, verbose=True):
+        """Keep the ``n`` most diverse structures, or representatives within ``stop_rmsd`` of every structure, by
+        greedy max-min selection under the heavy-atom RMSD (``firecode_amd.pruner.select_diverse``; no reference
+        counterpart: FIRECODE's ``most_diverse_conformers`` is a random draw).  Starts at the lowest energy when
+        energies are known, else at the first structure; the kept structures stay in selection order and
+        ``energies`` follow them.  Returns the ``DiverseSelection`` of the ensemble as it was."""
+        from firecode_amd.pruner import select_diverse
+
+        log = self.logfunction if verbose else None
+        n0, t0 = len(self.coords), perf_counter()
+        use_en = len(self.energies) == n0 and n0 > 0
+        sel = select_diverse(self.coords, self.atoms, n=n, stop_rmsd=stop_rmsd, heavy_atoms_only=heavy_atoms_only,
+                             energies=self.energies if use_en else None)
+        self.coords = self.coords[sel.indices]
+        if use_en:
+            self.apply_mask(("energies",), sel.indices)
+        if log is not None:
+            cover = float(sel.distances.max()) if n0 else 0.0
+            log(f"Kept {len(sel.indices)} of {n0} candidates for RMSD diversity (covering radius {cover:.3f} A, "
+                f"{perf_counter() - t0:.3f} s)")
+        return sel
+
     def similarity_pruning(self, moi=True, rmsd=True, rmsd_rot_corr=False, verbose=True, max_rmsd=None,
                            symmetric_torsions=None, graph=None, rotation_masks=None):
         """firecode/ensemble.py:185-276: MOI prune, RMSD prune, then (``rmsd_rot_corr``, at

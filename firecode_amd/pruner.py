@@ -5,6 +5,7 @@ Every function returns ``(structures[mask], mask)`` with ``mask`` a NumPy
 bool array in the caller's order, like the reference call sites expect
 (ensemble.py:211-235, embedder.py:1452-1496)."""
 
+from collections import namedtuple
 from time import perf_counter
 
 import numpy as np
@@ -97,6 +98,52 @@ def prune_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None,
             f"{stats[2]} similar, {stats[3]} grey, {stats[4]} ladder levels, "
             f"keeping {int(mask.sum())}/{N} in {perf_counter() - t0:.3f} s")
     return structures[mask], mask
+
+
+DiverseSelection = namedtuple("DiverseSelection", ["indices", "labels", "distances", "radii"])
+
+
+def select_diverse(structures, atoms, n=None, stop_rmsd=None, heavy_atoms_only=True, start=None, energies=None):
+    """RMSD-diverse selection: greedy max-min (farthest point, Gonzalez k-center) under the heavy-atom Kabsch RMSD
+    ``prune_by_rmsd`` uses (centred, ``rmsd_and_max(...)[0]``), on the GPU (fc_ensemble_select_diverse; the contract
+    is written out in include/fc_hip.h).  Either "the ``n`` most different conformers" (``n``) or "representatives
+    such that every conformer is within ``stop_rmsd`` of one" (``stop_rmsd``; with both, whichever comes first;
+    with only ``stop_rmsd``, ``n`` = N).  The first representative is ``start``, else the lowest energy of
+    ``energies`` (lowest index on ties), else 0.  No N x N matrix: one conformer is aligned against all N per step.
+
+    Returns ``DiverseSelection(indices, labels, distances, radii)``: indices (K,) into ``structures`` in selection
+    order; labels (N,) int32, the position in ``indices`` of each conformer's nearest representative; distances (N,)
+    to it; radii (K,) the covering radius just before each pick (nonincreasing, radii[0] = inf)."""
+    structures = L.f64(structures)
+    if structures.ndim != 3 or structures.shape[2] != 3:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {structures.shape}")
+    atoms = np.asarray(atoms)
+    if atoms.shape[0] != structures.shape[1]:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "len(atoms) != number of atoms")
+    N = structures.shape[0]
+    if n is None and stop_rmsd is None:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "select_diverse needs n, stop_rmsd or both")
+    if n is not None and (int(n) != n or int(n) < 1):
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"n={n!r}: at least one representative")
+    if stop_rmsd is not None and not float(stop_rmsd) >= 0.0:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"stop_rmsd={stop_rmsd!r} must be >= 0")
+    if energies is not None:
+        energies = np.asarray(energies, dtype=np.float64).reshape(-1)
+        if energies.shape[0] != N:
+            raise L.FirecodeHipInputError(L.FC_E_INVALID, "len(energies) != number of structures")
+    if start is not None and not 0 <= int(start) < max(N, 1):
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"start={start!r} outside [0, {N})")
+    heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
+    if not heavy.any():
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "the atom selection is empty (no heavy atom)")
+    if N == 0:
+        empty = np.zeros(0, dtype=np.int64)
+        return DiverseSelection(empty, np.zeros(0, dtype=np.int32), np.zeros(0), np.zeros(0))
+    if start is None:
+        start = int(np.argmin(energies)) if energies is not None else 0  # (argmin: the first of equal minima)
+    n_max = N if n is None else int(n)
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
+        return DiverseSelection(*ens.select_diverse(n_max, start=int(start), stop_rmsd=stop_rmsd))
 
 
 def rotation_mask(graph, torsion, n_atoms=None):

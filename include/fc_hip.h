@@ -135,6 +135,29 @@ int fc_ensemble_rmsd_and_max_all(fc_ensemble *ens, double *rmsd_out, double *max
  * symmetric, may be NULL (timing only); ms_kernel (may be NULL) = HIP-event time
  * of the two kernels. */
 int fc_ensemble_rmsd_values(fc_ensemble *ens, double *rmsd_out, double *ms_kernel);
+/* RMSD-diverse selection: greedy max-min (farthest point, Gonzalez k-center) under the ensemble's Kabsch RMSD --
+ * FIRECODE's csearch mode 1, "keep the n most diverse conformers" (firecode/torsion_module.py:608-611), whose
+ * most_diverse_conformers (:574-586) returns a random draw.  d(i, j) is the value fc_ensemble_rmsd_pairs returns for
+ * (i, j) within a few ulp (the ensemble's atom selection and centring; the rotation by Newton eigenvalue + adjugate
+ * eigenvector where the eigenvalue is clearly simple, the Jacobi sweeps otherwise).  The contract:
+ *
+ *   s[0] = start;  D[j] = d(s0, j);  D[s0] = 0;  L[j] = 0;  radius[0] = +inf
+ *   for k = 1 .. n_max-1, while fewer than N are selected:
+ *       m   = max D[j] over the conformers not yet selected;  s_k = the smallest such j with D[j] == m
+ *       if stop_rmsd >= 0 and m <= stop_rmsd: stop
+ *       radius[k] = m;  D[s_k] = 0;  L[s_k] = k
+ *       for all j: t = d(s_k, j); if t < D[j]: D[j] = t; L[j] = k      (strict: ties keep the earlier representative)
+ *
+ * Outputs: indices_out (n_max; the first *n_selected = K written) in selection order; radii_out (n_max or NULL) the
+ * covering radius just before each pick, nonincreasing, radii[0] = +inf; labels_out (N or NULL) the position in
+ * indices of each conformer's representative; dist_out (N or NULL) the distance to it (0 for a representative).
+ * No N x N matrix: a step aligns one conformer against all N (one kernel launch per step).  stop_rmsd < 0: no radius
+ * stop.  FC_E_INVALID before any device use: n_max < 1, start outside [0, N), NULL indices_out or n_selected, NaN
+ * stop_rmsd.  N = 0: *n_selected = 0.  Limits: N < 2^31 - 256; no atom limit (the representative is staged in LDS up
+ * to 2 048 selected atoms and read from HBM beyond). */
+int fc_ensemble_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd,
+                               int64_t *indices_out, double *radii_out, int32_t *labels_out, double *dist_out,
+                               int64_t *n_selected);
 /* a9: get_alignment_matrix(p, q) -- prism_pruner.rmsd; call site
  * hypermolecule_class.py:77.  M (3,3) row-major, applied as (M @ q.T).T */
 int fc_alignment_matrices(const double *p, const double *q, int64_t n_pairs, int64_t A,
@@ -594,6 +617,13 @@ int fc_bench_rmsd_and_max_all(fc_ensemble *ens, int64_t reps, double *ms_kernel_
 int fc_bench_rmsd_and_max_all_sampled(fc_ensemble *ens, int64_t reps, const int64_t *pair_i, const int64_t *pair_j,
                                       int64_t P, double *rmsd_out, double *maxdev_out, double *ms_kernel_mean,
                                       double *ms_total, int64_t *stats);
+/* `reps` selections (fc_ensemble_select_diverse, the same arguments; only the indices are copied back) one after the
+ * other: ms_device_mean = HIP events on the library's stream from the first step's launch to the last one's end (with a
+ * radius stop: the host's reads of the stop word every 64 steps included), ms_host_mean = wall-clock time per call;
+ * lanes_out (may be NULL) = lanes per conformer the step kernel used (1 or 8). */
+int fc_bench_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd, int64_t reps,
+                            double *ms_device_mean, double *ms_host_mean, int64_t *indices_out, int64_t *n_selected,
+                            int64_t *lanes_out);
 /* (fc_bench_prune_rmsd writes EIGHT stats: [6] = 16 x 32-pair units the subset stage of the lean fp32
  * screen queued for the full test in the last prune, [7] = 1 when its sample found similarity dense
  * and the single-stage kernel did the launch) */
