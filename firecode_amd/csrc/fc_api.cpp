@@ -41,6 +41,7 @@ int launch_mirror_upper(double *m_dev, int64_t N);
 int launch_gather_matrix_pairs(const double *, const double *, int64_t, const int64_t *, const int64_t *, int64_t,
                                double *, double *);
 void screen_select(int);
+int debug_screen_plan(int64_t, int64_t, int64_t, bool, double, double, int, int64_t *);
 int launch_simbits_screen(fc_ensemble *, double);
 int ensure_h2_operands(fc_ensemble *, double *);
 int launch_h2_cov_tile(const fc_ensemble *, int64_t, int64_t, float *);
@@ -3254,6 +3255,14 @@ int fc_screen_select(int kind) {
   FC_REQUIRE(kind == 0 || kind == 16 || kind == 32 || kind == 64, "kind must be 0 (automatic), 16, 32 or 64");
   screen_select(kind);
   return FC_OK;
+}
+
+int fc_debug_screen_plan(int64_t N, int64_t A, int64_t row_block, int64_t lean, double g_max, double max_rmsd, int64_t h2_model_ok,
+                         int64_t *plan_out) {
+  FC_API_LOCK;
+  FC_REQUIRE(plan_out && N >= 0 && N < (1ll << 31) && A >= 1 && row_block >= 1 && (h2_model_ok == 0 || h2_model_ok == 1),
+             "NULL plan_out, N outside 0..2^31, A < 1, row_block < 1 or h2_model_ok not 0 / 1");
+  return debug_screen_plan(N, A, row_block, lean != 0, g_max, max_rmsd, (int)h2_model_ok, plan_out);
 }
 
 int fc_bench_refine(fc_ensemble *ens, double max_rmsd, double max_dev, int64_t reps, double *ms_refine,

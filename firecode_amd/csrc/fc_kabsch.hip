@@ -440,9 +440,6 @@ __device__ __forceinline__ void push_pairs(uint64_t m, bool may, unsigned i, uns
 #ifndef FC_REFINE_ROUNDS
 #define FC_REFINE_ROUNDS 4  // measured: 8 -> 66 us, 4 -> 53 us, 2 -> 59 us, 1 (all redundant) -> 82 us; with the rounds' loads side by side (round 5): 2 -> 44, 4 -> 34, 8 -> 70 us (scratch)
 #endif
-#ifndef FC_V2_ALIGN
-#define FC_V2_ALIGN 1
-#endif
 constexpr int kStagePairs = 48;  // uint64 entries per workgroup
 constexpr int kStageWords = 24;  // uint32 entries per workgroup
 constexpr size_t kStageBytes = kStagePairs * 8 + kStageWords * 4 + 8;
@@ -2141,302 +2138,9 @@ k_screen_verdict(const double *__restrict__ Xa, const double *__restrict__ G, in
   }
 }
 
-// largest element of a non-negative array (bit patterns of non-negative doubles order like integers)
-__global__ void k_max_nonneg(const double *__restrict__ x, int64_t n, unsigned long long *__restrict__ out) {
-  double m = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const double v = x[i];
-    if (v > m) m = v;  // false for NaN
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_xor(m, off);
-    if (o > m) m = o;
-  }
-  if ((threadIdx.x & 63) == 0) atomicMax(out, (unsigned long long)__double_as_longlong(m));
-}
-
 __global__ void k_f64_to_f32(const double *__restrict__ x, int64_t n, float *__restrict__ y) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) y[i] = (float)x[i];
-}
-
-// ---------------------------------------------------------------------------
-// k_screen_rowsweep -- the same screen, other schedule.  MEASURED SLOWER, kept as evidence
-// (FC_SCREEN_V2=1): 1.05 ms with the phase barriers, 1.00 ms without them (-DFC_V2_ALIGN=0), against
-// 0.96 ms for the kernel above at 10^4 conformers (3.80 / 3.64 / 3.43 ms at 2*10^4).
-//
-// What the one-item-per-workgroup kernel above loses is known: the
-// polynomial epilogue of one wavefront is ADDED to the MFMA stream of the other wavefront of
-// its SIMD and issues at half rate while it runs alone; a freed slot waits ~6 us for its
-// next workgroup; the column tile is fetched in front of every item.  Here a workgroup is
-// 8 wavefronts (2 per SIMD, one workgroup per CU) that stays resident and sweeps a contiguous
-// run of items:
-//   * the next item's column tile arrives by LDS-DMA in the OTHER half of LDS while this one
-//     is computed (two 78 KB buffers);
-//   * barriers keep the wavefronts in phase -- K loop, epilogue, K loop, epilogue -- so the
-//     two wavefronts of a SIMD do their fp64 VALU work together, at full issue rate, and
-//     their MFMA work together;
-//   * no dispatch between items, equal item counts per workgroup (tail <= one item).
-// Wavefront w owns the 16-row tile w of the 128-row block.  A <= 52 atoms, row blocks of 128.
-// Why it loses: two fp64-VALU wavefronts on a SIMD only reach 1.4x the rate of one
-// (tools/ubench_f64: 52 vs 38 TFLOP/s), so aligned epilogues gain little, while waves in phase
-// stall together on the first operand loads of every K loop and wait for the slowest of eight
-// at every barrier; without the phase barriers the per-item barrier and the spills (124 B)
-// still cost more than the dispatch gap and the tile fill they remove.
-// ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(512, 1)
-k_screen_rowsweep(const double *__restrict__ Xs, const double *__restrict__ G, int64_t N, int64_t Npad,
-                  int A, double A_thr2, int64_t rank, int64_t world, uint64_t *__restrict__ bits, int64_t W,
-                  uint32_t *__restrict__ cand, unsigned long long *__restrict__ counters,
-                  uint64_t *__restrict__ pairq, unsigned long long Q, const uint64_t *__restrict__ item_table,
-                  unsigned long long n_items) {
-  extern __shared__ double lds[];
-  constexpr int TC = 64, IB = 128, NW = 8;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int KS = (A + 3) >> 2;
-  const int tile_doubles = KS * 12 * TC;
-  double *__restrict__ ldsGc = lds + 2 * tile_doubles;  // [2][TC] column sums of squares
-  double *__restrict__ ldsGr = ldsGc + 2 * TC;          // [IB] row sums of squares
-  uint64_t *__restrict__ stageQ = reinterpret_cast<uint64_t *>(ldsGr + IB);
-  uint32_t *__restrict__ stageW = reinterpret_cast<uint32_t *>(stageQ + kStagePairs);
-  unsigned *__restrict__ stageN = reinterpret_cast<unsigned *>(stageW + kStageWords);
-  const unsigned long long t_begin = n_items * blockIdx.x / gridDim.x;
-  const unsigned long long t_end = n_items * (blockIdx.x + 1ull) / gridDim.x;
-  if (t_begin >= t_end) return;
-  const int kq = lane >> 4, l15 = lane & 15;
-  const int boff = (kq >> 1) * (2 * TC) + (kq & 1) * 16 + l15;
-  const int cs_l = lane >> 4, k1_l = (lane >> 3) & 1, c15_l = (lane & 7) * 2;
-  uint16_t *bits16 = reinterpret_cast<uint16_t *>(bits);
-  const int n32 = (int)N;
-
-  auto dma_tile = [&](int64_t jt_, int which) {  // column tile jt_ -> buffer `which` (see the kernel above)
-    double *dst = lds + which * tile_doubles;
-    const int n_runs = KS * 6;
-    for (int q = wv; q < n_runs; q += NW) {
-      const int sc = q >> 1, kh = q & 1;
-      const int sg = sc / 3, c = sc - sg * 3;
-      const int a = sg * 4 + kh * 2 + k1_l;
-      const double *src = Xs + (int64_t)(a * 3 + c) * Npad + jt_ * TC + cs_l * 16 + c15_l;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                       (__attribute__((address_space(3))) void *)(dst + q * 128), 16, 0, 0);
-    }
-    if (tid < TC) {
-      const int64_t g = jt_ * TC + tid;
-      ldsGc[which * TC + tid] = g < Npad ? G[g] : 0.0;
-    }
-  };
-  auto flush_stage = [&]() {  // wavefront 0: publish and reset the staged candidates
-    {
-      const uint64_t e = lane < kStagePairs ? stageQ[lane] : ~0ull;
-      const bool valid = e != ~0ull;
-      const uint64_t mv = __ballot(valid);
-      if (mv != 0) {
-        unsigned long long gbase = 0;
-        if (lane == 0) gbase = atomicAdd(&counters[6], (unsigned long long)__popcll(mv));
-        gbase = __shfl(gbase, 0);
-        if (valid) {
-          const unsigned long long slot = gbase + (unsigned long long)__popcll(mv & ((1ull << lane) - 1ull));
-          if (slot < Q) pairq[slot] = e;
-        }
-      }
-      if (lane < kStagePairs) stageQ[lane] = ~0ull;
-    }
-    {
-      const uint32_t wq = lane < kStageWords ? stageW[lane] : ~0u;
-      const bool valid = wq != ~0u;
-      const uint64_t mv = __ballot(valid);
-      if (mv != 0) {
-        unsigned long long gbase = 0;
-        if (lane == 0) gbase = atomicAdd(&counters[4], (unsigned long long)__popcll(mv));
-        gbase = __shfl(gbase, 0);
-        if (valid) cand[gbase + (unsigned long long)__popcll(mv & ((1ull << lane) - 1ull))] = wq;
-      }
-      if (lane < kStageWords) stageW[lane] = ~0u;
-    }
-    if (lane < 2) stageN[lane] = 0u;
-  };
-
-  if (tid < kStagePairs) stageQ[tid] = ~0ull;
-  if (tid < kStageWords) stageW[tid] = ~0u;
-  if (tid < 2) stageN[tid] = 0u;
-  {
-    const uint64_t it0 = item_table[t_begin];
-    dma_tile((int64_t)(it0 & 0x7fffffffull), 0);
-  }
-  int64_t cur_lb = -1;
-  double a0[3], a1[3], a2[3];
-  unsigned voff[3] = {0, 0, 0};
-  bool pre_ok = false;  // a0..a2 hold the first three k-steps of this wavefront's rows
-
-  for (unsigned long long t = t_begin; t < t_end; ++t) {
-    const uint64_t item = item_table[t];
-    const int64_t lb = (int64_t)((item >> 32) & 0x7fffffffull);
-    const int64_t jt = (int64_t)(item & 0x7fffffffull);
-    const int p = (int)((t - t_begin) & 1ull);
-    const int64_t j0 = jt * TC;
-    const int64_t i0 = global_block(lb, rank, world) * IB;
-    const int64_t ib = i0 + (int64_t)wv * 16;
-    const int64_t lrow0 = lb * IB + (int64_t)wv * 16;
-    const double *__restrict__ cur = lds + p * tile_doubles;
-    __syncthreads();  // (A) this item's tile has landed; everybody is done with the other buffer
-    if (t + 1 < t_end) dma_tile((int64_t)(item_table[t + 1] & 0x7fffffffull), p ^ 1);
-    if (wv == 0 && t != t_begin) flush_stage();
-    if (lb != cur_lb) {
-      if (tid < IB) {
-        const int64_t g = i0 + tid;
-        ldsGr[tid] = g < Npad ? G[g] : 0.0;  // read after barrier (B)
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) voff[c] = (unsigned)((int64_t)(kq * 3 + c) * Npad + ib + l15);
-      cur_lb = lb;
-      pre_ok = false;
-#if !FC_V2_ALIGN
-      __syncthreads();  // block-uniform branch: the row sums are read in the first epilogue
-#endif
-    }
-    const bool row_on = ib < N && !(j0 + TC - 1 <= ib);
-    unsigned nz0 = 0, nz1 = 0, nz2 = 0, nz3 = 0;
-
-#pragma unroll 1
-    for (int half = 0; half < 2; ++half) {
-      const int cs0 = half * 2;
-      const bool below = j0 + (cs0 + 2) * 16 - 1 <= ib;  // both sub-tiles at or below the diagonal
-      const bool active = row_on && !below;
-      d4_t acc[2][9];
-      if (active) {
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int e = 0; e < 9; ++e) acc[tt][e] = d4_t{0.0, 0.0, 0.0, 0.0};
-        const double *__restrict__ lb0 = cur + cs0 * 32 + boff;
-        double b0[2][3], b1[2][3];
-        auto fetch_a = [&](double (&a)[3], int sx) {
-          const int sl = sx < KS ? sx : KS - 1;
-          const double *__restrict__ xs_s = Xs + (int64_t)sl * 12 * Npad;
-#pragma unroll
-          for (int c = 0; c < 3; ++c) a[c] = xs_s[voff[c]];
-        };
-        auto fetch_b = [&](double (&b)[2][3], int sx) {
-          const int sl = sx < KS ? sx : KS - 1;
-          const double *__restrict__ lb_s = lb0 + sl * (12 * TC);
-#pragma unroll
-          for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) b[tt][c] = lb_s[c * (4 * TC) + tt * 32];
-        };
-        auto mma = [&](const double (&a)[3], const double (&b)[2][3]) {
-#pragma unroll
-          for (int x = 0; x < 3; ++x)
-#pragma unroll
-            for (int y = 0; y < 3; ++y)
-#pragma unroll
-              for (int tt = 0; tt < 2; ++tt)
-                acc[tt][x * 3 + y] =
-                    __builtin_amdgcn_mfma_f64_16x16x4f64(a[x], b[tt][y], acc[tt][x * 3 + y], 0, 0, 0);
-        };
-        if (!pre_ok) {
-          fetch_a(a0, 0);
-          fetch_a(a1, 1);
-          fetch_a(a2, 2);
-        }
-        fetch_b(b0, 0);
-        fetch_b(b1, 1);
-#define FC_KSTEP2(AX, BX, U)          \
-  if (sgrp + (U) < KS) {              \
-    mma(AX, BX);                      \
-    fetch_a(AX, sgrp + (U) + 3);      \
-    fetch_b(BX, sgrp + (U) + 2);      \
-  }
-        for (int sgrp = 0; sgrp < KS; sgrp += 6) {
-          FC_KSTEP2(a0, b0, 0)
-          FC_KSTEP2(a1, b1, 1)
-          FC_KSTEP2(a2, b0, 2)
-          FC_KSTEP2(a0, b1, 3)
-          FC_KSTEP2(a1, b0, 4)
-          FC_KSTEP2(a2, b1, 5)
-        }
-#undef FC_KSTEP2
-        // the same rows serve the next unit (second half, or the next item of this row block)
-        fetch_a(a0, 0);
-        fetch_a(a1, 1);
-        fetch_a(a2, 2);
-        pre_ok = true;
-      }
-#if FC_V2_ALIGN
-      __syncthreads();  // (B)/(D): both wavefronts of a SIMD leave their K loops together
-#endif
-      if (active) {
-        const int ib32 = (int)ib;
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-          const int cs = cs0 + tt;
-          const int j = (int)j0 + cs * 16 + l15;
-          const double Gq = ldsGc[p * TC + cs * 16 + l15];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int i = ib32 + kq + 4 * r;
-            const double Gp = ldsGr[wv * 16 + kq + 4 * r];
-            double B9[9];
-#pragma unroll
-            for (int e = 0; e < 9; ++e) B9[e] = acc[tt][e][r];
-            bool may = kabsch_may_be_below(B9, Gp + Gq, A_thr2);
-            may = may && (j > i) && (j < n32) && (i < n32);
-            const uint64_t m = __ballot(may);
-            stage_pairs(m, may, (unsigned)i, (unsigned)j, stageQ, stageN, pairq, Q, counters, lane);
-            if (lane < 4) {
-              const unsigned piece = (unsigned)((m >> (16 * lane)) & 0xffffull);
-              if (ib32 + lane + 4 * r < n32) {
-                bits16[((lrow0 + lane + 4 * r) * W + jt) * 4 + cs] = (uint16_t)piece;
-                if (r == 0) nz0 |= piece;
-                if (r == 1) nz1 |= piece;
-                if (r == 2) nz2 |= piece;
-                if (r == 3) nz3 |= piece;
-              }
-            }
-          }
-        }
-      } else if (row_on && below && lane < 4) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t row = ib + lane + 4 * r;
-          if (row < N) {
-            bits16[((lrow0 + lane + 4 * r) * W + jt) * 4 + cs0] = 0;
-            bits16[((lrow0 + lane + 4 * r) * W + jt) * 4 + cs0 + 1] = 0;
-          }
-        }
-      }
-#if FC_V2_ALIGN
-      if (half == 0) __syncthreads();  // (C): ... and their epilogues together
-#endif
-    }
-    if (row_on) {  // queue the non-empty words of this row tile for the exact refine
-      const unsigned nz[4] = {nz0, nz1, nz2, nz3};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const bool has = lane < 4 && nz[r] != 0;
-        const uint64_t mw = __ballot(has);
-        if (mw == 0) continue;  // wave-uniform
-        const unsigned n = (unsigned)__popcll(mw);
-        const uint32_t word = (uint32_t)((lrow0 + lane + 4 * r) * W + jt);
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(stageN + 1, n);
-        base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-        const unsigned rank_in = (unsigned)__popcll(mw & ((1ull << lane) - 1ull));
-        if (base + n <= (unsigned)kStageWords) {
-          if (has) stageW[base + rank_in] = word;
-        } else {
-          unsigned long long gbase = 0;
-          if (lane == 0) gbase = atomicAdd(&counters[4], (unsigned long long)n);
-          gbase = __shfl(gbase, 0);
-          if (has) cand[gbase + rank_in] = word;
-        }
-      }
-    }
-  }
-  __syncthreads();
-  if (wv == 0) flush_stage();
 }
 
 // ---------------------------------------------------------------------------
@@ -3653,590 +3357,554 @@ void screen_select(int kind) { g_screen_forced = kind; }
 
 int h2_model_ok(bool *ok);  // fc_h2_check.hip
 
-// makes e->Xh for the scale the split-half screen would use; scale_out = 0: the screen does not apply
-static int ensure_h2_operands_upto(fc_ensemble *e, double *scale_out, int64_t max_ks2) {
-  *scale_out = 0.0;
-  const int64_t KS2 = (e->A + 31) / 32, A4 = (e->A + 3) / 4 * 4;
-  if (KS2 > max_ks2 || (uint64_t)(24 * KS2) * (uint64_t)e->Npad >= (1ull << 32)) return FC_OK;
-  if (!(e->g_max > 0.0) || !std::isfinite(e->g_max)) return FC_OK;
-  // largest |coordinate| <= sqrt(g_max): scaled into [2^12, 2^13] (halfs reach 65504; s^4 stays in fp32)
+// ---- which screen a prune runs (plan_screen) and its launch ------------------------------------------------------------
+// The switches of the choice (screen_knobs), read from the environment and from fc_screen_select.
+struct ScreenKnobs {
+  bool valu = false;       // FC_SCREEN_CFG=valu...: the VALU screen (a tuning / evidence switch)
+  char f32 = 0;            // first character of FC_SCREEN_F32: '0' no single-precision screen, '2' one whatever the band,
+                           // '3' the same, always speculative
+  bool h2 = true;          // FC_SCREEN_H2 != 0: the split-half screen where it applies
+  double band_max = 4.0;   // FC_SCREEN_BAND_MAX: the widest band, in thresholds^2, a single-precision screen takes
+  bool one_stage = false;  // FC_SCREEN_STAGES=1: never the two-stage fp32 launch
+  int forced = 0;          // fc_screen_select
+  bool timeline = false;   // FC_TIMELINE builds: FC_TIMELINE_OUT is set (the fp64 screen records its timeline)
+};
+// The ensemble and threshold the choice depends on.
+struct ScreenShape {
+  int64_t N, Npad, A, row_block, n_lblocks;  // n_lblocks: row blocks of this rank
+  bool lean;
+  double g_max;  // largest G (NaN: the single-precision screens decline)
+  double thr2;   // max_rmsd^2 + kScreenMargin
+  int h2_model;  // the f16 matrix-pipe model check: 1 passed, 0 failed, -1 not run yet
+};
+struct ScreenPlan {
+  int err = FC_OK;              // FC_E_INVALID / FC_E_LIMIT: the prune returns it, nothing is launched
+  bool needs_h2_model = false;  // a row needs the model check's verdict: run it, plan again
+  int kind = 0;                 // 16 split-half f16 / 32 fp32 / 64 fp64 matrix pipe, 1 VALU, 0 no screen
+  int tc = 64;                  // column tile
+  int64_t ks = 0;               // k-steps of the matrix-pipe kernel: of 32 atoms (split-half), of 4 atoms (fp32, fp64)
+  bool two_stage = false;       // fp32: subset stage, per-unit kernel, single-stage redo
+  bool speculative = false;     // single precision first, then k_screen_verdict and the fp64 screen gated on it
+  int fp64_waves = 0;           // 4 / 8: wavefronts per workgroup of the fp64 screen (kind 64, or behind a speculative one)
+  bool timeline = false;        // FC_TIMELINE builds: the fp64 screen records its timeline
+  bool valu_lds = false;        // the VALU screen keeps its column tile in LDS
+  size_t lds = 0, lds64 = 0;    // dynamic LDS of the screen / of the fp64 screen
+  KabschF32Bounds bd{};         // single precision: bounds of the polynomial test
+  double scale = 0.0;           // split-half: power of two of the operands
+  float hthr = 0.f;             // split-half: A thr^2 scale^2 / 2
+};
+
+// The power of two the split-half operands are scaled by: the largest |coordinate| <= sqrt(g_max) goes into [2^12, 2^13]
+// (halfs reach 65504; s^4 stays in fp32).  0: no finite non-zero largest norm to take it from -- the screen does not apply.
+static double h2_scale(double g_max) {
+  if (!(g_max > 0.0) || !std::isfinite(g_max)) return 0.0;
   int ex = 0;
-  (void)std::frexp(std::sqrt(e->g_max), &ex);  // sqrt(g_max) = m 2^ex, m in [0.5, 1)
-  const double scale = std::ldexp(1.0, 13 - ex);
-  if (!e->xh_valid || e->xh_scale != scale) {
-    FC_TRY(e->Xh.reserve((size_t)KS2 * 24 * (size_t)e->Npad * 16));
-    hipLaunchKernelGGL(k_f64_to_h2, dim3((unsigned)ceil_div(e->Npad, 256), (unsigned)(KS2 * 12)), dim3(256), 0, ctx().stream,
-                       e->Xs.as<double>(), e->Npad, (int)A4, (int)KS2, scale, e->Xh.as<h8_t>());
-    FC_TRY(check_launch("k_f64_to_h2"));
-    e->xh_valid = true;
-    e->xh_scale = scale;
-  }
-  *scale_out = scale;
+  (void)std::frexp(std::sqrt(g_max), &ex);  // sqrt(g_max) = m 2^ex, m in [0.5, 1)
+  return std::ldexp(1.0, 13 - ex);
+}
+// the split-half operands are addressed by 32-bit byte offsets
+static bool h2_offsets_fit(int64_t KS2, int64_t Npad) { return (uint64_t)(24 * KS2) * (uint64_t)Npad < (1ull << 32); }
+
+// e->Xh: the split-half copy of Xs for `scale`, unless the ensemble holds it already
+static int make_h2_operands(fc_ensemble *e, double scale) {
+  if (e->xh_valid && e->xh_scale == scale) return FC_OK;
+  const int64_t KS2 = (e->A + 31) / 32, A4 = (e->A + 3) / 4 * 4;
+  FC_TRY(e->Xh.reserve((size_t)KS2 * 24 * (size_t)e->Npad * 16));
+  hipLaunchKernelGGL(k_f64_to_h2, dim3((unsigned)ceil_div(e->Npad, 256), (unsigned)(KS2 * 12)), dim3(256), 0, ctx().stream,
+                     e->Xs.as<double>(), e->Npad, (int)A4, (int)KS2, scale, e->Xh.as<h8_t>());
+  FC_TRY(check_launch("k_f64_to_h2"));
+  e->xh_valid = true;
+  e->xh_scale = scale;
   return FC_OK;
 }
-int ensure_h2_operands(fc_ensemble *e, double *scale_out) { return ensure_h2_operands_upto(e, scale_out, kH2MaxKS2); }
+// the operands of the 64-column split-half screen (fc_debug_h2_covariance); scale_out = 0: the screen does not apply
+int ensure_h2_operands(fc_ensemble *e, double *scale_out) {
+  const int64_t KS2 = (e->A + 31) / 32;
+  *scale_out = KS2 <= kH2MaxKS2 && h2_offsets_fit(KS2, e->Npad) ? h2_scale(e->g_max) : 0.0;
+  return *scale_out > 0.0 ? make_h2_operands(e, *scale_out) : FC_OK;
+}
 
-int launch_simbits_screen(fc_ensemble *e, double thr2_margin) {
-  // Context::mark_after_screen: recorded once, right behind the main screen kernel of this launch
-  bool marked = false;
-  auto mark_main = [&]() {
-    if (!marked && ctx().mark_after_screen) (void)hipEventRecord(ctx().mark_after_screen, ctx().stream);
-    if (!marked && ctx().after_main_stream && ctx().after_main_event) {  // the rest of this launch: on the caller's other stream
-      (void)hipEventRecord(ctx().after_main_event, ctx().stream);
-      (void)hipStreamWaitEvent(ctx().after_main_stream, ctx().after_main_event, 0);
-      ctx().stream = ctx().after_main_stream;
-    }
-    marked = true;
+// e->Xsf and e->sub: the fp32 copy of Xs and the subset statistics of the fp32 screen, unless the ensemble holds them already
+static int make_f32_operands(fc_ensemble *e) {
+  if (e->xsf_valid) return FC_OK;
+  const int64_t n = (e->A + 3) / 4 * 4 * 3 * e->Npad;
+  FC_TRY(e->Xsf.reserve((size_t)n * sizeof(float)));
+  hipLaunchKernelGGL(k_f64_to_f32, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx().stream, e->Xs.as<double>(), n,
+                     e->Xsf.as<float>());
+  FC_TRY(check_launch("k_f64_to_f32"));
+  FC_TRY(e->sub.reserve((size_t)e->Npad * 8 * sizeof(float)));
+  hipLaunchKernelGGL(k_subset_stats, dim3((unsigned)ceil_div(e->Npad, 256)), dim3(256), 0, ctx().stream, e->Xs.as<double>(),
+                     e->Npad, (int)e->A, e->sub.as<float>());
+  FC_TRY(check_launch("k_subset_stats"));
+  e->xsf_valid = true;
+  return FC_OK;
+}
+
+// The switches of the screen choice, each read here and nowhere else: FC_SCREEN_CFG and FC_SCREEN_F32 on every call (the
+// tests change them between prunes), FC_SCREEN_H2, FC_SCREEN_BAND_MAX and FC_SCREEN_STAGES once per process.
+static ScreenKnobs screen_knobs() {
+  static const int h2 = [] {
+    const char *v = getenv("FC_SCREEN_H2");
+    return v ? atoi(v) : 1;
+  }();
+  static const double band_max = [] {
+    const char *v = getenv("FC_SCREEN_BAND_MAX");
+    const double x = v ? atof(v) : 4.0;
+    return x > 0.0 ? x : 4.0;
+  }();
+  static const int stages = [] {
+    const char *v = getenv("FC_SCREEN_STAGES");
+    return v ? atoi(v) : 0;
+  }();
+  ScreenKnobs k;
+  const char *cfg = getenv("FC_SCREEN_CFG"), *f32 = getenv("FC_SCREEN_F32");
+  k.valu = cfg && std::strncmp(cfg, "valu", 4) == 0;
+  k.f32 = f32 ? f32[0] : 0;
+  k.h2 = h2 != 0;
+  k.band_max = band_max;
+  k.one_stage = stages == 1;
+  k.forced = g_screen_forced;
+#ifdef FC_TIMELINE
+  k.timeline = getenv("FC_TIMELINE_OUT") != nullptr;
+#endif
+  return k;
+}
+
+// Which all-pairs screen a prune runs.  The rows are tried in order, the first that matches wins (DESIGN.md section 5.2
+// has the measurements behind them).  band(p0) = 2 p0 g_max / A: the mean square deviations above the threshold that the
+// bounded single-precision test cannot rule out; limit = FC_SCREEN_BAND_MAX thr^2 (default 4); forced = fc_screen_select;
+// F32 = FC_SCREEN_F32; rb = row block.
+//
+//   0  no local row block or no column tile: no screen
+//   1  FC_SCREEN_CFG=valu*: VALU (1)
+//   2  split-half, 32-column tile (16; 7-13 k-steps: 193-416 atoms; lean launches only): FC_SCREEN_H2 != 0, forced 0 or 16,
+//      F32 != 0, rb % 32 = 0, the tile fits the LDS, the model check passed, scale > 0 and a finite threshold > 0, and
+//      forced = 16, F32 = 2 / 3 or band(p0_h2) <= limit.  Never speculative
+//   3  fp32, 32-column tile (32; where the 64-column fp32 tile does not fit; lean launches only): forced 0 or 32, F32 != 0,
+//      rb % 32 = 0, the tile fits, p0_f32 < 2e-3, g_max finite, and forced = 32, F32 = 2 / 3 or band(p0_f32) <= limit.
+//      Never speculative
+//   4  64-column family, where the fp64 tile fits or a 64-column single-precision tile does:
+//      a  F32 counts as 0 when forced = 64, as 2 when forced = 16 or 32
+//      b  single precision: F32 != 0, rb % 64 = 0, no fp64 timeline (FC_TIMELINE builds)
+//      c  split-half: single precision, FC_SCREEN_H2 != 0, forced != 32, <= 6 k-steps, the model check passed, scale > 0
+//      d  forced = 16 without c: FC_E_INVALID
+//      e  unless F32 = 2 / 3, single precision stays only if band <= limit -- a split-half band too wide falls back to
+//         fp32 where its own bound passes (p0 < 2e-3, tile fits, band <= limit, forced != 16) -- and is speculative
+//         where band > 0.1 thr^2 and N^2 > 2 kRefineLanesMin.  F32 = 3: always speculative, F32 = 2: never
+//      f  no fp64 tile: VALU unless single precision stands; never speculative
+//      g  split-half (16; FC_E_LIMIT where its row block does not fit the LDS), else fp32 (32; two stages when lean,
+//         FC_SCREEN_STAGES != 1, >= 16 padded atoms, rb <= 256).  Speculative: k_screen_verdict, then the fp64 screen
+//         gated on it; the kind reported stays 16 / 32
+//      h  no single precision: fp64 (64), 4 waves where two tiles fit the LDS, else 8
+//   5  VALU (1), its column tile in LDS where it fits
+//
+// Pure host code: no device call, no allocation.  h2_model = -1 (the device's check not run yet) returns needs_h2_model
+// where a row needs its verdict.
+static ScreenPlan plan_screen(const ScreenShape &s, const ScreenKnobs &k) {
+  ScreenPlan p;
+  if (s.n_lblocks <= 0 || (s.Npad >> 6) == 0) return p;  // row 0
+  const int64_t A = s.A, rb = s.row_block, A4 = (A + 3) / 4 * 4, KS2 = (A + 31) / 32;
+  const uint64_t Npad = (uint64_t)s.Npad;
+  auto valu = [&]() {  // row 5
+    const size_t lds = (size_t)A * 3 * 64 * sizeof(double);
+    p.kind = 1;
+    p.valu_lds = lds <= kLdsLimit;
+    p.lds = p.valu_lds ? lds : 0;
+    return p;
   };
-  const int64_t NT = e->Npad >> 6;
-  const int64_t n_gblocks = ceil_div(e->N, e->row_block);
-  const int64_t n_lblocks = local_block_count(n_gblocks, e->rank, e->world);
-  if (n_lblocks <= 0 || NT == 0) {
-    mark_main();
+  if (k.valu) return valu();  // row 1
+
+  const double limit = k.band_max * s.thr2;
+  auto band = [&](const KabschF32Bounds &b) { return (double)b.p0 * 2.0 * s.g_max / (double)A; };
+  const bool any_band = k.f32 == '2' || k.f32 == '3';
+  const KabschF32Bounds bf = kabsch_f32_bounds(A4), bh = kabsch_h2_bounds(KS2);
+  const double scale = h2_scale(s.g_max);
+  const float hthr = (float)(0.5 * ((double)A * s.thr2) * (scale * scale));
+  const bool h2_scaled = s.h2_model > 0 && scale > 0.0 && std::isfinite(hthr) && hthr > 0.f;
+  auto split_half = [&](int tc, size_t lds) {
+    p.kind = 16, p.tc = tc, p.ks = KS2, p.lds = lds, p.bd = bh, p.scale = scale, p.hthr = hthr;
+    return p;
+  };
+  auto needs_h2_model = [&]() {
+    p.needs_h2_model = true;
+    return p;
+  };
+  auto error = [&](int err) {
+    p.err = err;
+    return p;
+  };
+  const bool fits32 = (uint64_t)A4 * 3 * Npad < (1ull << 32);
+  const size_t lds_f32 = (size_t)A4 * 3 * 64 * sizeof(float) + (64 + (size_t)rb) * sizeof(float) + kStageBytesF32;
+  const size_t lds_h2 = (size_t)KS2 * 24 * 1024 + (64 + (size_t)rb) * sizeof(float) + kStageBytesF32;
+
+  // row 2
+  const size_t lds_h2_32 = (size_t)KS2 * 24 * 512 + (32 + (size_t)rb) * sizeof(float) + kStageBytesF32;
+  if (s.lean && KS2 > kH2MaxKS2 && KS2 <= 13 && k.h2 && (k.forced == 0 || k.forced == 16) && k.f32 != '0' && rb % 32 == 0 &&
+      lds_h2_32 <= kLdsLimit && h2_offsets_fit(KS2, s.Npad)) {
+    if (s.h2_model < 0) return needs_h2_model();
+    if (h2_scaled && (k.forced == 16 || any_band || band(bh) <= limit)) return split_half(32, lds_h2_32);
+  }
+  // row 3
+  const size_t lds_f32_32 = (size_t)A4 * 3 * 32 * sizeof(float) + (32 + (size_t)rb) * sizeof(float) + kStageBytesF32;
+  if (s.lean && lds_f32 > kLdsLimit && lds_f32_32 <= kLdsLimit && (k.forced == 0 || k.forced == 32) && k.f32 != '0' &&
+      rb % 32 == 0 && bf.p0 < 2.0e-3f && fits32 && std::isfinite(s.g_max) && (k.forced == 32 || any_band || band(bf) <= limit)) {
+    p.kind = 32, p.tc = 32, p.ks = A4 / 4, p.lds = lds_f32_32, p.bd = bf;
+    return p;
+  }
+  // row 4
+  const size_t lds_m = ((size_t)A4 * 3 * 64 + 64 + (size_t)rb) * sizeof(double) + kStageBytes;
+  const bool two_blocks = 2 * lds_m <= kLdsLimit;
+  const bool fp64_ok = fits32 && 96 * Npad < (1ull << 32) /* row operands by 32-bit byte offsets */ && lds_m <= kLdsLimit &&
+                       rb % (two_blocks ? 64 : 128) == 0;
+  const bool single_fits = fits32 && rb % 64 == 0 && (lds_f32 <= kLdsLimit || (KS2 <= kH2MaxKS2 && lds_h2 <= kLdsLimit));
+  if (!fp64_ok && !single_fits) return valu();
+  const char f32 = k.forced == 64 ? '0' : (k.forced == 32 || k.forced == 16) ? '2' : k.f32;  // a
+  const bool single = f32 != '0' && !(k.timeline && two_blocks) && rb % 64 == 0;              // b
+  if (!fp64_ok && !single) return valu();
+  bool use_h2 = false;  // c
+  if (single && k.h2 && k.forced != 32 && KS2 <= kH2MaxKS2 && h2_offsets_fit(KS2, s.Npad)) {
+    if (s.h2_model < 0) return needs_h2_model();
+    use_h2 = h2_scaled;
+  }
+  if (k.forced == 16 && !use_h2) return error(FC_E_INVALID);  // d
+  // (p0: 1.9e-3 at five, 2.2e-3 at six k-steps of the split-half kernel; the fp32 kernel reaches 2e-3 at ~370 atoms; its
+  // tile has room for the two-stage launch's row data)
+  const size_t lds_f32_two = (size_t)A4 * 3 * 64 * sizeof(float) + (64 + (size_t)rb) * sizeof(float) * 6 + kStageBytesF32;
+  KabschF32Bounds bd = use_h2 ? bh : bf;
+  bool use_single = single && bd.p0 < (use_h2 ? 2.5e-3f : 2.0e-3f) && (use_h2 || lds_f32_two <= kLdsLimit);
+  bool speculative = f32 == '3';
+  if (use_single && f32 != '2' && f32 != '3') {  // e
+    // Beyond `limit` the fp64 screen takes the launch at once.  (1.0 until round 4: 30 000 x 80 ensembles whose skeleton
+    // happened to be stretched -- radius of gyration 10.7 instead of 7.4 A: band 0.265 against 0.127 A^2 at a threshold of
+    // 0.25 -- fell off that edge and took 11.7 instead of 2.3 ms per prune although not one of their pairs lies in the band.
+    // Whether the band is POPULATED is what k_screen_verdict measures on the device; the bound only says how wide it is.)
+    // Narrow bands are not worth the verdict's ~10 us, nor are small ensembles (N <= 512: all their pairs fit the short
+    // candidate queue, whatever the band holds costs the refine less than the verdict and the gated launch).
+    const bool worth_verdict = (double)s.N * (double)s.N > 2.0 * (double)kRefineLanesMin;
+    use_single = band(bd) <= limit;
+    speculative = band(bd) > 0.1 * s.thr2 && worth_verdict;
+    // the split-half bound is about twice the fp32 kernel's (66 u per 32 atoms against one u per atom): where its band is
+    // too wide and the fp32 kernel's is not -- 160 stretched atoms -- the fp32 matrix pipe still beats the other screens
+    if (!use_single && use_h2 && k.forced != 16 && lds_f32_two <= kLdsLimit && bf.p0 < 2.0e-3f && band(bf) <= limit) {
+      use_h2 = false, bd = bf, use_single = true;
+      speculative = band(bf) > 0.1 * s.thr2 && worth_verdict;
+    }
+  }
+  if (!fp64_ok) {  // f
+    if (!use_single) return valu();
+    speculative = false;
+  }
+  if (use_single && use_h2) {  // g
+    if (lds_h2 > kLdsLimit) return error(FC_E_LIMIT);
+    split_half(64, lds_h2);
+  } else if (use_single) {
+    p.kind = 32, p.ks = A4 / 4, p.bd = bd;
+    p.two_stage = s.lean && !k.one_stage && A4 >= 16 && rb <= 256;
+    p.lds = (size_t)A4 * 3 * 64 * sizeof(float) + (64 + (size_t)rb) * sizeof(float) * (p.two_stage ? 6 : 1) + kStageBytesF32;
+  }
+  p.speculative = use_single && speculative;
+  if (!use_single || p.speculative) {  // h, and the gated launch behind a speculative one
+    if (!use_single) p.kind = 64, p.ks = A4 / 4;
+    p.fp64_waves = two_blocks ? 4 : 8;
+    p.lds64 = lds_m;
+    p.timeline = k.timeline && two_blocks;
+  }
+  return p;
+}
+
+static int screen_plan_error(const ScreenPlan &p, int64_t row_block) {
+  if (p.err == FC_E_INVALID)
+    return set_error(FC_E_INVALID, "fc_screen_select(16): the split-half screen does not apply to this ensemble");
+  if (p.err == FC_E_LIMIT)
+    return set_error(FC_E_LIMIT, "split-half screen: row block of %lld rows does not fit LDS", (long long)row_block);
+  return FC_OK;
+}
+
+// the work items of a matrix-pipe launch: (local row block, column tile) pairs, from the table where there is one
+struct ScreenItems {
+  unsigned long long n = 0;
+  const uint64_t *table = nullptr;
+};
+static int screen_items(fc_ensemble *e, int64_t n_lblocks, int tc, ScreenItems *it) {
+  const int64_t nt = e->Npad / tc;
+  FC_TRY(screen_item_table(e, nt, n_lblocks, /*halves=*/tc == 64, tc));
+  it->n = (unsigned long long)nt * (unsigned long long)n_lblocks;
+  if (e->item_total > 0) it->n = (unsigned long long)e->item_total, it->table = e->item_table.as<uint64_t>();
+  if (it->n >= (1ull << 31)) return set_error(FC_E_LIMIT, "too many screen items for one launch");
+  return FC_OK;
+}
+
+// the split-half kernel of KS2 k-steps: 64-column tile up to kH2MaxKS2 (with the bit matrix or lean), 32-column tile beyond
+// (lean only)
+using H2Screen = decltype(&k_simbits_screen_mfma_h2<1, true>);
+static H2Screen h2_screen_kernel(int64_t KS2, bool bits) {
+  switch (KS2) {
+    case 1: return bits ? k_simbits_screen_mfma_h2<1, true> : k_simbits_screen_mfma_h2<1, false>;
+    case 2: return bits ? k_simbits_screen_mfma_h2<2, true> : k_simbits_screen_mfma_h2<2, false>;
+    case 3: return bits ? k_simbits_screen_mfma_h2<3, true> : k_simbits_screen_mfma_h2<3, false>;
+    case 4: return bits ? k_simbits_screen_mfma_h2<4, true> : k_simbits_screen_mfma_h2<4, false>;
+    case 5: return bits ? k_simbits_screen_mfma_h2<5, true> : k_simbits_screen_mfma_h2<5, false>;
+    case 6: return bits ? k_simbits_screen_mfma_h2<6, true> : k_simbits_screen_mfma_h2<6, false>;
+    case 7: return k_simbits_screen_mfma_h2<7, false, 32>;
+    case 8: return k_simbits_screen_mfma_h2<8, false, 32>;
+    case 9: return k_simbits_screen_mfma_h2<9, false, 32>;
+    case 10: return k_simbits_screen_mfma_h2<10, false, 32>;
+    case 11: return k_simbits_screen_mfma_h2<11, false, 32>;
+    case 12: return k_simbits_screen_mfma_h2<12, false, 32>;
+    default: return k_simbits_screen_mfma_h2<13, false, 32>;
+  }
+}
+
+static int launch_h2_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblocks) {
+  ScreenItems it;
+  FC_TRY(screen_items(e, n_lblocks, p.tc, &it));
+  FC_TRY(make_h2_operands(e, p.scale));
+  const H2Screen fn = h2_screen_kernel(p.ks, !e->lean);
+  if (p.lds > 64 * 1024)
+    FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+  const double s2 = p.scale * p.scale;
+  const float tiny_floor = std::max(4.0f * p.hthr, (float)e->A);
+  uint64_t *bits = p.tc == 64 ? e->bits.as<uint64_t>() : nullptr;
+#ifdef FC_H2_TIMELINE
+  static DevBuf tlbuf;
+  const bool h2_timeline = p.tc == 64 && e->lean && getenv("FC_H2_TIMELINE_OUT") != nullptr;
+  if (h2_timeline) {
+    FC_TRY(tlbuf.reserve(it.n * 4 * sizeof(unsigned long long)));
+    FC_HIP_TRY(hipMemsetAsync(tlbuf.p, 0, it.n * 4 * sizeof(unsigned long long), ctx().stream));
+    bits = tlbuf.as<uint64_t>();
+  } else if (e->lean) {
+    bits = nullptr;
+  }
+#endif
+  hipLaunchKernelGGL(fn, dim3((unsigned)it.n), dim3(256), p.lds, ctx().stream, e->Xh.as<h8_t>(), e->G.as<double>(), e->N,
+                     e->Npad, p.hthr, tiny_floor, (float)s2, p.bd, (int)e->row_block, e->rank, e->world, bits, e->W,
+                     e->cand.as<uint32_t>(), reinterpret_cast<unsigned long long *>(e->counters.p), e->pairq.as<uint64_t>(),
+                     (unsigned long long)e->pairq_cap, it.table, it.n);
+#ifdef FC_H2_TIMELINE
+  if (h2_timeline) {
+    std::vector<unsigned long long> h(it.n * 4);
+    FC_HIP_TRY(hipMemcpyAsync(h.data(), tlbuf.p, it.n * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx().stream));
+    FC_HIP_TRY(hipStreamSynchronize(ctx().stream));
+    if (FILE *f = fopen(getenv("FC_H2_TIMELINE_OUT"), "wb")) {
+      fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
+      fclose(f);
+    }
+  }
+#endif
+  FC_TRY(check_launch("k_simbits_screen_mfma_h2"));
+  if (p.tc == 32) e->item_key[3] = -1;  // (the table holds 32-column items: the next launch of another screen rebuilds it)
+  return FC_OK;
+}
+
+static int launch_f32_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblocks, double A_thr2) {
+  ScreenItems it;
+  FC_TRY(screen_items(e, n_lblocks, p.tc, &it));
+  FC_TRY(make_f32_operands(e));
+  auto *cnt = reinterpret_cast<unsigned long long *>(e->counters.p);
+  if (p.tc == 32) {  // lean, single stage
+    const void *fn = reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false, false, 32>);
+    FC_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, false, false, 32>), dim3((unsigned)it.n), dim3(256), p.lds, ctx().stream,
+                       e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, p.bd, (int)e->row_block, e->rank,
+                       e->world, nullptr, e->W, e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
+                       (unsigned long long)e->pairq_cap, it.table, it.n, nullptr, p.bd, 0.f, nullptr, 0, 0);
+    FC_TRY(check_launch("k_simbits_screen_mfma_f32"));
+    e->item_key[3] = -1;  // (the table holds 32-column items: the next launch of another screen rebuilds it)
     return FC_OK;
   }
-  const double A_thr2 = (double)e->A * thr2_margin;
-  const size_t lds = (size_t)e->A * 3 * 64 * sizeof(double);
-  dim3 grid((unsigned)NT, (unsigned)n_lblocks);
-  // tuning / evidence knob: "mfma" (default), "valu8x4", "valu4x8"
-  const char *cfg = getenv("FC_SCREEN_CFG");
-  const bool want_valu = cfg && std::strncmp(cfg, "valu", 4) == 0;
-  const bool alt = cfg && std::strcmp(cfg, "valu4x8") == 0;
-  // Structures of 193 ... 416 atoms (the poses of two or three docked molecules, firecode/embedder.py:1472-1474): the
-  // split-half screen with a 32-column tile, lean launches only.  Until round 5 they went to the fp32 matrix pipe up to
-  // 213 atoms (2.4 x the time per pair) and to the fp64 vector screen beyond (8 x).  No speculative mode here (no fp64
-  // matrix-pipe screen stands behind it at these sizes): the band rule decides alone, as for 105 ... 192 atoms.
-  {
-    const int64_t KS2n = (e->A + 31) / 32;
-    static const int h2_env_n = [] {
-      const char *v = getenv("FC_SCREEN_H2");
-      return v ? atoi(v) : 1;
-    }();
-    const char *f32_env_n = getenv("FC_SCREEN_F32");
-    const size_t lds_n = (size_t)KS2n * 24 * 512 + (32 + (size_t)e->row_block) * sizeof(float) + kStageBytesF32;
-    if (!want_valu && e->lean && KS2n > kH2MaxKS2 && KS2n <= 13 && h2_env_n != 0 && (g_screen_forced == 0 || g_screen_forced == 16) &&
-        !(f32_env_n && f32_env_n[0] == '0') && e->row_block % 32 == 0 && lds_n <= kLdsLimit &&
-        (uint64_t)(24 * KS2n) * (uint64_t)e->Npad < (1ull << 32)) {
-      if (e->g_max < 0.0) {
-        auto *cnt_max = reinterpret_cast<unsigned long long *>(e->counters.p) + (kCounters - 1);
-        FC_HIP_TRY(hipMemsetAsync(cnt_max, 0, sizeof(unsigned long long), ctx().stream));
-        hipLaunchKernelGGL(k_max_nonneg, dim3((unsigned)std::min<int64_t>(ceil_div(e->Npad, 256), 256)), dim3(256), 0, ctx().stream,
-                           e->G.as<double>(), e->Npad, cnt_max);
-        FC_TRY(check_launch("k_max_nonneg"));
-        unsigned long long bits_max = 0;
-        FC_TRY(d2h(&bits_max, cnt_max, sizeof bits_max));
-        FC_TRY(sync());
-        FC_HIP_TRY(hipMemsetAsync(cnt_max, 0, sizeof(unsigned long long), ctx().stream));
-        std::memcpy(&e->g_max, &bits_max, sizeof(double));
-      }
-      bool model_ok = false;
-      FC_TRY(h2_model_ok(&model_ok));
-      double scale_n = 0.0;
-      if (model_ok) FC_TRY(ensure_h2_operands_upto(e, &scale_n, 13));
-      const KabschF32Bounds bdn = kabsch_h2_bounds(KS2n);
-      const double s2 = scale_n * scale_n;
-      const float hthr = (float)(0.5 * A_thr2 * s2);
-      static const double kBandMaxN = [] {
-        const char *v = getenv("FC_SCREEN_BAND_MAX");
-        const double x = v ? atof(v) : 4.0;
-        return x > 0.0 ? x : 4.0;
-      }();
-      const double band = (double)bdn.p0 * 2.0 * e->g_max / (double)e->A;
-      const bool band_ok = g_screen_forced == 16 || (f32_env_n && (f32_env_n[0] == '2' || f32_env_n[0] == '3')) || band <= kBandMaxN * thr2_margin;
-      if (scale_n > 0.0 && std::isfinite(hthr) && hthr > 0.f && band_ok) {
-        const int64_t NTn = e->Npad / 32;
-        FC_TRY(screen_item_table(e, NTn, n_lblocks, /*halves=*/false, 32));
-        unsigned long long n_items = (unsigned long long)NTn * (unsigned long long)n_lblocks;
-        const uint64_t *item_table_dev = nullptr;
-        if (e->item_total > 0) n_items = (unsigned long long)e->item_total, item_table_dev = e->item_table.as<uint64_t>();
-        if (n_items >= (1ull << 31)) return set_error(FC_E_LIMIT, "too many screen items for one launch");
-        auto *cnt = reinterpret_cast<unsigned long long *>(e->counters.p);
-        const float tiny_floor = std::max(4.0f * hthr, (float)e->A);
-#define FC_LAUNCH_H2N(KS2_)                                                                                                 \
-  do {                                                                                                                      \
-    const void *fn_ = reinterpret_cast<const void *>(k_simbits_screen_mfma_h2<KS2_, false, 32>);                            \
-    FC_HIP_TRY(hipFuncSetAttribute(fn_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_n));                           \
-    hipLaunchKernelGGL((k_simbits_screen_mfma_h2<KS2_, false, 32>), dim3((unsigned)n_items), dim3(256), lds_n, ctx().stream, \
-                       e->Xh.as<h8_t>(), e->G.as<double>(), e->N, e->Npad, hthr, tiny_floor, (float)s2, bdn, (int)e->row_block, \
-                       e->rank, e->world, nullptr, e->W, e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),              \
-                       (unsigned long long)e->pairq_cap, item_table_dev, n_items);                                          \
-  } while (0)
-        switch (KS2n) {
-          case 7: FC_LAUNCH_H2N(7); break;
-          case 8: FC_LAUNCH_H2N(8); break;
-          case 9: FC_LAUNCH_H2N(9); break;
-          case 10: FC_LAUNCH_H2N(10); break;
-          case 11: FC_LAUNCH_H2N(11); break;
-          case 12: FC_LAUNCH_H2N(12); break;
-          default: FC_LAUNCH_H2N(13); break;
-        }
-#undef FC_LAUNCH_H2N
-        FC_TRY(check_launch("k_simbits_screen_mfma_h2<narrow>"));
-        e->item_key[3] = -1;  // (the table holds 32-column items: the next launch of another screen rebuilds it)
-        g_last_screen = 16;
-        mark_main();
-        return FC_OK;
-      }
-    }
+  // Subset stage (lean prunes only).  Measured on one box, screen kernels alone on the chip:
+  // 10^4 x 50: 0.432 ms (subset stage 0.31 + per-unit kernel 0.10 + verdict and gated launches)
+  // against 0.462 ms single-stage; 3*10^4 x 80: 4.77 ms against 6.81 ms (two workgroups per CU there);
+  // continuous RMSD distribution (dense: the sample's verdict sends everything to the single-stage
+  // launch): 1.70 ms against 1.72 ms.  FC_SCREEN_STAGES=1: never; structures below four k-steps and
+  // row blocks above 256 rows (no room for their unit list in the staging area) take the single stage.
+  const bool two = p.two_stage;
+  const KabschF32Bounds bd = p.bd;
+  const size_t lds_f = p.lds;
+  const dim3 mgrid((unsigned)it.n);
+  const unsigned long long n_items = it.n;
+  const uint64_t *item_table_dev = it.table;
+  if (lds_f > 64 * 1024) {
+    FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
+    FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
+    FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
   }
-  // Structures whose band is too wide for the split-half bound (extended ones: radius of gyration beyond ~11-14 A at these
-  // sizes) and whose 64-column fp32 tile does not fit the LDS (214 atoms and more): the fp32 matrix-pipe kernel with a
-  // 32-column tile, lean single-stage launches, up to the size at which its own bound stops being small (p0 < 2e-3:
-  // ~370 atoms).  They went to the fp64 vector screen (8-12 ms per 7.2e7 pairs at 224 ... 384 atoms).
-  {
-    const int64_t A4n = (e->A + 3) / 4 * 4;
-    const char *f32_env_n = getenv("FC_SCREEN_F32");
-    const size_t lds_wide = (size_t)A4n * 3 * 64 * sizeof(float) + (64 + (size_t)e->row_block) * sizeof(float) + kStageBytesF32;
-    const size_t lds_n = (size_t)A4n * 3 * 32 * sizeof(float) + (32 + (size_t)e->row_block) * sizeof(float) + kStageBytesF32;
-    const KabschF32Bounds bfn = kabsch_f32_bounds(A4n);
-    if (!want_valu && e->lean && lds_wide > kLdsLimit && lds_n <= kLdsLimit && (g_screen_forced == 0 || g_screen_forced == 32) &&
-        !(f32_env_n && f32_env_n[0] == '0') && e->row_block % 32 == 0 && bfn.p0 < 2.0e-3f &&
-        (uint64_t)A4n * 3 * (uint64_t)e->Npad < (1ull << 32)) {
-      if (e->g_max < 0.0) {
-        auto *cnt_max = reinterpret_cast<unsigned long long *>(e->counters.p) + (kCounters - 1);
-        FC_HIP_TRY(hipMemsetAsync(cnt_max, 0, sizeof(unsigned long long), ctx().stream));
-        hipLaunchKernelGGL(k_max_nonneg, dim3((unsigned)std::min<int64_t>(ceil_div(e->Npad, 256), 256)), dim3(256), 0, ctx().stream,
-                           e->G.as<double>(), e->Npad, cnt_max);
-        FC_TRY(check_launch("k_max_nonneg"));
-        unsigned long long bits_max = 0;
-        FC_TRY(d2h(&bits_max, cnt_max, sizeof bits_max));
-        FC_TRY(sync());
-        FC_HIP_TRY(hipMemsetAsync(cnt_max, 0, sizeof(unsigned long long), ctx().stream));
-        std::memcpy(&e->g_max, &bits_max, sizeof(double));
-      }
-      static const double kBandMaxF = [] {
-        const char *v = getenv("FC_SCREEN_BAND_MAX");
-        const double x = v ? atof(v) : 4.0;
-        return x > 0.0 ? x : 4.0;
-      }();
-      const double band_f = (double)bfn.p0 * 2.0 * e->g_max / (double)e->A;
-      const bool band_ok = g_screen_forced == 32 || (f32_env_n && (f32_env_n[0] == '2' || f32_env_n[0] == '3')) || band_f <= kBandMaxF * thr2_margin;
-      if (band_ok && std::isfinite(e->g_max)) {
-        if (!e->xsf_valid) {
-          const int64_t n = A4n * 3 * e->Npad;
-          FC_TRY(e->Xsf.reserve((size_t)n * sizeof(float)));
-          hipLaunchKernelGGL(k_f64_to_f32, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx().stream, e->Xs.as<double>(), n,
-                             e->Xsf.as<float>());
-          FC_TRY(check_launch("k_f64_to_f32"));
-          FC_TRY(e->sub.reserve((size_t)e->Npad * 8 * sizeof(float)));
-          hipLaunchKernelGGL(k_subset_stats, dim3((unsigned)ceil_div(e->Npad, 256)), dim3(256), 0, ctx().stream, e->Xs.as<double>(),
-                             e->Npad, (int)e->A, e->sub.as<float>());
-          FC_TRY(check_launch("k_subset_stats"));
-          e->xsf_valid = true;
-        }
-        const int64_t NTn = e->Npad / 32;
-        FC_TRY(screen_item_table(e, NTn, n_lblocks, /*halves=*/false, 32));
-        unsigned long long n_items = (unsigned long long)NTn * (unsigned long long)n_lblocks;
-        const uint64_t *item_table_dev = nullptr;
-        if (e->item_total > 0) n_items = (unsigned long long)e->item_total, item_table_dev = e->item_table.as<uint64_t>();
-        if (n_items >= (1ull << 31)) return set_error(FC_E_LIMIT, "too many screen items for one launch");
-        auto *cnt = reinterpret_cast<unsigned long long *>(e->counters.p);
-        const void *fn_ = reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false, false, 32>);
-        FC_HIP_TRY(hipFuncSetAttribute(fn_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_n));
-        hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, false, false, 32>), dim3((unsigned)n_items), dim3(256), lds_n, ctx().stream,
-                           e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bfn, (int)e->row_block, e->rank,
-                           e->world, nullptr, e->W, e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
-                           (unsigned long long)e->pairq_cap, item_table_dev, n_items, nullptr, bfn, 0.f, nullptr, 0, 0);
-        FC_TRY(check_launch("k_simbits_screen_mfma_f32<narrow>"));
-        e->item_key[3] = -1;  // (the table holds 32-column items: the next launch of another screen rebuilds it)
-        g_last_screen = 32;
-        mark_main();
-        return FC_OK;
-      }
-    }
-  }
-  {
-    const size_t lds_m = ((size_t)((e->A + 3) / 4) * 4 * 3 * 64 + 64 + (size_t)e->row_block) * sizeof(double) + kStageBytes;
-    const bool fits32 = (uint64_t)((e->A + 3) / 4 * 4) * 3 * (uint64_t)e->Npad < (1ull << 32);
-    const bool two_blocks_fit = 2 * lds_m <= kLdsLimit;
-    // the fp64 matrix-pipe screen needs its column tile in LDS (up to ~100 atoms); the single-precision
-    // screens reach further (fp32 tile: half the bytes; split-half: 128 atoms) and then run without the
-    // fp64 screen behind them -- no speculative mode, and a band too wide for them means the VALU screen
-    const bool mfma64_ok = fits32 && 96 * (uint64_t)e->Npad < (1ull << 32) /* row operands by 32-bit byte offsets */ &&
-                           lds_m <= kLdsLimit && e->row_block % (two_blocks_fit ? 64 : 128) == 0;
-    const int64_t A4s = (e->A + 3) / 4 * 4, KS2s = (e->A + 31) / 32;
-    const bool single_ok = fits32 && e->row_block % 64 == 0 &&
-                           ((size_t)A4s * 3 * 64 * sizeof(float) + (64 + (size_t)e->row_block) * sizeof(float) + kStageBytesF32 <= kLdsLimit ||
-                            (KS2s <= kH2MaxKS2 && (size_t)KS2s * 24 * 1024 + (64 + (size_t)e->row_block) * sizeof(float) + kStageBytesF32 <= kLdsLimit));
-    bool done = true;  // false: the matrix-pipe path declined, the VALU screen below takes the launch
-    auto mfma_path = [&]() -> int {
-      auto *cnt = reinterpret_cast<unsigned long long *>(e->counters.p);
-      const bool two_blocks = 2 * lds_m <= kLdsLimit;
-      const void *fn = two_blocks ? reinterpret_cast<const void *>(k_simbits_screen_mfma<4>)
-                                  : reinterpret_cast<const void *>(k_simbits_screen_mfma<8>);
-      if (mfma64_ok && lds_m > 64 * 1024) {
-        hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
-        if (err != hipSuccess)
-          return set_error(FC_E_HIP, "hipFuncSetAttribute(LDS=%zu) failed: %s", lds_m,
-                           hipGetErrorString(err));
-      }
-      if (mfma64_ok && getenv("FC_DEBUG")) {
-        int nb = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, two_blocks ? 256 : 512, lds_m);
-        fprintf(stderr, "[fc] screen_mfma<%d>: LDS %zu B, occupancy API says %d blocks/CU\n",
-                two_blocks ? 4 : 8, lds_m, nb);
-      }
-      // one workgroup per item; world == 1: only the items that touch the upper triangle
-      unsigned long long n_items = (unsigned long long)NT * (unsigned long long)n_lblocks;
-      const uint64_t *item_table_dev = nullptr;
-      static int use_v2 = -1;
-      if (use_v2 < 0) {
-        const char *v = getenv("FC_SCREEN_V2");
-        use_v2 = (v && v[0] == '1') ? 1 : 0;
-      }
-      const bool want_v2 = use_v2 && mfma64_ok && two_blocks && e->row_block == 128;
-      FC_TRY(screen_item_table(e, NT, n_lblocks, /*halves=*/!want_v2));
-      if (e->item_total > 0) {
-        n_items = (unsigned long long)e->item_total;
-        item_table_dev = e->item_table.as<uint64_t>();
-      }
-      if (n_items >= (1ull << 31)) return set_error(FC_E_LIMIT, "too many screen items for one launch");
-      const dim3 mgrid((unsigned)n_items);
-      double *dbg = nullptr;
-      const unsigned long long *gate = nullptr;  // set behind a speculative fp32 screen
-#ifdef FC_TIMELINE
-      static DevBuf tlbuf;
-      const bool timeline = two_blocks && getenv("FC_TIMELINE_OUT") != nullptr;
-      if (timeline) {
-        FC_TRY(tlbuf.reserve(n_items * 4 * sizeof(unsigned long long)));
-        FC_HIP_TRY(hipMemsetAsync(tlbuf.p, 0, n_items * 4 * sizeof(unsigned long long), ctx().stream));
-        dbg = tlbuf.as<double>();
-      }
-#endif
-      if (want_v2 && e->item_total > 0 && dbg == nullptr) {
-        // row-sweep schedule: plain item list (no half items), one resident workgroup per CU
-        const size_t tile = (size_t)((e->A + 3) / 4) * 4 * 3 * 64 * sizeof(double);
-        const size_t lds2 = 2 * tile + (size_t)(2 * 64 + 128) * sizeof(double) + kStageBytes;
-        if (lds2 <= kLdsLimit) {
-          FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_screen_rowsweep),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-          const unsigned wgs = (unsigned)std::min<unsigned long long>((unsigned long long)ctx().n_cu,
-                                                                      (unsigned long long)e->item_total);
-          hipLaunchKernelGGL(k_screen_rowsweep, dim3(wgs), dim3(512), lds2, ctx().stream, e->Xs.as<double>(),
-                             e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, e->rank, e->world,
-                             e->bits.as<uint64_t>(), e->W, e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
-                             (unsigned long long)e->pairq_cap, e->item_table.as<uint64_t>(),
-                             (unsigned long long)e->item_total);
-          g_last_screen = 64;
-          mark_main();
-          return check_launch("k_screen_rowsweep");
-        }
-      }
-      // Default: the single-precision screen (fp32 MFMA + bounded fp32 polynomial; candidates are
-      // decided by the exact fp64 refine either way).  FC_SCREEN_F32=0, a timeline build's probe,
-      // or so many atoms that the proven bounds stop being small select the fp64 screen below.
-      const char *f32_env = g_screen_forced == 64 ? "0" : (g_screen_forced == 32 || g_screen_forced == 16) ? "2" : getenv("FC_SCREEN_F32");
-      const int64_t A4 = (e->A + 3) / 4 * 4;
-      auto ensure_gmax = [&]() -> int {
-        if (e->g_max >= 0.0) return FC_OK;
-        auto *cnt_max = reinterpret_cast<unsigned long long *>(e->counters.p) + (kCounters - 1);
-        FC_HIP_TRY(hipMemsetAsync(cnt_max, 0, sizeof(unsigned long long), ctx().stream));
-        hipLaunchKernelGGL(k_max_nonneg, dim3((unsigned)std::min<int64_t>(ceil_div(e->Npad, 256), 256)), dim3(256), 0,
-                           ctx().stream, e->G.as<double>(), e->Npad, cnt_max);
-        FC_TRY(check_launch("k_max_nonneg"));
-        unsigned long long bits_max = 0;
-        FC_TRY(d2h(&bits_max, cnt_max, sizeof bits_max));
-        FC_TRY(sync());
-        FC_HIP_TRY(hipMemsetAsync(cnt_max, 0, sizeof(unsigned long long), ctx().stream));
-        std::memcpy(&e->g_max, &bits_max, sizeof(double));
-        return FC_OK;
-      };
-      // The split-half kernel (f16 matrix pipe at single-precision accuracy) takes the place of the fp32-MFMA
-      // kernel where it applies: at most 128 atoms, a finite non-zero largest norm to take the scale from.
-      // FC_SCREEN_H2=0 / fc_screen_select(32): the fp32-MFMA kernel; fc_screen_select(16): this one whatever the band.
-      static const int h2_env = [] {
-        const char *v = getenv("FC_SCREEN_H2");
-        return v ? atoi(v) : 1;
-      }();
-      const int64_t KS2 = (e->A + 31) / 32;
-      bool use_h2 = false;
-      double h2_scale = 1.0;
-      const bool f32_allowed = !(f32_env && f32_env[0] == '0') && dbg == nullptr && e->row_block % 64 == 0;
-      if (!mfma64_ok && !f32_allowed) {
-        done = false;
-        return FC_OK;
-      }
-      if (f32_allowed && h2_env != 0 && g_screen_forced != 32 && KS2 <= kH2MaxKS2 &&
-          (uint64_t)(24 * KS2) * (uint64_t)e->Npad < (1ull << 32)) {
-        FC_TRY(ensure_gmax());
-        bool model_ok = false;
-        FC_TRY(h2_model_ok(&model_ok));  // this device's f16 matrix pipe behaves as kabsch_h2_bounds assumes (checked once)
-        if (model_ok) {
-          FC_TRY(ensure_h2_operands(e, &h2_scale));
-          const double s2 = h2_scale * h2_scale;
-          use_h2 = h2_scale > 0.0 && std::isfinite((float)(0.5 * A_thr2 * s2)) && (float)(0.5 * A_thr2 * s2) > 0.f;
-        }
-      }
-      KabschF32Bounds bd = use_h2 ? kabsch_h2_bounds(KS2) : kabsch_f32_bounds(A4);
-      const size_t lds_f32_tile = (size_t)A4 * 3 * 64 * sizeof(float) + (64 + (size_t)e->row_block) * sizeof(float) * 6 + kStageBytesF32;
-      // (p0: 1.9e-3 at five, 2.2e-3 at six k-steps of the split-half kernel; the fp32 kernel reaches 2e-3 at ~370 atoms)
-      bool use_f32 = f32_allowed && bd.p0 < (use_h2 ? 2.5e-3f : 2.0e-3f) && (use_h2 || lds_f32_tile <= kLdsLimit);
-      if (g_screen_forced == 16 && !use_h2) return set_error(FC_E_INVALID, "fc_screen_select(16): the split-half screen does not apply to this ensemble");
-      bool speculative = f32_env && f32_env[0] == '3';  // FC_SCREEN_F32=3: always with the verdict
-      if (use_f32 && !(f32_env && (f32_env[0] == '2' || f32_env[0] == '3'))) {  // FC_SCREEN_F32=2 / 3: no matter how wide the band
-        // Band of mean square deviations above the threshold that the bounded fp32 test cannot
-        // rule out: the factor (L - lambda_max)/s = A (msd - thr2) / (2 s) of P has to clear
-        // p0 / (product of the other three factors: 8 (f2+f3)(f1+f3)(f1+f2) for singular values
-        // f_i s of B, 1.3 for a chain, 2.4 for a ball; 1 assumed).  Large structures with a
-        // tight threshold make it wide -- many candidates for the exact refine -- so the fp64
-        // screen takes those at once; in between, k_screen_verdict decides on the device.
-        FC_TRY(ensure_gmax());
-        const double band = (double)bd.p0 * 2.0 * e->g_max / (double)e->A;
-        // Beyond kBandMax thresholds^2 the fp64 screen takes the launch at once.  (1.0 until round 4: 30 000 x 80 ensembles
-        // whose skeleton happened to be stretched -- radius of gyration 10.7 instead of 7.4 A: band 0.265 against 0.127 A^2
-        // at a threshold of 0.25 -- fell off that edge and took 11.7 instead of 2.3 ms per prune although not one of
-        // their pairs lies in the band.  Whether the band is POPULATED is what k_screen_verdict measures on the device;
-        // the bound only says how wide it is, and up to 4 thresholds^2 -- pairs below 2.2 x the rmsd threshold -- the
-        // speculative launch is the better bet: a verdict against it costs the split-half screen once, ~ 1/5 of the
-        // fp64 screen it then runs.)
-        static const double kBandMax = [] {
-          const char *v = getenv("FC_SCREEN_BAND_MAX");
-          const double x = v ? atof(v) : 4.0;
-          return x > 0.0 ? x : 4.0;
-        }();
-        use_f32 = band <= kBandMax * thr2_margin;
-        // narrow band: not worth the verdict's ~10 us.  Nor is a small ensemble (all its pairs fit the short candidate queue,
-        // N <= 512): whatever the band holds costs the exact refine less than the verdict and the gated launch behind it cost
-        // every call (9 of the 150-180 us of a drop-in prune at FIRECODE's own sizes)
-        const bool worth_verdict = (double)e->N * (double)e->N > 2.0 * (double)kRefineLanesMin;
-        speculative = band > 0.1 * thr2_margin && worth_verdict;
-        if (!use_f32 && use_h2 && g_screen_forced != 16 && lds_f32_tile <= kLdsLimit) {
-          // the split-half bound is about twice the fp32 kernel's (66 u per 32 atoms against one u per atom): where its band
-          // is too wide and the fp32 kernel's is not -- 160 stretched atoms -- the fp32 matrix pipe is still 2.5 x faster
-          // than the vector screen that would take the launch otherwise
-          const KabschF32Bounds bf = kabsch_f32_bounds(A4);
-          const double band_f = (double)bf.p0 * 2.0 * e->g_max / (double)e->A;
-          if (bf.p0 < 2.0e-3f && band_f <= kBandMax * thr2_margin) {
-            use_h2 = false;
-            bd = bf;
-            use_f32 = true;
-            speculative = band_f > 0.1 * thr2_margin && worth_verdict;
-          }
-        }
-      }
-      if (!mfma64_ok) {
-        if (!use_f32) {  // no fp64 matrix-pipe screen to fall back on at this size
-          done = false;
-          return FC_OK;
-        }
-        speculative = false;
-      }
-      if (use_f32 && use_h2) {
-        const size_t lds_h = (size_t)KS2 * 24 * 1024 + (64 + (size_t)e->row_block) * sizeof(float) + kStageBytesF32;
-        if (lds_h > kLdsLimit) return set_error(FC_E_LIMIT, "split-half screen: row block of %lld rows does not fit LDS", (long long)e->row_block);
-        const double s2 = h2_scale * h2_scale;
-        const float hthr = (float)(0.5 * A_thr2 * s2);
-        const float tiny_floor = std::max(4.0f * hthr, (float)e->A);
-#define FC_LAUNCH_H2(KS2_, BITS_)                                                                                       \
-  do {                                                                                                                  \
-    const void *fn_ = reinterpret_cast<const void *>(k_simbits_screen_mfma_h2<KS2_, BITS_>);                            \
-    if (lds_h > 64 * 1024) FC_HIP_TRY(hipFuncSetAttribute(fn_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h)); \
-    hipLaunchKernelGGL((k_simbits_screen_mfma_h2<KS2_, BITS_>), mgrid, dim3(256), lds_h, ctx().stream, e->Xh.as<h8_t>(), \
-                       e->G.as<double>(), e->N, e->Npad, hthr, tiny_floor, (float)s2, bd, (int)e->row_block, e->rank,   \
-                       e->world, e->bits.as<uint64_t>(), e->W, e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),    \
-                       (unsigned long long)e->pairq_cap, item_table_dev, n_items);                                      \
-  } while (0)
-#define FC_LAUNCH_H2_K(BITS_)                  \
-  switch (KS2) {                               \
-    case 1: FC_LAUNCH_H2(1, BITS_); break;     \
-    case 2: FC_LAUNCH_H2(2, BITS_); break;     \
-    case 3: FC_LAUNCH_H2(3, BITS_); break;     \
-    case 4: FC_LAUNCH_H2(4, BITS_); break;     \
-    case 5: FC_LAUNCH_H2(5, BITS_); break;     \
-    default: FC_LAUNCH_H2(6, BITS_); break;    \
-  }
-#ifdef FC_H2_TIMELINE
-        static DevBuf tlbuf;
-        const bool h2_timeline = e->lean && getenv("FC_H2_TIMELINE_OUT") != nullptr;
-        uint64_t *const bits_saved = e->bits.as<uint64_t>();
-        if (h2_timeline) {
-          FC_TRY(tlbuf.reserve(n_items * 4 * sizeof(unsigned long long)));
-          FC_HIP_TRY(hipMemsetAsync(tlbuf.p, 0, n_items * 4 * sizeof(unsigned long long), ctx().stream));
-          e->bits.p = tlbuf.p;
-        } else if (e->lean) {
-          e->bits.p = nullptr;
-        }
-#endif
-        if (e->lean) {
-          FC_LAUNCH_H2_K(false)
-        } else {
-          FC_LAUNCH_H2_K(true)
-        }
-#undef FC_LAUNCH_H2_K
-#undef FC_LAUNCH_H2
-#ifdef FC_H2_TIMELINE
-        e->bits.p = bits_saved;
-        if (h2_timeline) {
-          std::vector<unsigned long long> h(n_items * 4);
-          FC_HIP_TRY(hipMemcpyAsync(h.data(), tlbuf.p, n_items * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx().stream));
-          FC_HIP_TRY(hipStreamSynchronize(ctx().stream));
-          if (FILE *f = fopen(getenv("FC_H2_TIMELINE_OUT"), "wb")) {
-            fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
-            fclose(f);
-          }
-        }
-#endif
-        FC_TRY(check_launch("k_simbits_screen_mfma_h2"));
-        mark_main();
-        g_last_screen = 16;
-      } else if (use_f32) {
-        // Subset stage (lean prunes only).  Measured on one box, screen kernels alone on the chip:
-        // 10^4 x 50: 0.432 ms (subset stage 0.31 + per-unit kernel 0.10 + verdict and gated launches)
-        // against 0.462 ms single-stage; 3*10^4 x 80: 4.77 ms against 6.81 ms (two workgroups per CU there);
-        // continuous RMSD distribution (dense: the sample's verdict sends everything to the single-stage
-        // launch): 1.70 ms against 1.72 ms.  FC_SCREEN_STAGES=1: never; structures below four k-steps and
-        // row blocks above 256 rows (no room for their unit list in the staging area) take the single stage.
-        static const int stages_env = [] {
-          const char *v = getenv("FC_SCREEN_STAGES");
-          return v ? atoi(v) : 0;
-        }();
-        const bool two = e->lean && stages_env != 1 && A4 >= 16 && e->row_block <= 256;
-        const size_t lds_f = (size_t)A4 * 3 * 64 * sizeof(float) + (64 + (size_t)e->row_block) * sizeof(float) * (two ? 6 : 1) +
-                             kStageBytesF32;
-        if (!e->xsf_valid) {
-          const int64_t n = A4 * 3 * e->Npad;
-          FC_TRY(e->Xsf.reserve((size_t)n * sizeof(float)));
-          hipLaunchKernelGGL(k_f64_to_f32, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx().stream,
-                             e->Xs.as<double>(), n, e->Xsf.as<float>());
-          FC_TRY(check_launch("k_f64_to_f32"));
-          FC_TRY(e->sub.reserve((size_t)e->Npad * 8 * sizeof(float)));
-          hipLaunchKernelGGL(k_subset_stats, dim3((unsigned)ceil_div(e->Npad, 256)), dim3(256), 0, ctx().stream,
-                             e->Xs.as<double>(), e->Npad, (int)e->A, e->sub.as<float>());
-          FC_TRY(check_launch("k_subset_stats"));
-          e->xsf_valid = true;
-        }
-        if (lds_f > 64 * 1024) {
-          FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-          FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-          FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-        }
-        // stage 1 accumulates the even k-steps: A4_S atoms (padding included), A_S real ones; its bounds
-        // carry 8 u more per entry for the rank-one centring term (two rounded factors, 1/A_S, the fma)
-        const int64_t KS_all = A4 / 4, KS1 = (KS_all + 1) / 2;
-        int64_t A_S = 0;
-        for (int64_t a = 0; a < e->A; ++a) A_S += ((a >> 2) & 1) ? 0 : 1;
-        const KabschF32Bounds bd1 = kabsch_f32_bounds(4 * KS1 + 8);
-        const float inv_AS = (float)(1.0 / (double)std::max<int64_t>(A_S, 1));
-        const float *sub_dev = two ? e->sub.as<float>() : nullptr;
-        if (two) {
-          // subset stage over all units -> queue of the units it could not rule out -> the full test for
-          // those, one wavefront per unit; when more than ~a third of the units are queued (dense
-          // similarity) the per-unit kernel steps aside and the single-stage tiled kernel redoes the launch
-          const unsigned long long units_per_item = (unsigned long long)(e->row_block / 16) * 2ull;
-          FC_TRY(e->unitq.reserve((size_t)(n_items * units_per_item) * sizeof(uint64_t)));
-          const unsigned long long n_sample = (n_items + 15ull) / 16ull, n_rest = n_items - n_sample;
-          // "dense": more than a third of the sampled units could not be ruled out by the subset stage
-          const unsigned long long max_sample_units = n_sample * units_per_item / 3ull;
+  // stage 1 accumulates the even k-steps: A4_S atoms (padding included), A_S real ones; its bounds
+  // carry 8 u more per entry for the rank-one centring term (two rounded factors, 1/A_S, the fma)
+  const int64_t KS_all = p.ks, KS1 = (KS_all + 1) / 2;
+  int64_t A_S = 0;
+  for (int64_t a = 0; a < e->A; ++a) A_S += ((a >> 2) & 1) ? 0 : 1;
+  const KabschF32Bounds bd1 = kabsch_f32_bounds(4 * KS1 + 8);
+  const float inv_AS = (float)(1.0 / (double)std::max<int64_t>(A_S, 1));
+  const float *sub_dev = two ? e->sub.as<float>() : nullptr;
+  if (two) {
+    // subset stage over all units -> queue of the units it could not rule out -> the full test for
+    // those, one wavefront per unit; when more than ~a third of the units are queued (dense
+    // similarity) the per-unit kernel steps aside and the single-stage tiled kernel redoes the launch
+    const unsigned long long units_per_item = (unsigned long long)(e->row_block / 16) * 2ull;
+    FC_TRY(e->unitq.reserve((size_t)(n_items * units_per_item) * sizeof(uint64_t)));
+    const unsigned long long n_sample = (n_items + 15ull) / 16ull, n_rest = n_items - n_sample;
+    // "dense": more than a third of the sampled units could not be ruled out by the subset stage
+    const unsigned long long max_sample_units = n_sample * units_per_item / 3ull;
 #define FC_LAUNCH_F32_LEAN(GRID, SUB, PART, GATE, STAGED_)                                                            \
   hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, false, STAGED_>), dim3((unsigned)(GRID)), dim3(256), lds_f, ctx().stream, \
                      e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bd, (int)e->row_block,  \
                      e->rank, e->world, e->bits.as<uint64_t>(), e->W, e->cand.as<uint32_t>(), cnt,                    \
                      e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap, item_table_dev, n_items, SUB, bd1,    \
                      inv_AS, e->unitq.as<uint64_t>(), PART, GATE)
-          FC_LAUNCH_F32_LEAN(n_sample, sub_dev, 1, 0, true);
-          hipLaunchKernelGGL(k_screen_density_verdict, dim3(1), dim3(64), 0, ctx().stream, cnt, max_sample_units);
-          if (n_rest > 0) FC_LAUNCH_F32_LEAN(n_rest, sub_dev, 2, 1, true);
-          FC_TRY(check_launch("k_simbits_screen_mfma_f32<subset stage>"));
-          hipLaunchKernelGGL(k_screen_units_f32, dim3((unsigned)(ctx().n_cu * 3)), dim3(256), 0, ctx().stream,
-                             e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bd,
-                             e->unitq.as<uint64_t>(), cnt, e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap);
-          FC_TRY(check_launch("k_screen_units_f32"));
-          FC_LAUNCH_F32_LEAN(n_items, nullptr, 0, 2, false);
+    FC_LAUNCH_F32_LEAN(n_sample, sub_dev, 1, 0, true);
+    hipLaunchKernelGGL(k_screen_density_verdict, dim3(1), dim3(64), 0, ctx().stream, cnt, max_sample_units);
+    if (n_rest > 0) FC_LAUNCH_F32_LEAN(n_rest, sub_dev, 2, 1, true);
+    FC_TRY(check_launch("k_simbits_screen_mfma_f32<subset stage>"));
+    hipLaunchKernelGGL(k_screen_units_f32, dim3((unsigned)(ctx().n_cu * 3)), dim3(256), 0, ctx().stream,
+                       e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bd,
+                       e->unitq.as<uint64_t>(), cnt, e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap);
+    FC_TRY(check_launch("k_screen_units_f32"));
+    FC_LAUNCH_F32_LEAN(n_items, nullptr, 0, 2, false);
 #undef FC_LAUNCH_F32_LEAN
-        } else if (e->lean)
-          hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, false>), mgrid, dim3(256), lds_f, ctx().stream,
-                             e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bd,
-                             (int)e->row_block, e->rank, e->world, e->bits.as<uint64_t>(), e->W,
-                             e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
-                             (unsigned long long)e->pairq_cap, item_table_dev, n_items, nullptr, bd1, inv_AS, nullptr, 0, 0);
-        else
-          hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, true>), mgrid, dim3(256), lds_f, ctx().stream,
-                             e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bd,
-                             (int)e->row_block, e->rank, e->world, e->bits.as<uint64_t>(), e->W,
-                             e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
-                             (unsigned long long)e->pairq_cap, item_table_dev, n_items, nullptr, bd1, inv_AS, nullptr, 0, 0);
-        FC_TRY(check_launch("k_simbits_screen_mfma_f32"));
-        mark_main();
-        g_last_screen = 32;
-      }
-      if (use_f32) {
-        if (!speculative) return FC_OK;
-        // speculative: the verdict kernel decides on the device whether the fp64 screen below
-        // has to redo the launch (k_screen_verdict); its workgroups return at once otherwise
-        const double owned_pairs = 0.5 * (double)e->N * (double)e->N / (double)e->world;
-        // a false candidate costs ~1 ns (staging, one atom pass of the refine: tools/broad_probe.py), a second
-        // screen in fp64 ~0.017 ns per owned pair at 52 padded atoms and in proportion to them beyond
-        const auto max_false = (unsigned long long)std::max(1024.0, 0.015 * ((double)A4 / 52.0) * owned_pairs);
-        hipLaunchKernelGGL(k_screen_verdict, dim3(4), dim3(256), 0, ctx().stream, e->Xa.as<double>(),
-                           e->G.as<double>(), (int)e->A, A_thr2, e->pairq.as<uint64_t>(),
-                           (unsigned long long)e->pairq_cap, max_false, cnt, ctx().optimistic_screen ? 1 : 0);
-        FC_TRY(check_launch("k_screen_verdict"));
-        if (ctx().optimistic_screen) return FC_OK;
-        gate = cnt + 11;
-      }
-      if (two_blocks)
-        hipLaunchKernelGGL(k_simbits_screen_mfma<4>, mgrid, dim3(256), lds_m, ctx().stream,
-                           e->Xs.as<double>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2,
-                           (int)e->row_block, e->rank, e->world, e->bits.as<uint64_t>(), e->W,
-                           e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
-                           (unsigned long long)e->pairq_cap, item_table_dev, n_items, dbg, gate);
-      else
-        hipLaunchKernelGGL(k_simbits_screen_mfma<8>, mgrid, dim3(512), lds_m, ctx().stream,
-                           e->Xs.as<double>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2,
-                           (int)e->row_block, e->rank, e->world, e->bits.as<uint64_t>(), e->W,
-                           e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
-                           (unsigned long long)e->pairq_cap, item_table_dev, n_items, dbg, gate);
-      if (gate == nullptr) g_last_screen = 64;
-      FC_TRY(check_launch("k_simbits_screen_mfma"));
-      mark_main();
+  } else if (e->lean)
+    hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, false>), mgrid, dim3(256), lds_f, ctx().stream,
+                       e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bd,
+                       (int)e->row_block, e->rank, e->world, e->bits.as<uint64_t>(), e->W,
+                       e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
+                       (unsigned long long)e->pairq_cap, item_table_dev, n_items, nullptr, bd1, inv_AS, nullptr, 0, 0);
+  else
+    hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, true>), mgrid, dim3(256), lds_f, ctx().stream,
+                       e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bd,
+                       (int)e->row_block, e->rank, e->world, e->bits.as<uint64_t>(), e->W,
+                       e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
+                       (unsigned long long)e->pairq_cap, item_table_dev, n_items, nullptr, bd1, inv_AS, nullptr, 0, 0);
+  return check_launch("k_simbits_screen_mfma_f32");
+}
+
+// gate: behind a speculative screen, the verdict's word (the workgroups return at once unless it says "redo")
+static int launch_fp64_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblocks, double A_thr2,
+                              const unsigned long long *gate) {
+  const auto fn = p.fp64_waves == 4 ? k_simbits_screen_mfma<4> : k_simbits_screen_mfma<8>;
+  const int threads = 64 * p.fp64_waves;
+  if (p.lds64 > 64 * 1024) {
+    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)p.lds64);
+    if (err != hipSuccess)
+      return set_error(FC_E_HIP, "hipFuncSetAttribute(LDS=%zu) failed: %s", p.lds64, hipGetErrorString(err));
+  }
+  if (getenv("FC_DEBUG")) {
+    int nb = -1;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(fn), threads, p.lds64);
+    fprintf(stderr, "[fc] screen_mfma<%d>: LDS %zu B, occupancy API says %d blocks/CU\n", p.fp64_waves, p.lds64, nb);
+  }
+  // one workgroup per item; world == 1: only the items that touch the upper triangle
+  ScreenItems it;
+  FC_TRY(screen_items(e, n_lblocks, 64, &it));
+  double *dbg = nullptr;
 #ifdef FC_TIMELINE
-      if (timeline) {
-        std::vector<unsigned long long> h(n_items * 4);
-        FC_HIP_TRY(hipMemcpyAsync(h.data(), tlbuf.p, n_items * 4 * sizeof(unsigned long long),
-                                  hipMemcpyDeviceToHost, ctx().stream));
-        FC_HIP_TRY(hipStreamSynchronize(ctx().stream));
-        if (FILE *f = fopen(getenv("FC_TIMELINE_OUT"), "wb")) {
-          fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
-          fclose(f);
-        }
-      }
+  static DevBuf tlbuf;
+  if (p.timeline) {
+    FC_TRY(tlbuf.reserve(it.n * 4 * sizeof(unsigned long long)));
+    FC_HIP_TRY(hipMemsetAsync(tlbuf.p, 0, it.n * 4 * sizeof(unsigned long long), ctx().stream));
+    dbg = tlbuf.as<double>();
+  }
 #endif
-      return FC_OK;
-    };
-    if (!want_valu && (mfma64_ok || single_ok)) {
-      FC_TRY(mfma_path());
-      if (done) return FC_OK;
+  hipLaunchKernelGGL(fn, dim3((unsigned)it.n), dim3(threads), p.lds64, ctx().stream, e->Xs.as<double>(), e->G.as<double>(), e->N,
+                     e->Npad, (int)e->A, A_thr2, (int)e->row_block, e->rank, e->world, e->bits.as<uint64_t>(), e->W,
+                     e->cand.as<uint32_t>(), reinterpret_cast<unsigned long long *>(e->counters.p), e->pairq.as<uint64_t>(),
+                     (unsigned long long)e->pairq_cap, it.table, it.n, dbg, gate, nullptr);
+  FC_TRY(check_launch("k_simbits_screen_mfma"));
+#ifdef FC_TIMELINE
+  if (p.timeline) {
+    std::vector<unsigned long long> h(it.n * 4);
+    FC_HIP_TRY(hipMemcpyAsync(h.data(), tlbuf.p, it.n * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx().stream));
+    FC_HIP_TRY(hipStreamSynchronize(ctx().stream));
+    if (FILE *f = fopen(getenv("FC_TIMELINE_OUT"), "wb")) {
+      fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
+      fclose(f);
     }
   }
-#define FC_LAUNCH_SCREEN(LDSFLAG, TI_, NW_, SMEM)                                                   \
-  hipLaunchKernelGGL((k_simbits_screen<LDSFLAG, TI_, NW_>), grid, dim3(NW_ * 64), SMEM,            \
-                     ctx().stream, e->Xs.as<double>(), e->G.as<double>(), e->N, e->Npad,           \
-                     (int)e->A, A_thr2, (int)e->row_block, e->rank, e->world,                      \
-                     e->bits.as<uint64_t>(), e->W, e->cand.as<uint32_t>(),                         \
-                     reinterpret_cast<unsigned long long *>(e->counters.p),                        \
-                     e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap)
-  if (lds <= kLdsLimit) {
-    const void *fn = alt ? reinterpret_cast<const void *>(k_simbits_screen<true, 4, 8>)
-                         : reinterpret_cast<const void *>(k_simbits_screen<true, 8, 4>);
-    if (lds > 64 * 1024) {
-      hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (err != hipSuccess)
-        return set_error(FC_E_HIP, "hipFuncSetAttribute(LDS=%zu) failed: %s", lds,
-                         hipGetErrorString(err));
-    }
-    if (alt) FC_LAUNCH_SCREEN(true, 4, 8, lds);
-    else FC_LAUNCH_SCREEN(true, 8, 4, lds);
-  } else {
-    if (alt) FC_LAUNCH_SCREEN(false, 4, 8, 0);
-    else FC_LAUNCH_SCREEN(false, 8, 4, 0);
+#endif
+  return FC_OK;
+}
+
+static int launch_valu_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblocks, double A_thr2) {
+  const auto fn = p.valu_lds ? k_simbits_screen<true, 8, 4> : k_simbits_screen<false, 8, 4>;
+  if (p.lds > 64 * 1024) {
+    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    if (err != hipSuccess)
+      return set_error(FC_E_HIP, "hipFuncSetAttribute(LDS=%zu) failed: %s", p.lds, hipGetErrorString(err));
   }
-#undef FC_LAUNCH_SCREEN
-  g_last_screen = 1;
-  mark_main();
+  hipLaunchKernelGGL(fn, dim3((unsigned)(e->Npad >> 6), (unsigned)n_lblocks), dim3(256), p.lds, ctx().stream, e->Xs.as<double>(),
+                     e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, (int)e->row_block, e->rank, e->world,
+                     e->bits.as<uint64_t>(), e->W, e->cand.as<uint32_t>(), reinterpret_cast<unsigned long long *>(e->counters.p),
+                     e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap);
   return check_launch("k_simbits_screen");
+}
+
+// plan_screen's choice, then the operands of that screen alone and its launch
+int launch_simbits_screen(fc_ensemble *e, double thr2_margin) {
+  // Context::mark_after_screen: recorded once, right behind the main screen kernel of this launch
+  auto mark_main = []() {
+    if (ctx().mark_after_screen) (void)hipEventRecord(ctx().mark_after_screen, ctx().stream);
+    if (ctx().after_main_stream && ctx().after_main_event) {  // the rest of this launch: on the caller's other stream
+      (void)hipEventRecord(ctx().after_main_event, ctx().stream);
+      (void)hipStreamWaitEvent(ctx().after_main_stream, ctx().after_main_event, 0);
+      ctx().stream = ctx().after_main_stream;
+    }
+  };
+  // (every ensemble comes with its largest G from its build; NaN: the single-precision screens decline)
+  if (e->g_max < 0.0) return set_error(FC_E_INVALID, "internal: the screen of an ensemble whose largest G was never set");
+  const int64_t n_lblocks = local_block_count(ceil_div(e->N, e->row_block), e->rank, e->world);
+  ScreenShape s{e->N, e->Npad, e->A, e->row_block, n_lblocks, e->lean, e->g_max, thr2_margin, -1};
+  const ScreenKnobs knobs = screen_knobs();
+  ScreenPlan p = plan_screen(s, knobs);
+  if (p.needs_h2_model) {  // this device's f16 matrix pipe behaves as kabsch_h2_bounds assumes (checked once per process)
+    bool ok = false;
+    FC_TRY(h2_model_ok(&ok));
+    s.h2_model = ok ? 1 : 0;
+    p = plan_screen(s, knobs);
+  }
+  FC_TRY(screen_plan_error(p, e->row_block));
+  if (p.kind == 0) {
+    mark_main();
+    return FC_OK;
+  }
+  const double A_thr2 = (double)e->A * thr2_margin;
+  switch (p.kind) {
+    case 16: FC_TRY(launch_h2_screen(e, p, n_lblocks)); break;
+    case 32: FC_TRY(launch_f32_screen(e, p, n_lblocks, A_thr2)); break;
+    case 64: FC_TRY(launch_fp64_screen(e, p, n_lblocks, A_thr2, nullptr)); break;
+    default: FC_TRY(launch_valu_screen(e, p, n_lblocks, A_thr2));
+  }
+  g_last_screen = p.kind;
+  mark_main();
+  if (!p.speculative) return FC_OK;
+  // speculative: the verdict kernel decides on the device whether the fp64 screen behind it has to redo the launch
+  // (k_screen_verdict); its workgroups return at once otherwise
+  auto *cnt = reinterpret_cast<unsigned long long *>(e->counters.p);
+  const double owned_pairs = 0.5 * (double)e->N * (double)e->N / (double)e->world;
+  // a false candidate costs ~1 ns (staging, one atom pass of the refine: tools/broad_probe.py), a second
+  // screen in fp64 ~0.017 ns per owned pair at 52 padded atoms and in proportion to them beyond
+  const auto max_false = (unsigned long long)std::max(1024.0, 0.015 * ((double)((e->A + 3) / 4 * 4) / 52.0) * owned_pairs);
+  hipLaunchKernelGGL(k_screen_verdict, dim3(4), dim3(256), 0, ctx().stream, e->Xa.as<double>(), e->G.as<double>(), (int)e->A,
+                     A_thr2, e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap, max_false, cnt,
+                     ctx().optimistic_screen ? 1 : 0);
+  FC_TRY(check_launch("k_screen_verdict"));
+  if (ctx().optimistic_screen) return FC_OK;  // (the caller redoes a prune the verdict voted down)
+  return launch_fp64_screen(e, p, n_lblocks, A_thr2, cnt + 11);
+}
+
+int debug_screen_plan(int64_t N, int64_t A, int64_t row_block, bool lean, double g_max, double max_rmsd, int h2_model,
+                      int64_t plan_out[5]) {
+  const ScreenShape s{N, ceil_div(std::max<int64_t>(N, 1), 64) * 64, A, row_block, ceil_div(N, row_block), lean, g_max,
+                      max_rmsd * max_rmsd + kScreenMargin, h2_model};
+  const ScreenPlan p = plan_screen(s, screen_knobs());
+  plan_out[0] = p.kind;
+  plan_out[1] = p.kind ? p.tc : 0;
+  plan_out[2] = p.kind ? (p.two_stage ? 2 : 1) : 0;
+  plan_out[3] = p.speculative ? 1 : 0;
+  plan_out[4] = p.fp64_waves;
+  return screen_plan_error(p, row_block);
 }
 
 int launch_simbits_refine(fc_ensemble *e, double max_rmsd, double max_dev, const double *energies_dev,

@@ -575,6 +575,15 @@ int fc_screen_last_kind(void);
  * 64 = the fp64 screen (the reference's arithmetic in every kernel of the step).  Process-wide;
  * results never depend on it. */
 int fc_screen_select(int kind);
+/* Which screen a prune of this shape would launch, without a device: the rule of launch_simbits_screen (fc_kabsch.hip,
+ * plan_screen) on N conformers of A selected atoms, one rank, the given row block, lean (1: the pair lists only) or not,
+ * largest G g_max (sum of squares of a centred conformer; NaN: the single-precision screens decline) and threshold
+ * max_rmsd, with the f16 matrix-pipe model check taken as h2_model_ok (0 / 1), and FC_SCREEN_* and fc_screen_select read
+ * as a prune reads them.  plan_out[0..4] = kind (as fc_screen_last_kind; 0: no screen), column tile, stages (2: the
+ * two-stage fp32 launch), speculative (1: verdict and gated fp64 screen behind it), fp64 waves (4 / 8 where the fp64
+ * screen runs, 0 otherwise).  Returns the error the prune would return (FC_E_INVALID / FC_E_LIMIT) or FC_OK. */
+int fc_debug_screen_plan(int64_t N, int64_t A, int64_t row_block, int64_t lean, double g_max, double max_rmsd,
+                         int64_t h2_model_ok, int64_t plan_out[5]);
 /* Checks of what the split-half screen (kind 16) assumes, for the tests -- no FIRECODE call maps to them.
  * fc_debug_mfma_f16_model: runs the model check of v_mfma_f32_16x16x32_f16 the library runs itself before it
  * uses that screen: flags_out[0..7] = 1 where the pattern behaves as assumed (subnormal inputs honoured, one

@@ -1481,7 +1481,7 @@ def test_prune_large_extended_structures_on_the_fp32_pipe(fc, n, a, seed):
     assert np.array_equal(m3.astype(bool), ref) and int(st[2]) == int(np.triu(S0, 1).sum())
 
 
-@pytest.mark.parametrize("cfg", ["valu8x4", "valu4x8"])
+@pytest.mark.parametrize("cfg", ["valu8x4"])
 def test_valu_screen_kernels_still_agree(fc, cfg, monkeypatch):
     monkeypatch.setenv("FC_SCREEN_CFG", cfg)
     X, atoms, _ = syn.synthetic_ensemble(500, 33, seed=97)
