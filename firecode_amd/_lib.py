@@ -91,6 +91,7 @@ _SIGNATURES = {
                                _f64, _f64, _p_f64, _f64, _i64, _p_u8, _p_u64],
     "fc_align_by_moi": [_p_f64, _i64, _i64, _p_f64, _p_f64],
     "fc_prune_moi": [_p_f64, _i64, _i64, _p_f64, _f64, _p_f64, _f64, _i64, _p_u8],
+    "fc_moi_simbits": [_p_f64, _i64, _i64, _p_f64, _f64, _p_f64, _f64, _p_u64],
     "fc_align_to_first": [_p_f64, _i64, _i64, _p_i64, _i64, _p_f64],
     "fc_rototranslate": [_p_f64, _i64, _i64, _p_f64, _p_f64, _p_f64],
     "fc_clash_self": [_p_f64, _i64, _i64, _f64, _f64, _p_i64],

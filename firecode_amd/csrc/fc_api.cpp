@@ -1862,6 +1862,30 @@ int fc_prune_moi(const double *coords, int64_t N, int64_t A, const double *masse
   return ladder_single(&e, e.bits.as<uint64_t>(), min_per_group, mask_out, nullptr, nullptr);
 }
 
+// the similarity bits the MOI ladder replays, for callers (and tests) that want the matrix itself
+int fc_moi_simbits(const double *coords, int64_t N, int64_t A, const double *masses, double max_deviation,
+                   const double *energies, double max_dE, uint64_t *bits_out) {
+  FC_API_LOCK;
+  FC_REQUIRE(N >= 0 && A >= 1, "bad shape");
+  if (N == 0) return FC_OK;
+  FC_REQUIRE(coords && masses && bits_out, "NULL pointer argument");
+  FC_TRY(ensure_init());
+  const int64_t W = ceil_div(N, 64);
+  DevBuf dc, dm, dmom, den, dbits;
+  FC_TRY(upload(dc, coords, (size_t)N * A * 3));
+  FC_TRY(upload(dm, masses, (size_t)A));
+  FC_TRY(dmom.reserve((size_t)N * 3 * sizeof(double)));
+  if (energies) FC_TRY(upload(den, energies, (size_t)N));
+  const size_t bytes = (size_t)N * W * sizeof(uint64_t);
+  FC_TRY(dbits.reserve(bytes));
+  FC_HIP_TRY(hipMemsetAsync(dbits.p, 0, bytes, ctx().stream));  // the kernel skips the words left of the diagonal
+  FC_TRY(launch_inertia_moments(dc.as<double>(), N, A, dm.as<double>(), dmom.as<double>()));
+  FC_TRY(launch_moi_simbits(dmom.as<double>(), N, max_deviation, energies ? den.as<double>() : nullptr, max_dE,
+                            dbits.as<uint64_t>(), W));
+  FC_TRY(d2h(bits_out, dbits.p, bytes));
+  return sync();
+}
+
 // ---- the similarity stages of the drivers on ONE upload --------------------------
 // firecode/ensemble.py:205-235 and embedder.py:1445-1474 run prune_by_moment_of_inertia, apply its mask,
 // then prune_by_rmsd on the survivors; each call of the reference re-reads host arrays.  Here the
@@ -1967,6 +1991,10 @@ int fc_prune_rmsd_rot_corr(const double *coords, int64_t N, int64_t A, const uin
     FC_REQUIRE(n_angles[t] >= 1 && n_angles[t] <= max_angles, "torsion %lld: bad angle count", (long long)t);
   }
   if ((size_t)4 * A * 24 > 160 * 1024) return set_error(FC_E_LIMIT, "A=%lld too large for the LDS slice", (long long)A);
+  // k_rotcorr_simbits has the row in blockIdx.y, whose extent is 65 535 on every HIP device
+  if (N > FC_ROTCORR_MAX_ROWS)
+    return set_error(FC_E_LIMIT, "N=%lld exceeds FC_ROTCORR_MAX_ROWS=%d structures: thin the ensemble with the MOI / RMSD stages first",
+                     (long long)N, FC_ROTCORR_MAX_ROWS);
   FC_TRY(ensure_init());
   fc_ensemble e;
   e.N = N;

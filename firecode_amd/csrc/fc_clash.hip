@@ -308,8 +308,9 @@ int launch_clash_self(const double *coords_dev, int64_t N, int64_t A, double lo,
   if (N == 0) return FC_OK;
   const double lo2 = sq_threshold_le(lo);
   const double hi2 = sq_threshold_lt(hi);
-  hipLaunchKernelGGL(k_clash_self, dim3((unsigned)N), dim3(64), (size_t)A * 3 * sizeof(double),
-                     ctx().stream, coords_dev, N, (int)A, lo2, hi2, counts_dev);
+  const size_t lds = (size_t)A * 3 * sizeof(double);
+  FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_clash_self), lds, "k_clash_self"));
+  hipLaunchKernelGGL(k_clash_self, dim3((unsigned)N), dim3(64), lds, ctx().stream, coords_dev, N, (int)A, lo2, hi2, counts_dev);
   return check_launch("k_clash_self");
 }
 
@@ -318,8 +319,9 @@ int launch_clash_fragments(const double *coords_dev, int64_t N, int64_t A, const
                            uint8_t *pass_dev) {
   if (N == 0) return FC_OK;
   const double thr2 = (n_ids == 2) ? sq_threshold_lt(thresh) : sq_threshold_le(thresh);
-  hipLaunchKernelGGL(k_clash_fragments, dim3((unsigned)N), dim3(64),
-                     (size_t)A * 3 * sizeof(double), ctx().stream, coords_dev, N, (int)A,
+  const size_t lds = (size_t)A * 3 * sizeof(double);
+  FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_clash_fragments), lds, "k_clash_fragments"));
+  hipLaunchKernelGGL(k_clash_fragments, dim3((unsigned)N), dim3(64), lds, ctx().stream, coords_dev, N, (int)A,
                      (int)ids[0], (int)ids[1], n_ids == 3 ? (int)ids[2] : 0, (int)n_ids, thr2,
                      max_clashes, counts_dev, pass_dev);
   return check_launch("k_clash_fragments");
@@ -328,8 +330,9 @@ int launch_clash_fragments(const double *coords_dev, int64_t N, int64_t A, const
 int launch_clash_graph(const double *coords_dev, int64_t N, int64_t A, const uint8_t *adj_dev,
                        double thresh, int64_t *counts_dev) {
   if (N == 0) return FC_OK;
-  hipLaunchKernelGGL(k_clash_graph, dim3((unsigned)N), dim3(64), (size_t)A * 3 * sizeof(double),
-                     ctx().stream, coords_dev, N, (int)A, adj_dev, sq_threshold_lt(thresh), counts_dev);
+  const size_t lds = (size_t)A * 3 * sizeof(double);
+  FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_clash_graph), lds, "k_clash_graph"));
+  hipLaunchKernelGGL(k_clash_graph, dim3((unsigned)N), dim3(64), lds, ctx().stream, coords_dev, N, (int)A, adj_dev, sq_threshold_lt(thresh), counts_dev);
   return check_launch("k_clash_graph");
 }
 
@@ -379,8 +382,9 @@ int launch_embed_poses_clash(const double *m1_dev, int64_t A1, const double *m2_
   int64_t blocks = ceil_div(P, 4);
   const int64_t cap = (int64_t)ctx().n_cu * 32;  // persistent-style grid, waves stride over poses
   if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(k_embed_poses_clash, dim3((unsigned)blocks), dim3(256),
-                     (size_t)4 * A1 * 3 * sizeof(double), ctx().stream, m1_dev, (int)A1, m2_dev,
+  const size_t lds = (size_t)4 * A1 * 3 * sizeof(double);
+  FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_embed_poses_clash), lds, "k_embed_poses_clash"));
+  hipLaunchKernelGGL(k_embed_poses_clash, dim3((unsigned)blocks), dim3(256), lds, ctx().stream, m1_dev, (int)A1, m2_dev,
                      (int)A2, c1_dev, c2_dev, R1_dev, t1_dev, R2_dev, t2_dev, P, thr2, max_clashes,
                      counts_dev, pass_dev, poses_dev);
   return check_launch("k_embed_poses_clash");

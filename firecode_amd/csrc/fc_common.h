@@ -284,7 +284,20 @@ inline int check_launch(const char *what) {
   return FC_OK;
 }
 
+// A launch with more than 64 KiB of dynamic LDS needs the function attribute raised first (gfx950 has 160 KiB per
+// workgroup).  The attribute is set for the size of the call at hand, so a refusal names the size that was asked for.
+inline int allow_dynamic_lds(const void *kernel, size_t bytes, const char *what) {
+  if (bytes <= ((size_t)64 << 10)) return FC_OK;
+  hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess)
+    return set_error(FC_E_HIP, "hipFuncSetAttribute(%s, LDS=%zu) failed: %s", what, bytes, hipGetErrorString(e));
+  return FC_OK;
+}
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// One grid dimension takes fewer than 2^32 threads; a launch that asks for more is not refused by the runtime, it runs
+// a truncated grid and leaves the rest of the output unwritten.  Launchers whose grid grows with N^2 check first.
+inline bool grid_x_fits(int64_t blocks, int64_t threads_per_block) { return blocks * threads_per_block < ((int64_t)1 << 32); }
 
 // A^2 added to max_rmsd^2 in the all-pairs screens (and in the refine's own early exit)
 constexpr double kScreenMargin = 1e-6;

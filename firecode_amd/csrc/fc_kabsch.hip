@@ -3341,6 +3341,8 @@ int launch_pairs_exact(const fc_ensemble *e, const int64_t *pi_dev, const int64_
 int launch_matrix_exact(const fc_ensemble *e, double *rmsd_dev, double *maxdev_dev) {
   const int64_t waves = e->N * (e->Npad >> 6);
   if (waves == 0) return FC_OK;
+  if (!grid_x_fits(ceil_div(waves, 4), 256))
+    return set_error(FC_E_LIMIT, "N=%lld structures exceed one launch of the all-pairs matrix kernel", (long long)e->N);
   hipLaunchKernelGGL(k_matrix_exact, dim3((unsigned)ceil_div(waves, 4)), dim3(256), 0,
                      ctx().stream, e->Xs.as<double>(), e->N, e->Npad, (int)e->A, rmsd_dev,
                      maxdev_dev);

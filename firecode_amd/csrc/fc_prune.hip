@@ -456,23 +456,27 @@ k_inertia_moments(const double *__restrict__ coords, int64_t N, int64_t A,
   moments[n * 3 + 2] = w[2];
 }
 
-// MOI similarity bits: bit j of row i (j > i) = all_k |I_i[k]-I_j[k]| / I_i[k] < tol
+// MOI similarity bits: bit j of row i (j > i) = all_k !(|I_i[k]-I_j[k]| / I_i[k] >= tol)
 // [&& |E_i - E_j| < max_dE].  One wavefront per (row, 64-column word).
+// The negated >= is the oracle's early exit, not the same as < : 0/0 (two zero moments: linear
+// molecules on an axis, single atoms) is not a number, fails >= and leaves the pair similar
+// ("MOI prune: zero moments").
 __global__ void __launch_bounds__(256)
 k_moi_simbits(const double *__restrict__ moments, int64_t N, double tol,
               const double *__restrict__ energies, double max_dE, uint64_t *__restrict__ bits,
               int64_t W) {
   const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t i = wave / W, jt = wave % W;
-  if (i >= N) return;
+  // row in blockIdx.x, four words of it per workgroup in blockIdx.y: a flat index over the N * W wavefronts
+  // passes 2^32 threads at N = 65 536, more than one grid dimension takes
+  const int64_t i = blockIdx.x, jt = (int64_t)blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (jt >= W) return;
   if (jt * 64 + 63 <= i) return;
   const int64_t j = jt * 64 + lane;
   bool sim = false;
   if (j < N && j > i) {
     const double a0 = moments[i * 3], a1 = moments[i * 3 + 1], a2 = moments[i * 3 + 2];
     const double b0 = moments[j * 3], b1 = moments[j * 3 + 1], b2 = moments[j * 3 + 2];
-    sim = (fabs(a0 - b0) / a0 < tol) && (fabs(a1 - b1) / a1 < tol) && (fabs(a2 - b2) / a2 < tol);
+    sim = !(fabs(a0 - b0) / a0 >= tol) && !(fabs(a1 - b1) / a1 >= tol) && !(fabs(a2 - b2) / a2 >= tol);
     if (energies != nullptr) sim = sim && (fabs(energies[i] - energies[j]) < max_dE);
   }
   const uint64_t word = __ballot(sim);
@@ -1644,9 +1648,11 @@ int launch_inertia_moments(const double *coords_dev, int64_t N, int64_t A, const
 
 int launch_moi_simbits(const double *moments_dev, int64_t N, double tol, const double *energies_dev,
                        double max_dE, uint64_t *bits_dev, int64_t W) {
-  const int64_t waves = N * W;
-  if (waves == 0) return FC_OK;
-  hipLaunchKernelGGL(k_moi_simbits, dim3((unsigned)ceil_div(waves, 4)), dim3(256), 0, ctx().stream,
+  if (N * W == 0) return FC_OK;
+  // (N * 256 threads along x, W / 4 blocks along y: N < 2^24 and W <= 4 * 65535; a bit matrix of that size is 35 TB)
+  if (N >= ((int64_t)1 << 24) || ceil_div(W, 4) > 65535)
+    return set_error(FC_E_LIMIT, "N=%lld structures exceed the grid of the MOI similarity kernel", (long long)N);
+  hipLaunchKernelGGL(k_moi_simbits, dim3((unsigned)N, (unsigned)ceil_div(W, 4)), dim3(256), 0, ctx().stream,
                      moments_dev, N, tol, energies_dev, max_dE, bits_dev, W);
   return check_launch("k_moi_simbits");
 }
@@ -1875,6 +1881,9 @@ int launch_tfd_simbits(const double *tf_dev, int64_t N, int64_t Q, double thresh
                        int64_t row_end, uint64_t *bits_dev, int64_t W) {
   const int64_t waves = (row_end - row_begin) * W;
   if (waves <= 0) return FC_OK;
+  if (!grid_x_fits(ceil_div(waves, 4), 256))
+    return set_error(FC_E_LIMIT, "%lld rows x %lld words exceed one launch of the TFD bit kernel: pass fewer rows per call",
+                     (long long)(row_end - row_begin), (long long)W);
   hipLaunchKernelGGL(k_tfd_simbits, dim3((unsigned)ceil_div(waves, 4)), dim3(256), 0, ctx().stream,
                      tf_dev, N, (int)Q, thresh, row_begin, row_end, bits_dev, W);
   return check_launch("k_tfd_simbits");

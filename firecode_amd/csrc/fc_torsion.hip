@@ -981,8 +981,10 @@ int launch_rotcorr_simbits(const double *X_dev, int64_t N, int64_t A, const uint
                            double max_rmsd, double max_dev, const double *energies_dev, double max_dE,
                            uint64_t *bits_dev, int64_t W) {
   if (N < 2) return FC_OK;
-  hipLaunchKernelGGL(k_rotcorr_simbits, dim3((unsigned)ceil_div(N, 4), (unsigned)N), dim3(256),
-                     (size_t)4 * A * 3 * sizeof(double), ctx().stream, X_dev, N, (int)A, heavy_dev, tors_dev,
+  const size_t lds = (size_t)4 * A * 3 * sizeof(double);
+  FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_rotcorr_simbits), lds, "k_rotcorr_simbits"));
+  // the row index is blockIdx.y: fc_prune_rmsd_rot_corr refuses N > FC_ROTCORR_MAX_ROWS before it comes here
+  hipLaunchKernelGGL(k_rotcorr_simbits, dim3((unsigned)ceil_div(N, 4), (unsigned)N), dim3(256), lds, ctx().stream, X_dev, N, (int)A, heavy_dev, tors_dev,
                      (int)T, rotmasks_dev, angles_dev, n_angles_dev, max_angles, max_rmsd, max_dev, energies_dev,
                      max_dE, reinterpret_cast<unsigned long long *>(bits_dev), W);
   return check_launch("k_rotcorr_simbits");

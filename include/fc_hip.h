@@ -306,7 +306,12 @@ int fc_prune_rmsd_sharded(fc_ensemble *ens, double max_rmsd, double max_dev, int
  * (angles (T,max_angles), n_angles (T); 0 first, as Torsion.get_angles gives them).
  * Structures are centred on their plain mean; similarity = rmsd_and_max over heavy_mask atoms
  * after the torsional correction; then the same k-ladder as fc_prune_rmsd.  coords in processing
- * order (energy-sorted by the caller when energies are given).  bits_out: optional (N, W). */
+ * order (energy-sorted by the caller when energies are given).  bits_out: optional (N, W).
+ * Limits, both refused with FC_E_LIMIT before the device is touched: 4*A*24 bytes <= 160 KiB of LDS
+ * (A <= 1706), and N <= FC_ROTCORR_MAX_ROWS: the kernel takes one grid row per structure, and 65 535
+ * is the y extent every HIP device guarantees.  The stage is meant for ensembles the MOI and RMSD
+ * stages have already thinned (one wavefront per pair: 2e9 of them at the limit). */
+#define FC_ROTCORR_MAX_ROWS 65535
 int fc_prune_rmsd_rot_corr(const double *coords, int64_t N, int64_t A, const uint8_t *heavy_mask,
                            const int64_t *torsions, int64_t T, const uint8_t *rotation_masks,
                            const double *angles, const int32_t *n_angles, int64_t max_angles,
@@ -327,6 +332,13 @@ int fc_inertia_moments(const double *coords, int64_t N, int64_t A, const double 
 int fc_prune_moi(const double *coords, int64_t N, int64_t A, const double *masses,
                  double max_deviation, const double *energies, double max_dE,
                  int64_t min_per_group, uint8_t *mask_out);
+/* The similarity bits fc_prune_moi replays: bit j of row i (j > i only) is set when
+ *   not (|I_i[k] - I_j[k]| / I_i[k] >= max_deviation)   for k = 0, 1, 2
+ * [and |E_i - E_j| < max_dE when energies are given].  The negated form is the reference's early exit:
+ * a zero moment against a zero moment (0/0, not a number) does not tell two structures apart, a zero
+ * moment against a non-zero one (infinite) does.  bits_out (N, ceil(N/64)) words. */
+int fc_moi_simbits(const double *coords, int64_t N, int64_t A, const double *masses, double max_deviation,
+                   const double *energies, double max_dE, uint64_t *bits_out);
 
 /* ---- a2/a3: the similarity stages of the drivers on ONE upload -- Ensemble.similarity_pruning
  * (firecode/ensemble.py:205-235) and Embedder.similarity_refining (embedder.py:1445-1474) run

@@ -469,17 +469,23 @@ def align_by_moi(masses, structures):
 
 def prune_by_moment_of_inertia(structures, atoms, max_deviation=0.01, energies=None, max_dE=0.0):
     """MOI pruning (call sites ensemble.py:211-216, embedder.py:1452-1454):
-    same greedy scheme; similar <=> all three ``|I1_k - I2_k| / I1_k <
-    max_deviation`` (1 %: CHANGELOG.md:256), I1 being the earlier structure
-    of the pair in processing order."""
+    same greedy scheme; a pair is told apart by the first moment with
+    ``|I1_k - I2_k| / I1_k >= max_deviation`` (1 %: CHANGELOG.md:256), I1 being
+    the earlier structure of the pair in processing order, and is similar when
+    no moment does.  That is ``<`` for every ordinary pair; the early exit is
+    the rule where the two forms differ: 0/0 (both moments zero: atoms on one
+    coordinate axis, a single atom) is not a number, fails ``>=`` and leaves
+    the pair similar, x/0 (infinite) tells it apart.  PARITY UNPINNED; the
+    kernel (k_moi_simbits) writes the same negated comparison."""
     structures = np.asarray(structures, dtype=np.float64)
     masses = np.array([MASSES_TABLE[a] for a in atoms])
     moi = np.array([get_inertia_moments(s, masses) for s in structures])
 
     def similar(a, b):
-        for k in range(3):
-            if abs(moi[a, k] - moi[b, k]) / moi[a, k] >= max_deviation:
-                return False
+        with np.errstate(divide="ignore", invalid="ignore"):  # 0/0 and x/0 are part of the rule, see above
+            for k in range(3):
+                if abs(moi[a, k] - moi[b, k]) / moi[a, k] >= max_deviation:
+                    return False
         return True
 
     mask = greedy_prune(len(structures), similar, energies=energies, max_dE=max_dE)

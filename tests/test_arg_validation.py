@@ -113,3 +113,49 @@ def test_prune_many_rejects_bad_lists():
     with pytest.raises(fc.FirecodeHipInputError):  # threshold
         L.call("fc_prune_rmsd_many", one, 1, 0.0, 1.0, 20, masks, None)
     L.call("fc_prune_rmsd_many", None, 0, 0.5, 1.0, 20, None, None)  # empty queue: nothing to do
+
+
+# ---- size limits: FC_E_LIMIT comes back from the host checks, before any device call ---------------------
+def _limit(fn):
+    with pytest.raises(fc.FirecodeHipInputError) as e:
+        fn()
+    assert e.value.code == L.FC_E_LIMIT, e.value
+    return str(e.value)
+
+
+def test_clash_entry_points_refuse_more_atoms_than_the_lds_holds():
+    A = 160 * 1024 // 24 + 1  # 6827
+    X = np.zeros((1, A, 3))
+    n, ok = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.uint8)
+    assert "6826" in _limit(lambda: L.call("fc_clash_self", L.pf(X), 1, A, 0.0, 0.5, L.pi(n)))
+    assert "6826" in _limit(lambda: L.call("fc_clash_fragments", L.pf(X), 1, A, L.pi(L.i64([3, 4])), 2, 1.0, 0, L.pi(n), L.pb(ok)))
+    assert "6826" in _limit(lambda: L.call("fc_clash_graph", L.pf(X), 1, A, L.pb(np.zeros((A, A), dtype=np.uint8)), 1.0, L.pi(n)))
+    assert "6826" in _limit(lambda: fc.algebra.count_clashes_batch(X))
+    _limit(lambda: fc.utils.compenetration_check_batch(X, ids=[3, 4, 5]))
+
+
+def _pose_args(A1=3, A2=2, P=2):
+    return dict(m1=np.zeros((2, A1, 3)), m2=np.zeros((3, A2, 3)), c1=np.zeros(P, dtype=np.int64), c2=np.zeros(P, dtype=np.int64),
+                R1=np.tile(np.eye(3), (P, 1, 1)), t1=np.zeros((P, 3)), R2=np.tile(np.eye(3), (P, 1, 1)), t2=np.zeros((P, 3)))
+
+
+def test_pose_kernel_refuses_too_many_atoms_and_bad_conformer_ids():
+    assert "1707" in _limit(lambda: fc.embeds.embed_poses_clash(**_pose_args(A1=1707)))
+    for which, bad in (("c1", 2), ("c1", -1), ("c2", 3), ("c2", -1)):
+        a = _pose_args()
+        a[which][1] = bad  # m1 has 2 conformers, m2 has 3
+        with pytest.raises(fc.FirecodeHipInputError) as e:
+            fc.embeds.embed_poses_clash(**a)
+        assert e.value.code == L.FC_E_INVALID and "pose 1" in str(e.value)
+
+
+def test_rot_corr_refuses_sizes_its_launch_cannot_take():
+    def call(N, A):
+        X = np.zeros((N, A, 3))
+        mask = np.zeros(N, dtype=np.uint8)
+        L.call("fc_prune_rmsd_rot_corr", L.pf(X), N, A, L.pb(np.ones(A, dtype=np.uint8)), None, 0, None, None, None, 1,
+               0.25, 0.5, None, 0.0, 20, L.pb(mask), None)
+
+    assert "1707" in _limit(lambda: call(3, 1707))  # 4 structures of 1707 atoms do not fit the 160 KiB of LDS
+    msg = _limit(lambda: call(65536, 3))  # one grid row per structure: 65 535 is what every device guarantees
+    assert "65535" in msg and "FC_ROTCORR_MAX_ROWS" in msg

@@ -1277,10 +1277,12 @@ def test_trimolecular_cyclical_embed_vs_oracle(fc, seed, thresh, pairing):
         assert det["passed"].sum() > det["accepted"].sum()
 
 
-def _tbu_ensemble(seed=0, n_backbone=4, jitter=0.01):
+def _tbu_ensemble(seed=0, n_backbone=4, jitter=0.01, n_spectators=0):
     """A chain C0-C1-C2-C3 whose C3 carries three methyls (a 3-fold locally symmetric rotor)
     and C0 carries two equivalent carbons (a 2-fold one); conformers = backbone dihedral in
-    `n_backbone` values x rotor turned by 0/120/240 (+ a few degrees) x flipper by 0/180"""
+    `n_backbone` values x rotor turned by 0/120/240 (+ a few degrees) x flipper by 0/180.
+    `n_spectators` more atoms (carbons and hydrogens in turn, bonded to nothing, a blob beside C1)
+    ride along rigidly with C0-C1-C2: no torsion moves them, the heavy ones count in the RMSD."""
     import networkx as nx
 
     rng = np.random.default_rng(seed)
@@ -1298,6 +1300,11 @@ def _tbu_ensemble(seed=0, n_backbone=4, jitter=0.01):
     atoms = np.array(["C"] * 9 + ["H"] * 3)
     edges = [(0, 1), (1, 2), (2, 3), (3, 4), (3, 5), (3, 6), (0, 7), (0, 8), (4, 9), (5, 10), (6, 11)]
     graph = nx.Graph(edges)
+    if n_spectators:
+        spect = np.array([-2.2, -6.0, 0.0]) + np.random.default_rng(1000 + seed).normal(scale=1.5, size=(n_spectators, 3))
+        base = np.concatenate([base, spect])
+        atoms = np.concatenate([atoms, np.array(["C", "H"] * n_spectators)[:n_spectators]])
+        graph.add_nodes_from(range(12, 12 + n_spectators))
     nx.set_node_attributes(graph, {i: str(a) for i, a in enumerate(atoms)}, "atoms")  # as graphize() leaves them
     torsions = [(1, 2, 3, 4, 3), (2, 1, 0, 7, 2)]
     masks = np.array([fc_rotation_mask(graph, t[:4], len(atoms)) for t in torsions])
