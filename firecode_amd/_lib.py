@@ -98,6 +98,10 @@ _SIGNATURES = {
     "fc_clash_fragments": [_p_f64, _i64, _i64, _p_i64, _i64, _f64, _i64, _p_i64, _p_u8],
     "fc_clash_graph": [_p_f64, _i64, _i64, _p_u8, _f64, _p_i64],
     "fc_fitness_check": [_p_f64, _i64, _i64, _p_i64, _p_f64, _i64, _f64, _p_f64, _p_u8],
+    "fc_bond_changes": [_p_f64, _i64, _i64, C.POINTER(C.c_int32), _i64, _p_f64, _p_f64, _i64, _p_u64, _p_i64, _p_i64,
+                        _i64, _i64, _p_i64, _p_u8],
+    "fc_bond_changes_list": [_p_f64, _i64, _i64, C.POINTER(C.c_int32), _i64, _p_f64, _p_f64, _i64, _p_u64, _p_i64,
+                             _p_i64, _i64, _p_i64, _p_i64],
     "fc_embed_poses_clash": [_p_f64, _i64, _i64, _p_f64, _i64, _i64, _p_i64, _p_i64, _p_f64, _p_f64,
                              _p_f64, _p_f64, _i64, _f64, _i64, _p_i64, _p_u8, _p_f64],
     "fc_embed_mol_transforms": [_p_f64, _i64, _i64, _p_i64, _i64, _p_f64, _p_f64, _i64, _p_f64, _i64, _p_f64, _p_f64],

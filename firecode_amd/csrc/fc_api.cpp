@@ -2138,6 +2138,74 @@ int fc_clash_graph(const double *coords, int64_t N, int64_t A, const uint8_t *ad
   return sync();
 }
 
+// ---- bond-topology check (molecule_check / scramble_check, firecode/utils.py:341-400) ---------------------------
+// every argument is checked here, before the device is touched
+static int bond_check_args(BondJob &j) {
+  FC_REQUIRE(j.N >= 0 && j.A >= 1, "bad shape");
+  if (j.A > INT32_MAX - 1) return set_error(FC_E_LIMIT, "A=%lld: atom indices are 32-bit", (long long)j.A);
+  FC_REQUIRE(j.n_class >= 1 && j.n_class <= 64, "n_class=%lld outside 1..64", (long long)j.n_class);
+  FC_REQUIRE((j.ref_coords != nullptr) != (j.ref_bits != nullptr),
+             "exactly one reference: ref_coords (molecule mode) or ref_bits (scramble mode)");
+  FC_REQUIRE(!j.ref_coords || j.ref_stride == 0 || j.ref_stride == 3 * j.A, "ref_stride must be 0 or 3*A");
+  if (j.N == 0) return FC_OK;
+  FC_REQUIRE(j.coords && j.atom_class && j.class_thresh, "NULL pointer argument");
+  for (int64_t a = 0; a < j.A; ++a)
+    FC_REQUIRE(j.atom_class[a] >= 0 && j.atom_class[a] < j.n_class, "atom_class[%lld] out of range", (long long)a);
+  for (int64_t p = 0; p < j.n_class; ++p)
+    for (int64_t q = 0; q < j.n_class; ++q) {
+      const double u = j.class_thresh[p * j.n_class + q], v = j.class_thresh[q * j.n_class + p];
+      FC_REQUIRE(u == v || (u != u && v != v), "class_thresh must be symmetric");
+    }
+  if (j.excl_offsets) {
+    FC_REQUIRE(j.excl_sets == 1 || j.excl_sets == j.N, "excl_sets must be 1 or N");
+    FC_REQUIRE(j.excl_offsets[0] == 0, "excl_offsets[0] must be 0");
+    for (int64_t s = 0; s < j.excl_sets; ++s)
+      FC_REQUIRE(j.excl_offsets[s + 1] >= j.excl_offsets[s], "excl_offsets must be non-decreasing");
+    FC_REQUIRE(j.excl_offsets[j.excl_sets] == 0 || j.excl_atoms, "NULL excl_atoms");
+  }
+  if (j.offsets) {
+    FC_REQUIRE(j.offsets[0] == 0, "offsets[0] must be 0");
+    for (int64_t n = 0; n < j.N; ++n) FC_REQUIRE(j.offsets[n + 1] >= j.offsets[n], "offsets must be non-decreasing");
+    FC_REQUIRE(j.offsets[j.N] == 0 || j.bonds_out, "NULL bonds_out");
+  } else {
+    FC_REQUIRE(j.counts_out || j.ok_out, "no output requested");
+  }
+  return FC_OK;
+}
+
+int fc_bond_changes(const double *coords, int64_t N, int64_t A, const int32_t *atom_class, int64_t n_class,
+                    const double *class_thresh, const double *ref_coords, int64_t ref_stride, const uint64_t *ref_bits,
+                    const int64_t *excl_offsets, const int64_t *excl_atoms, int64_t excl_sets, int64_t max_newbonds,
+                    int64_t *counts_out, uint8_t *ok_out) {
+  FC_API_LOCK;
+  BondJob j;
+  j.coords = coords, j.N = N, j.A = A, j.atom_class = atom_class, j.n_class = n_class, j.class_thresh = class_thresh;
+  j.ref_coords = ref_coords, j.ref_stride = ref_stride, j.ref_bits = ref_bits;
+  j.excl_offsets = excl_offsets, j.excl_atoms = excl_atoms, j.excl_sets = excl_sets;
+  j.max_newbonds = max_newbonds, j.counts_out = counts_out, j.ok_out = ok_out;
+  FC_TRY(bond_check_args(j));
+  if (N == 0) return FC_OK;
+  FC_TRY(ensure_init());
+  return bond_changes(j);
+}
+
+int fc_bond_changes_list(const double *coords, int64_t N, int64_t A, const int32_t *atom_class, int64_t n_class,
+                         const double *class_thresh, const double *ref_coords, int64_t ref_stride,
+                         const uint64_t *ref_bits, const int64_t *excl_offsets, const int64_t *excl_atoms,
+                         int64_t excl_sets, const int64_t *offsets, int64_t *bonds_out) {
+  FC_API_LOCK;
+  BondJob j;
+  j.coords = coords, j.N = N, j.A = A, j.atom_class = atom_class, j.n_class = n_class, j.class_thresh = class_thresh;
+  j.ref_coords = ref_coords, j.ref_stride = ref_stride, j.ref_bits = ref_bits;
+  j.excl_offsets = excl_offsets, j.excl_atoms = excl_atoms, j.excl_sets = excl_sets;
+  FC_REQUIRE(offsets != nullptr, "NULL offsets");
+  j.offsets = offsets, j.bonds_out = bonds_out;
+  FC_TRY(bond_check_args(j));
+  if (N == 0) return FC_OK;
+  FC_TRY(ensure_init());
+  return bond_changes(j);
+}
+
 int fc_fitness_check(const double *coords, int64_t N, int64_t A, const int64_t *pairs,
                      const double *targets, int64_t C, double threshold, double *error_out,
                      uint8_t *pass_out) {

@@ -14,6 +14,7 @@
 // (sq_threshold_lt / sq_threshold_le below).
 #include "fc_common.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace fc {
@@ -146,6 +147,136 @@ k_clash_graph(const double *__restrict__ coords, int64_t N, int A, const uint8_t
   }
   cnt = wave_sum(cnt);
   if (lane == 0) counts[n] = 2 * (int64_t)cnt;  // (i1,i2) and (i2,i1) are both visited
+}
+
+// ---------------------------------------------------------------------------
+// Bond-topology check -- firecode/utils.py:341-400 (molecule_check, scramble_check); contract in
+// include/fc_hip.h and DESIGN.md section 11.  i < j are bonded iff fl(cdist) < thr(class_i, class_j), decided as
+// d2 < T2 (T2 = sq_threshold_lt(thr), one per class pair, in LDS).  A pair is CHANGED when bonded now differs from
+// the reference (bit matrix, or the same test on reference coordinates) and neither atom is excluded.
+// Work unit = (structure n, row tile t): rows [rows[t], rows[t+1]) of the upper triangle, walked by ONE wavefront
+// as a row-major run of pairs, 64 consecutive pairs per step -- the ballot of a step orders the changed pairs of
+// the run row-major, which the fill pass (FILL) writes at the tile's offset.  Coordinates are read from global
+// memory (L1/L2), not staged: any atom count fits.  Persistent grid: waves stride over the N x T units (int64).
+// ---------------------------------------------------------------------------
+struct BondArgs {
+  const double *coords;
+  int64_t N;
+  int A;
+  const int32_t *cls;
+  int n_class;
+  const double *T2;
+  const double *ref;  // reference coordinates or nullptr (then ref_bits)
+  int64_t ref_stride;
+  const uint64_t *ref_bits;
+  int W;  // words per bit row: ceil(A / 64)
+  const uint64_t *excl;  // excl_sets x W words or nullptr
+  int64_t excl_sets;
+  const int32_t *rows;  // T + 1 tile boundaries
+  int T;
+};
+
+// pairs of the rows before row r
+__device__ __forceinline__ int64_t pairs_before(int64_t r, int64_t A) { return r * (2 * A - r - 1) / 2; }
+
+template <bool FILL>
+__global__ void __launch_bounds__(256)
+k_bond_changes(BondArgs a, int32_t *__restrict__ tile_counts, const int64_t *__restrict__ tile_off,
+               int64_t *__restrict__ bonds, int64_t E) {
+  extern __shared__ double sT2[];
+  for (int k = threadIdx.x; k < a.n_class * a.n_class; k += blockDim.x) sT2[k] = a.T2[k];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int64_t A = a.A;
+  const int64_t units = a.N * (int64_t)a.T;
+  for (int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < units; u += (int64_t)gridDim.x * 4) {
+    const int64_t n = u / a.T;
+    const int t = (int)(u - n * a.T);
+    const int r0 = a.rows[t], r1 = a.rows[t + 1];
+    const int64_t P = pairs_before(r1, A) - pairs_before(r0, A);
+    const double *x = a.coords + n * A * 3;
+    const double *xr = a.ref ? a.ref + n * a.ref_stride : nullptr;
+    const uint64_t *ex = a.excl ? a.excl + (a.excl_sets == 1 ? 0 : n) * a.W : nullptr;
+    // this lane's pair (i, i + 1 + off); row i holds A - 1 - i pairs
+    int i = r0;
+    int64_t off = lane;
+    while (i < r1 && off >= A - 1 - i) off -= A - 1 - i++;
+    int64_t base = FILL ? tile_off[u] : 0;
+    int cnt = 0;
+    for (int64_t q0 = 0; q0 < P; q0 += 64) {
+      const int j = i + 1 + (int)off;
+      bool changed = false, now = false;
+      if (q0 + lane < P) {
+        const double t2 = sT2[a.cls[i] * a.n_class + a.cls[j]];
+        const int64_t i3 = (int64_t)i * 3, j3 = (int64_t)j * 3;
+        now = dist2(x[i3], x[i3 + 1], x[i3 + 2], x[j3], x[j3 + 1], x[j3 + 2]) < t2;
+        const bool was = xr ? dist2(xr[i3], xr[i3 + 1], xr[i3 + 2], xr[j3], xr[j3 + 1], xr[j3 + 2]) < t2
+                            : ((a.ref_bits[(int64_t)i * a.W + (j >> 6)] >> (j & 63)) & 1) != 0;
+        changed = now != was;
+        if (changed && ex) changed = (((ex[i >> 6] >> (i & 63)) | (ex[j >> 6] >> (j & 63))) & 1) == 0;
+      }
+      if (FILL) {
+        const unsigned long long m = __ballot(changed);
+        if (changed) {
+          const int64_t pos = base + __popcll(m & ((1ull << lane) - 1));
+          if (pos < E) {  // (the entry point has checked the offsets against the counts)
+            bonds[pos * 3] = i;
+            bonds[pos * 3 + 1] = j;
+            bonds[pos * 3 + 2] = now ? 1 : -1;
+          }
+        }
+        base += __popcll(m);
+      } else {
+        cnt += changed ? 1 : 0;
+      }
+      off += 64;
+      while (i < r1 && off >= A - 1 - i) off -= A - 1 - i++;
+    }
+    if (!FILL) {
+      cnt = wave_sum(cnt);
+      if (lane == 0) tile_counts[u] = cnt;
+    }
+  }
+}
+
+// excluded atoms: CSR list -> one bit row per set (rows zeroed by the launcher); out-of-range values are ignored,
+// as the reference's `a in bond` never matches them
+__global__ void __launch_bounds__(256)
+k_excl_bits(const int64_t *__restrict__ offsets, const int64_t *__restrict__ atoms, int64_t S, int64_t A, int W,
+            uint64_t *__restrict__ bits) {
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < S; s += (int64_t)gridDim.x * blockDim.x) {
+    uint64_t *b = bits + s * W;
+    for (int64_t k = offsets[s]; k < offsets[s + 1]; ++k) {
+      const int64_t v = atoms[k];
+      if (v >= 0 && v < A) b[v >> 6] |= 1ull << (v & 63);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256)
+k_bond_counts(const int32_t *__restrict__ tile_counts, int64_t N, int T, int64_t max_newbonds,
+              int64_t *__restrict__ counts, uint8_t *__restrict__ ok) {
+  for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
+    int64_t s = 0;
+    for (int t = 0; t < T; ++t) s += tile_counts[n * T + t];
+    counts[n] = s;
+    ok[n] = (s <= max_newbonds) ? 1 : 0;  // a negative max_newbonds is never met
+  }
+}
+
+// list pass: per-tile write offsets from the caller's per-structure offsets; *bad = 1 where they disagree with the
+// counts just computed (nothing is written then)
+__global__ void __launch_bounds__(256)
+k_bond_tile_offsets(const int32_t *__restrict__ tile_counts, int64_t N, int T, const int64_t *__restrict__ offsets,
+                    int64_t *__restrict__ tile_off, int32_t *__restrict__ bad) {
+  for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
+    int64_t run = offsets[n];
+    for (int t = 0; t < T; ++t) {
+      tile_off[n * T + t] = run;
+      run += tile_counts[n * T + t];
+    }
+    if (run != offsets[n + 1]) *bad = 1;
+  }
 }
 
 // fitness_check (firecode/optimization_methods.py:163-180): sum over constraints
@@ -334,6 +465,113 @@ int launch_clash_graph(const double *coords_dev, int64_t N, int64_t A, const uin
   FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_clash_graph), lds, "k_clash_graph"));
   hipLaunchKernelGGL(k_clash_graph, dim3((unsigned)N), dim3(64), lds, ctx().stream, coords_dev, N, (int)A, adj_dev, sq_threshold_lt(thresh), counts_dev);
   return check_launch("k_clash_graph");
+}
+
+// Row tiles of a structure of A atoms: consecutive rows until a tile holds pairs_per_tile pairs; the last tile always
+// holds the last pair (A-2, A-1).  T + 1 boundaries, the last one A.
+static void bond_tiles(int64_t A, int64_t pairs_per_tile, std::vector<int32_t> &rows) {
+  rows.assign(1, 0);
+  int64_t acc = 0;
+  for (int64_t r = 0; r + 2 < A; ++r) {  // never cut after row A-2, the last one with pairs
+    acc += A - 1 - r;
+    if (acc >= pairs_per_tile) {
+      rows.push_back((int32_t)(r + 1));
+      acc = 0;
+    }
+  }
+  rows.push_back((int32_t)A);
+}
+
+template <class T>
+static int bond_upload(DevBuf &b, const T *host, size_t count) {
+  FC_TRY(b.reserve(count * sizeof(T)));
+  return h2d(b.p, host, count * sizeof(T));
+}
+
+// count pass (job.counts_out / ok_out) or list pass (job.offsets / bonds_out); arguments validated by the entry point
+int bond_changes(const BondJob &job) {
+  const int64_t N = job.N, A = job.A, W = (A + 63) / 64, nc = job.n_class;
+  const bool list = job.offsets != nullptr;
+  if (N == 0) return FC_OK;
+  // tiles: at least 4096 pairs, more when N x pairs would give more than 64 units per CU (fewer, longer units)
+  const int64_t P = A * (A - 1) / 2;
+  const int64_t want_units = (int64_t)ctx().n_cu * 64;
+  int64_t ppt = std::max<int64_t>(4096, (int64_t)std::ceil((double)N * (double)P / (double)want_units));
+  ppt = std::min<int64_t>(ppt, (int64_t)1 << 30);
+  std::vector<int32_t> rows;
+  bond_tiles(A, ppt, rows);
+  const int64_t T = (int64_t)rows.size() - 1;
+  std::vector<double> T2((size_t)(nc * nc));
+  for (int64_t k = 0; k < nc * nc; ++k) T2[k] = sq_threshold_lt(job.class_thresh[k]);
+  const int64_t ref_count = job.ref_coords ? (job.ref_stride ? N * A * 3 : A * 3) : 0;
+  const int64_t E = list ? job.offsets[N] : 0;
+  // everything the call holds on the device at once: FC_E_LIMIT when it cannot fit
+  const double need = 8.0 * (double)N * A * 3 + 8.0 * ref_count + (job.ref_bits ? 8.0 * A * W : 0.0) +
+                      (job.excl_offsets ? 8.0 * ((double)job.excl_sets * (W + 1) + job.excl_offsets[job.excl_sets]) : 0.0) +
+                      4.0 * N * T + (list ? 8.0 * N * T + 8.0 * (N + 1) + 24.0 * E : 9.0 * N);
+  if (need > (double)ctx().hbm)
+    return set_error(FC_E_LIMIT, "bond check of %lld x %lld atoms needs %.3g bytes of device memory, the device has %zu",
+                     (long long)N, (long long)A, need, ctx().hbm);
+  // persistent grids: at most 16 workgroups per CU; waves / threads stride over their units (int64 indices)
+  const int64_t cap = (int64_t)ctx().n_cu * 16;
+  DevBuf dc, dcls, dT2, dref, dbits, dexo, dexa, dex, drows, dtc;
+  FC_TRY(bond_upload(dc, job.coords, (size_t)(N * A * 3)));
+  FC_TRY(bond_upload(dcls, job.atom_class, (size_t)A));
+  FC_TRY(bond_upload(dT2, T2.data(), T2.size()));
+  FC_TRY(bond_upload(drows, rows.data(), rows.size()));
+  if (job.ref_coords) FC_TRY(bond_upload(dref, job.ref_coords, (size_t)ref_count));
+  if (job.ref_bits) FC_TRY(bond_upload(dbits, job.ref_bits, (size_t)(A * W)));
+  if (job.excl_offsets) {
+    const int64_t S = job.excl_sets, K = job.excl_offsets[S];
+    FC_TRY(bond_upload(dexo, job.excl_offsets, (size_t)(S + 1)));
+    FC_TRY(bond_upload(dexa, job.excl_atoms, (size_t)K));
+    FC_TRY(dex.reserve((size_t)(S * W) * sizeof(uint64_t)));
+    FC_HIP_TRY(hipMemsetAsync(dex.p, 0, (size_t)(S * W) * sizeof(uint64_t), ctx().stream));
+    hipLaunchKernelGGL(k_excl_bits, dim3((unsigned)std::min<int64_t>(ceil_div(S, 256), cap)), dim3(256), 0, ctx().stream, dexo.as<int64_t>(),
+                       dexa.as<int64_t>(), S, A, (int)W, dex.as<uint64_t>());
+    FC_TRY(check_launch("k_excl_bits"));
+  }
+  FC_TRY(dtc.reserve((size_t)(N * T) * sizeof(int32_t)));
+  const BondArgs args{dc.as<double>(), N, (int)A, dcls.as<int32_t>(), (int)nc, dT2.as<double>(),
+                      job.ref_coords ? dref.as<double>() : nullptr, job.ref_stride,
+                      job.ref_bits ? dbits.as<uint64_t>() : nullptr, (int)W,
+                      job.excl_offsets ? dex.as<uint64_t>() : nullptr, job.excl_sets, drows.as<int32_t>(), (int)T};
+  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(ceil_div(N * T, 4), cap));
+  const size_t lds = (size_t)(nc * nc) * sizeof(double);
+  FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_bond_changes<false>), lds, "k_bond_changes"));
+  hipLaunchKernelGGL(k_bond_changes<false>, dim3((unsigned)blocks), dim3(256), lds, ctx().stream, args,
+                     dtc.as<int32_t>(), (const int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0);
+  FC_TRY(check_launch("k_bond_changes"));
+  if (!list) {
+    DevBuf dn, dok;
+    FC_TRY(dn.reserve((size_t)N * sizeof(int64_t)));
+    FC_TRY(dok.reserve((size_t)N));
+    hipLaunchKernelGGL(k_bond_counts, dim3((unsigned)std::min<int64_t>(ceil_div(N, 256), cap)), dim3(256), 0, ctx().stream, dtc.as<int32_t>(),
+                       N, (int)T, job.max_newbonds, dn.as<int64_t>(), dok.as<uint8_t>());
+    FC_TRY(check_launch("k_bond_counts"));
+    if (job.counts_out) FC_TRY(d2h(job.counts_out, dn.p, (size_t)N * sizeof(int64_t)));
+    if (job.ok_out) FC_TRY(d2h(job.ok_out, dok.p, (size_t)N));
+    return sync();
+  }
+  DevBuf doff, dto, dbad, dbonds;
+  FC_TRY(bond_upload(doff, job.offsets, (size_t)(N + 1)));
+  FC_TRY(dto.reserve((size_t)(N * T) * sizeof(int64_t)));
+  FC_TRY(dbad.reserve(sizeof(int32_t)));
+  FC_HIP_TRY(hipMemsetAsync(dbad.p, 0, sizeof(int32_t), ctx().stream));
+  hipLaunchKernelGGL(k_bond_tile_offsets, dim3((unsigned)std::min<int64_t>(ceil_div(N, 256), cap)), dim3(256), 0, ctx().stream,
+                     dtc.as<int32_t>(), N, (int)T, doff.as<int64_t>(), dto.as<int64_t>(), dbad.as<int32_t>());
+  FC_TRY(check_launch("k_bond_tile_offsets"));
+  int32_t bad = 0;
+  FC_TRY(d2h(&bad, dbad.p, sizeof(int32_t)));
+  FC_TRY(sync());
+  if (bad) return set_error(FC_E_INVALID, "offsets do not match the counts of changed bonds");
+  if (E == 0) return FC_OK;
+  FC_TRY(dbonds.reserve((size_t)(E * 3) * sizeof(int64_t)));
+  hipLaunchKernelGGL(k_bond_changes<true>, dim3((unsigned)blocks), dim3(256), lds, ctx().stream, args,
+                     (int32_t *)nullptr, dto.as<int64_t>(), dbonds.as<int64_t>(), E);
+  FC_TRY(check_launch("k_bond_changes<fill>"));
+  FC_TRY(d2h(job.bonds_out, dbonds.p, (size_t)(E * 3) * sizeof(int64_t)));
+  return sync();
 }
 
 int launch_fitness(const double *coords_dev, int64_t N, int64_t A, const int64_t *pairs_dev,

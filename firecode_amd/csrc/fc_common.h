@@ -299,6 +299,28 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // a truncated grid and leaves the rest of the output unwritten.  Launchers whose grid grows with N^2 check first.
 inline bool grid_x_fits(int64_t blocks, int64_t threads_per_block) { return blocks * threads_per_block < ((int64_t)1 << 32); }
 
+// One bond-topology check (fc_bond_changes / fc_bond_changes_list; fc_clash.hip).  Host pointers, validated by the
+// entry point; the launcher uploads them.
+struct BondJob {
+  const double *coords = nullptr;      // (N, A, 3)
+  int64_t N = 0, A = 0;
+  const int32_t *atom_class = nullptr;  // (A,) in [0, n_class)
+  int64_t n_class = 0;
+  const double *class_thresh = nullptr;  // (n_class, n_class) distance thresholds, symmetric
+  const double *ref_coords = nullptr;    // molecule mode: 3A doubles (ref_stride 0) or (N, A, 3) (ref_stride 3A)
+  int64_t ref_stride = 0;
+  const uint64_t *ref_bits = nullptr;    // scramble mode: (A, ceil(A/64)) words, bit j of row i = bond i-j
+  const int64_t *excl_offsets = nullptr;  // (excl_sets + 1,) or nullptr
+  const int64_t *excl_atoms = nullptr;
+  int64_t excl_sets = 0;                  // 1 (shared) or N
+  int64_t max_newbonds = 0;
+  int64_t *counts_out = nullptr;          // count pass (N,)
+  uint8_t *ok_out = nullptr;
+  const int64_t *offsets = nullptr;       // list pass: (N + 1,) from the counts
+  int64_t *bonds_out = nullptr;           // (offsets[N], 3): i, j, +1 formed / -1 broken
+};
+int bond_changes(const BondJob &job);
+
 // A^2 added to max_rmsd^2 in the all-pairs screens (and in the refine's own early exit)
 constexpr double kScreenMargin = 1e-6;
 // candidate-pair queues longer than this go to the one-lane-per-pair refine kernels (k_refine_buckets / k_refine_pairs);

@@ -8,6 +8,7 @@ from time import perf_counter
 
 import numpy as np
 
+from firecode_amd import _lib as L
 from firecode_amd.pruner import prune_by_moment_of_inertia, prune_by_rmsd
 from firecode_amd.utils import compenetration_check_batch, fitness_check_batch
 
@@ -37,6 +38,30 @@ def fitness_refining(structures, constrained_indices, constrained_distances, thr
     mask, _ = fitness_check_batch(structures, constrained_indices, constrained_distances, threshold)
     if not mask.all():
         _log(logfunction, f"Discarded {int((~mask).sum())} candidates for unfitness ({int(mask.sum())} left)")
+    return mask
+
+
+def scramble_refining(structures, atoms, graphs, constrained_indices, internal_constraints=(), exit_status=None,
+                      max_newbonds=0):
+    """embedder.py:2181-2194 / 2430-2443 (``optimization_refining``) in one call: structure i is checked with
+    ``scramble_check(atoms, structures[i], excluded_atoms=concat(constrained_indices[i], internal_constraints).ravel(),
+    mols_graphs=graphs, max_newbonds)`` only where ``exit_status[i]`` is true (all, when None) -> ``exit_status & ok``."""
+    from firecode_amd.utils import scramble_check_batch
+
+    X = np.asarray(structures, dtype=np.float64)
+    N = X.shape[0] if X.ndim == 3 else -1
+    status = np.ones(max(N, 0), dtype=bool) if exit_status is None else np.array(exit_status, dtype=bool).reshape(-1)
+    if N < 0 or status.shape[0] != N or len(constrained_indices) != N:
+        raise L.FirecodeHipInputError(
+            L.FC_E_INVALID, f"structures (N, A, 3), exit_status and constrained_indices of N entries: got {X.shape}, "
+                            f"{status.shape[0]} and {len(constrained_indices)}")
+    internal = np.asarray(internal_constraints)
+    sel = np.flatnonzero(status)
+    excluded = [(np.concatenate([np.asarray(constrained_indices[i]), internal]) if len(internal_constraints) > 0
+                 else np.asarray(constrained_indices[i])).ravel() for i in sel]
+    ok, _ = scramble_check_batch(atoms, X[sel], excluded, graphs, max_newbonds=max_newbonds)
+    mask = status.copy()
+    mask[sel] = ok
     return mask
 
 

@@ -382,6 +382,37 @@ int fc_clash_fragments(const double *coords, int64_t N, int64_t A, const int64_t
  * NON-BONDED pairs with d < thresh; adj is an (A, A) byte adjacency matrix. */
 int fc_clash_graph(const double *coords, int64_t N, int64_t A, const uint8_t *adj, double thresh,
                    int64_t *counts_out);
+/* ---- bond-topology check: molecule_check / scramble_check (firecode/utils.py:341-400), batched over N structures
+ * (DESIGN.md section 11).  The bond rule is graphize's: i < j are bonded in a structure iff
+ *   fl(sqrt(((dx*dx) + dy*dy) + dz*dz)) < class_thresh[atom_class[i] * n_class + atom_class[j]]     (strict <)
+ * -- the caller fills class_thresh (n_class x n_class, symmetric, 1 <= n_class <= 64) with graphize's own
+ * fl(1.2 * fl(r_p + r_q)); the library turns each entry into a squared threshold once (no square roots on the device).
+ * For structure n (coords (N, A, 3)):
+ *   delta(n) = { i < j : bonded(coords[n], i, j) != (i, j) in B_ref(n) }  minus every pair with i or j in excluded(n)
+ *   counts_out[n] = |delta(n)|,  ok_out[n] = counts_out[n] <= max_newbonds   (negative max_newbonds: never ok)
+ * Exactly one reference:
+ *   molecule mode  ref_coords: B_ref(n) = the bonds of ref_coords + n * ref_stride (ref_stride 0: one (A, 3) reference
+ *                  shared by all structures; 3A: (N, A, 3), one per structure), ref_bits = NULL;
+ *   scramble mode  ref_bits: (A, ceil(A/64)) uint64 words, bit j of row i (word j/64, bit j%64) set when i-j is a
+ *                  reference bond (only i < j is read), shared by all structures; ref_coords = NULL.
+ * excluded(n): CSR over atom indices -- excl_offsets (excl_sets + 1, [0] = 0, non-decreasing), excl_atoms; excl_sets
+ * = 1 (one set for all structures) or N; values outside [0, A) and duplicates are ignored.  excl_offsets = NULL: none.
+ * counts_out / ok_out (N, either may be NULL).
+ * fc_bond_changes_list: the changed bonds themselves.  offsets (N + 1) = 0 followed by the running sum of the
+ * counts of fc_bond_changes on the same inputs; bonds_out (offsets[N], 3) int64: rows offsets[n] .. offsets[n+1]-1
+ * are structure n's (i, j, +1 formed / -1 broken) in row-major (i, j) order.  FC_E_INVALID when the offsets do not
+ * match the counts (nothing is written).
+ * FC_E_INVALID before any device use: bad shape, NULL pointers, class or stride out of range, both or neither
+ * reference, malformed offsets.  N = 0: nothing to do.  FC_E_LIMIT: A >= 2^31, or more device memory than the device
+ * has.  Any A and N otherwise: structures are read from HBM in row tiles, not staged in LDS. */
+int fc_bond_changes(const double *coords, int64_t N, int64_t A, const int32_t *atom_class, int64_t n_class,
+                    const double *class_thresh, const double *ref_coords, int64_t ref_stride, const uint64_t *ref_bits,
+                    const int64_t *excl_offsets, const int64_t *excl_atoms, int64_t excl_sets, int64_t max_newbonds,
+                    int64_t *counts_out, uint8_t *ok_out);
+int fc_bond_changes_list(const double *coords, int64_t N, int64_t A, const int32_t *atom_class, int64_t n_class,
+                         const double *class_thresh, const double *ref_coords, int64_t ref_stride,
+                         const uint64_t *ref_bits, const int64_t *excl_offsets, const int64_t *excl_atoms,
+                         int64_t excl_sets, const int64_t *offsets, int64_t *bonds_out);
 /* a21: fitness_check (optimization_methods.py:163-180) for N structures with C
  * constraints each: pairs (N, C, 2), targets (N, C) (NaN = no target);
  * pass_out[n] = sum(|x_a - x_b| - target) < threshold; error_out may be NULL. */
