@@ -12,7 +12,7 @@
 // correctly rounded, so  fl(sqrt(d2)) < t  <=>  d2 < T(t)  with
 // T(t) = min{x : fl(sqrt(x)) >= t}, computed once on the host
 // (sq_threshold_lt / sq_threshold_le below).
-#include "fc_common.h"
+#include "fc_internal.h"
 
 #include <algorithm>
 #include <cmath>

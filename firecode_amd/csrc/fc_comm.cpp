@@ -17,7 +17,7 @@
 #include <algorithm>
 #include <memory>
 
-#include "fc_common.h"
+#include "fc_internal.h"
 
 namespace fc {
 namespace {

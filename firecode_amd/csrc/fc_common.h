@@ -294,6 +294,9 @@ inline int allow_dynamic_lds(const void *kernel, size_t bytes, const char *what)
   return FC_OK;
 }
 
+// LDS budget: 160 KiB per CU (and per workgroup) on gfx950; a column tile of the screens is A*3*64*8 bytes
+constexpr size_t kLdsLimit = 160 * 1024;
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // One grid dimension takes fewer than 2^32 threads; a launch that asks for more is not refused by the runtime, it runs
 // a truncated grid and leaves the rest of the output unwritten.  Launchers whose grid grows with N^2 check first.

@@ -33,7 +33,7 @@
 //
 // Limits: the representative's A x 24 bytes are staged in LDS up to kDiverseLdsAtoms atoms (48 KiB); beyond that the
 // same kernel reads them from global memory (k_diverse_step<.., false>): no size limit of its own besides N < 2^31.
-#include "fc_common.h"
+#include "fc_internal.h"
 #include "fc_kabsch_math.h"
 
 #include <cfloat>

@@ -13,14 +13,12 @@
 // n1*n2*2*na1*na2 poses are the cross product of two small tables of
 // pre-transformed structures (n_i * 2 * na_i each), and the clash test is an
 // all-pairs distance count between the tables, restricted to equal o.
-#include "fc_common.h"
+#include "fc_internal.h"
 #include "fc_kabsch_math.h"
 
 #include <algorithm>
 
 namespace fc {
-
-double sq_threshold_lt(double t);  // fc_clash.hip
 
 // rot_mat_from_pointer (prism_pruner.algebra): scalar-last quaternion -> matrix
 __device__ __forceinline__ void rot_axis_angle(double ax, double ay, double az, double angle_deg,

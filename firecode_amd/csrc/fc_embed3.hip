@@ -20,14 +20,12 @@
 //  * The accept filter is sequential in pose order; one wavefront walks it with the poses
 //    kept so far spread over its lanes; the covariance of two poses is the sum over the
 //    three molecules, read from LDS -- no pose is materialised.
-#include "fc_common.h"
+#include "fc_internal.h"
 #include "fc_kabsch_math.h"
 
 #include <algorithm>
 
 namespace fc {
-
-double sq_threshold_le(double t);  // fc_clash.hip
 
 namespace {
 

@@ -11,7 +11,7 @@
 // any fails the launcher keeps to the fp32-MFMA screen.  Also here: the 16 x 16 tile of covariances exactly as the screen
 // accumulates them (same instructions, same order), for the tests that compare them with fp64 arithmetic.
 // The reference has no counterpart: this is test and safety infrastructure of the screen, not a FIRECODE row.
-#include "fc_common.h"
+#include "fc_internal.h"
 #include "fc_kabsch_math.h"
 
 namespace fc {

@@ -1,0 +1,182 @@
+// fc_internal.h -- every function that one translation unit of libfc_hip.so defines and another one uses is declared
+// here and nowhere else, grouped by the file that defines it (what fc_common.h already declares stays there).  The
+// defining file includes this header too: a signature that drifts fails to compile instead of failing to link, or
+// linking and misbehaving.  Default arguments appear here only.  It brings fc_common.h with it.
+#pragma once
+
+#include "fc_common.h"
+
+namespace fc {
+
+// ---- fc_kabsch.hip ---------------------------------------------------------------------------------------
+int prebuild_screen_items(fc_ensemble *e);
+int launch_rmsd_values(fc_ensemble *e, double small_rmsd, double *rmsd_dev, double *maxdev_dev, int64_t rank = 0,
+                       int64_t world = 1, bool explicit_sum = false);
+int launch_gather_matrix_pairs(const double *rmsd_m, const double *maxdev_m, int64_t N, const int64_t *pi_dev,
+                               const int64_t *pj_dev, int64_t P, double *rmsd_out, double *maxdev_out);
+int launch_mirror_upper(double *m_dev, int64_t N);
+int launch_scatter_pairs(const uint64_t *pairs_dev, int64_t n_pairs, int64_t N, int64_t W, uint64_t *bits_dev);
+int launch_prep_begin(fc_ensemble *e);
+int launch_prep_body(const double *coords_dev, int64_t N, int64_t A_all, const int32_t *sel_dev, int64_t A, int center,
+                     fc_ensemble *e, const int32_t *conf_idx_dev);
+int launch_pairs_exact(const fc_ensemble *e, const int64_t *pi_dev, const int64_t *pj_dev, int64_t P, double *rmsd_dev,
+                       double *maxdev_dev, double *R_dev);
+int launch_matrix_exact(const fc_ensemble *e, double *rmsd_dev, double *maxdev_dev);
+int last_screen_kind();
+void screen_select(int kind);
+int ensure_h2_operands(fc_ensemble *e, double *scale_out);
+int launch_simbits_screen(fc_ensemble *e, double thr2_margin);
+int debug_screen_plan(int64_t N, int64_t A, int64_t row_block, bool lean, double g_max, double max_rmsd, int h2_model,
+                      int64_t plan_out[5]);
+int launch_simbits_refine(fc_ensemble *e, double max_rmsd, double max_dev, const double *energies_dev, double max_dE);
+int launch_align_to_first(const double *coords_dev, int64_t N, int64_t A, const int64_t *idx_dev, int64_t n_idx,
+                          double *out_dev);
+int launch_alignment_matrices(const double *p_dev, const double *q_dev, int64_t n, int64_t A, double *M_dev);
+int warm_kabsch();
+// ---- fc_h2_check.hip -------------------------------------------------------------------------------------
+int h2_model_ok(bool *ok);
+int h2_model_report(int64_t trials, int64_t *flags_out, double *worst_out);
+int launch_h2_cov_tile(const fc_ensemble *e, int64_t ib, int64_t jb, float *out_dev);
+int warm_h2_check();
+// ---- fc_prune.hip ----------------------------------------------------------------------------------------
+int launch_leader_chunk(const double *tf_dev, int64_t Q, int64_t chunk0, int64_t P, const uint8_t *pass_dev,
+                        double *accT_dev, int64_t cap, unsigned long long *n_acc_dev, double thresh,
+                        uint8_t *rejected_dev, uint8_t *accept_dev);
+int launch_pack_mask(const uint8_t *mask_dev, int64_t N, uint64_t *mbits_dev, int64_t W,
+                     unsigned long long *counters_dev);
+int launch_level(const uint64_t *bits_dev, int64_t W, const uint64_t *mbits_dev, const uint8_t *mask_in,
+                 uint8_t *mask_out, int64_t N, int64_t k, int64_t IB, int64_t rank, int64_t world, int64_t rows_local);
+int launch_mask_init(uint64_t *mb_dev, int64_t N, int64_t W, int64_t total_words);
+int launch_level_fused(const uint64_t *bits_dev, int64_t W, const uint64_t *mb_in, uint64_t *mb_out, int64_t N,
+                       int64_t k, int64_t min_per_group, unsigned long long *counters);
+void prune_conventions_set(int drop_later);
+int prune_drop_later();
+int launch_ladder_pairs_many(const uint64_t *pairs_dev, uint64_t *buckets_dev, const unsigned long long *n_pairs_dev,
+                             const unsigned long long *n_cand_dev, unsigned long long cand_cap, unsigned long long cap,
+                             int64_t N, int64_t W, int64_t min_per_group, const int64_t *ladder_dev,
+                             const int64_t *ladder_host, int n_ladder, uint64_t *mask_bufs_dev, uint64_t *mask_out_dev,
+                             unsigned long long *counters_dev);
+int launch_ladder_pairs(const uint64_t *pairs_dev, uint64_t *buckets_dev, const unsigned long long *n_pairs_dev,
+                        const unsigned long long *n_cand_dev, unsigned long long cand_cap, unsigned long long cap,
+                        int64_t N, int64_t W, int64_t min_per_group, const int64_t *ladder_dev, int n_ladder,
+                        uint64_t *mask_out_dev, unsigned long long *counters_dev);
+int launch_export_pairs(const uint64_t *simq_dev, const unsigned long long *counters_dev, unsigned long long cand_cap,
+                        int64_t cap, uint64_t *out_dev);
+int launch_compact_gathered(const uint64_t *gathered_dev, int world, int64_t cap, uint64_t *list_dev,
+                            unsigned long long *counters_dev);
+int launch_copy_bytes(const uint8_t *src, uint8_t *dst, int64_t n);
+int launch_inertia_moments(const double *coords_dev, int64_t N, int64_t A, const double *masses_dev,
+                           double *moments_dev);
+int launch_moi_simbits(const double *moments_dev, int64_t N, double tol, const double *energies_dev, double max_dE,
+                       uint64_t *bits_dev, int64_t W);
+int launch_transpose_pad(const double *in_dev, int64_t N, int64_t Q, int64_t Npad, double *out_dev);
+int launch_gather_transpose_pad(const double *in_dev, const double *first_dev, const int64_t *idx_dev, int64_t M,
+                                int64_t Q, int64_t Npad, double *out_dev);
+int launch_tfd_first_match(const double *tfT_dev, int64_t N, int64_t Npad, int64_t Q, double thresh, int64_t *fm_dev,
+                           float *tfF_scratch);
+int launch_tfd_simbits(const double *tf_dev, int64_t N, int64_t Q, double thresh, int64_t row_begin, int64_t row_end,
+                       uint64_t *bits_dev, int64_t W);
+int warm_prune();
+// ---- fc_clash.hip ----------------------------------------------------------------------------------------
+double sq_threshold_lt(double t);
+double sq_threshold_le(double t);
+int launch_clash_self(const double *coords_dev, int64_t N, int64_t A, double lo, double hi, int64_t *counts_dev);
+int launch_clash_fragments(const double *coords_dev, int64_t N, int64_t A, const int64_t *ids, int64_t n_ids,
+                           double thresh, int64_t max_clashes, int64_t *counts_dev, uint8_t *pass_dev);
+int launch_clash_graph(const double *coords_dev, int64_t N, int64_t A, const uint8_t *adj_dev, double thresh,
+                       int64_t *counts_dev);
+int launch_fitness(const double *coords_dev, int64_t N, int64_t A, const int64_t *pairs_dev, const double *targets_dev,
+                   int64_t C, double threshold, double *err_dev, uint8_t *pass_dev);
+int launch_rototranslate(const double *coords_dev, int64_t n, int64_t A, const double *R_dev, const double *t_dev,
+                         double *out_dev);
+int launch_center_structures(const double *coords_dev, int64_t N, int64_t A, double *out_dev);
+int launch_moi_diag_pairs(const double *moments_dev, int64_t N, double *P_dev, double *Q_dev);
+int launch_set_identity(double *M_dev);
+int launch_embed_poses_clash(const double *m1_dev, int64_t A1, const double *m2_dev, int64_t A2, const int64_t *c1_dev,
+                             const int64_t *c2_dev, const double *R1_dev, const double *t1_dev, const double *R2_dev,
+                             const double *t2_dev, int64_t P, double thresh, int64_t max_clashes, int64_t *counts_dev,
+                             uint8_t *pass_dev, double *poses_dev);
+int warm_clash();
+// ---- fc_torsion.hip --------------------------------------------------------------------------------------
+int launch_torsion_scan(const double *base_dev, int64_t A, const int64_t *torsions_dev, int64_t T,
+                        const uint8_t *rotmasks_dev, const int16_t *mv_dev, const int16_t *rs_dev,
+                        const int32_t *nmv_dev, const int32_t *nrs_dev, const int64_t *angles_dev, int64_t S,
+                        double thresh, int64_t backoff, double *out_dev, int64_t *rot_dev, const int64_t *quads_dev,
+                        int64_t Q, double *tf_dev);
+int launch_rotcorr_simbits(const double *X_dev, int64_t N, int64_t A, const uint8_t *heavy_dev, const int64_t *tors_dev,
+                           int64_t T, const uint8_t *rotmasks_dev, const double *angles_dev,
+                           const int32_t *n_angles_dev, int max_angles, double max_rmsd, double max_dev,
+                           const double *energies_dev, double max_dE, uint64_t *bits_dev, int64_t W);
+int launch_torsion_fingerprint(const double *coords_dev, int64_t N, int64_t A, const int64_t *quads_dev, int64_t Q,
+                               double *tf_dev);
+int launch_angle_grid(const int64_t *values_dev, const int64_t *first_dev, const int64_t *counts_dev, int64_t T,
+                      int64_t S, int64_t *out_dev);
+int launch_rows_to_sets(const int64_t *idx_dev, const int64_t *rows_dev, int64_t n, int64_t *out_dev);
+int launch_select_rotated(const int64_t *rot_dev, int64_t S, int64_t *idx_dev, int64_t *count_dev, DevBuf &tmp);
+int warm_torsion();
+// ---- fc_embed.hip ----------------------------------------------------------------------------------------
+int launch_string_transforms(const double *cen1, const double *vec1, int64_t n1, int64_t K1, const double *cen2,
+                             const double *vec2, int64_t n2, int64_t K2, const double *angles, int64_t nA,
+                             double *R_dev, double *t_dev, int64_t *c1_dev, int64_t *c2_dev);
+int launch_pose_fingerprints(const double *m1, int64_t A1, const double *m2, int64_t A2, const int64_t *c1,
+                             const int64_t *c2, const double *R2, const double *t2, int64_t P, const int64_t *quads,
+                             int64_t Q, const uint8_t *pass, double *tf);
+int launch_embed_group_dedupe(const double *X1a, int64_t n1, int64_t A1, int64_t na1, const double *X2a, int64_t n2,
+                              int64_t A2, int64_t na2, double thr, const uint8_t *pass_dev, uint8_t *accept_dev);
+int launch_embed_mol_transforms(const double *coords_dev, int64_t n, int64_t A, const int64_t *reactive_dev, int nr,
+                                const double *ps_dev, const double *pe_dev, int mol, const double *angles_dev,
+                                int64_t na, double *R_dev, double *t_dev);
+int launch_embed_pretransform(const double *coords_dev, int64_t n, int64_t A, int64_t na, const double *R_dev,
+                              const double *t_dev, int aos, int64_t S, double *out_dev);
+int launch_embed_grid_clash(const double *X1_dev, int64_t n1, int64_t A1, int64_t na1, const double *X2s_dev,
+                            int64_t n2, int64_t A2, int64_t na2, int64_t S2, double thresh, int64_t max_clashes,
+                            void *scratch, size_t scratch_bytes, uint8_t *pass_dev, int32_t *counts_dev);
+int warm_embed();
+// ---- fc_embed3.hip ---------------------------------------------------------------------------------------
+size_t tri_group_lds_bytes(int64_t Atot, int U, int S);
+int launch_tri_embed(const double *const coords_dev[3], const int64_t *const reactive_dev[3], const int64_t A[3],
+                     const int64_t nr[3], int64_t J, const int64_t *conf_dev, const double *piv_start_dev,
+                     const double *piv_end_dev, const double *vecs_dev, const double *dirs0_dev, const uint8_t *run_dev,
+                     const int64_t *rtab_dev, const double *norms_dev, const double *ua_dev, int U,
+                     const int32_t *aidx_dev, int S, double thresh, int max_clashes, double rmsd_thr, double *dirs_dev,
+                     double *Rt_dev, uint8_t *pass_dev, uint8_t *accept_dev);
+int warm_embed3();
+// ---- fc_diverse.hip --------------------------------------------------------------------------------------
+int diverse_lanes(int64_t N);
+int select_diverse(fc_ensemble *e, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
+                   double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected, double *ms_device);
+int warm_diverse();
+// ---- fc_tfd_ladder.hip -----------------------------------------------------------------------------------
+int tfd_ladder_device(const int64_t *fm_dev, const int64_t *fm_host, int64_t N, uint8_t *mask_out);
+int pyset_order_pairs_device(const int64_t *pairs_host, int64_t n, int64_t *order_out);
+int warm_tfd_ladder();
+// ---- fc_tfd_host.cpp -------------------------------------------------------------------------------------
+void pyset_order_ints(const int64_t *keys, int64_t n, std::vector<int64_t> &out);
+void pyset_order_pairs(const int64_t *pairs, int64_t n, std::vector<int64_t> &out);
+int tfd_apply_levels_host(const int64_t *fm, int64_t N, const std::vector<const uint8_t *> &level_flags,
+                          int first_level, const uint8_t *first_last_flags, uint8_t *mask_out, int64_t active_known);
+int tfd_ladder_host_only(const int64_t *fm, int64_t N, uint8_t *mask_out);
+int tfd_ladder_from_first_match(const int64_t *fm, int64_t N, uint8_t *mask_out, const int64_t *fm_dev = nullptr);
+int tfd_ladder_from_device(const int64_t *fm_dev, int64_t N, uint8_t *mask_out);
+uint32_t host_component_first_big(const uint32_t *mx, const uint32_t *mp, const uint32_t *ms, int64_t n,
+                                  uint32_t n_graph);
+int tfd_ladder_emulate_device(const int64_t *fm, int64_t N, uint8_t *mask_out);
+// ---- fc_comm.cpp -----------------------------------------------------------------------------------------
+int comm_rank();
+int comm_world();
+int comm_allgather_dev(const void *send_dev, void *recv_dev, size_t bytes, int lane);
+void comm_teardown();
+// ---- fc_xyz.cpp ------------------------------------------------------------------------------------------
+int xyz_write(const char *path, const char *const *atoms, int64_t A, const double *coords, int64_t N, const char *label,
+              int mode);
+int xyz_read(const char *path, int64_t *N_io, int64_t *A_io, char *atoms_out, double *coords_out);
+
+// ---- shared by the fc_api_*.cpp files ----------------------------------------------------------------------------
+// host array -> device buffer (grown to fit)
+template <class T>
+inline int upload(DevBuf &b, const T *host, size_t count) {
+  FC_TRY(b.reserve(count * sizeof(T)));
+  return h2d(b.p, host, count * sizeof(T));
+}
+
+}  // namespace fc

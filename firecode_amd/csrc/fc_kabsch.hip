@@ -13,7 +13,7 @@
 // scalar unit fetches with s_load (wave-uniform address).
 #include <type_traits>
 
-#include "fc_common.h"
+#include "fc_internal.h"
 #include <vector>
 #include "fc_kabsch_math.h"
 
@@ -21,9 +21,6 @@
 #include <cstdlib>
 
 namespace fc {
-
-// LDS budget: a column tile is A*3*64*8 bytes; 160 KiB per CU on gfx950
-static constexpr size_t kLdsLimit = 160 * 1024;
 
 // ---------------------------------------------------------------------------
 // k_prep: AoS (N, A_all, 3) -> conformer-minor SoA of the selected atoms,
@@ -3277,7 +3274,7 @@ int launch_scatter_pairs(const uint64_t *pairs_dev, int64_t n_pairs, int64_t N, 
 }
 
 // ---------------------------------------------------------------------------
-// host-side launchers (called from fc_api.cpp)
+// host-side launchers (called from fc_api_prune.cpp and fc_api_geom.cpp; declared in fc_internal.h)
 // ---------------------------------------------------------------------------
 // the largest G lands in the last counter word (zeroed here); ensemble_build reads it behind its own wait
 int launch_prep_begin(fc_ensemble *e) {
@@ -3356,8 +3353,6 @@ int last_screen_kind() { return g_last_screen; }
 // fc_screen_select: 0 = automatic (FC_SCREEN_F32 / FC_SCREEN_H2 / band estimate), 16 / 32 / 64 = that screen whatever the band
 static int g_screen_forced = 0;
 void screen_select(int kind) { g_screen_forced = kind; }
-
-int h2_model_ok(bool *ok);  // fc_h2_check.hip
 
 // ---- which screen a prune runs (plan_screen) and its launch ------------------------------------------------------------
 // The switches of the choice (screen_knobs), read from the environment and from fc_screen_select.

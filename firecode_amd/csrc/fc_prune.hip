@@ -10,7 +10,7 @@
 // similar.  Rejections inside a level do not feed back into that level, so a
 // level is a data-parallel map over rows of the bit matrix:
 //     out[i] = in[i] && !any_{i<j<last(i)} ( in[j] && sim[i][j] )
-#include "fc_common.h"
+#include "fc_internal.h"
 #include "fc_kabsch_math.h"
 
 namespace fc {

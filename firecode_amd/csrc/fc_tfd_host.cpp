@@ -31,7 +31,7 @@
 #include <new>
 #include <system_error>
 
-#include "fc_common.h"
+#include "fc_internal.h"
 #include "fc_tfd_core.h"
 
 namespace fc {
@@ -738,7 +738,6 @@ int tfd_ladder_host_only(const int64_t *fm, int64_t N, uint8_t *mask_out) {
   }
 }
 
-int tfd_ladder_device(const int64_t *fm_dev, const int64_t *fm_host, int64_t N, uint8_t *mask_out);  // fc_tfd_ladder.hip
 constexpr int64_t kDeviceLadderMin = 20000;  // below: a few hundred microseconds of host work, less than the device's launches
 
 // fm_dev (may be nullptr): the same array on the device -- the ladder then runs there (FC_TFD_GPU=0: on the host anyway)

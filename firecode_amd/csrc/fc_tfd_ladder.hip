@@ -29,17 +29,12 @@
 #include <cstdlib>
 #include <vector>
 
-#include "fc_common.h"
+#include "fc_internal.h"
 #include "fc_tfd_core.h"
 
 namespace fc {
 
 using namespace tfd;
-
-int tfd_apply_levels_host(const int64_t *fm, int64_t N, const std::vector<const uint8_t *> &level_flags, int first_level,
-                          const uint8_t *first_last_flags, uint8_t *mask_out, int64_t active_known);  // fc_tfd_host.cpp
-uint32_t host_component_first_big(const uint32_t *mx, const uint32_t *mp, const uint32_t *ms, int64_t n, uint32_t n_graph);
-int tfd_ladder_host_only(const int64_t *fm, int64_t N, uint8_t *mask_out);
 
 namespace {
 
@@ -820,7 +815,7 @@ static int launch_comp(hipStream_t st, const CompRecord *rec, const uint32_t *li
     attr_set = true;
   }
   // as many workgroups as fit the chip at once (by their LDS), or fewer when the class cannot have that many components
-  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)(160 * 1024) / (int64_t)(lds + 1024)));
+  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)kLdsLimit / (int64_t)(lds + 1024)));
   const int64_t work = BLOCK ? most : ceil_div(most, 4);
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(work, (int64_t)ctx().n_cu * per_cu));
   if (BLOCK) hipLaunchKernelGGL((k_comp_block<CAP, TBL, CAP2>), dim3(grid), dim3(256), lds, st, rec, list, count, mx, mp, ms, flags);

@@ -14,12 +14,10 @@
 // (rest x moving) rectangle over the 64 lanes and reduces with a ballot.
 #include <hipcub/hipcub.hpp>
 
-#include "fc_common.h"
+#include "fc_internal.h"
 #include "fc_kabsch_math.h"
 
 namespace fc {
-
-double sq_threshold_lt(double t);  // fc_clash.hip
 
 // rot_mat_from_pointer: scalar-last quaternion [sin(a/2) n, cos(a/2)] -> matrix.  The sine and cosine of the half
 // angle depend on the angle alone: callers that apply the same angle again and again (the 5-degree back-off of the

@@ -25,7 +25,7 @@
 #include <string>
 #include <vector>
 
-#include "fc_common.h"
+#include "fc_internal.h"
 
 namespace fc {
 
