@@ -58,6 +58,8 @@ _SIGNATURES = {
     "fc_ensemble_shape": [_ens, _p_i64, _p_i64],
     "fc_kabsch_rmsd_pairs": [_p_f64, _i64, _i64, _p_u8, _p_i64, _p_i64, _i64, C.c_int, _p_f64, _p_f64],
     "fc_ensemble_rmsd_pairs": [_ens, _p_i64, _p_i64, _i64, _p_f64, _p_f64],
+    "fc_kabsch_rmsd_pairs_inv": [_p_f64, _i64, _i64, _p_u8, _p_i64, _p_i64, _i64, C.c_int, _p_f64, _p_f64],
+    "fc_ensemble_rmsd_pairs_inv": [_ens, _p_i64, _p_i64, _i64, _p_f64, _p_f64],
     "fc_ensemble_rmsd_matrix": [_ens, _p_f64, _p_f64],
     "fc_ensemble_rmsd_values": [_ens, _p_f64, _p_f64],
     "fc_ensemble_rmsd_and_max_all": [_ens, _p_f64, _p_f64, _p_f64],
@@ -71,6 +73,8 @@ _SIGNATURES = {
     "fc_alignment_matrices": [_p_f64, _p_f64, _i64, _i64, _p_f64],
     "fc_rmsd_simbits": [_ens, _f64, _f64, _p_f64, _f64, _i64, _i64, _p_u64, _p_i64],
     "fc_prune_rmsd": [_ens, _f64, _f64, _p_f64, _f64, _i64, _p_u8, _p_i64],
+    "fc_rmsd_simbits_enant": [_ens, _f64, _f64, _p_f64, _f64, _i64, _i64, _p_u64, _p_i64],
+    "fc_prune_rmsd_enant": [_ens, _f64, _f64, _p_f64, _f64, _i64, _p_u8, _p_i64],
     "fc_prune_rmsd_host": [_p_f64, _i64, _i64, _p_u8, C.c_int, _f64, _f64, _p_f64, _f64, _i64, _p_u8, _p_i64],
     "fc_greedy_prune_from_bits": [_p_u64, _i64, _i64, _p_u8],
     "fc_prune_rmsd_begin": [_ens, _f64, _f64, _p_f64, _f64, _i64, _i64, _i64, _p_i64],
@@ -381,6 +385,14 @@ def device_info():
     return {"name": name.value.decode(), "n_cu": ncu.value, "hbm_bytes": hbm.value}
 
 
+def check_flag(name, value):
+    """The boolean keywords of the enantiomer-aware forms (``inverted=``, ``prune_enantiomers=``): a real bool, checked
+    before any device use -- ``1``, ``"yes"`` or an array would otherwise pick a kernel by truthiness."""
+    if not isinstance(value, (bool, np.bool_)):
+        raise FirecodeHipInputError(FC_E_INVALID, f"{name} must be a bool, got {value!r}")
+    return bool(value)
+
+
 class DeviceEnsemble:
     """HBM-resident prepared ensemble (fc_ensemble)."""
 
@@ -419,11 +431,15 @@ class DeviceEnsemble:
             raise FirecodeHipInputError(FC_E_INVALID, "ensemble already destroyed")
         return self._h
 
-    def rmsd_pairs(self, pair_i, pair_j):
+    def rmsd_pairs(self, pair_i, pair_j, inverted=False):
+        """(rmsd, maxdev) of the pairs; ``inverted=True``: of (X_i, -X_j), the partner's mirror image
+        (fc_ensemble_rmsd_pairs_inv)."""
+        inverted = check_flag("inverted", inverted)
         pi_, pj_ = i64(pair_i), i64(pair_j)
         P = int(pi_.shape[0])
         r, m = np.empty(P), np.empty(P)
-        call("fc_ensemble_rmsd_pairs", self.handle, pi(pi_), pi(pj_), P, pf(r), pf(m))
+        call("fc_ensemble_rmsd_pairs_inv" if inverted else "fc_ensemble_rmsd_pairs", self.handle, pi(pi_), pi(pj_), P,
+             pf(r), pf(m))
         return r, m
 
     def select_diverse(self, n_max, start=0, stop_rmsd=None):
@@ -499,20 +515,26 @@ class DeviceEnsemble:
              C.byref(k), C.byref(t), pi(stats))
         return k.value, t.value, stats, r, m
 
-    def simbits(self, max_rmsd, max_dev, energies=None, max_dE=0.0, row_begin=0, row_end=None):
+    def simbits(self, max_rmsd, max_dev, energies=None, max_dE=0.0, row_begin=0, row_end=None, prune_enantiomers=False):
+        """Similarity bits (fc_rmsd_simbits); ``prune_enantiomers=True``: a pair is also similar when it is so with one
+        partner inverted (fc_rmsd_simbits_enant; the contract is in include/fc_hip.h)."""
+        enant = check_flag("prune_enantiomers", prune_enantiomers)
         row_end = self.N if row_end is None else int(row_end)
         bits = np.zeros((row_end - row_begin, self.W), dtype=np.uint64)
         grey = C.c_int64(0)
         en = None if energies is None else f64(energies)
-        call("fc_rmsd_simbits", self.handle, float(max_rmsd), float(max_dev), pf(en), float(max_dE),
+        call("fc_rmsd_simbits_enant" if enant else "fc_rmsd_simbits", self.handle, float(max_rmsd), float(max_dev), pf(en), float(max_dE),
              int(row_begin), row_end, pw(bits), C.byref(grey))
         return bits, grey.value
 
-    def prune(self, max_rmsd, max_dev, energies=None, max_dE=0.0, min_per_group=20):
+    def prune(self, max_rmsd, max_dev, energies=None, max_dE=0.0, min_per_group=20, prune_enantiomers=False):
+        """The whole stage (fc_prune_rmsd) -> (mask, stats); ``prune_enantiomers=True``: mirror images count as
+        duplicates (fc_prune_rmsd_enant)."""
+        enant = check_flag("prune_enantiomers", prune_enantiomers)
         mask = np.zeros(self.N, dtype=np.uint8)
         stats = np.zeros(6, dtype=np.int64)
         en = None if energies is None else f64(energies)
-        call("fc_prune_rmsd", self.handle, float(max_rmsd), float(max_dev), pf(en), float(max_dE),
+        call("fc_prune_rmsd_enant" if enant else "fc_prune_rmsd", self.handle, float(max_rmsd), float(max_dev), pf(en), float(max_dE),
              int(min_per_group), pb(mask), pi(stats))
         return mask.astype(bool), stats
 

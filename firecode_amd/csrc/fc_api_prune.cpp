@@ -594,8 +594,8 @@ int fc_ensemble_shape(const fc_ensemble *ens, int64_t *N, int64_t *A_selected) {
 }
 
 // ---- a4 ------------------------------------------------------------------------
-int fc_ensemble_rmsd_pairs(fc_ensemble *ens, const int64_t *pair_i, const int64_t *pair_j,
-                           int64_t P, double *rmsd_out, double *maxdev_out) {
+static int ensemble_rmsd_pairs(fc_ensemble *ens, const int64_t *pair_i, const int64_t *pair_j, int64_t P, double *rmsd_out,
+                               double *maxdev_out, bool inverted) {
   FC_API_LOCK;
   FC_REQUIRE(ens != nullptr, "ens is NULL");
   FC_REQUIRE(ens->epoch == ctx().epoch, "this ensemble was created before fc_shutdown / a device switch: create it again");
@@ -613,21 +613,39 @@ int fc_ensemble_rmsd_pairs(fc_ensemble *ens, const int64_t *pair_i, const int64_
   FC_TRY(dr.reserve((size_t)P * sizeof(double)));
   FC_TRY(dm.reserve((size_t)P * sizeof(double)));
   FC_TRY(launch_pairs_exact(ens, di.as<int64_t>(), dj.as<int64_t>(), P, dr.as<double>(),
-                            dm.as<double>(), nullptr));
+                            dm.as<double>(), nullptr, inverted));
   FC_TRY(d2h(rmsd_out, dr.p, (size_t)P * sizeof(double)));
   FC_TRY(d2h(maxdev_out, dm.p, (size_t)P * sizeof(double)));
   return sync();
 }
+int fc_ensemble_rmsd_pairs(fc_ensemble *ens, const int64_t *pair_i, const int64_t *pair_j,
+                           int64_t P, double *rmsd_out, double *maxdev_out) {
+  return ensemble_rmsd_pairs(ens, pair_i, pair_j, P, rmsd_out, maxdev_out, false);
+}
+// the values of (X_i, -X_j): the partner inverted through the origin (include/fc_hip.h, "enantiomer-aware forms")
+int fc_ensemble_rmsd_pairs_inv(fc_ensemble *ens, const int64_t *pair_i, const int64_t *pair_j, int64_t P, double *rmsd_out,
+                               double *maxdev_out) {
+  return ensemble_rmsd_pairs(ens, pair_i, pair_j, P, rmsd_out, maxdev_out, true);
+}
 
-int fc_kabsch_rmsd_pairs(const double *coords, int64_t N, int64_t A, const uint8_t *atom_mask,
-                         const int64_t *pair_i, const int64_t *pair_j, int64_t P, int center,
-                         double *rmsd_out, double *maxdev_out) {
+static int kabsch_rmsd_pairs(const double *coords, int64_t N, int64_t A, const uint8_t *atom_mask, const int64_t *pair_i,
+                             const int64_t *pair_j, int64_t P, int center, double *rmsd_out, double *maxdev_out,
+                             bool inverted) {
   FC_API_LOCK;
   fc_ensemble *e = nullptr;
   FC_TRY(fc_ensemble_create(coords, N, A, atom_mask, center, &e));
-  const int rc = fc_ensemble_rmsd_pairs(e, pair_i, pair_j, P, rmsd_out, maxdev_out);
+  const int rc = ensemble_rmsd_pairs(e, pair_i, pair_j, P, rmsd_out, maxdev_out, inverted);
   fc_ensemble_destroy(e);
   return rc;
+}
+int fc_kabsch_rmsd_pairs(const double *coords, int64_t N, int64_t A, const uint8_t *atom_mask,
+                         const int64_t *pair_i, const int64_t *pair_j, int64_t P, int center,
+                         double *rmsd_out, double *maxdev_out) {
+  return kabsch_rmsd_pairs(coords, N, A, atom_mask, pair_i, pair_j, P, center, rmsd_out, maxdev_out, false);
+}
+int fc_kabsch_rmsd_pairs_inv(const double *coords, int64_t N, int64_t A, const uint8_t *atom_mask, const int64_t *pair_i,
+                             const int64_t *pair_j, int64_t P, int center, double *rmsd_out, double *maxdev_out) {
+  return kabsch_rmsd_pairs(coords, N, A, atom_mask, pair_i, pair_j, P, center, rmsd_out, maxdev_out, true);
 }
 
 // all pairs, both outputs: covariance tiles on the fp64 matrix pipe, rotation + explicit rotated
@@ -917,6 +935,35 @@ int fc_prune_rmsd(fc_ensemble *ens, double max_rmsd, double max_dev, const doubl
   note_candidates(ens, cnt[6], cnt[2]);
   if (stats) fill_stats(stats, ens->N * (ens->N - 1) / 2, cnt, levels, survivors);
   return FC_OK;
+}
+
+// ---- enantiomer-aware forms (include/fc_hip.h): the same entry points with fc_ensemble::enant set for the call ----
+// The flag selects the ENANT instantiations of the screen and refine kernels (launch_simbits_screen / _refine); it is
+// cleared when the call returns, whatever it returns, so no other entry point ever sees it.
+namespace {
+struct EnantScope {
+  fc_ensemble *e;
+  explicit EnantScope(fc_ensemble *ens) : e(ens) { e->enant = true; }
+  ~EnantScope() { e->enant = false; }
+  EnantScope(const EnantScope &) = delete;
+  EnantScope &operator=(const EnantScope &) = delete;
+};
+}  // namespace
+
+int fc_rmsd_simbits_enant(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                          int64_t row_begin, int64_t row_end, uint64_t *bits_out, int64_t *n_grey) {
+  FC_API_LOCK;
+  FC_REQUIRE(ens && bits_out, "NULL pointer argument");
+  EnantScope scope(ens);
+  return fc_rmsd_simbits(ens, max_rmsd, max_dev, energies, max_dE, row_begin, row_end, bits_out, n_grey);
+}
+
+int fc_prune_rmsd_enant(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                        int64_t min_per_group, uint8_t *mask_out, int64_t *stats) {
+  FC_API_LOCK;
+  FC_REQUIRE(ens && mask_out, "NULL pointer argument");
+  EnantScope scope(ens);
+  return fc_prune_rmsd(ens, max_rmsd, max_dev, energies, max_dE, min_per_group, mask_out, stats);
 }
 
 // prune_by_rmsd(host arrays) as ONE call (firecode/ensemble.py:230-235, firecode/embedder.py:1472-1474): upload, preparation,

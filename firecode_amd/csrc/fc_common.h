@@ -412,6 +412,10 @@ struct fc_ensemble {
   // set by the entry points whose consumer is the pair ladder or the exchange, which repeat the prune
   // with lean = false when the pair queue overflowed
   bool lean = false;
+  // enantiomer-aware prune (fc_prune_rmsd_enant / fc_rmsd_simbits_enant): a pair is similar as it is OR with one partner
+  // inverted through the origin.  Set for the duration of one such call (fc::EnantScope), false everywhere else:
+  // launch_simbits_screen and launch_simbits_refine read it to pick the ENANT instantiations of their kernels
+  bool enant = false;
   // second prune workspace over the same coordinates (Xs/Xa/G are views): lets the refine and
   // ladder of one prune run beside the screen of the next one (fc_bench_prune_rmsd)
   fc_ensemble *twin = nullptr;

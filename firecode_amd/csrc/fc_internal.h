@@ -20,7 +20,7 @@ int launch_prep_begin(fc_ensemble *e);
 int launch_prep_body(const double *coords_dev, int64_t N, int64_t A_all, const int32_t *sel_dev, int64_t A, int center,
                      fc_ensemble *e, const int32_t *conf_idx_dev);
 int launch_pairs_exact(const fc_ensemble *e, const int64_t *pi_dev, const int64_t *pj_dev, int64_t P, double *rmsd_dev,
-                       double *maxdev_dev, double *R_dev);
+                       double *maxdev_dev, double *R_dev, bool inverted = false);  // inverted: the values of (X_i, -X_j)
 int launch_matrix_exact(const fc_ensemble *e, double *rmsd_dev, double *maxdev_dev);
 int last_screen_kind();
 void screen_select(int kind);

@@ -203,7 +203,11 @@ k_prep_tile(const double *__restrict__ coords, int64_t N, int64_t A_all, const i
 // ---------------------------------------------------------------------------
 // Exact pair evaluation on the SoA layout: covariance, optimal rotation,
 // explicit rotated difference -> (rmsd, maxdev).  One lane per pair.
+// INV (all four forms): the values of (p, -q) -- the partner inverted through the origin, i.e. its mirror image --
+// from the same sums: covariance -B, rotation R' = kabsch_rotation(-B), difference p - R' (-q) = p + R' q.  Negation is
+// exact, so these are the values the proper form gives on negated coordinates, bit for bit (R_out: R').
 // ---------------------------------------------------------------------------
+template <bool INV = false>
 __device__ __forceinline__ void pair_exact(const double *__restrict__ Xs, int64_t Npad, int A,
                                            int64_t i, int64_t j, double &rmsd, double &maxdev,
                                            double *R_out = nullptr) {
@@ -223,15 +227,21 @@ __device__ __forceinline__ void pair_exact(const double *__restrict__ Xs, int64_
     B[8] = fma(pz, qz, B[8]);
   }
   double R[9];
+  if (INV) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) B[k] = -B[k];
+  }
   (void)kabsch_rotation(B, R);
   double ssq = 0.0, mx = 0.0;
   for (int a = 0; a < A; ++a) {
     const double *pa = Xs + (int64_t)(a * 3) * Npad;
     const double px = pa[i], py = pa[Npad + i], pz = pa[2 * Npad + i];
     const double qx = pa[j], qy = pa[Npad + j], qz = pa[2 * Npad + j];
-    const double dx = px - (R[0] * qx + R[1] * qy + R[2] * qz);
-    const double dy = py - (R[3] * qx + R[4] * qy + R[5] * qz);
-    const double dz = pz - (R[6] * qx + R[7] * qy + R[8] * qz);
+    const double rx = R[0] * qx + R[1] * qy + R[2] * qz, ry = R[3] * qx + R[4] * qy + R[5] * qz;
+    const double rz = R[6] * qx + R[7] * qy + R[8] * qz;
+    const double dx = INV ? px + rx : px - rx;
+    const double dy = INV ? py + ry : py - ry;
+    const double dz = INV ? pz + rz : pz - rz;
     const double s = dx * dx + dy * dy + dz * dz;
     ssq += s;
     mx = fmax(mx, s);
@@ -247,6 +257,7 @@ __device__ __forceinline__ void pair_exact(const double *__restrict__ Xs, int64_
 // Same evaluation from the conformer-major copy Xa: a lane that owns one pair
 // streams two contiguous A*24-byte blocks instead of gathering 6*A strided
 // doubles -- used wherever lanes of a wave hold unrelated pairs.
+template <bool INV = false>
 __device__ __forceinline__ void pair_exact_aos(const double *__restrict__ Xa, int A, int64_t i,
                                                int64_t j, double &rmsd, double &maxdev,
                                                double *R_out = nullptr) {
@@ -261,14 +272,20 @@ __device__ __forceinline__ void pair_exact_aos(const double *__restrict__ Xa, in
     B[6] = fma(pz, qx, B[6]); B[7] = fma(pz, qy, B[7]); B[8] = fma(pz, qz, B[8]);
   }
   double R[9];
+  if (INV) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) B[k] = -B[k];
+  }
   (void)kabsch_rotation(B, R);
   double ssq = 0.0, mx = 0.0;
   for (int a = 0; a < A; ++a) {
     const double px = p[a * 3], py = p[a * 3 + 1], pz = p[a * 3 + 2];
     const double qx = q[a * 3], qy = q[a * 3 + 1], qz = q[a * 3 + 2];
-    const double dx = px - (R[0] * qx + R[1] * qy + R[2] * qz);
-    const double dy = py - (R[3] * qx + R[4] * qy + R[5] * qz);
-    const double dz = pz - (R[6] * qx + R[7] * qy + R[8] * qz);
+    const double rx = R[0] * qx + R[1] * qy + R[2] * qz, ry = R[3] * qx + R[4] * qy + R[5] * qz;
+    const double rz = R[6] * qx + R[7] * qy + R[8] * qz;
+    const double dx = INV ? px + rx : px - rx;
+    const double dy = INV ? py + ry : py - ry;
+    const double dz = INV ? pz + rz : pz - rz;
     const double s = dx * dx + dy * dy + dz * dz;
     ssq += s;
     mx = fmax(mx, s);
@@ -299,6 +316,7 @@ __device__ __forceinline__ double group8_max(double v) {
   return v;
 }
 
+template <bool INV = false>
 __device__ __forceinline__ void pair_exact_group8(const double *__restrict__ Xa, int A, int64_t i,
                                                   int64_t j, int sub, double &rmsd, double &maxdev) {
   const double *__restrict__ p = Xa + i * (int64_t)A * 3;
@@ -314,14 +332,20 @@ __device__ __forceinline__ void pair_exact_group8(const double *__restrict__ Xa,
 #pragma unroll
   for (int e = 0; e < 9; ++e) B[e] = group8_sum(B[e]);
   double R[9];
+  if (INV) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) B[k] = -B[k];
+  }
   (void)kabsch_rotation(B, R);  // identical in the 8 lanes of the group
   double ssq = 0.0, mx = 0.0;
   for (int a = sub; a < A; a += 8) {
     const double px = p[a * 3], py = p[a * 3 + 1], pz = p[a * 3 + 2];
     const double qx = q[a * 3], qy = q[a * 3 + 1], qz = q[a * 3 + 2];
-    const double dx = px - (R[0] * qx + R[1] * qy + R[2] * qz);
-    const double dy = py - (R[3] * qx + R[4] * qy + R[5] * qz);
-    const double dz = pz - (R[6] * qx + R[7] * qy + R[8] * qz);
+    const double rx = R[0] * qx + R[1] * qy + R[2] * qz, ry = R[3] * qx + R[4] * qy + R[5] * qz;
+    const double rz = R[6] * qx + R[7] * qy + R[8] * qz;
+    const double dx = INV ? px + rx : px - rx;
+    const double dy = INV ? py + ry : py - ry;
+    const double dz = INV ? pz + rz : pz - rz;
     const double s = dx * dx + dy * dy + dz * dz;
     ssq += s;
     mx = fmax(mx, s);
@@ -344,6 +368,7 @@ __device__ __forceinline__ double wave_max_f64(double v) {
   return v;
 }
 
+template <bool INV = false>
 __device__ __forceinline__ void pair_exact_wave(const double *__restrict__ Xs, int64_t Npad, int A,
                                                 int64_t i, int64_t j, int lane, double &rmsd,
                                                 double &maxdev) {
@@ -359,15 +384,21 @@ __device__ __forceinline__ void pair_exact_wave(const double *__restrict__ Xs, i
 #pragma unroll
   for (int e = 0; e < 9; ++e) B[e] = wave_sum_f64(B[e]);
   double R[9];
+  if (INV) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) B[k] = -B[k];
+  }
   (void)kabsch_rotation(B, R);
   double ssq = 0.0, mx = 0.0;
   for (int a = lane; a < A; a += 64) {
     const double *pa = Xs + (int64_t)(a * 3) * Npad;
     const double px = pa[i], py = pa[Npad + i], pz = pa[2 * Npad + i];
     const double qx = pa[j], qy = pa[Npad + j], qz = pa[2 * Npad + j];
-    const double dx = px - (R[0] * qx + R[1] * qy + R[2] * qz);
-    const double dy = py - (R[3] * qx + R[4] * qy + R[5] * qz);
-    const double dz = pz - (R[6] * qx + R[7] * qy + R[8] * qz);
+    const double rx = R[0] * qx + R[1] * qy + R[2] * qz, ry = R[3] * qx + R[4] * qy + R[5] * qz;
+    const double rz = R[6] * qx + R[7] * qy + R[8] * qz;
+    const double dx = INV ? px + rx : px - rx;
+    const double dy = INV ? py + ry : py - ry;
+    const double dz = INV ? pz + rz : pz - rz;
     const double s = dx * dx + dy * dy + dz * dz;
     ssq += s;
     mx = fmax(mx, s);
@@ -376,6 +407,7 @@ __device__ __forceinline__ void pair_exact_wave(const double *__restrict__ Xs, i
   maxdev = sqrt(wave_max_f64(mx));
 }
 
+template <bool INV = false>
 __global__ void __launch_bounds__(256)
 k_pairs_exact(const double *__restrict__ Xa, int A, const int64_t *__restrict__ pi,
               const int64_t *__restrict__ pj, int64_t P, double *__restrict__ rmsd,
@@ -383,7 +415,7 @@ k_pairs_exact(const double *__restrict__ Xa, int A, const int64_t *__restrict__ 
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P) return;
   double r, m;
-  pair_exact_aos(Xa, A, pi[p], pj[p], r, m, Rout ? Rout + p * 9 : nullptr);
+  pair_exact_aos<INV>(Xa, A, pi[p], pj[p], r, m, Rout ? Rout + p * 9 : nullptr);
   rmsd[p] = r;
   maxdev[p] = m;
 }
@@ -545,7 +577,9 @@ __device__ __forceinline__ void stage_pairs_wave32(uint64_t m, bool may, unsigne
 // = one uint64 word of the bit matrix, written by lane 0 (no atomics).
 // Pairs that pass the screen are re-evaluated exactly by k_simbits_refine.
 // ---------------------------------------------------------------------------
-template <bool USE_LDS, int TI, int NW>
+// ENANT (every screen below): the test at |det B| -- the pair may be similar as it is OR with one partner inverted
+// (kabsch_may_be_below).  Same matrix work, same polynomial, same queues.
+template <bool USE_LDS, int TI, int NW, bool ENANT = false>
 __global__ void __launch_bounds__(NW * 64)
 k_simbits_screen(const double *__restrict__ Xs, const double *__restrict__ G, int64_t N,
                  int64_t Npad, int A, double A_thr2, int IB, int64_t rank, int64_t world,
@@ -619,7 +653,7 @@ k_simbits_screen(const double *__restrict__ Xs, const double *__restrict__ G, in
     for (int k = 0; k < TI; ++k) {
       const int64_t i = ib + k;
       const double Gp = G[i];  // Npad-padded, wave-uniform
-      bool may = kabsch_may_be_below(acc[k], Gp + Gq, A_thr2);
+      bool may = kabsch_may_be_below<ENANT>(acc[k], Gp + Gq, A_thr2);
       may = may && (j > i) && (j < N) && (i < N);
       const uint64_t word = __ballot(may);
       push_pairs(word, may, (unsigned)i, (unsigned)j, pairq, Q, counters, lane);
@@ -670,7 +704,7 @@ typedef double d4_t __attribute__((ext_vector_type(4)));
 // difference).  The difference carries ~u (Gp + Gq) of rounding, so it holds 5e-11 in the rmsd only for pairs further
 // apart than ~1e-3 A (msd A > 2e-10 (Gp + Gq)^2 / A): closer pairs go to the fix-up kernel like the pairs whose rotation
 // was declined.  EIG = false (the launcher's retry when the fix-up queue overflowed: an ensemble of near-duplicates): the sum.
-template <int NW, int MODE = 0, int TC = 64, bool EIG = false>
+template <int NW, int MODE = 0, int TC = 64, bool EIG = false, bool ENANT = false>
 __global__ void __launch_bounds__(NW * 64, 2)
 k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ G, int64_t N,
                       int64_t Npad, int A, double A_thr2, int IB, int64_t rank, int64_t world,
@@ -680,6 +714,7 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
                       double *__restrict__ rmsd_out = nullptr, const unsigned long long *__restrict__ gate = nullptr,
                       double *__restrict__ maxdev_out = nullptr) {
   static_assert(!EIG || MODE == 2, "EIG: the complete alignments");
+  static_assert(!ENANT || MODE == 0, "ENANT: the screen only");
   constexpr bool VALUES = MODE != 0;  // 1: rmsd values (Newton), 2: (rmsd, maxdev) by explicit difference
   // sub-tiles (16 columns) per unit: two share the row operands in the screens; the complete-alignment
   // mode takes one at a time -- its epilogue (four rotations, an atom pass) needs the registers the second
@@ -1099,7 +1134,7 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
             stage_pairs(__ballot(redo), redo, (unsigned)i, (unsigned)j, stageQ, stageN, pairq, Q, counters, lane);
             continue;
           }
-          bool may = kabsch_may_be_below(B9, Gp + Gq, A_thr2);
+          bool may = kabsch_may_be_below<ENANT>(B9, Gp + Gq, A_thr2);
           may = may && (j > i) && (j < n32) && (i < n32);
           mr[r] = __ballot(may);
           if constexpr (MODE == 0)
@@ -1221,7 +1256,7 @@ typedef float f4_t __attribute__((ext_vector_type(4)));
 // two kernels, so that neither carries the other's registers
 // TC: conformers of the column tile: 64; 32 for structures whose 64-column tile does not fit the LDS (214 ... ~370 atoms: lean,
 // single-stage launches only) -- two runs of 32 columns per LDS-DMA instruction, one 16 x 32 unit per row tile
-template <int NW, bool BITS = true, bool STAGED = false, int TC = 64>
+template <int NW, bool BITS = true, bool STAGED = false, int TC = 64, bool ENANT = false>
 __global__ void __launch_bounds__(NW * 64, FC_F32_WGS)
 k_simbits_screen_mfma_f32(const float *__restrict__ Xsf, const double *__restrict__ G, int64_t N,
                           int64_t Npad, int A, double A_thr2, KabschF32Bounds bd, int IB, int64_t rank,
@@ -1425,7 +1460,7 @@ k_simbits_screen_mfma_f32(const float *__restrict__ Xsf, const double *__restric
           B9[0] = fmaf(px, qx, acc[t][0][r]); B9[1] = fmaf(px, qy, acc[t][1][r]); B9[2] = fmaf(px, qz, acc[t][2][r]);
           B9[3] = fmaf(py, qx, acc[t][3][r]); B9[4] = fmaf(py, qy, acc[t][4][r]); B9[5] = fmaf(py, qz, acc[t][5][r]);
           B9[6] = fmaf(pz, qx, acc[t][6][r]); B9[7] = fmaf(pz, qy, acc[t][7][r]); B9[8] = fmaf(pz, qz, acc[t][8][r]);
-          bool may = kabsch_may_be_below_f32(B9, sp[3] + gqc, half_A_thr2, bd1, sp[4] + gqu);
+          bool may = kabsch_may_be_below_f32<ENANT>(B9, sp[3] + gqc, half_A_thr2, bd1, sp[4] + gqu);
           may = may && (j > i) && (j < n32) && (i < n32);
           any1 = any1 || may;
         }
@@ -1449,7 +1484,7 @@ k_simbits_screen_mfma_f32(const float *__restrict__ Xsf, const double *__restric
 #ifdef FC_F32_ABLATE_POLY  // timing experiment only (results are wrong): the K loop without the polynomial
         bool may = (B9[0] + B9[4] + B9[8]) * B9[1] * B9[2] * B9[3] * B9[5] * B9[6] * B9[7] == 12345.678f;
 #else
-        bool may = kabsch_may_be_below_f32(B9, Gp + Gq, half_A_thr2, bd, Gp + Gq);
+        bool may = kabsch_may_be_below_f32<ENANT>(B9, Gp + Gq, half_A_thr2, bd, Gp + Gq);
 #endif
         may = may && (j > i) && (j < n32) && (i < n32);
         mr[r] = __ballot(may);
@@ -1571,6 +1606,7 @@ k_simbits_screen_mfma_f32(const float *__restrict__ Xsf, const double *__restric
 // Steps aside (counters[15]) when the sample of the subset stage found similarity dense: the
 // single-stage tiled kernel launched behind it then does the whole launch.
 // ---------------------------------------------------------------------------
+template <bool ENANT = false>
 __global__ void __launch_bounds__(256, 3)
 k_screen_units_f32(const float *__restrict__ Xsf, const double *__restrict__ G, int64_t N, int64_t Npad, int A,
                    double A_thr2, KabschF32Bounds bd, const uint64_t *__restrict__ unitq,
@@ -1662,7 +1698,7 @@ k_screen_units_f32(const float *__restrict__ Xsf, const double *__restrict__ G, 
         float B9[9];
 #pragma unroll
         for (int e = 0; e < 9; ++e) B9[e] = acc[t][e][r];
-        bool may = kabsch_may_be_below_f32(B9, Gp + Gq, half_A_thr2, bd, Gp + Gq);
+        bool may = kabsch_may_be_below_f32<ENANT>(B9, Gp + Gq, half_A_thr2, bd, Gp + Gq);
         may = may && (j > i) && (j < n32) && (i < n32);
         stage_pairs<kStagePairsF32>(__ballot(may), may, (unsigned)i, (unsigned)j, stageQ, stageN, pairq, Q, counters, lane);
       }
@@ -1743,7 +1779,7 @@ constexpr int64_t kH2MaxKS2 = 6;
 // TC: conformers of the column tile.  64; 32 for structures of 193 ... 416 atoms (7 ... 13 k-steps; lean launches only:
 // the bit-matrix layout is one 64-column word per tile) -- 12 KB of tile per k-step instead of 24, the row operands of
 // all k-steps still in registers (24 per k-step, one wavefront per SIMD has 512)
-template <int KS2, bool BITS, int TC = 64>
+template <int KS2, bool BITS, int TC = 64, bool ENANT = false>
 __global__ void __launch_bounds__(256, (KS2 <= 2 ? FC_H2_WGS : KS2 <= 3 ? 2 : 1))  // (four k-steps and more: the column tile leaves one workgroup per CU anyway)
 k_simbits_screen_mfma_h2(const h8_t *__restrict__ Xh, const double *__restrict__ G, int64_t N, int64_t Npad,
                          float half_A_thr2, float tiny_floor, float scale2, KabschF32Bounds bd, int IB, int64_t rank,
@@ -1912,7 +1948,7 @@ k_simbits_screen_mfma_h2(const h8_t *__restrict__ Xh, const double *__restrict__
                                             12345.678f * (Gp + Gq));
         rdm[r] = 0;
 #else
-        mr[r] = kabsch_may_be_below_f32_2t_wave(B9, Gp + Gq, half_A_thr2, bd, tiny_floor, rdm[r]);
+        mr[r] = kabsch_may_be_below_f32_2t_wave<ENANT>(B9, Gp + Gq, half_A_thr2, bd, tiny_floor, rdm[r]);
 #endif
       }
 #ifndef FC_ABLATE_REDO  // timing experiment only
@@ -1924,7 +1960,7 @@ k_simbits_screen_mfma_h2(const h8_t *__restrict__ Xh, const double *__restrict__
 #pragma unroll
           for (int e = 0; e < 9; ++e) B9[e] = acc[e][r];
           const uint64_t m3 =
-              __builtin_amdgcn_ballot_w64(kabsch_may_be_below_f32(B9, Gp + Gq, half_A_thr2, bd, Gp + Gq, tiny_floor));
+              __builtin_amdgcn_ballot_w64(kabsch_may_be_below_f32<ENANT>(B9, Gp + Gq, half_A_thr2, bd, Gp + Gq, tiny_floor));
           mr[r] = (mr[r] & ~rdm[r]) | (m3 & rdm[r]);
         }
       }
@@ -2081,6 +2117,7 @@ k_subset_stats(const double *__restrict__ Xs, int64_t Npad, int A, float *__rest
 // workgroups return at once.  Results do not depend on the verdict (both screens only ever add
 // candidates); time is bounded by fp32 screen + fp64 screen whatever the data look like.
 // ---------------------------------------------------------------------------
+template <bool ENANT = false>
 __global__ void __launch_bounds__(256)
 k_screen_verdict(const double *__restrict__ Xa, const double *__restrict__ G, int A, double A_thr2,
                  const uint64_t *__restrict__ pairq, unsigned long long Q, unsigned long long max_false,
@@ -2116,7 +2153,7 @@ k_screen_verdict(const double *__restrict__ Xa, const double *__restrict__ G, in
       B[e9] += __shfl_xor(B[e9], 1);
       B[e9] += __shfl_xor(B[e9], 2);
     }
-    pass = (on && sub == 0 && kabsch_may_be_below(B, G[i] + G[j], A_thr2)) ? 1 : 0;
+    pass = (on && sub == 0 && kabsch_may_be_below<ENANT>(B, G[i] + G[j], A_thr2)) ? 1 : 0;
   }
   const int passed_here = __syncthreads_count(pass);
   if (threadIdx.x == 0) {
@@ -2155,6 +2192,11 @@ __global__ void k_f64_to_f32(const double *__restrict__ x, int64_t n, float *__r
 // ---------------------------------------------------------------------------
 // counters words of the XCD-partitioned candidate queue (k_pairq_partition -> k_refine_pairs)
 
+// ENANT (the three refine kernels): similar = similar as it is OR with the partner inverted.  The second handedness
+// comes from the same covariance with its sign changed (-B, rotation R' of -B, difference p + R' q) and is evaluated
+// only where the fp64 polynomial passes at -det B: a wavefront without such a pair skips it.  One pair counts once in
+// counters[1] and [3] whichever handedness is grey.
+template <bool ENANT = false>
 __global__ void __launch_bounds__(256)
 k_refine_pairs(const double *__restrict__ Xs, const double *__restrict__ G, int64_t N, int64_t Npad, int A,
                double max_rmsd, double max_dev, const double *__restrict__ energies, double max_dE, int IB,
@@ -2215,6 +2257,13 @@ k_refine_pairs(const double *__restrict__ Xs, const double *__restrict__ G, int6
     // the fp64 screen polynomial on this exact covariance first: the single-precision screens pass dissimilar
     // pairs inside their band, and what the fp64 screen would have dropped needs neither a rotation nor a
     // second pass over the atoms
+    bool sim = false, grey = false;
+#pragma unroll
+    for (int hand = 0; hand < (ENANT ? 2 : 1); ++hand) {
+    if (hand == 1) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) B[k] = -B[k];
+    }
     const bool may = on && kabsch_may_be_below(B, Gs, (double)A * (max_rmsd * max_rmsd + kScreenMargin));
     double ssq = 0.0, mx = 0.0;
     if (__any(may)) {
@@ -2232,6 +2281,10 @@ k_refine_pairs(const double *__restrict__ Xs, const double *__restrict__ G, int6
         } else {
           neg_rotation_from_quaternion(Q4, nR);
         }
+      }
+      if (hand == 1) {  // p - R' (-q): the fused chains below add nR q, so nR = +R'
+#pragma unroll
+        for (int k = 0; k < 9; ++k) nR[k] = -nR[k];
       }
       double PA[3], QA[3], PB[3], QB[3];
       auto dev = [&](const double (&P)[3], const double (&Qv)[3]) {
@@ -2255,11 +2308,13 @@ k_refine_pairs(const double *__restrict__ Xs, const double *__restrict__ G, int6
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    bool sim = false, grey = false;
     if (on) {
       const double r = sqrt(ssq / (double)A), m = sqrt(mx);
-      sim = may && (r < max_rmsd) && (m < max_dev);
-      grey = may && ((fabs(r - max_rmsd) < 1e-9) || (r < max_rmsd && fabs(m - max_dev) < 1e-9));
+      sim = sim || (may && (r < max_rmsd) && (m < max_dev));
+      grey = grey || (may && ((fabs(r - max_rmsd) < 1e-9) || (r < max_rmsd && fabs(m - max_dev) < 1e-9)));
+    }
+    }
+    if (on) {
       if (energies != nullptr) sim = sim && (fabs(energies[i] - energies[j]) < max_dE);
       if (!sim && bits != nullptr) {
         const int64_t lrow = (((int64_t)i / IB) / world) * IB + ((int64_t)i % IB);
@@ -2432,6 +2487,7 @@ k_bucket_scatter(const uint64_t *__restrict__ pairq, const unsigned long long *_
   }
 }
 
+template <bool ENANT = false>
 __global__ void __launch_bounds__(kBucketChunk, FC_RB_WPS)  // (second figure: wavefronts per SIMD; 3 = 168 registers, no spills: 0.320 ms against 0.332 with 4 and 37 spilled)
 k_refine_buckets(const double *__restrict__ Xs, const double *__restrict__ G, int64_t N, int64_t Npad, int A,
                  double max_rmsd, double max_dev, const double *__restrict__ energies, double max_dE, int IB,
@@ -2624,6 +2680,13 @@ k_refine_buckets(const double *__restrict__ Xs, const double *__restrict__ G, in
       const unsigned long long tp1 = wall_clock64();
 #endif
       const double Gs = G[i] + G[j];
+      bool sim = false, grey = false;
+#pragma unroll
+      for (int hand = 0; hand < (ENANT ? 2 : 1); ++hand) {
+      if (hand == 1) {
+#pragma unroll
+        for (int kk = 0; kk < 9; ++kk) B[kk] = -B[kk];
+      }
       const bool may = on && kabsch_may_be_below(B, Gs, A_thr2);
       double ssq = 0.0, mx = 0.0;
       if (__any(may)) {
@@ -2646,6 +2709,10 @@ k_refine_buckets(const double *__restrict__ Xs, const double *__restrict__ G, in
           } else {
             neg_rotation_from_quaternion(Q4, nR);
           }
+        }
+        if (hand == 1) {  // p - R' (-q): the fused chains below add nR q, so nR = +R'
+#pragma unroll
+          for (int kk = 0; kk < 9; ++kk) nR[kk] = -nR[kk];
         }
 #ifdef FC_RB_TIMELINE
         if (wv == 0 && lane == 0) atomicAdd(&counters[24], wall_clock64() - tp1);  // polynomial + rotation
@@ -2686,11 +2753,13 @@ k_refine_buckets(const double *__restrict__ Xs, const double *__restrict__ G, in
         atomicAdd(&counters[27], 1ull);
       }
 #endif
-      bool sim = false, grey = false;
       if (on) {
         const double r = sqrt(ssq / (double)A), m = sqrt(mx);
-        sim = may && (r < max_rmsd) && (m < max_dev);
-        grey = may && ((fabs(r - max_rmsd) < 1e-9) || (r < max_rmsd && fabs(m - max_dev) < 1e-9));
+        sim = sim || (may && (r < max_rmsd) && (m < max_dev));
+        grey = grey || (may && ((fabs(r - max_rmsd) < 1e-9) || (r < max_rmsd && fabs(m - max_dev) < 1e-9)));
+      }
+      }
+      if (on) {
         if (energies != nullptr) sim = sim && (fabs(energies[i] - energies[j]) < max_dE);
         if (!sim && bits != nullptr) {
           const int64_t lrow = (((int64_t)i / IB) / world) * IB + ((int64_t)i % IB);
@@ -2750,6 +2819,7 @@ k_refine_buckets(const double *__restrict__ Xs, const double *__restrict__ G, in
 // [&& |E_i - E_j| < max_dE].  counters[1] += candidates, [2] += similar,
 // [3] += pairs within 1e-9 of a threshold ("grey").
 // ---------------------------------------------------------------------------
+template <bool ENANT = false>
 __global__ void __launch_bounds__(256)
 k_simbits_refine(const double *__restrict__ Xs, const double *__restrict__ Xa, int64_t N,
                  int64_t Npad, int A, double max_rmsd,
@@ -2836,6 +2906,13 @@ k_simbits_refine(const double *__restrict__ Xs, const double *__restrict__ Xa, i
       // passes dissimilar pairs inside its band, and what the fp64 screen would have dropped
       // needs neither a rotation nor a second pass over the atoms (same decision as with the
       // fp64 screen; a wave without any other pair skips both).
+      bool sim = false, grey = false;
+#pragma unroll
+      for (int hand = 0; hand < (ENANT ? 2 : 1); ++hand) {
+      if (hand == 1) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) B[k] = -B[k];
+      }
       const bool may = on && kabsch_may_be_below(B, Gs, (double)A * (max_rmsd * max_rmsd + kScreenMargin));
       const bool any_may = __any(may);
       // rotation: Newton eigenvalue + adjugate eigenvector where the eigenvalue is clearly simple
@@ -2844,6 +2921,10 @@ k_simbits_refine(const double *__restrict__ Xs, const double *__restrict__ Xa, i
       if (any_may) {
         const bool fast = may && kabsch_rotation_qcp(B, Gs, R);
         if (may && !fast) (void)kabsch_rotation(B, R);
+        if (hand == 1) {  // p - R' (-q) = p - (-R') q
+#pragma unroll
+          for (int k = 0; k < 9; ++k) R[k] = -R[k];
+        }
       }
       double ssq_own = 0.0, mx_own = 0.0;
       if (any_may) {  // (the deviation pass the same way: all rounds' atoms requested before any is used)
@@ -2886,12 +2967,14 @@ k_simbits_refine(const double *__restrict__ Xs, const double *__restrict__ Xa, i
           }
         }
       }
-      bool sim = false, grey = false;
+      if (on) {
+        const double r = sqrt(ssq_own / (double)A), m = sqrt(mx_own);
+        sim = sim || (may && (r < max_rmsd) && (m < max_dev));
+        grey = grey || (may && ((fabs(r - max_rmsd) < 1e-9) || (r < max_rmsd && fabs(m - max_dev) < 1e-9)));
+      }
+      }
       if (on) {
         const int64_t i = (int64_t)(e >> 32), j = (int64_t)(e & 0xffffffffull);
-        const double r = sqrt(ssq_own / (double)A), m = sqrt(mx_own);
-        sim = may && (r < max_rmsd) && (m < max_dev);
-        grey = may && ((fabs(r - max_rmsd) < 1e-9) || (r < max_rmsd && fabs(m - max_dev) < 1e-9));
         if (energies != nullptr) sim = sim && (fabs(energies[i] - energies[j]) < max_dE);
         if (!sim && bits != nullptr) {
           const int64_t lrow = ((i / IB) / world) * IB + (i % IB);
@@ -2933,7 +3016,12 @@ k_simbits_refine(const double *__restrict__ Xs, const double *__restrict__ Xa, i
       double r, m;
       pair_exact_wave(Xs, Npad, A, i, j, lane, r, m);
       bool sim = (r < max_rmsd) && (m < max_dev);
-      const bool grey = (fabs(r - max_rmsd) < 1e-9) || (r < max_rmsd && fabs(m - max_dev) < 1e-9);
+      bool grey = (fabs(r - max_rmsd) < 1e-9) || (r < max_rmsd && fabs(m - max_dev) < 1e-9);
+      if (ENANT) {  // (the word queue carries no polynomial verdict: both handednesses, always)
+        pair_exact_wave<true>(Xs, Npad, A, i, j, lane, r, m);
+        sim = sim || ((r < max_rmsd) && (m < max_dev));
+        grey = grey || (fabs(r - max_rmsd) < 1e-9) || (r < max_rmsd && fabs(m - max_dev) < 1e-9);
+      }
       if (energies != nullptr) sim = sim && (fabs(energies[i] - energies[j]) < max_dE);
       if (sim) out |= 1ull << b;
       if (grey) g |= 1ull << b;
@@ -2948,6 +3036,11 @@ k_simbits_refine(const double *__restrict__ Xs, const double *__restrict__ Xa, i
       pair_exact(Xs, Npad, A, i, j, r, m);
       sim = (r < max_rmsd) && (m < max_dev);
       grey = (fabs(r - max_rmsd) < 1e-9) || (r < max_rmsd && fabs(m - max_dev) < 1e-9);
+      if (ENANT) {
+        pair_exact<true>(Xs, Npad, A, i, j, r, m);
+        sim = sim || ((r < max_rmsd) && (m < max_dev));
+        grey = grey || (fabs(r - max_rmsd) < 1e-9) || (r < max_rmsd && fabs(m - max_dev) < 1e-9);
+      }
       if (energies != nullptr) sim = sim && (fabs(energies[i] - energies[j]) < max_dE);
     }
     out = __ballot(sim);
@@ -3328,9 +3421,9 @@ int launch_prep_body(const double *coords_dev, int64_t N, int64_t A_all, const i
 }
 
 int launch_pairs_exact(const fc_ensemble *e, const int64_t *pi_dev, const int64_t *pj_dev,
-                       int64_t P, double *rmsd_dev, double *maxdev_dev, double *R_dev) {
+                       int64_t P, double *rmsd_dev, double *maxdev_dev, double *R_dev, bool inverted) {
   if (P == 0) return FC_OK;
-  hipLaunchKernelGGL(k_pairs_exact, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, ctx().stream,
+  hipLaunchKernelGGL(inverted ? k_pairs_exact<true> : k_pairs_exact<false>, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, ctx().stream,
                      e->Xa.as<double>(), (int)e->A, pi_dev, pj_dev, P, rmsd_dev, maxdev_dev, R_dev);
   return check_launch("k_pairs_exact");
 }
@@ -3634,29 +3727,33 @@ static int screen_items(fc_ensemble *e, int64_t n_lblocks, int tc, ScreenItems *
 // the split-half kernel of KS2 k-steps: 64-column tile up to kH2MaxKS2 (with the bit matrix or lean), 32-column tile beyond
 // (lean only)
 using H2Screen = decltype(&k_simbits_screen_mfma_h2<1, true>);
-static H2Screen h2_screen_kernel(int64_t KS2, bool bits) {
+template <bool ENANT>
+static H2Screen h2_screen_kernel_of(int64_t KS2, bool bits) {
   switch (KS2) {
-    case 1: return bits ? k_simbits_screen_mfma_h2<1, true> : k_simbits_screen_mfma_h2<1, false>;
-    case 2: return bits ? k_simbits_screen_mfma_h2<2, true> : k_simbits_screen_mfma_h2<2, false>;
-    case 3: return bits ? k_simbits_screen_mfma_h2<3, true> : k_simbits_screen_mfma_h2<3, false>;
-    case 4: return bits ? k_simbits_screen_mfma_h2<4, true> : k_simbits_screen_mfma_h2<4, false>;
-    case 5: return bits ? k_simbits_screen_mfma_h2<5, true> : k_simbits_screen_mfma_h2<5, false>;
-    case 6: return bits ? k_simbits_screen_mfma_h2<6, true> : k_simbits_screen_mfma_h2<6, false>;
-    case 7: return k_simbits_screen_mfma_h2<7, false, 32>;
-    case 8: return k_simbits_screen_mfma_h2<8, false, 32>;
-    case 9: return k_simbits_screen_mfma_h2<9, false, 32>;
-    case 10: return k_simbits_screen_mfma_h2<10, false, 32>;
-    case 11: return k_simbits_screen_mfma_h2<11, false, 32>;
-    case 12: return k_simbits_screen_mfma_h2<12, false, 32>;
-    default: return k_simbits_screen_mfma_h2<13, false, 32>;
+    case 1: return bits ? k_simbits_screen_mfma_h2<1, true, 64, ENANT> : k_simbits_screen_mfma_h2<1, false, 64, ENANT>;
+    case 2: return bits ? k_simbits_screen_mfma_h2<2, true, 64, ENANT> : k_simbits_screen_mfma_h2<2, false, 64, ENANT>;
+    case 3: return bits ? k_simbits_screen_mfma_h2<3, true, 64, ENANT> : k_simbits_screen_mfma_h2<3, false, 64, ENANT>;
+    case 4: return bits ? k_simbits_screen_mfma_h2<4, true, 64, ENANT> : k_simbits_screen_mfma_h2<4, false, 64, ENANT>;
+    case 5: return bits ? k_simbits_screen_mfma_h2<5, true, 64, ENANT> : k_simbits_screen_mfma_h2<5, false, 64, ENANT>;
+    case 6: return bits ? k_simbits_screen_mfma_h2<6, true, 64, ENANT> : k_simbits_screen_mfma_h2<6, false, 64, ENANT>;
+    case 7: return k_simbits_screen_mfma_h2<7, false, 32, ENANT>;
+    case 8: return k_simbits_screen_mfma_h2<8, false, 32, ENANT>;
+    case 9: return k_simbits_screen_mfma_h2<9, false, 32, ENANT>;
+    case 10: return k_simbits_screen_mfma_h2<10, false, 32, ENANT>;
+    case 11: return k_simbits_screen_mfma_h2<11, false, 32, ENANT>;
+    case 12: return k_simbits_screen_mfma_h2<12, false, 32, ENANT>;
+    default: return k_simbits_screen_mfma_h2<13, false, 32, ENANT>;
   }
+}
+static H2Screen h2_screen_kernel(int64_t KS2, bool bits, bool enant) {
+  return enant ? h2_screen_kernel_of<true>(KS2, bits) : h2_screen_kernel_of<false>(KS2, bits);
 }
 
 static int launch_h2_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblocks) {
   ScreenItems it;
   FC_TRY(screen_items(e, n_lblocks, p.tc, &it));
   FC_TRY(make_h2_operands(e, p.scale));
-  const H2Screen fn = h2_screen_kernel(p.ks, !e->lean);
+  const H2Screen fn = h2_screen_kernel(p.ks, !e->lean, e->enant);
   if (p.lds > 64 * 1024)
     FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
   const double s2 = p.scale * p.scale;
@@ -3693,15 +3790,16 @@ static int launch_h2_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lbloc
   return FC_OK;
 }
 
-static int launch_f32_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblocks, double A_thr2) {
+template <bool ENANT>
+static int launch_f32_screen_of(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblocks, double A_thr2) {
   ScreenItems it;
   FC_TRY(screen_items(e, n_lblocks, p.tc, &it));
   FC_TRY(make_f32_operands(e));
   auto *cnt = reinterpret_cast<unsigned long long *>(e->counters.p);
   if (p.tc == 32) {  // lean, single stage
-    const void *fn = reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false, false, 32>);
+    const void *fn = reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false, false, 32, ENANT>);
     FC_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-    hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, false, false, 32>), dim3((unsigned)it.n), dim3(256), p.lds, ctx().stream,
+    hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, false, false, 32, ENANT>), dim3((unsigned)it.n), dim3(256), p.lds, ctx().stream,
                        e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, p.bd, (int)e->row_block, e->rank,
                        e->world, nullptr, e->W, e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
                        (unsigned long long)e->pairq_cap, it.table, it.n, nullptr, p.bd, 0.f, nullptr, 0, 0);
@@ -3722,11 +3820,11 @@ static int launch_f32_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblo
   const unsigned long long n_items = it.n;
   const uint64_t *item_table_dev = it.table;
   if (lds_f > 64 * 1024) {
-    FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, true>),
+    FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, true, false, 64, ENANT>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-    FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false>),
+    FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false, false, 64, ENANT>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
-    FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false, true>),
+    FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma_f32<4, false, true, 64, ENANT>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
   }
   // stage 1 accumulates the even k-steps: A4_S atoms (padding included), A_S real ones; its bounds
@@ -3747,7 +3845,7 @@ static int launch_f32_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblo
     // "dense": more than a third of the sampled units could not be ruled out by the subset stage
     const unsigned long long max_sample_units = n_sample * units_per_item / 3ull;
 #define FC_LAUNCH_F32_LEAN(GRID, SUB, PART, GATE, STAGED_)                                                            \
-  hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, false, STAGED_>), dim3((unsigned)(GRID)), dim3(256), lds_f, ctx().stream, \
+  hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, false, STAGED_, 64, ENANT>), dim3((unsigned)(GRID)), dim3(256), lds_f, ctx().stream, \
                      e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bd, (int)e->row_block,  \
                      e->rank, e->world, e->bits.as<uint64_t>(), e->W, e->cand.as<uint32_t>(), cnt,                    \
                      e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap, item_table_dev, n_items, SUB, bd1,    \
@@ -3756,31 +3854,35 @@ static int launch_f32_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblo
     hipLaunchKernelGGL(k_screen_density_verdict, dim3(1), dim3(64), 0, ctx().stream, cnt, max_sample_units);
     if (n_rest > 0) FC_LAUNCH_F32_LEAN(n_rest, sub_dev, 2, 1, true);
     FC_TRY(check_launch("k_simbits_screen_mfma_f32<subset stage>"));
-    hipLaunchKernelGGL(k_screen_units_f32, dim3((unsigned)(ctx().n_cu * 3)), dim3(256), 0, ctx().stream,
+    hipLaunchKernelGGL(k_screen_units_f32<ENANT>, dim3((unsigned)(ctx().n_cu * 3)), dim3(256), 0, ctx().stream,
                        e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bd,
                        e->unitq.as<uint64_t>(), cnt, e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap);
     FC_TRY(check_launch("k_screen_units_f32"));
     FC_LAUNCH_F32_LEAN(n_items, nullptr, 0, 2, false);
 #undef FC_LAUNCH_F32_LEAN
   } else if (e->lean)
-    hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, false>), mgrid, dim3(256), lds_f, ctx().stream,
+    hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, false, false, 64, ENANT>), mgrid, dim3(256), lds_f, ctx().stream,
                        e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bd,
                        (int)e->row_block, e->rank, e->world, e->bits.as<uint64_t>(), e->W,
                        e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
                        (unsigned long long)e->pairq_cap, item_table_dev, n_items, nullptr, bd1, inv_AS, nullptr, 0, 0);
   else
-    hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, true>), mgrid, dim3(256), lds_f, ctx().stream,
+    hipLaunchKernelGGL((k_simbits_screen_mfma_f32<4, true, false, 64, ENANT>), mgrid, dim3(256), lds_f, ctx().stream,
                        e->Xsf.as<float>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_thr2, bd,
                        (int)e->row_block, e->rank, e->world, e->bits.as<uint64_t>(), e->W,
                        e->cand.as<uint32_t>(), cnt, e->pairq.as<uint64_t>(),
                        (unsigned long long)e->pairq_cap, item_table_dev, n_items, nullptr, bd1, inv_AS, nullptr, 0, 0);
   return check_launch("k_simbits_screen_mfma_f32");
 }
+static int launch_f32_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblocks, double A_thr2) {
+  return e->enant ? launch_f32_screen_of<true>(e, p, n_lblocks, A_thr2) : launch_f32_screen_of<false>(e, p, n_lblocks, A_thr2);
+}
 
 // gate: behind a speculative screen, the verdict's word (the workgroups return at once unless it says "redo")
 static int launch_fp64_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblocks, double A_thr2,
                               const unsigned long long *gate) {
-  const auto fn = p.fp64_waves == 4 ? k_simbits_screen_mfma<4> : k_simbits_screen_mfma<8>;
+  const auto fn = e->enant ? (p.fp64_waves == 4 ? k_simbits_screen_mfma<4, 0, 64, false, true> : k_simbits_screen_mfma<8, 0, 64, false, true>)
+                            : (p.fp64_waves == 4 ? k_simbits_screen_mfma<4> : k_simbits_screen_mfma<8>);
   const int threads = 64 * p.fp64_waves;
   if (p.lds64 > 64 * 1024) {
     hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3825,7 +3927,8 @@ static int launch_fp64_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lbl
 }
 
 static int launch_valu_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lblocks, double A_thr2) {
-  const auto fn = p.valu_lds ? k_simbits_screen<true, 8, 4> : k_simbits_screen<false, 8, 4>;
+  const auto fn = e->enant ? (p.valu_lds ? k_simbits_screen<true, 8, 4, true> : k_simbits_screen<false, 8, 4, true>)
+                            : (p.valu_lds ? k_simbits_screen<true, 8, 4> : k_simbits_screen<false, 8, 4>);
   if (p.lds > 64 * 1024) {
     hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
     if (err != hipSuccess)
@@ -3883,7 +3986,7 @@ int launch_simbits_screen(fc_ensemble *e, double thr2_margin) {
   // a false candidate costs ~1 ns (staging, one atom pass of the refine: tools/broad_probe.py), a second
   // screen in fp64 ~0.017 ns per owned pair at 52 padded atoms and in proportion to them beyond
   const auto max_false = (unsigned long long)std::max(1024.0, 0.015 * ((double)((e->A + 3) / 4 * 4) / 52.0) * owned_pairs);
-  hipLaunchKernelGGL(k_screen_verdict, dim3(4), dim3(256), 0, ctx().stream, e->Xa.as<double>(), e->G.as<double>(), (int)e->A,
+  hipLaunchKernelGGL(e->enant ? k_screen_verdict<true> : k_screen_verdict<false>, dim3(4), dim3(256), 0, ctx().stream, e->Xa.as<double>(), e->G.as<double>(), (int)e->A,
                      A_thr2, e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap, max_false, cnt,
                      ctx().optimistic_screen ? 1 : 0);
   FC_TRY(check_launch("k_screen_verdict"));
@@ -3923,7 +4026,7 @@ int launch_simbits_refine(fc_ensemble *e, double max_rmsd, double max_dev, const
   // are 156 KB of tile and do not fit beside them (tools/refine_stress.py found that launch refused)
   static const size_t lds_bk_static = [] {
     hipFuncAttributes fa{};
-    return hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_refine_buckets)) == hipSuccess ? (size_t)fa.sharedSizeBytes
+    return hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_refine_buckets<false>)) == hipSuccess ? (size_t)fa.sharedSizeBytes
                                                                                                         : (size_t)(16 * 1024);
   }();
   static const bool debug_form = getenv("FC_DEBUG") != nullptr;
@@ -3953,14 +4056,14 @@ int launch_simbits_refine(fc_ensemble *e, double max_rmsd, double max_dev, const
                        (unsigned long long)e->pairq_cap, geom, nb, bk, off, e->sortq.as<uint64_t>());
     FC_TRY(check_launch("k_bucket_scatter"));
     if (lds_bk > 64 * 1024)
-      FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_refine_buckets),
+      FC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(e->enant ? k_refine_buckets<true> : k_refine_buckets<false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bk));
     static const int per_cu_b = [] {
       const char *v = getenv("FC_REFINE_GRID");
       const int k = v ? atoi(v) : 2;
       return k >= 1 && k <= 8 ? k : 2;
     }();
-    hipLaunchKernelGGL(k_refine_buckets, dim3((unsigned)(ctx().n_cu * per_cu_b)), dim3(kBucketChunk), lds_bk, ctx().stream,
+    hipLaunchKernelGGL(e->enant ? k_refine_buckets<true> : k_refine_buckets<false>, dim3((unsigned)(ctx().n_cu * per_cu_b)), dim3(kBucketChunk), lds_bk, ctx().stream,
                        e->Xs.as<double>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, max_rmsd, max_dev, energies_dev,
                        max_dE, (int)e->row_block, e->world, e->lean ? nullptr : e->bits.as<uint64_t>(), e->W, cnt,
                        (unsigned long long)e->pairq_cap, geom, bk, off, e->bk_list.as<int>(), st_off, xoff, n_st, x_stride,
@@ -3977,7 +4080,7 @@ int launch_simbits_refine(fc_ensemble *e, double max_rmsd, double max_dev, const
       const int k = v ? atoi(v) : 2;
       return k >= 1 && k <= 64 ? k : 2;
     }();
-    hipLaunchKernelGGL(k_refine_pairs, dim3((unsigned)(ctx().n_cu * per_cu)), dim3(256), 0, ctx().stream,
+    hipLaunchKernelGGL(e->enant ? k_refine_pairs<true> : k_refine_pairs<false>, dim3((unsigned)(ctx().n_cu * per_cu)), dim3(256), 0, ctx().stream,
                        e->Xs.as<double>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, max_rmsd, max_dev, energies_dev,
                        max_dE, (int)e->row_block, e->world, e->lean ? nullptr : e->bits.as<uint64_t>(), e->W,
                        reinterpret_cast<unsigned long long *>(e->counters.p), e->pairq.as<uint64_t>(),
@@ -3989,7 +4092,7 @@ int launch_simbits_refine(fc_ensemble *e, double max_rmsd, double max_dev, const
     const int k = v ? atoi(v) : 16;
     return k >= 1 && k <= 64 ? k : 16;
   }();
-  hipLaunchKernelGGL(k_simbits_refine, dim3((unsigned)(ctx().n_cu * per_cu8)), dim3(256), 0,
+  hipLaunchKernelGGL(e->enant ? k_simbits_refine<true> : k_simbits_refine<false>, dim3((unsigned)(ctx().n_cu * per_cu8)), dim3(256), 0,
                      ctx().stream, e->Xs.as<double>(), e->Xa.as<double>(), e->N, e->Npad, (int)e->A,
                      max_rmsd, max_dev, energies_dev, max_dE, lanes ? -(int)e->row_block : (int)e->row_block, e->rank, e->world,
                      e->rows_local,

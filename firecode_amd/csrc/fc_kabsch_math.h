@@ -143,6 +143,10 @@ __host__ __device__ __forceinline__ double kabsch_rotation(const double (&B)[9],
 // P, P', P'', P''' are all >= 0 at L.  Returns true when the pair MAY be
 // similar (it is then re-evaluated exactly); false only when it provably
 // (with a 1e-12 relative guard on P) is not.
+// ENANT (the enantiomer-aware prune): "may be similar in EITHER handedness".  Inverting one
+// structure through the origin turns B into -B: n2 and |cof B|_F^2 are even in B, det B changes sign, and P', P are
+// decreasing in det B (L > 0 where the test decides: `tiny`), so the OR of the two tests is this test at |det B|.
+template <bool ENANT = false>
 __host__ __device__ __forceinline__ bool kabsch_may_be_below(const double (&B)[9], double GpGq,
                                                      double A_thr2) {
   // the screen has a 1e-6 A^2 margin and a 1e-12 relative guard: fused
@@ -168,7 +172,8 @@ __host__ __device__ __forceinline__ bool kabsch_may_be_below(const double (&B)[9
   const double c00 = Syy * Szz - Syz * Szy, c01 = Syz * Szx - Syx * Szz, c02 = Syx * Szy - Syy * Szx;
   const double c10 = Sxz * Szy - Sxy * Szz, c11 = Sxx * Szz - Sxz * Szx, c12 = Sxy * Szx - Sxx * Szy;
   const double c20 = Sxy * Syz - Sxz * Syy, c21 = Sxz * Syx - Sxx * Syz, c22 = Sxx * Syy - Sxy * Syx;
-  const double detB = Sxx * c00 + Sxy * c01 + Sxz * c02;
+  const double det = Sxx * c00 + Sxy * c01 + Sxz * c02;
+  const double detB = ENANT ? fabs(det) : det;
   const double e2 = c00 * c00 + c01 * c01 + c02 * c02 + c10 * c10 + c11 * c11 + c12 * c12 +
                     c20 * c20 + c21 * c21 + c22 * c22;
   const double P2 = 2.0 * L2 + u;
@@ -214,6 +219,8 @@ inline KabschF32Bounds kabsch_f32_bounds(int64_t A4) {
 // tiny_floor: pairs with s at or below it go to the exact path untested (the plain test passes
 // 4 * half_A_thr2: a structure that small against the threshold cannot be screened; the split-half kernel
 // passes the larger of that and the scale its absolute error term needs).
+// ENANT: the test at |det B| (see kabsch_may_be_below); |d |det B|| <= |d det B|, the bounds stand.
+template <bool ENANT = false>
 __device__ __forceinline__ bool kabsch_may_be_below_f32(const float (&B)[9], float s, float half_A_thr2,
                                                         const KabschF32Bounds &bd, float s_bound, float tiny_floor) {
 #pragma clang fp contract(fast)
@@ -229,7 +236,8 @@ __device__ __forceinline__ bool kabsch_may_be_below_f32(const float (&B)[9], flo
   const float c00 = Syy * Szz - Syz * Szy, c01 = Syz * Szx - Syx * Szz, c02 = Syx * Szy - Syy * Szx;
   const float c10 = Sxz * Szy - Sxy * Szz, c11 = Sxx * Szz - Sxz * Szx, c12 = Sxy * Szx - Sxx * Szy;
   const float c20 = Sxy * Syz - Sxz * Syy, c21 = Sxz * Syx - Sxx * Syz, c22 = Sxx * Syy - Sxy * Syx;
-  const float detB = Sxx * c00 + Sxy * c01 + Sxz * c02;
+  const float det = Sxx * c00 + Sxy * c01 + Sxz * c02;
+  const float detB = ENANT ? fabsf(det) : det;
   const float e2 = c00 * c00 + c01 * c01 + c02 * c02 + c10 * c10 + c11 * c11 + c12 * c12 +
                    c20 * c20 + c21 * c21 + c22 * c22;
   const float P2 = 2.0f * L2 + uu;
@@ -240,9 +248,10 @@ __device__ __forceinline__ bool kabsch_may_be_below_f32(const float (&B)[9], flo
   // to the exact path; so does an underflow of s^4 to zero
   return tiny | !(P2 > bd.p2 * s2) | !(P1 > bd.p1 * (s2 * s)) | !(P0 > bd.p0 * (s2 * s2));
 }
+template <bool ENANT = false>
 __device__ __forceinline__ bool kabsch_may_be_below_f32(const float (&B)[9], float s, float half_A_thr2,
                                                         const KabschF32Bounds &bd, float s_bound) {
-  return kabsch_may_be_below_f32(B, s, half_A_thr2, bd, s_bound, 4.0f * half_A_thr2);
+  return kabsch_may_be_below_f32<ENANT>(B, s, half_A_thr2, bd, s_bound, 4.0f * half_A_thr2);
 }
 
 // The same decision with TWO sign tests instead of three (the split-half kernel, whose matrix work is so
@@ -256,6 +265,7 @@ __device__ __forceinline__ bool kabsch_may_be_below_f32(const float (&B)[9], flo
 // Branch-free: returns the conservative verdict (u <= 0 counts as "may be similar") and reports in `redo` the
 // lanes that should take the three-test form instead (the caller does that behind ONE wave-uniform branch per
 // group of pairs: a branch per pair costs the wave a VALU -> SALU round trip each).
+template <bool ENANT = false>
 __device__ __forceinline__ bool kabsch_may_be_below_f32_2t(const float (&B)[9], float s, float half_A_thr2,
                                                            const KabschF32Bounds &bd, float tiny_floor, bool &redo) {
 #pragma clang fp contract(fast)
@@ -270,7 +280,8 @@ __device__ __forceinline__ bool kabsch_may_be_below_f32_2t(const float (&B)[9], 
   const float c00 = Syy * Szz - Syz * Szy, c01 = Syz * Szx - Syx * Szz, c02 = Syx * Szy - Syy * Szx;
   const float c10 = Sxz * Szy - Sxy * Szz, c11 = Sxx * Szz - Sxz * Szx, c12 = Sxy * Szx - Sxx * Szy;
   const float c20 = Sxy * Syz - Sxz * Syy, c21 = Sxz * Syx - Sxx * Syz, c22 = Sxx * Syy - Sxy * Syx;
-  const float detB = Sxx * c00 + Sxy * c01 + Sxz * c02;
+  const float det = Sxx * c00 + Sxy * c01 + Sxz * c02;
+  const float detB = ENANT ? fabsf(det) : det;  // (the second largest root stays <= f1 for either sign of f3)
   const float e2 = c00 * c00 + c01 * c01 + c02 * c02 + c10 * c10 + c11 * c11 + c12 * c12 +
                    c20 * c20 + c21 * c21 + c22 * c22;
   const float P0 = uu * uu - 4.0f * (e2 + 2.0f * L * detB);
@@ -285,6 +296,7 @@ __device__ __forceinline__ bool kabsch_may_be_below_f32_2t(const float (&B)[9], 
 // per-lane booleans to keep in vector registers across the rare branches (the compiler packed them into bytes:
 // ~22 vector instructions per 16 x 16 sub-tile of a kernel bound by vector issue).  Same comparisons, same NaN
 // behaviour as kabsch_may_be_below_f32_2t: a failed `>` counts as "may be similar".  All 64 lanes must be active.
+template <bool ENANT = false>
 __device__ __forceinline__ uint64_t kabsch_may_be_below_f32_2t_wave(const float (&B)[9], float s, float half_A_thr2,
                                                                     const KabschF32Bounds &bd, float tiny_floor,
                                                                     uint64_t &redo) {
@@ -299,7 +311,8 @@ __device__ __forceinline__ uint64_t kabsch_may_be_below_f32_2t_wave(const float 
   const float c00 = Syy * Szz - Syz * Szy, c01 = Syz * Szx - Syx * Szz, c02 = Syx * Szy - Syy * Szx;
   const float c10 = Sxz * Szy - Sxy * Szz, c11 = Sxx * Szz - Sxz * Szx, c12 = Sxy * Szx - Sxx * Szy;
   const float c20 = Sxy * Syz - Sxz * Syy, c21 = Sxz * Syx - Sxx * Syz, c22 = Sxx * Syy - Sxy * Syx;
-  const float detB = Sxx * c00 + Sxy * c01 + Sxz * c02;
+  const float det = Sxx * c00 + Sxy * c01 + Sxz * c02;
+  const float detB = ENANT ? fabsf(det) : det;  // (the second largest root stays <= f1 for either sign of f3)
   const float e2 = c00 * c00 + c01 * c01 + c02 * c02 + c10 * c10 + c11 * c11 + c12 * c12 +
                    c20 * c20 + c21 * c21 + c22 * c22;
   const float P0 = uu * uu - 4.0f * (e2 + 2.0f * L * detB);

@@ -130,7 +130,7 @@ class Ensemble:
         return sel
 
     def similarity_pruning(self, moi=True, rmsd=True, rmsd_rot_corr=False, verbose=True, max_rmsd=None,
-                           symmetric_torsions=None, graph=None, rotation_masks=None):
+                           symmetric_torsions=None, graph=None, rotation_masks=None, prune_enantiomers=False):
         """firecode/ensemble.py:185-276: MOI prune, RMSD prune, then (``rmsd_rot_corr``, at
         most 1000 structures, :246-270) the symmetry-corrected RMSD prune; masks propagated to
         ``energies``.  Log messages as the reference words them, except the elapsed-time field: its
@@ -138,7 +138,14 @@ class Ensemble:
         ``max_rmsd=None``: the pruner's default, like the reference, which passes none (:230).  The rot-corr stage needs the locally symmetric torsions
         ``(i1, i2, i3, i4, n_fold)``: like the reference (:250) the graph is built with
         ``graphize(atoms, coords[0])`` when none is given, and ``prune_by_rmsd_rot_corr`` perceives the
-        torsions from it (``symmetric_torsions=`` / ``rotation_masks=`` override the perception)."""
+        torsions from it (``symmetric_torsions=`` / ``rotation_masks=`` override the perception).
+        ``prune_enantiomers=True``: the RMSD stage (only that stage) counts mirror images as duplicates
+        (``prune_by_rmsd(..., prune_enantiomers=True)``); its log line then reads "RMSD similarity (mirror images
+        included)"."""
+        from firecode_amd import _lib as L
+
+        enant = L.check_flag("prune_enantiomers", prune_enantiomers)
+        rmsd_label = "RMSD similarity (mirror images included)" if enant else "RMSD similarity"
         log = self.logfunction if verbose else None
         if log is not None:
             log("--> Similarity Processing")
@@ -153,12 +160,13 @@ class Ensemble:
 
             n0, t0 = len(self.coords), perf_counter()
             m_moi, m_both, counts = prune_similarity(self.coords, self.atoms, max_rmsd=max_rmsd,
-                                                     energies=self.energies if use_en else None, max_dE=max_dE)
+                                                     energies=self.energies if use_en else None, max_dE=max_dE,
+                                                     prune_enantiomers=enant)
             dt = perf_counter() - t0
             if counts[1] < n0 and log is not None:
                 log(f"Discarded {n0 - int(counts[1])} candidates for MOI similarity ({int(counts[1])} left, {dt:.3f} s)")
             if counts[2] < counts[1] and log is not None:
-                log(f"Discarded {int(counts[1] - counts[2])} candidates for RMSD similarity ({int(counts[2])} left, {dt:.3f} s)")
+                log(f"Discarded {int(counts[1] - counts[2])} candidates for {rmsd_label} ({int(counts[2])} left, {dt:.3f} s)")
             self.coords = self.coords[m_both]
             self.apply_mask(("energies",), m_both)
         elif moi:
@@ -172,10 +180,11 @@ class Ensemble:
         elif rmsd:
             n0, t0 = len(self.coords), perf_counter()
             self.coords, mask = prune_by_rmsd(
-                self.coords, self.atoms, max_rmsd, energies=self.energies if use_en else None, max_dE=max_dE)
+                self.coords, self.atoms, max_rmsd, energies=self.energies if use_en else None, max_dE=max_dE,
+                prune_enantiomers=enant)
             self.apply_mask(("energies",), mask)
             if n0 > len(self.coords) and log is not None:
-                log(f"Discarded {n0 - len(self.coords)} candidates for RMSD similarity "
+                log(f"Discarded {n0 - len(self.coords)} candidates for {rmsd_label} "
                     f"({len(self.coords)} left, {perf_counter() - t0:.3f} s)")
         if rmsd:
             if rmsd_rot_corr:

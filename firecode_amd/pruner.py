@@ -67,11 +67,16 @@ def _unsort(mask_sorted, order):
 
 
 def prune_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None, max_dE=0.0,
-                  debugfunction=None, heavy_atoms_only=True, min_per_group=20):
+                  debugfunction=None, heavy_atoms_only=True, min_per_group=20, prune_enantiomers=False):
     """Heavy-atom Kabsch-RMSD pruning: a pair is similar when
     ``rmsd < max_rmsd and maxdev < max_dev`` (default ``2*max_rmsd``; ``max_rmsd`` defaults to
-    ``CONVENTIONS["default_max_rmsd"]``, the case of firecode/ensemble.py:230 which passes none)."""
+    ``CONVENTIONS["default_max_rmsd"]``, the case of firecode/ensemble.py:230 which passes none).
+
+    ``prune_enantiomers=True``: mirror images count as duplicates -- a pair is also similar when it passes the same
+    two tests with one partner inverted through its centroid (fc_prune_rmsd_enant; the contract is written out in
+    include/fc_hip.h).  Upstream's ``prune_enantiomers`` / ``ENANTIOMERS`` option, removed there for speed."""
     t0 = perf_counter()
+    enant = L.check_flag("prune_enantiomers", prune_enantiomers)
     structures = L.f64(structures)
     if structures.ndim != 3 or structures.shape[2] != 3:
         raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {structures.shape}")
@@ -85,16 +90,22 @@ def prune_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None,
     heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
     order, en_sorted = _sorted_by_energy(structures, energies)
     X = structures if order is None else np.ascontiguousarray(structures[order])
-    # one C call (fc_prune_rmsd_host): upload, preparation, prune, mask
-    m8 = np.zeros(N, dtype=np.uint8)
-    stats = np.zeros(6, dtype=np.int64)
-    hm = np.ascontiguousarray(heavy, dtype=np.uint8)
-    L.call("fc_prune_rmsd_host", L.pf(X), N, X.shape[1], L.pb(hm), 1, float(max_rmsd), float(max_dev),
-           L.pf(None if en_sorted is None else L.f64(en_sorted)), float(max_dE), int(min_per_group), L.pb(m8), L.pi(stats))
-    mask = _unsort(m8.view(np.bool_), order)
+    if enant:  # the resident form: the one-call host path stays the default's
+        with L.DeviceEnsemble(X, atom_mask=heavy, center=True) as ens:
+            m_sorted, stats = ens.prune(max_rmsd, max_dev, energies=en_sorted, max_dE=max_dE, min_per_group=min_per_group,
+                                        prune_enantiomers=True)
+    else:
+        # one C call (fc_prune_rmsd_host): upload, preparation, prune, mask
+        m8 = np.zeros(N, dtype=np.uint8)
+        stats = np.zeros(6, dtype=np.int64)
+        hm = np.ascontiguousarray(heavy, dtype=np.uint8)
+        L.call("fc_prune_rmsd_host", L.pf(X), N, X.shape[1], L.pb(hm), 1, float(max_rmsd), float(max_dev),
+               L.pf(None if en_sorted is None else L.f64(en_sorted)), float(max_dE), int(min_per_group), L.pb(m8), L.pi(stats))
+        m_sorted = m8.view(np.bool_)
+    mask = _unsort(m_sorted, order)
     if debugfunction is not None:
         debugfunction(
-            f"DEBUG: prune_by_rmsd [gfx950] - {stats[0]} pairs screened, {stats[1]} refined, "
+            f"DEBUG: prune_by_rmsd [gfx950{', mirror images included' if enant else ''}] - {stats[0]} pairs screened, {stats[1]} refined, "
             f"{stats[2]} similar, {stats[3]} grey, {stats[4]} ladder levels, "
             f"keeping {int(mask.sum())}/{N} in {perf_counter() - t0:.3f} s")
     return structures[mask], mask
@@ -305,13 +316,17 @@ def prune_by_moment_of_inertia(structures, atoms, max_deviation=None, energies=N
 
 
 def prune_similarity(structures, atoms, moi=True, rmsd=True, max_rmsd=None, max_dev=None, max_deviation=None,
-                     energies=None, max_dE=0.0, heavy_atoms_only=True, min_per_group=20):
+                     energies=None, max_dE=0.0, heavy_atoms_only=True, min_per_group=20, prune_enantiomers=False):
     """The MOI and RMSD stages of ``Ensemble.similarity_pruning`` (firecode/ensemble.py:205-235) /
     ``Embedder.similarity_refining`` (embedder.py:1445-1474) on ONE upload of the coordinates
     (``fc_prune_similarity``): the MOI stage runs on the resident structures, its survivors are gathered
     on the device into the RMSD stage's layout, the masks are composed on the way out.  Stage by
     stage the masks equal ``prune_by_moment_of_inertia`` followed by ``prune_by_rmsd`` on its output.
-    Returns ``(mask_after_moi, mask_after_both, (n_in, n_after_moi, n_after_rmsd))`` in the caller's order."""
+    Returns ``(mask_after_moi, mask_after_both, (n_in, n_after_moi, n_after_rmsd))`` in the caller's order.
+
+    ``prune_enantiomers=True``: the MOI stage as it is, then the enantiomer-aware RMSD stage (``prune_by_rmsd(...,
+    prune_enantiomers=True)``) on its survivors -- two uploads; same masks / counts contract."""
+    enant = L.check_flag("prune_enantiomers", prune_enantiomers)
     structures = L.f64(structures)
     if structures.ndim != 3 or structures.shape[2] != 3:
         raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {structures.shape}")
@@ -330,6 +345,20 @@ def prune_similarity(structures, atoms, moi=True, rmsd=True, max_rmsd=None, max_
     order, en_sorted = _sorted_by_energy(structures, energies)
     X = structures if order is None else np.ascontiguousarray(structures[order])
     m1, m2 = np.zeros(N, dtype=np.uint8), np.zeros(N, dtype=np.uint8)
+    if enant and rmsd:
+        if moi:
+            L.call("fc_prune_similarity", L.pf(X), N, A, L.pb(heavy), L.pf(masses), 1, float(max_deviation), 0, max_rmsd,
+                   max_dev, L.pf(en_sorted), max_dE, int(min_per_group), L.pb(m1), L.pb(m2), L.pi(counts))
+        else:
+            m1[:] = 1
+        keep = m1.astype(bool)
+        with L.DeviceEnsemble(np.ascontiguousarray(X[keep]), atom_mask=heavy.astype(bool), center=True) as ens:
+            sub, _ = ens.prune(max_rmsd, max_dev, energies=None if en_sorted is None else en_sorted[keep], max_dE=max_dE,
+                               min_per_group=min_per_group, prune_enantiomers=True)
+        m2[:] = 0
+        m2[np.flatnonzero(keep)[sub]] = 1
+        counts[:] = (N, int(keep.sum()), int(m2.sum()))
+        return _unsort(m1.astype(bool), order), _unsort(m2.astype(bool), order), counts
     L.call("fc_prune_similarity", L.pf(X), N, A, L.pb(heavy), L.pf(masses), int(bool(moi)), float(max_deviation),
            int(bool(rmsd)), max_rmsd, max_dev, L.pf(en_sorted), max_dE, int(min_per_group), L.pb(m1), L.pb(m2),
            L.pi(counts))
@@ -337,12 +366,14 @@ def prune_similarity(structures, atoms, moi=True, rmsd=True, max_rmsd=None, max_
 
 
 def prune(structures, atoms, max_rmsd=0.25, energies=None, max_dE=0.0, logfunction=None,
-          debugfunction=None):
+          debugfunction=None, prune_enantiomers=False):
     """Combined pipeline used by firecode/interfaces/goat.py:399: MOI, then RMSD.
-    (The symmetry-corrected stage is a later row of SURVEY.md section 8f.)"""
+    (The symmetry-corrected stage is a later row of SURVEY.md section 8f.)
+    ``prune_enantiomers``: as in ``prune_similarity``."""
     structures = L.f64(structures)
     n0 = len(structures)
-    _, mask, _ = prune_similarity(structures, atoms, max_rmsd=max_rmsd, energies=energies, max_dE=max_dE)
+    _, mask, _ = prune_similarity(structures, atoms, max_rmsd=max_rmsd, energies=energies, max_dE=max_dE,
+                                  prune_enantiomers=prune_enantiomers)
     for fn in (logfunction, debugfunction):
         if fn is not None:
             fn(f"Discarded {n0 - int(mask.sum())} candidates for MOI+RMSD similarity ({int(mask.sum())} left)")

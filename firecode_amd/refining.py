@@ -104,12 +104,16 @@ def energy_pruning(energies, kcal_thresh=10.0, logfunction=None):
 
 def similarity_refining(structures, atoms, rmsd_thr=0.5, quadruplets=None, tfd=False, moi=True, rmsd=True,
                         max_structures=None, logfunction=None, debugfunction=None, rmsd_rot_corr=False,
-                        symmetric_torsions=None, graph=None, rotation_masks=None):
+                        symmetric_torsions=None, graph=None, rotation_masks=None, prune_enantiomers=False):
     """embedder.py:1410-1514: [TFD] -> MOI -> RMSD -> [symmetry-corrected RMSD, at most 1000
     structures and only with the molecular graph (``embed_graph``), :1480-1505] (no energies are passed
     at these call sites).  ``max_structures``: the reference skips MOI/RMSD above
     1e5 structures (embedder.py:1446,1467); the GPU path has no such cap unless
-    one is given.  Returns the cumulative mask over the input structures."""
+    one is given.  Returns the cumulative mask over the input structures.
+    ``prune_enantiomers=True``: the RMSD stage (only) counts mirror images as duplicates; its log line reads
+    "RMSD similarity (mirror images included)"."""
+    enant = L.check_flag("prune_enantiomers", prune_enantiomers)
+    rmsd_label = "RMSD similarity (mirror images included)" if enant else "RMSD similarity"
     structures = np.asarray(structures, dtype=np.float64)
     alive = np.arange(len(structures))
 
@@ -118,38 +122,39 @@ def similarity_refining(structures, atoms, rmsd_thr=0.5, quadruplets=None, tfd=F
         t0 = perf_counter()
         _, m = fn(structures[alive], *args, **kw)
         if not m.all():
-            _log(logfunction, f"Discarded {int((~m).sum())} candidates for {label} similarity "
+            _log(logfunction, f"Discarded {int((~m).sum())} candidates for {label} "
                               f"({int(m.sum())} left, {perf_counter() - t0:.3f} s)")
         alive = alive[m]
 
     if tfd and quadruplets is not None and len(quadruplets) > 0:
         from firecode_amd.torsion_module import prune_conformers_tfd
 
-        stage(prune_conformers_tfd, "TFD", quadruplets)
+        stage(prune_conformers_tfd, "TFD similarity", quadruplets)
     capped = max_structures is not None and len(alive) > max_structures
     if moi and rmsd and not capped:
         # both stages on ONE upload (fc_prune_similarity): the MOI survivors are gathered on the device
         from firecode_amd.pruner import prune_similarity
 
         t0 = perf_counter()
-        _, m_both, counts = prune_similarity(structures[alive], atoms, max_rmsd=rmsd_thr)
+        _, m_both, counts = prune_similarity(structures[alive], atoms, max_rmsd=rmsd_thr, prune_enantiomers=enant)
         dt = perf_counter() - t0
-        for label, a, b in (("MOI", counts[0], counts[1]), ("RMSD", counts[1], counts[2])):
+        for label, a, b in (("MOI similarity", counts[0], counts[1]), (rmsd_label, counts[1], counts[2])):
             if b < a:
-                _log(logfunction, f"Discarded {int(a - b)} candidates for {label} similarity ({int(b)} left, {dt:.3f} s)")
+                _log(logfunction, f"Discarded {int(a - b)} candidates for {label} ({int(b)} left, {dt:.3f} s)")
         if debugfunction is not None:
             debugfunction(f"DEBUG: prune_similarity [gfx950] - MOI + RMSD on one upload, {int(counts[0])} -> "
                           f"{int(counts[1])} -> {int(counts[2])} in {dt:.3f} s")
         alive = alive[m_both]
     else:
-        for flag, fn, label, args in ((moi, prune_by_moment_of_inertia, "MOI", (atoms,)),
-                                      (rmsd, prune_by_rmsd, "RMSD", (atoms, rmsd_thr))):
+        for flag, fn, label, args, kw in ((moi, prune_by_moment_of_inertia, "MOI", (atoms,), {}),
+                                          (rmsd, prune_by_rmsd, "RMSD", (atoms, rmsd_thr),
+                                           {"prune_enantiomers": True} if enant else {})):
             if not flag:
                 continue
             if max_structures is not None and len(alive) > max_structures:
                 _log(logfunction, f"Skipped {label} pruning (>{max_structures} structures)")
                 continue
-            stage(fn, label, *args, debugfunction=debugfunction)
+            stage(fn, rmsd_label if label == "RMSD" else f"{label} similarity", *args, debugfunction=debugfunction, **kw)
     if rmsd_rot_corr and (symmetric_torsions is not None or graph is not None):
         # embedder.py:1485-1496: runs whenever the embedder holds the graph; the torsions come from
         # it unless the caller names them
@@ -158,7 +163,7 @@ def similarity_refining(structures, atoms, rmsd_thr=0.5, quadruplets=None, tfd=F
 
             stage(lambda X: prune_by_rmsd_rot_corr(X, atoms, graph, max_rmsd=rmsd_thr, torsions=symmetric_torsions,
                                                    rotation_masks=rotation_masks, debugfunction=debugfunction),
-                  "symmetry-corrected RMSD")
+                  "symmetry-corrected RMSD similarity")
         else:
             _log(logfunction, "Skipped rotationally-corrected RMSD pruning (>1k structures)")
     mask = np.zeros(len(structures), dtype=bool)

@@ -6,9 +6,12 @@ import numpy as np
 from firecode_amd import _lib as L
 
 
-def rmsd_and_max_batch(structures, pair_i, pair_j, center=False, atom_mask=None):
+def rmsd_and_max_batch(structures, pair_i, pair_j, center=False, atom_mask=None, inverted=False):
     """(rmsd, maxdev) of P conformer pairs of one (N, A, 3) block -- the batched
-    form the one-pair name wraps (fc_kabsch_rmsd_pairs)."""
+    form the one-pair name wraps (fc_kabsch_rmsd_pairs).  ``inverted=True``: the values of
+    ``rmsd_and_max(p, -q, center)`` -- the partner inverted through the origin, its mirror image
+    (fc_kabsch_rmsd_pairs_inv): with ``center`` the centroids are removed first, then q is negated."""
+    inverted = L.check_flag("inverted", inverted)
     X = L.f64(structures)
     if X.ndim != 3 or X.shape[2] != 3:
         raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {X.shape}")
@@ -16,16 +19,18 @@ def rmsd_and_max_batch(structures, pair_i, pair_j, center=False, atom_mask=None)
     P = int(pi_.shape[0])
     r, m = np.empty(P), np.empty(P)
     am = None if atom_mask is None else L.u8(np.asarray(atom_mask, dtype=bool))
-    L.call("fc_kabsch_rmsd_pairs", L.pf(X), X.shape[0], X.shape[1], L.pb(am), L.pi(pi_), L.pi(pj_), P,
+    L.call("fc_kabsch_rmsd_pairs_inv" if inverted else "fc_kabsch_rmsd_pairs", L.pf(X), X.shape[0], X.shape[1], L.pb(am), L.pi(pi_), L.pi(pj_), P,
            int(bool(center)), L.pf(r), L.pf(m))
     return r, m
 
 
-def rmsd_and_max(p, q, center=False):
+def rmsd_and_max(p, q, center=False, inverted=False):
     """``rmsd_and_max(p, q, center=False) -> (rmsd, maxdev)`` as called at
-    firecode/utils.py:499, embedder.py:1784, ase_manipulations.py:1384."""
+    firecode/utils.py:499, embedder.py:1784, ase_manipulations.py:1384.
+    ``inverted=True``: against the mirror image of q (see ``rmsd_and_max_batch``)."""
+    inverted = L.check_flag("inverted", inverted)
     X = np.stack([L.f64(p), L.f64(q)])
-    r, m = rmsd_and_max_batch(X, [0], [1], center=center)
+    r, m = rmsd_and_max_batch(X, [0], [1], center=center, inverted=inverted)
     return float(r[0]), float(m[0])
 
 

@@ -190,6 +190,34 @@ int fc_prune_rmsd(fc_ensemble *ens, double max_rmsd, double max_dev, const doubl
 int fc_prune_rmsd_host(const double *coords, int64_t N, int64_t A, const uint8_t *atom_mask, int center, double max_rmsd,
                        double max_dev, const double *energies, double max_dE, int64_t min_per_group, uint8_t *mask_out,
                        int64_t *stats);
+/* ---- enantiomer-aware forms: mirror images count as duplicates ----
+ * The contract, once.  X = the prepared ensemble (atom selection applied, each conformer centred on the centroid of its
+ * selected atoms when created with center = 1).  For a pair (i, j):
+ *
+ *   (r+, m+) = rmsd_and_max(X[i],  X[j])      the values of fc_ensemble_rmsd_pairs: best PROPER rotation
+ *   (r-, m-) = rmsd_and_max(X[i], -X[j])      partner inverted through the origin = its mirror image, any mirror plane
+ *   similar_enant(i, j) = (r+ < max_rmsd && m+ < max_dev) || (r- < max_rmsd && m- < max_dev)
+ *                         [&& |E_i - E_j| < max_dE when energies != NULL: applies to both handednesses]
+ *
+ * -- the OR of two complete tests, not "the smaller rmsd, then its max deviation".  Comparison operators, max_dev,
+ * conformer order, fc_prune_conventions and the k-ladder exactly as in fc_rmsd_simbits / fc_prune_rmsd: only the
+ * predicate changes.  A pair is grey when EITHER handedness is within 1e-9 of a threshold by the rule of
+ * fc_rmsd_simbits; it is counted once (n_grey, stats[3]).  Explicit entry points, no mode on the handle: every other
+ * entry point does what it did.  Same argument checks, error codes and limits as the sibling named in each line; the
+ * screen that runs is the one the default prune of the same ensemble runs (fc_screen_last_kind).
+ *
+ * fc_ensemble_rmsd_pairs_inv / fc_kabsch_rmsd_pairs_inv: (r-, m-) of fc_ensemble_rmsd_pairs / fc_kabsch_rmsd_pairs'
+ * pairs, literally rmsd_and_max(p, -q, center): with center = 1 the centroids are removed first, then q is negated;
+ * with center = 0 the caller's coordinates are negated as they are.
+ * fc_rmsd_simbits_enant: fc_rmsd_simbits with similar_enant.   fc_prune_rmsd_enant: fc_prune_rmsd with it (stats alike). */
+int fc_ensemble_rmsd_pairs_inv(fc_ensemble *ens, const int64_t *pair_i, const int64_t *pair_j, int64_t P,
+                               double *rmsd_out, double *maxdev_out);
+int fc_kabsch_rmsd_pairs_inv(const double *coords, int64_t N, int64_t A, const uint8_t *atom_mask, const int64_t *pair_i,
+                             const int64_t *pair_j, int64_t P, int center, double *rmsd_out, double *maxdev_out);
+int fc_rmsd_simbits_enant(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                          int64_t row_begin, int64_t row_end, uint64_t *bits_out, int64_t *n_grey);
+int fc_prune_rmsd_enant(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                        int64_t min_per_group, uint8_t *mask_out, int64_t *stats);
 /* One of the conventions of prism_pruner's pruner that the reference tree does not show (SURVEY.md
  * Appendix A) as a switch: 0 (default) = inside a chunk a structure is removed at the first LATER
  * similar one; 1 = the mirror rule (a structure falls to any earlier similar one of its chunk).
