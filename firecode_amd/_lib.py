@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FC_LIB_PATH") or os.path.join(_HERE, "libfc_hip.so")  # FC_LIB_PATH: a tuning build
 
 FC_OK = 0
-FC_E_INVALID, FC_E_NODEVICE, FC_E_HIP, FC_E_NOMEM, FC_E_LIMIT = -1, -2, -3, -4, -5
+FC_E_INVALID, FC_E_NODEVICE, FC_E_HIP, FC_E_NOMEM, FC_E_LIMIT, FC_E_INTERNAL = -1, -2, -3, -4, -5, -6
 
 
 class FirecodeHipError(RuntimeError):
@@ -77,6 +77,10 @@ _SIGNATURES = {
     "fc_prune_rmsd_enant": [_ens, _f64, _f64, _p_f64, _f64, _i64, _p_u8, _p_i64],
     "fc_prune_rmsd_host": [_p_f64, _i64, _i64, _p_u8, C.c_int, _f64, _f64, _p_f64, _f64, _i64, _p_u8, _p_i64],
     "fc_greedy_prune_from_bits": [_p_u64, _i64, _i64, _p_u8],
+    "fc_rmsd_clusters": [_ens, _f64, _f64, _p_f64, _f64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_i64, _p_i64],
+    "fc_rmsd_clusters_enant": [_ens, _f64, _f64, _p_f64, _f64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_i64, _p_i64],
+    "fc_clusters_from_pairs": [_p_u64, _i64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_i64],
+    "fc_clusters_from_bits": [_p_u64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_i64],
     "fc_prune_rmsd_begin": [_ens, _f64, _f64, _p_f64, _f64, _i64, _i64, _i64, _p_i64],
     "fc_prune_level": [_ens, _i64, _p_u8, _p_u8],
     "fc_prune_similar_pairs": [_ens, _p_u64, _i64, _p_i64],
@@ -537,6 +541,21 @@ class DeviceEnsemble:
         call("fc_prune_rmsd_enant" if enant else "fc_prune_rmsd", self.handle, float(max_rmsd), float(max_dev), pf(en), float(max_dE),
              int(min_per_group), pb(mask), pi(stats))
         return mask.astype(bool), stats
+
+    def clusters(self, max_rmsd, max_dev, energies=None, max_dE=0.0, prune_enantiomers=False):
+        """Connected components of the prune's similarity graph (fc_rmsd_clusters; ``prune_enantiomers=True``:
+        fc_rmsd_clusters_enant; the contract is in include/fc_hip.h) -> ``(labels (N,) int32, reps (K,) int64, sizes (K,)
+        int64, stats)`` in processing order: clusters numbered by ascending smallest member, which is their
+        representative.  stats: pairs, refined, edges, grey, 1 if the bit-matrix path ran, K."""
+        enant = check_flag("prune_enantiomers", prune_enantiomers)
+        labels = np.zeros(self.N, dtype=np.int32)
+        reps, sizes = np.zeros(self.N, dtype=np.int64), np.zeros(self.N, dtype=np.int64)
+        stats = np.zeros(6, dtype=np.int64)
+        k = C.c_int64(0)
+        en = None if energies is None else f64(energies)
+        call("fc_rmsd_clusters_enant" if enant else "fc_rmsd_clusters", self.handle, float(max_rmsd), float(max_dev), pf(en),
+             float(max_dE), ptr(labels, C.c_int32), pi(reps), pi(sizes), C.byref(k), pi(stats))
+        return labels, reps[:k.value].copy(), sizes[:k.value].copy(), stats
 
     def prune_begin(self, max_rmsd, max_dev, rank, world, row_block=128, energies=None, max_dE=0.0):
         stats = np.zeros(6, dtype=np.int64)

@@ -1017,6 +1017,158 @@ int fc_greedy_prune_from_bits(const uint64_t *bits, int64_t N, int64_t min_per_g
   return ladder_single(&e, min_per_group, job);
 }
 
+// ---- similarity clusters (the contract: include/fc_hip.h; the kernels: fc_clusters.hip) ------------------------------
+namespace {
+// what one labelling left in the pinned staging area: the result region of the workspace, then `extra` counter words
+struct ClusterResult {
+  const char *host = nullptr;
+  ClusterLayout L{};
+  const unsigned long long *status() const { return reinterpret_cast<const unsigned long long *>(host + L.status); }
+  const unsigned long long *extra() const { return reinterpret_cast<const unsigned long long *>(host + L.parent); }
+};
+
+// labels the graph and brings the result to the host: enqueue, ONE copy chain into pinned memory, one wait.
+// counters_dev (may be null): 16 counter words of the prune that travel behind the result.
+int clusters_run(const ClusterGraph &g, int64_t N, DevBuf &work, const void *counters_dev, ClusterResult *out) {
+  const ClusterLayout L = cluster_layout(N);
+  FC_TRY(work.reserve(L.total));
+  FC_TRY(pinned_reserve(L.parent + 16 * sizeof(uint64_t)));
+  FC_TRY(launch_clusters(g, N, work));
+  char *host = static_cast<char *>(ctx().pinned);
+  FC_TRY(d2h(host, work.p, L.result_bytes));
+  if (counters_dev) FC_TRY(d2h(host + L.parent, counters_dev, 16 * sizeof(uint64_t)));
+  FC_TRY(sync());
+  out->host = host, out->L = L;
+  if (out->status()[kClStatusErr] != 0ull)
+    return set_error(FC_E_INTERNAL, "cluster labelling: a union exceeded its retry bound on the device");
+  return FC_OK;
+}
+
+void clusters_unpack(const ClusterResult &r, int64_t N, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
+                     int64_t *n_clusters) {
+  const int64_t K = (int64_t)r.status()[kClStatusK];
+  std::memcpy(labels_out, r.host + r.L.labels, (size_t)N * sizeof(int32_t));
+  std::memcpy(reps_out, r.host + r.L.reps, (size_t)K * sizeof(int64_t));
+  std::memcpy(sizes_out, r.host + r.L.sizes, (size_t)K * sizeof(int64_t));
+  *n_clusters = K;
+}
+
+// the body of fc_rmsd_clusters behind its argument checks; may return with work in flight (the caller drains on error)
+int rmsd_clusters_run(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE, DevBuf &work,
+                      int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int64_t *n_clusters, int64_t *stats) {
+  const int64_t N = ens->N;
+  FC_TRY(ensemble_shard(ens, 0, 1, default_row_block()));
+  auto *cnt = reinterpret_cast<unsigned long long *>(ens->counters.p);
+  // lean first, as fc_prune_rmsd: only the pair lists.  The hook kernel itself declines the list when the candidate queue
+  // overflowed (counters[6] > pairq_cap, read on the device); the host sees that with the results and only then asks for
+  // the bit matrix
+  FC_TRY(simbits_local(ens, max_rmsd, max_dev, energies, max_dE, true, /*lean=*/true));
+  ClusterGraph g;
+  g.pairs_dev = ens->simq.as<uint64_t>(), g.n_pairs_dev = cnt + 2;
+  g.n_cand_dev = cnt + 6, g.cand_cap = (unsigned long long)ens->pairq_cap, g.redo_dev = cnt + 12;
+  // (the similar-pair count last seen for these coordinates, as the ladder's form is chosen; -1: nothing seen yet)
+  g.known_short = ens->last_similar >= 0 && ens->last_similar < kClShortList;
+  ClusterResult res;
+  FC_TRY(clusters_run(g, N, work, cnt, &res));
+  int64_t from_bits = 0;
+  if (res.status()[kClStatusList] == 0ull) {
+    FC_TRY(simbits_local(ens, max_rmsd, max_dev, energies, max_dE, true, /*lean=*/false));
+    ClusterGraph gb;
+    gb.bits_dev = ens->bits.as<uint64_t>(), gb.W = ens->W;
+    FC_TRY(clusters_run(gb, N, work, cnt, &res));
+    from_bits = 1;
+  }
+  const unsigned long long *c = res.extra();
+  note_candidates(ens, c[6], c[2]);
+  clusters_unpack(res, N, labels_out, reps_out, sizes_out, n_clusters);
+  if (stats) fill_stats(stats, N * (N - 1) / 2, c, from_bits, *n_clusters);
+  return FC_OK;
+}
+}  // namespace
+
+int fc_rmsd_clusters(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                     int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int64_t *n_clusters, int64_t *stats) {
+  FC_API_LOCK;
+  FC_REQUIRE(ens && n_clusters, "NULL pointer argument");
+  FC_REQUIRE(max_rmsd > 0.0 && max_dev > 0.0, "thresholds must be positive");
+  *n_clusters = 0;
+  if (stats) std::memset(stats, 0, 6 * sizeof(int64_t));
+  FC_TRY(ensure_init());
+  if (ens->N == 0) return FC_OK;
+  FC_REQUIRE(labels_out && reps_out && sizes_out, "NULL pointer argument");
+  FC_REQUIRE(ens->N <= (int64_t)INT32_MAX - 256, "N=%lld: clusters index conformers with 32 bits", (long long)ens->N);
+  DevBuf work;
+  const int rc = rmsd_clusters_run(ens, max_rmsd, max_dev, energies, max_dE, work, labels_out, reps_out, sizes_out,
+                                   n_clusters, stats);
+  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());  // nothing of `work` may be in flight when it goes out of scope
+  return rc;
+}
+
+int fc_rmsd_clusters_enant(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                           int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int64_t *n_clusters,
+                           int64_t *stats) {
+  FC_API_LOCK;
+  FC_REQUIRE(ens && n_clusters, "NULL pointer argument");
+  EnantScope scope(ens);
+  return fc_rmsd_clusters(ens, max_rmsd, max_dev, energies, max_dE, labels_out, reps_out, sizes_out, n_clusters, stats);
+}
+
+// a caller's graph: checks on the host, one upload, the same labelling
+static int clusters_from_graph(const uint64_t *pairs, int64_t n_pairs, const uint64_t *bits, int64_t N, int32_t *labels_out,
+                               int64_t *reps_out, int64_t *sizes_out, int64_t *n_clusters) {
+  FC_TRY(ensure_init());
+  DevBuf graph, work;
+  ClusterGraph g;
+  ClusterResult res;
+  int rc = FC_OK;
+  if (bits != nullptr) {
+    const int64_t W = ceil_div(N, 64);
+    rc = upload(graph, bits, (size_t)N * (size_t)W);
+    g.bits_dev = graph.as<uint64_t>(), g.W = W;
+  } else {
+    rc = upload(graph, pairs, (size_t)n_pairs);  // (n_pairs == 0: an 8-byte block that is never read)
+    g.pairs_dev = graph.as<uint64_t>(), g.n_pairs_host = (unsigned long long)n_pairs;
+    g.known_short = n_pairs < kClShortList;
+  }
+  if (rc == FC_OK) rc = clusters_run(g, N, work, nullptr, &res);
+  if (rc != FC_OK) {
+    (void)hipStreamSynchronize(cur_stream());  // nothing of `graph` / `work` may be in flight when they go out of scope
+    return rc;
+  }
+  clusters_unpack(res, N, labels_out, reps_out, sizes_out, n_clusters);
+  return FC_OK;
+}
+
+int fc_clusters_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int32_t *labels_out, int64_t *reps_out,
+                           int64_t *sizes_out, int64_t *n_clusters) {
+  FC_API_LOCK;
+  FC_REQUIRE(n_clusters != nullptr, "n_clusters is NULL");
+  FC_REQUIRE(N >= 0 && n_pairs >= 0, "bad arguments N=%lld n_pairs=%lld", (long long)N, (long long)n_pairs);
+  FC_REQUIRE(N <= (int64_t)INT32_MAX - 256, "N=%lld: clusters index conformers with 32 bits", (long long)N);
+  FC_REQUIRE(pairs != nullptr || n_pairs == 0, "pairs is NULL");
+  for (int64_t p = 0; p < n_pairs; ++p) {
+    const uint64_t i = pairs[p] >> 32, j = pairs[p] & 0xffffffffull;
+    FC_REQUIRE(i != j && i < (uint64_t)N && j < (uint64_t)N, "pair %lld = (%llu, %llu): i == j or an index outside [0, %lld)",
+               (long long)p, (unsigned long long)i, (unsigned long long)j, (long long)N);
+  }
+  *n_clusters = 0;
+  if (N == 0) return FC_OK;
+  FC_REQUIRE(labels_out && reps_out && sizes_out, "NULL pointer argument");
+  return clusters_from_graph(pairs, n_pairs, nullptr, N, labels_out, reps_out, sizes_out, n_clusters);
+}
+
+int fc_clusters_from_bits(const uint64_t *bits, int64_t N, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
+                          int64_t *n_clusters) {
+  FC_API_LOCK;
+  FC_REQUIRE(n_clusters != nullptr, "n_clusters is NULL");
+  FC_REQUIRE(N >= 0, "N=%lld < 0", (long long)N);
+  FC_REQUIRE(N <= (int64_t)INT32_MAX - 256, "N=%lld: clusters index conformers with 32 bits", (long long)N);
+  *n_clusters = 0;
+  if (N == 0) return FC_OK;
+  FC_REQUIRE(bits && labels_out && reps_out && sizes_out, "NULL pointer argument");
+  return clusters_from_graph(nullptr, 0, bits, N, labels_out, reps_out, sizes_out, n_clusters);
+}
+
 int fc_prune_rmsd_begin(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies,
                         double max_dE, int64_t rank, int64_t world, int64_t row_block,
                         int64_t *stats) {

@@ -1,0 +1,349 @@
+// fc_clusters.hip -- connected components of a similarity graph on the device (include/fc_hip.h, "similarity clusters";
+// DESIGN.md section 13): labels, representatives and sizes from the exactly-similar pair list of the RMSD stage, from its
+// bit matrix, or from a caller's graph in either form.
+//
+// A lock-free union-find over parent[N] (int32).  The LARGER root is always hooked under the SMALLER one, so
+//   - a non-root's parent is strictly smaller than its index: every walk ends, whatever it reads on the way;
+//   - a component's final root is its smallest member: the representative the contract asks for, without a second pass.
+// Launches: init -> hook (pairs or bits; long lists in phases with a compression between them, below) -> flatten +
+// root flags -> scan -> label.  Only the hook kernels have threads that read what other workgroups of the SAME launch
+// write; they read and write parent[] with agent-scope atomics only (below).  Behind a kernel boundary plain loads are
+// enough.
+#include "fc_internal.h"
+
+namespace fc {
+
+namespace {
+
+constexpr int kClThreads = 256;
+
+// Inside the hook kernel every access to parent[] is an agent-scope atomic: the L2s of the eight XCDs are not coherent
+// for plain loads within a launch, and a retry that re-read a stale parent from its own XCD's L2 could spin for as
+// long as the line stays resident.
+__device__ __forceinline__ int32_t cl_load(const int32_t *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void cl_store(int32_t *p, int32_t v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// root of x with path halving.  A halving store that loses against another one costs time only: whatever lands in
+// parent[x] was an ancestor of x when it was read, so it is smaller than x and in x's tree for good (trees only merge).
+// At most x steps: every step moves to a strictly smaller index.
+__device__ __forceinline__ int32_t cl_find(int32_t *parent, int32_t x) {
+  for (;;) {
+    const int32_t p = cl_load(parent + x);
+    if (p == x) return x;
+    const int32_t g = cl_load(parent + p);
+    if (g == p) return p;
+    cl_store(parent + x, g);
+    x = g;
+  }
+}
+
+// One union.  Every successful CAS removes a root, every failed one means that another thread's CAS on the same word
+// succeeded: at most N - 1 failures over the whole launch.  The cap is a multiple of that; reaching it is a bug in this
+// file and ends as an error word (FC_E_INTERNAL on the host), never as a hang.
+__device__ __forceinline__ void cl_unite(int32_t *parent, int32_t a, int32_t b, int64_t retry_cap,
+                                         unsigned long long *status) {
+  // both ends under one parent already: the same tree, and nothing to write (what the later phases of a long list mostly
+  // finds: two loads of words that nobody writes any more)
+  if (cl_load(parent + a) == cl_load(parent + b)) return;
+  for (int64_t tries = 0;; ++tries) {
+    a = cl_find(parent, a);
+    b = cl_find(parent, b);
+    if (a == b) return;
+    const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
+    int32_t expected = hi;
+    if (__hip_atomic_compare_exchange_strong(parent + hi, &expected, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT))
+      return;
+    if (tries >= retry_cap) {
+      status[kClStatusErr] = 1ull;
+      return;
+    }
+    a = expected;  // what hi was hooked under meanwhile
+    b = lo;
+  }
+}
+
+// Long lists in phases.  With every edge of a dense graph in flight at once, hundreds of unions per vertex meet on the
+// few words near the root of the giant component: CAS retries, halving stores and dependent agent-scope loads of lines
+// that every atomic drops from the L2s serialise (7.6e5 edges on 10^4 conformers: one launch took 5 ms).  What costs is
+// the number of unions in flight that meet on the same words, so the forest is grown under little contention first:
+//   seed    parent[larger end] = min(itself, smaller end) for EVERY entry: one atomic that returns nothing -- no read, no
+//           retry (25 us for that list).  It unites nothing by the hooking rule; it leaves every vertex pointing at its
+//           smallest smaller neighbour, a forest inside the components whose roots are the local minima of the graph
+//           (about N / degree of them instead of N).  A launch of its own in front of any CAS: the invariants (parent
+//           <= index, parent in the same component) hold throughout;
+//   coarse  the hooking rule on 1/1024 of the entries: enough to join most of those few trees (42 us);
+//   fine    on the next 31/1024, then on the rest (7 us each): after a compression nearly every union starts with
+//           "both ends under one parent already" -- two loads of words that nobody writes any more.
+// k_cl_compress (parent[i] = root(i)) runs between the phases.  An entry's class is a multiplicative hash of its position,
+// so that no stride of the list or of the bit rows lines up with it.  Which entries a phase takes changes the order of
+// the unions, never the components.
+__device__ __forceinline__ void cl_seed(int32_t *parent, int32_t hi, int32_t lo) {
+  (void)__hip_atomic_fetch_min(parent + hi, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// an entry's sampling class, 0 .. 1023: the phases take [0, 1), [1, 32) and [32, 1024)
+__device__ __forceinline__ unsigned cl_class(unsigned long long idx) { return ((uint32_t)idx * 2654435761u) >> 22; }
+constexpr unsigned kClClasses = 1024, kClCoarse = 1, kClFine = 32;
+constexpr unsigned long long kClSplitMin = (unsigned long long)kClShortList;  // entries from which a list is split
+constexpr unsigned long long kClNeverSplit = ~0ull;
+
+__global__ void __launch_bounds__(kClThreads)
+k_cl_init(int32_t *__restrict__ parent, int64_t N, unsigned long long *__restrict__ status, unsigned long long n_pairs) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N) parent[i] = (int32_t)i;
+  if (i == 0) {
+    status[kClStatusErr] = 0ull;
+    status[kClStatusList] = 1ull;
+    status[kClStatusK] = 0ull;
+    status[kClStatusPairs] = n_pairs;
+  }
+}
+
+// One thread per entry of a device pair list ((i << 32) | j, either order, duplicates allowed) whose length is a
+// device word: counters[2] of the refine, read here as the ladder reads it, with no host round trip.  The list is
+// declined -- status[kClStatusList] = 0, nothing hooked -- when the refine's candidate queue overflowed (it then wrote no
+// complete list; n_cand_ptr / cand_cap) or the screen's verdict asked for a redo (redo_ptr): the same conditions, decided
+// in the same place, as k_ladder_pairs' counters[9].  Entries with i == j or an index >= N are padding and never act.
+// seed: the seed launch; otherwise the entries of the classes [c_lo, c_hi).  A list shorter than split_min is not split:
+// the launch that takes the last classes hooks ALL of it and the others return -- decided here from the device's
+// length, so every launch sequence is right for any list.
+__global__ void __launch_bounds__(kClThreads)
+k_cl_hook_pairs(const uint64_t *__restrict__ pairs, const unsigned long long *__restrict__ n_pairs_ptr,
+                const unsigned long long *__restrict__ n_cand_ptr, unsigned long long cand_cap,
+                const unsigned long long *__restrict__ redo_ptr, int64_t N, int32_t *parent,
+                unsigned long long *status, bool seed, unsigned c_lo, unsigned c_hi, unsigned long long split_min) {
+  const unsigned long long P = *n_pairs_ptr;
+  const bool declined = (n_cand_ptr != nullptr && (*n_cand_ptr > cand_cap || P > cand_cap)) ||
+                        (redo_ptr != nullptr && *redo_ptr != 0ull);
+  if (declined) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) status[kClStatusList] = 0ull;
+    return;
+  }
+  const bool split = P >= split_min;
+  const bool last = !seed && c_hi == kClClasses;
+  if (!last && !split) return;
+  const uint32_t n32 = (uint32_t)N;
+  const int64_t retry_cap = 4 * N + 1024;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  for (unsigned long long p = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += stride) {
+    if (!seed && split && (cl_class(p) < c_lo || cl_class(p) >= c_hi)) continue;
+    const uint64_t e = pairs[p];
+    const uint32_t i = (uint32_t)(e >> 32), j = (uint32_t)(e & 0xffffffffull);
+    if (i == j || i >= n32 || j >= n32) continue;
+    if (seed) {
+      cl_seed(parent, (int32_t)(i > j ? i : j), (int32_t)(i > j ? j : i));
+      continue;
+    }
+    cl_unite(parent, (int32_t)i, (int32_t)j, retry_cap, status);
+  }
+}
+
+// One thread per 64-bit word of the bit matrix (row i, word w; row stride W words), walking its set bits.  Only bits
+// j > i are read: words left of the diagonal word are skipped (the RMSD stage never writes them), the diagonal word is
+// masked.  seed: the seed launch (one seed per word: its first neighbour); otherwise the words of the classes [c_lo, c_hi).
+__global__ void __launch_bounds__(kClThreads)
+k_cl_hook_bits(const uint64_t *__restrict__ bits, int64_t W, int64_t N, int32_t *parent, unsigned long long *status,
+               bool seed, unsigned c_lo, unsigned c_hi) {
+  const int64_t total = N * W;
+  const int64_t retry_cap = 4 * N + 1024;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t i = t / W, w = t - i * W;
+    if (w < (i >> 6)) continue;
+    if (!seed && (cl_class((unsigned long long)t) < c_lo || cl_class((unsigned long long)t) >= c_hi)) continue;
+    uint64_t word = bits[t];
+    if (w == (i >> 6)) word &= (i & 63) == 63 ? 0ull : ~0ull << ((i & 63) + 1);
+    if (seed) {
+      const int64_t j = w * 64 + __ffsll((unsigned long long)word) - 1;
+      if (word && j < N) cl_seed(parent, (int32_t)j, (int32_t)i);
+      continue;
+    }
+    while (word) {
+      const int b = __ffsll((unsigned long long)word) - 1;
+      word &= word - 1;
+      const int64_t j = w * 64 + b;
+      if (j < N) cl_unite(parent, (int32_t)i, (int32_t)j, retry_cap, status);
+    }
+  }
+}
+
+// between the phases of a long list: parent[i] = root of i, in place.  Other threads walk through parent[i] while it is
+// rewritten; old and new value are both ancestors of i, and no root changes in this launch.
+__global__ void __launch_bounds__(kClThreads)
+k_cl_compress(int32_t *parent, int64_t N) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  int32_t x = (int32_t)i;
+  for (int32_t p = cl_load(parent + x); p != x; p = cl_load(parent + x)) x = p;
+  cl_store(parent + i, x);
+}
+
+// root[i] = root of i (out of place: nothing this launch reads is written by it), and the root flags of 64 consecutive
+// conformers packed into one word with the wave64 ballot.
+__global__ void __launch_bounds__(kClThreads)
+k_cl_flatten(const int32_t *__restrict__ parent, int64_t N, int32_t *__restrict__ root, uint64_t *__restrict__ flags,
+             int64_t W) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool is_root = false;
+  if (i < N) {
+    int32_t x = (int32_t)i;
+    for (int32_t p = parent[x]; p != x; p = parent[x]) x = p;
+    root[i] = x;
+    is_root = x == (int32_t)i;
+  }
+  const uint64_t m = __ballot(is_root);
+  if ((threadIdx.x & 63) == 0 && (i >> 6) < W) flags[i >> 6] = m;
+}
+
+// exclusive prefix of the per-word root counts; one workgroup loops over the W words (15 625 at 10^6 conformers)
+__global__ void __launch_bounds__(1024)
+k_cl_scan(const uint64_t *__restrict__ flags, int64_t W, int32_t *__restrict__ prefix,
+          unsigned long long *__restrict__ status) {
+  __shared__ int s_wave[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int carry = 0;
+  for (int64_t base = 0; base < W; base += 1024) {
+    const int64_t w = base + tid;
+    const int c = w < W ? __popcll(flags[w]) : 0;
+    int v = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(v, o);
+      if (lane >= o) v += t;
+    }
+    if (lane == 63) s_wave[wave] = v;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int s = s_wave[q];
+      if (q < wave) before += s;
+      all += s;
+    }
+    if (w < W) prefix[w] = carry + before + v - c;
+    carry += all;
+    __syncthreads();
+  }
+  if (tid == 0) status[kClStatusK] = (unsigned long long)carry;
+}
+
+// label[i] = rank of i's root among the roots; the root itself writes reps[rank]; sizes[rank] counts members.  The
+// adds are aggregated within the wavefront first (up to four distinct clusters per wavefront through a ballot each,
+// the rest one by one): one giant cluster costs N / 64 adds to its word, not N.  Integer adds: the order does not show.
+__global__ void __launch_bounds__(kClThreads)
+k_cl_label(const int32_t *__restrict__ root, int64_t N, const uint64_t *__restrict__ flags,
+           const int32_t *__restrict__ prefix, int32_t *__restrict__ labels, int64_t *__restrict__ reps,
+           unsigned long long *__restrict__ sizes) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  bool pending = i < N;
+  int32_t rank = -1;
+  if (pending) {
+    const int32_t r = root[i];
+    rank = prefix[r >> 6] + __popcll(flags[r >> 6] & ((1ull << (r & 63)) - 1ull));
+    labels[i] = rank;
+    if ((int64_t)r == i) reps[rank] = i;
+  }
+  for (int round = 0; round < 4; ++round) {
+    const uint64_t mp = __ballot(pending);
+    if (mp == 0) break;  // wave-uniform
+    const int leader = __ffsll((unsigned long long)mp) - 1;
+    const int32_t lr = __shfl(rank, leader);
+    const bool same = pending && rank == lr;
+    const uint64_t ms = __ballot(same);
+    if (lane == leader) atomicAdd(&sizes[lr], (unsigned long long)__popcll(ms));
+    pending = pending && !same;
+  }
+  if (pending) atomicAdd(&sizes[rank], 1ull);
+}
+
+int cl_blocks(int64_t items, int per_cu) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, kClThreads), (int64_t)ctx().n_cu * per_cu));
+}
+
+}  // namespace
+
+// Everything behind the graph: the caller has reserved `work` (cluster_layout(N).total bytes) and, for the pair form,
+// left the list where `g` says.  Enqueues only; the result region of `work` is complete when the stream has drained.
+int launch_clusters(const ClusterGraph &g, int64_t N, DevBuf &work) {
+  const ClusterLayout L = cluster_layout(N);
+  if (work.p == nullptr || work.bytes < L.total) return set_error(FC_E_INVALID, "cluster workspace too small");
+  if (N < 1 || N > (int64_t)INT32_MAX - 256) return set_error(FC_E_LIMIT, "N=%lld: clusters index conformers with 32 bits", (long long)N);
+  if ((g.pairs_dev != nullptr) == (g.bits_dev != nullptr)) return set_error(FC_E_INVALID, "one of pair list / bit matrix");
+  char *base = static_cast<char *>(work.p);
+  auto *labels = reinterpret_cast<int32_t *>(base + L.labels);
+  auto *reps = reinterpret_cast<int64_t *>(base + L.reps);
+  auto *sizes = reinterpret_cast<unsigned long long *>(base + L.sizes);
+  auto *status = reinterpret_cast<unsigned long long *>(base + L.status);
+  auto *parent = reinterpret_cast<int32_t *>(base + L.parent);
+  auto *root = reinterpret_cast<int32_t *>(base + L.root);
+  auto *flags = reinterpret_cast<uint64_t *>(base + L.flags);
+  auto *prefix = reinterpret_cast<int32_t *>(base + L.prefix);
+  const int64_t W = ceil_div(N, 64);
+  hipStream_t st = cur_stream();
+  const unsigned per_n = (unsigned)ceil_div(N, kClThreads);
+  FC_HIP_TRY(hipMemsetAsync(sizes, 0, (size_t)N * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_cl_init, dim3(per_n), dim3(kClThreads), 0, st, parent, N, status, g.n_pairs_host);
+  FC_TRY(check_launch("k_cl_init"));
+  const auto compress = [&]() {
+    hipLaunchKernelGGL(k_cl_compress, dim3(per_n), dim3(kClThreads), 0, st, parent, N);
+    return check_launch("k_cl_compress");
+  };
+  if (g.pairs_dev != nullptr) {
+    const unsigned long long *n_pairs_dev = g.n_pairs_dev != nullptr ? g.n_pairs_dev : status + kClStatusPairs;
+    // the list's length is on the device only: the grid is sized for the chip, the kernels stride.  g.known_short: the
+    // caller has seen this list's length (or a recent one of these coordinates) -- the launches that would find
+    // nothing to do are left out; a list that is long after all is then hooked in one launch, slowly and correctly
+    const dim3 grid((unsigned)(ctx().n_cu * 8));
+    const unsigned long long split_min = g.known_short ? kClNeverSplit : kClSplitMin;
+    const auto hook = [&](bool seed, unsigned c_lo, unsigned c_hi) {
+      hipLaunchKernelGGL(k_cl_hook_pairs, grid, dim3(kClThreads), 0, st, g.pairs_dev, n_pairs_dev, g.n_cand_dev, g.cand_cap,
+                         g.redo_dev, N, parent, status, seed, c_lo, c_hi, split_min);
+      return check_launch("k_cl_hook_pairs");
+    };
+    if (!g.known_short) {
+      FC_TRY(hook(true, 0, 0));
+      FC_TRY(compress());
+      FC_TRY(hook(false, 0, kClCoarse));
+      FC_TRY(compress());
+      FC_TRY(hook(false, kClCoarse, kClFine));
+      FC_TRY(compress());
+    }
+    FC_TRY(hook(false, kClFine, kClClasses));  // (all of a list that is not split)
+  } else {
+    if (g.W < W) return set_error(FC_E_INVALID, "bit rows of %lld words, %lld needed", (long long)g.W, (long long)W);
+    const dim3 grid((unsigned)cl_blocks(N * g.W, 16));
+    const bool split = (unsigned long long)N * (unsigned long long)g.W >= 1024ull;  // (the bit matrix is the dense case)
+    const auto hook = [&](bool seed, unsigned c_lo, unsigned c_hi) {
+      hipLaunchKernelGGL(k_cl_hook_bits, grid, dim3(kClThreads), 0, st, g.bits_dev, g.W, N, parent, status, seed, c_lo, c_hi);
+      return check_launch("k_cl_hook_bits");
+    };
+    if (split) {
+      FC_TRY(hook(true, 0, 0));
+      FC_TRY(compress());
+      FC_TRY(hook(false, 0, kClCoarse));
+      FC_TRY(compress());
+      FC_TRY(hook(false, kClCoarse, kClFine));
+      FC_TRY(compress());
+    }
+    FC_TRY(hook(false, split ? kClFine : 0u, kClClasses));
+  }
+  hipLaunchKernelGGL(k_cl_flatten, dim3(per_n), dim3(kClThreads), 0, st, parent, N, root, flags, W);
+  FC_TRY(check_launch("k_cl_flatten"));
+  hipLaunchKernelGGL(k_cl_scan, dim3(1), dim3(1024), 0, st, flags, W, prefix, status);
+  FC_TRY(check_launch("k_cl_scan"));
+  hipLaunchKernelGGL(k_cl_label, dim3(per_n), dim3(kClThreads), 0, st, root, N, flags, prefix, labels, reps, sizes);
+  return check_launch("k_cl_label");
+}
+
+__global__ void k_warm_clusters() {}
+int warm_clusters() {
+  hipLaunchKernelGGL(k_warm_clusters, dim3(1), dim3(64), 0, ctx().stream);
+  return check_launch("k_warm_clusters");
+}
+
+}  // namespace fc

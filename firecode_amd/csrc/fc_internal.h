@@ -146,6 +146,47 @@ int diverse_lanes(int64_t N);
 int select_diverse(fc_ensemble *e, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
                    double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected, double *ms_device);
 int warm_diverse();
+// ---- fc_clusters.hip -------------------------------------------------------------------------------------
+// the graph whose components are labelled: a device pair list OR a bit matrix
+struct ClusterGraph {
+  const uint64_t *pairs_dev = nullptr;               // (i << 32) | j, either order, duplicates allowed
+  const unsigned long long *n_pairs_dev = nullptr;   // the list's length on the device (counters + 2); nullptr: n_pairs_host
+  unsigned long long n_pairs_host = 0;
+  bool known_short = false;                          // speed only: the list is known to be short, hook it in one launch
+  const unsigned long long *n_cand_dev = nullptr;    // counters + 6: the list is declined when it exceeds cand_cap
+  unsigned long long cand_cap = 0;
+  const unsigned long long *redo_dev = nullptr;      // counters + 12: ... or when the screen's verdict asked for a redo
+  const uint64_t *bits_dev = nullptr;                // rows of W words, only bits j > i are read
+  int64_t W = 0;
+};
+// words of the status block behind the results
+constexpr int kClStatusErr = 0;    // 1: a union ran into its retry cap (FC_E_INTERNAL)
+constexpr int kClStatusList = 1;   // 1: the pair list produced the result, 0: the hook kernel declined it
+constexpr int kClStatusK = 2;      // number of clusters
+constexpr int kClStatusPairs = 3;  // length of a list uploaded by the caller
+constexpr int64_t kClShortList = 1 << 16;  // pair lists below this are hooked in one launch (fc_clusters.hip)
+// one block: labels | reps | sizes | status (the part that travels to the host, result_bytes from offset 0) | scratch
+struct ClusterLayout {
+  size_t labels, reps, sizes, status, result_bytes, parent, root, flags, prefix, total;
+};
+inline ClusterLayout cluster_layout(int64_t N) {
+  const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t n = (size_t)(N > 0 ? N : 1), w = (n + 63) / 64;
+  ClusterLayout L{};
+  L.labels = 0;
+  L.reps = up(n * sizeof(int32_t));
+  L.sizes = L.reps + up(n * sizeof(int64_t));
+  L.status = L.sizes + up(n * sizeof(int64_t));
+  L.result_bytes = L.status + 4 * sizeof(uint64_t);
+  L.parent = up(L.result_bytes);
+  L.root = L.parent + up(n * sizeof(int32_t));
+  L.flags = L.root + up(n * sizeof(int32_t));
+  L.prefix = L.flags + up(w * sizeof(uint64_t));
+  L.total = L.prefix + up(w * sizeof(int32_t));
+  return L;
+}
+int launch_clusters(const ClusterGraph &g, int64_t N, DevBuf &work);
+int warm_clusters();
 // ---- fc_tfd_ladder.hip -----------------------------------------------------------------------------------
 int tfd_ladder_device(const int64_t *fm_dev, const int64_t *fm_host, int64_t N, uint8_t *mask_out);
 int pyset_order_pairs_device(const int64_t *pairs_host, int64_t n, int64_t *order_out);

@@ -129,6 +129,17 @@ class Ensemble:
                 f"{perf_counter() - t0:.3f} s)")
         return sel
 
+    def cluster_by_rmsd(self, max_rmsd=None, heavy_atoms_only=True, prune_enantiomers=False, verbose=True):
+        """Which conformers belong together (``firecode_amd.pruner.cluster_by_rmsd``): the connected components of the
+        graph the RMSD stage of ``similarity_pruning`` prunes, with its energies and window (``max_dE = 1.0`` when there is
+        one energy per conformer).  Returns the ``RmsdClusters``; the ensemble is not masked."""
+        from firecode_amd.pruner import cluster_by_rmsd
+
+        use_en = len(self.energies) == len(self.coords)
+        return cluster_by_rmsd(self.coords, self.atoms, max_rmsd, energies=self.energies if use_en else None,
+                               max_dE=1.0 if use_en else 0.0, debugfunction=self.logfunction if verbose else None,
+                               heavy_atoms_only=heavy_atoms_only, prune_enantiomers=prune_enantiomers)
+
     def similarity_pruning(self, moi=True, rmsd=True, rmsd_rot_corr=False, verbose=True, max_rmsd=None,
                            symmetric_torsions=None, graph=None, rotation_masks=None, prune_enantiomers=False):
         """firecode/ensemble.py:185-276: MOI prune, RMSD prune, then (``rmsd_rot_corr``, at

@@ -157,6 +157,108 @@ def select_diverse(structures, atoms, n=None, stop_rmsd=None, heavy_atoms_only=T
         return DiverseSelection(*ens.select_diverse(n_max, start=int(start), stop_rmsd=stop_rmsd))
 
 
+RmsdClusters = namedtuple("RmsdClusters", ["labels", "representatives", "sizes"])
+
+
+def cluster_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None, max_dE=0.0, debugfunction=None,
+                    heavy_atoms_only=True, prune_enantiomers=False):
+    """Which conformers belong together: the connected components of the similarity graph ``prune_by_rmsd`` prunes
+    (an edge where ``rmsd < max_rmsd and maxdev < max_dev`` [and ``|dE| < max_dE``]; with ``prune_enantiomers=True``
+    also where that holds for the mirror image), on the GPU (fc_rmsd_clusters; the contract is written out in
+    include/fc_hip.h).  Unlike the greedy mask the answer does not depend on the order of the conformers, on
+    ``min_per_group`` or on ``CONVENTIONS["drop"]``.
+
+    Returns ``RmsdClusters(labels, representatives, sizes)``: labels (N,) int32 in the caller's order; representatives
+    (K,) int64 indices into ``structures``; sizes (K,) int64.  A cluster's representative is its first member in
+    processing order -- lowest energy (earliest on ties) when ``energies`` is usable, lowest index otherwise -- and
+    clusters are numbered in the order of their representatives."""
+    t0 = perf_counter()
+    enant = L.check_flag("prune_enantiomers", prune_enantiomers)
+    structures = L.f64(structures)
+    if structures.ndim != 3 or structures.shape[2] != 3:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {structures.shape}")
+    atoms = np.asarray(atoms)
+    if atoms.shape[0] != structures.shape[1]:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "len(atoms) != number of atoms")
+    max_rmsd, max_dev, max_dE = _thresholds(max_rmsd, max_dev, max_dE)
+    N = structures.shape[0]
+    if N == 0:
+        return RmsdClusters(np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))
+    heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
+    order, en_sorted = _sorted_by_energy(structures, energies)
+    X = structures if order is None else np.ascontiguousarray(structures[order])
+    with L.DeviceEnsemble(X, atom_mask=heavy, center=True) as ens:
+        labels_sorted, reps_sorted, sizes, stats = ens.clusters(max_rmsd, max_dev, energies=en_sorted, max_dE=max_dE,
+                                                                prune_enantiomers=enant)
+    if order is None:
+        labels, reps = labels_sorted, reps_sorted
+    else:
+        labels = np.empty_like(labels_sorted)
+        labels[order] = labels_sorted
+        reps = order[reps_sorted].astype(np.int64)
+    if debugfunction is not None:
+        debugfunction(
+            f"DEBUG: cluster_by_rmsd [gfx950{', mirror images included' if enant else ''}] - {stats[0]} pairs screened, "
+            f"{stats[2]} similar, {len(sizes)} clusters, largest {int(sizes.max())}, in {perf_counter() - t0:.3f} s")
+    return RmsdClusters(labels, reps, sizes)
+
+
+def _clusters_from_graph(name, graph, n):
+    labels = np.zeros(n, dtype=np.int32)
+    reps, sizes = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    import ctypes as C
+
+    k = C.c_int64(0)
+    args = (L.pw(graph), int(graph.shape[0]), n) if name == "fc_clusters_from_pairs" else (L.pw(graph), n)
+    L.call(name, *args, L.ptr(labels, C.c_int32), L.pi(reps), L.pi(sizes), C.byref(k))
+    return RmsdClusters(labels, reps[:k.value].copy(), sizes[:k.value].copy())
+
+
+def _vertex_count(n):
+    if isinstance(n, (bool, np.bool_)) or int(n) != n or int(n) < 0:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"n={n!r}: a vertex count >= 0")
+    if int(n) > 2 ** 31 - 257:
+        raise L.FirecodeHipInputError(L.FC_E_LIMIT, f"n={n!r}: clusters index vertices with 32 bits")
+    return int(n)
+
+
+def clusters_from_pairs(pairs, n):
+    """The labelling of ``cluster_by_rmsd`` on a caller's graph (fc_clusters_from_pairs): ``pairs`` (P,) uint64
+    ``(i << 32) | j`` -- the format of ``DeviceEnsemble.similar_pairs`` -- in either order, duplicates allowed, or a
+    (P, 2) integer array of (i, j); ``n`` vertices.  ``i == j`` or an index outside [0, n) is refused before any device
+    use.  Returns ``RmsdClusters``: clusters numbered by ascending smallest member, which is their representative."""
+    n = _vertex_count(n)
+    pairs = np.asarray(pairs)
+    if pairs.ndim == 2 and pairs.shape[1] == 2:
+        ij = pairs.astype(np.int64)
+        if ij.size and (ij.min() < 0 or ij.max() >= n):
+            raise L.FirecodeHipInputError(L.FC_E_INVALID, f"a pair index outside [0, {n})")
+        pairs = (ij[:, 0].astype(np.uint64) << np.uint64(32)) | ij[:, 1].astype(np.uint64)
+    elif pairs.ndim != 1:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"pairs must be (P,) uint64 or (P, 2), got {pairs.shape}")
+    if pairs.size and pairs.dtype.kind not in "ui":
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"pairs must be integers, got {pairs.dtype}")
+    if pairs.size and pairs.dtype.kind == "i" and pairs.min() < 0:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "negative pair word")
+    pairs = np.ascontiguousarray(pairs, dtype=np.uint64)
+    hi, lo = pairs >> np.uint64(32), pairs & np.uint64(0xFFFFFFFF)
+    if pairs.size and ((hi == lo).any() or hi.max() >= n or lo.max() >= n):
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"a pair with i == j or an index outside [0, {n})")
+    return _clusters_from_graph("fc_clusters_from_pairs", pairs, n)
+
+
+def clusters_from_bits(bits, n):
+    """The labelling of ``cluster_by_rmsd`` on a caller's (n, ceil(n/64)) uint64 bit matrix in the layout of
+    ``greedy_prune_from_bits`` / ``DeviceEnsemble.simbits`` / ``fc_tfd_simbits`` (fc_clusters_from_bits): an edge
+    (i, j) where bit j of row i is set; only bits j > i are read."""
+    n = _vertex_count(n)
+    bits = np.asarray(bits)
+    if bits.dtype != np.uint64 or bits.ndim != 2 or bits.shape != (n, (n + 63) // 64):
+        raise L.FirecodeHipInputError(
+            L.FC_E_INVALID, f"bits must be ({n}, {(n + 63) // 64}) uint64, got {bits.shape} {bits.dtype}")
+    return _clusters_from_graph("fc_clusters_from_bits", np.ascontiguousarray(bits), n)
+
+
 def rotation_mask(graph, torsion, n_atoms=None):
     """``_get_rotation_mask`` (firecode/torsion_module.py:354-382): the atoms that rotate
     with i4 -- reachable from i4 once the i2-i3 edge is removed -- with i3 excluded."""

@@ -42,6 +42,7 @@ extern "C" {
 #define FC_E_HIP (-3)       /* HIP runtime error (message has the hipError)   */
 #define FC_E_NOMEM (-4)     /* device allocation failed                       */
 #define FC_E_LIMIT (-5)     /* size outside what a kernel supports            */
+#define FC_E_INTERNAL (-6)  /* a device-side bound of the library's own was hit: a bug, reported instead of a hang */
 /* FC_E_LIMIT as CONTRACT -- where the reference has no size regime and this library refuses (everything else is served at
  * any size, more slowly beyond the tiled kernels: complete alignments above 104 atoms and prune screens above 192 atoms
  * leave the matrix pipes, tests/test_gpu_parity.py checks them at 105 ... 320 atoms):
@@ -228,6 +229,41 @@ int fc_prune_conventions(int drop_later);
 /* greedy k-ladder replay over caller-supplied bits (N rows x ceil(N/64) words) */
 int fc_greedy_prune_from_bits(const uint64_t *bits, int64_t N, int64_t min_per_group,
                               uint8_t *mask_out);
+
+/* ---- similarity clusters: the connected components of the prune's graph ----
+ * The contract, once.  X = the prepared ensemble in processing order.  G = the undirected graph on its N conformers with
+ * an edge (i, j) exactly when bit j of row i of fc_rmsd_simbits would be set (fc_rmsd_clusters_enant: of
+ * fc_rmsd_simbits_enant): the same thresholds, the same "<", max_dev, energy window and grey counting.
+ * fc_prune_conventions and min_per_group play no part.  Outputs:
+ *
+ *   labels_out (N, int32)                 the cluster of each conformer; clusters are numbered 0 .. K-1 by ascending
+ *                                         smallest member index
+ *   reps_out   (N entries, K written)     the smallest member index of each cluster
+ *   sizes_out  (N entries, K written)     member counts
+ *   *n_clusters = K
+ *
+ * The result is a function of G alone: not of launch order, nor of which internal path ran (the exact similar-pair list
+ * in the usual case; the bit matrix when similarity is dense or the candidate queue overflowed).  The host pre-sorts by
+ * energy with the stable argsort of prune_by_rmsd, so "smallest index" is "lowest energy, earliest on ties" whenever
+ * energies are given.  stats (6 values, may be NULL): [0] pairs evaluated, [1] pairs refined, [2] edges, [3] grey pairs,
+ * [4] 1 if the bit-matrix path produced the result, else 0, [5] K.  N = 0: K = 0.  Limit: N < 2^31 - 256.
+ * Argument checks as in fc_prune_rmsd (FC_E_INVALID: NULL ens / outputs, thresholds <= 0).  FC_E_INTERNAL: a union
+ * exceeded its retry bound on the device (cannot happen by the termination argument of fc_clusters.hip; an error code
+ * instead of a hang if that argument is ever broken).
+ *
+ * fc_clusters_from_pairs / fc_clusters_from_bits: the same labelling of a caller's graph, host arrays in (e.g. the output
+ * of fc_prune_similar_pairs, fc_tfd_simbits, fc_moi_simbits).  pairs: n_pairs entries (i << 32) | j, in either order,
+ * duplicates allowed; i == j or an index >= N is FC_E_INVALID, checked on the host before any device use.  bits: N rows
+ * of ceil(N/64) words, the layout of fc_greedy_prune_from_bits; only bits j > i are read. */
+int fc_rmsd_clusters(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                     int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int64_t *n_clusters, int64_t *stats);
+int fc_rmsd_clusters_enant(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                           int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int64_t *n_clusters,
+                           int64_t *stats);
+int fc_clusters_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int32_t *labels_out, int64_t *reps_out,
+                           int64_t *sizes_out, int64_t *n_clusters);
+int fc_clusters_from_bits(const uint64_t *bits, int64_t N, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
+                          int64_t *n_clusters);
 
 /* sharded form (conformer rows dealt block-cyclically to ranks):
  * fc_prune_rmsd_begin computes this rank's rows of the bit matrix;
