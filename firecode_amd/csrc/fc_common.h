@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/fc_hip.h"
+#include "fc_items.h"
 #include "fc_tuning.h"
 
 namespace fc {
@@ -339,17 +340,7 @@ constexpr unsigned long long kRefineLanesMin = 1ull << 17;
 constexpr size_t kCounters = 64 + 20 * 16;
 constexpr int kCntLevel = 64, kCntLevelStride = 16;
 
-// Row blocks of the bit matrix are dealt to ranks in snake order (0..W-1,
-// W-1..0, 0..W-1, ...): the work of a row block falls linearly with its index,
-// so pairs of consecutive cycles carry equal work on every rank.
-__host__ __device__ inline int64_t global_block(int64_t local_block, int64_t rank, int64_t world) {
-  return local_block * world + ((local_block & 1) ? (world - 1 - rank) : rank);
-}
-inline int64_t local_block_count(int64_t n_gblocks, int64_t rank, int64_t world) {
-  int64_t n = 0;
-  while (global_block(n, rank, world) < n_gblocks) ++n;  // strictly increasing in n
-  return n;
-}
+// (global_block, local_block_count -- the snake order of the row blocks -- and the item tables: fc_items.h)
 
 }  // namespace fc
 

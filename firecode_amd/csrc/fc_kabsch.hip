@@ -472,6 +472,9 @@ __device__ __forceinline__ void push_pairs(uint64_t m, bool may, unsigned i, uns
 constexpr int kStagePairs = 48;  // uint64 entries per workgroup
 constexpr int kStageWords = 24;  // uint32 entries per workgroup
 constexpr size_t kStageBytes = kStagePairs * 8 + kStageWords * 4 + 8;
+// complete alignments: row blocks of 128 that share one fill of the column tile (launch_rmsd_values; DESIGN.md section 5.1:
+// 10^4 x 50 per pass, single row blocks 2.42 ms, chunks of 2 / 3 / 4 / 8: 2.39 / 2.40 / 2.41 / 2.53 -- longer items end the launch unevenly)
+constexpr int64_t kCompleteRowChunk = 2;
 
 // the single-precision screen has LDS to spare (three workgroups of 42 KB per CU): its staging
 // area takes the candidates of an ensemble with ~4 % of similar pairs before it has to fall back
@@ -739,8 +742,10 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
   uint64_t *__restrict__ stageQ = reinterpret_cast<uint64_t *>(ldsG + TC + IB);
   uint32_t *__restrict__ stageW = reinterpret_cast<uint32_t *>(stageQ + kStagePairs);
   unsigned *__restrict__ stageN = reinterpret_cast<unsigned *>(stageW + kStageWords);  // [pairs, words]
-#ifdef FC_TIMELINE  // tuning build: per-item start / fill-done / end timestamps (100 MHz)
-  unsigned long long *tl = reinterpret_cast<unsigned long long *>(rmsd_out);
+#ifdef FC_TIMELINE  // tuning build: per-item start / fill-done / end timestamps (100 MHz), into a buffer of their own:
+  // the screen has no use for rmsd_out, the complete alignments none for bits
+  unsigned long long *tl = MODE == 2 ? reinterpret_cast<unsigned long long *>(bits) : reinterpret_cast<unsigned long long *>(rmsd_out);
+  constexpr bool TL = MODE == 0 || MODE == 2;
 #endif
   // One (row block, column tile) item per workgroup.  A persistent variant (grid = what the
   // chip holds, items drawn from a device counter) was built and measured with
@@ -751,7 +756,7 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
   const unsigned long long b = blockIdx.x;
   if (b >= n_items) return;
 #ifdef FC_TIMELINE
-  if (!VALUES && tl && tid == 0) {
+  if (TL && tl && tid == 0) {
     tl[(size_t)b * 4] = wall_clock64();
     tl[(size_t)b * 4 + 3] = b;
   }
@@ -760,14 +765,18 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
   // touch the upper triangle (lb << 32 | jt), or the plain 2-D enumeration when there is none
   // bit 31 / bit 63 of an entry: the item covers only the first / second half of the row
   // block's 16-row tiles (the last items of a launch are halves, which shortens the tail)
+  // MODE 2: the item may keep its column tile for several consecutive LOCAL row blocks (item_blocks, fc_items.h): one
+  // fill, one barrier and one zeroing of the staging area for all of them.  The waves walk the 16-row tiles of all these
+  // blocks in one sequence; row tile `it` lies in local block lb + it / (IB / 16).
   int64_t jt, lb;
   int it_first = 0, it_last = IB >> 4;
   if (item_table != nullptr) {
     const uint64_t it = item_table[b];
-    lb = (int64_t)((it >> 32) & 0x7fffffffull);
-    jt = (int64_t)(it & 0x7fffffffull);
-    if (it & (1ull << 31)) it_last = IB >> 5;
-    if (it & (1ull << 63)) it_first = IB >> 5;
+    lb = item_block(it);
+    jt = item_tile(it);
+    if constexpr (MODE == 2) it_last = (IB >> 4) * item_blocks(it);
+    if (it & kItemFirstHalf) it_last = IB >> 5;
+    if (it & kItemSecondHalf) it_first = IB >> 5;
   } else {
     const int64_t NT = Npad / TC;
     jt = (int64_t)(b % (unsigned long long)NT);
@@ -816,7 +825,7 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
     if (tid < 2) stageN[tid] = 0u;
     __syncthreads();
 #ifdef FC_TIMELINE
-    if (!VALUES && tl && tid == 0) tl[(size_t)b * 4 + 1] = wall_clock64();
+    if (TL && tl && tid == 0) tl[(size_t)b * 4 + 1] = wall_clock64();
 #endif
   }
   const int kq = lane >> 4, l15 = lane & 15;
@@ -835,8 +844,18 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
   // instead of in front of the next K loop.  pre_it = row tile those registers hold.
   double a0[3], a1[3], a2[3];
   int pre_it = -1;
+  // first row of row tile it_ (MODE 2: under snake order the blocks of an item are not neighbours)
+  const int tpb = IB >> 4;
+  auto tile_row = [&](int it_) -> int64_t {
+    if constexpr (MODE == 2) {
+      const int k = it_ / tpb;
+      return global_block(lb + k, rank, world) * IB + (int64_t)(it_ - k * tpb) * 16;
+    } else {
+      return i0 + (int64_t)it_ * 16;
+    }
+  };
   auto row_offsets = [&](int it_, unsigned (&vo)[3]) {
-    const int64_t ib_ = i0 + (int64_t)it_ * 16;
+    const int64_t ib_ = tile_row(it_);
 #pragma unroll
     for (int c = 0; c < 3; ++c) vo[c] = (unsigned)(((int64_t)(kq * 3 + c) * Npad + ib_ + l15) * 8);  // BYTES inside a k-step
   };
@@ -855,10 +874,15 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
   };
 
   for (int it = it_first + wv; it < it_last; it += NW) {
-    const int64_t ib = i0 + (int64_t)it * 16;
-    if (ib >= N) break;
-    if (j0 + TC - 1 <= ib) break;
+    const int64_t ib = tile_row(it);
+    if (ib >= N) break;             // (ib grows with it, also across the row blocks of an item: global_block is strictly
+    if (j0 + TC - 1 <= ib) break;   //  increasing in the local block -- a later block never sits higher in the triangle)
     const int64_t lrow0 = lb * IB + (int64_t)it * 16;
+    // MODE 2: the row sums of this tile, one per lane's row -- from global memory in front of the K loop's loads (the LDS
+    // copy holds one row block's); a wait for it never stands behind the row-operand prefetch of the next unit
+    double Gp_row = 0.0;
+    if constexpr (MODE == 2) Gp_row = G[ib + l15];
+    (void)Gp_row;
     unsigned nz = 0;  // lanes 0..15: OR of the 16-bit pieces written for row ib + lane
     // per-lane element offsets of the lane's row operand inside one k-step
     // (fits 32 bits: checked by the launcher)
@@ -874,6 +898,10 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
           bits16[((lrow0 + lane) * W + jt) * 4 + cs0 + 1] = 0;
         }
         continue;
+      }
+      // MODE 2: nothing is stored for a sub-tile whose columns are all padding (wave-uniform; the later ones are too)
+      if constexpr (MODE == 2) {
+        if (j0 + cs0 * 16 >= N) continue;
       }
       d4_t acc[NT][9];  // (written by the first k-step, whose third operand is the constant zero: no 36 moves per sub-tile)
 
@@ -935,9 +963,14 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
       }
 #undef FC_KSTEP
       {  // request the next unit's first three k-steps now; they land during the epilogue
-        const int nit = half < NU - 1 ? it : it + NW;
-        const bool more = half < NU - 1 || ((nit < it_last) && (i0 + (int64_t)nit * 16 < N) &&
-                                        !(j0 + TC - 1 <= i0 + (int64_t)nit * 16));
+        // (MODE 2: the unit behind this one has no real column -- see the skip above: the tile's last unit is this one)
+        const bool same_tile = half < NU - 1 && !(MODE == 2 && j0 + (cs0 + NT) * 16 >= N);
+        const int nit = same_tile ? it : it + NW;
+        bool more = same_tile;
+        if (!same_tile && nit < it_last) {
+          const int64_t nib = tile_row(nit);
+          more = nib < N && !(j0 + TC - 1 <= nib);
+        }
         if (more) {
           unsigned vn[3];
           row_offsets(nit, vn);
@@ -974,7 +1007,7 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
           // Pairs whose largest eigenvalue is not clearly simple are queued for k_rmsd_fix_small (Jacobi).
           const int i = ib32 + l15;
           const int jb = (int)j0 + cs * 16 + 4 * kq;
-          const double Gp = ldsG[TC + it * 16 + l15];
+          const double Gp = Gp_row;
           double nR[4][9];
           bool ok4[4];
           double msdA4[4] = {0.0, 0.0, 0.0, 0.0};  // EIG: (Gp + Gq) - 2 lambda
@@ -1181,7 +1214,7 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
   if constexpr (MODE == 0) flush_pairs_wave32(sq32_wave, n_staged32, (unsigned)i0, (unsigned)j0, pairq, Q, counters, lane);
   __syncthreads();
 #ifdef FC_TIMELINE
-  if (!VALUES && tl && tid == 0) tl[(size_t)b * 4 + 2] = wall_clock64();
+  if (TL && tl && tid == 0) tl[(size_t)b * 4 + 2] = wall_clock64();
 #endif
   if (wv == 0) {
     if constexpr (MODE != 0) {
@@ -3161,39 +3194,30 @@ k_scatter_pairs(const uint64_t *__restrict__ pairs, int64_t n_pairs, int64_t N, 
 }
 
 // Items of the MFMA screen = (local row block, column tile) pairs that touch the upper
-// triangle, in dispatch order (row blocks ascending, tiles left to right); built on the host
+// triangle, in dispatch order (build_items, fc_items.h); built on the host
 // and kept on the device until N or the sharding changes.  Without it (row blocks that are not
 // a multiple of 64) the kernel enumerates all NT x n_lblocks pairs and skips the empty ones.
-static int screen_item_table(fc_ensemble *e, int64_t NT, int64_t n_lblocks, bool halves = true, int64_t tc = 64) {
-  const int64_t rb_key = (e->row_block * 2 + (halves ? 1 : 0)) * 128 + tc;
+// chunk (the complete alignments only; 0 = not theirs): row blocks that share an item's column tile.
+static int screen_item_table(fc_ensemble *e, int64_t NT, int64_t n_lblocks, bool halves = true, int64_t tc = 64, int64_t chunk = 0,
+                             bool tail_order = true) {
+  const int64_t rb_key = (((e->row_block * 2 + (halves ? 1 : 0)) * 128 + tc) * 32 + chunk) * 2 + (tail_order ? 1 : 0);
   if (e->item_key[0] == e->N && e->item_key[1] == e->rank && e->item_key[2] == e->world &&
       e->item_key[3] == rb_key)
     return FC_OK;
   e->item_total = 0;
   e->item_key[0] = e->N; e->item_key[1] = e->rank; e->item_key[2] = e->world; e->item_key[3] = rb_key;
-  if (e->row_block % tc != 0) return FC_OK;
-  const int64_t r = e->row_block / tc;
-  std::vector<uint64_t> items;
-  for (int64_t l = 0; l < n_lblocks; ++l) {
-    const int64_t first = r * global_block(l, e->rank, e->world);
-    for (int64_t jt = first; jt < NT; ++jt) items.push_back(((uint64_t)l << 32) | (uint64_t)jt);
-  }
-  // the last items of the launch as two half-row-block items each: workgroups finish within
-  // half an item of each other instead of a whole one (FC_SCREEN_TAIL_SLOTS items, default
-  // one round of resident workgroups; needs 8 row tiles per block and 4-wave workgroups)
-  {
-    int64_t tail = 2 * (int64_t)ctx().n_cu;
-    if (const char *v = getenv("FC_SCREEN_TAIL_SLOTS")) tail = std::strtoll(v, nullptr, 10);
-    if (halves && e->row_block == 128 && tail > 0 && (int64_t)items.size() > 4 * tail && e->A <= 52) {
-      std::vector<uint64_t> halves;
-      for (int64_t k = (int64_t)items.size() - tail; k < (int64_t)items.size(); ++k) {
-        halves.push_back(items[(size_t)k] | (1ull << 31));
-        halves.push_back(items[(size_t)k] | (1ull << 63));
-      }
-      items.resize(items.size() - (size_t)tail);
-      items.insert(items.end(), halves.begin(), halves.end());
-    }
-  }
+  ItemPlan plan;
+  plan.N = e->N; plan.rank = e->rank; plan.world = e->world;
+  plan.row_block = e->row_block; plan.tc = tc; plan.NT = NT; plan.n_lblocks = n_lblocks;
+  // halves: FC_SCREEN_TAIL_SLOTS items, default one round of resident workgroups; needs 8 row tiles per block and
+  // 4-wave workgroups
+  plan.tail = 2 * (int64_t)ctx().n_cu;
+  if (const char *v = getenv("FC_SCREEN_TAIL_SLOTS")) plan.tail = std::max<int64_t>(0, std::strtoll(v, nullptr, 10));
+  plan.halves = halves && e->row_block == 128 && e->A <= 52;
+  plan.real_columns_only = chunk > 0;
+  plan.chunk = std::max<int64_t>(1, chunk);
+  plan.tail_order = tail_order;
+  std::vector<uint64_t> items = build_items(plan);
   if (items.empty() || items.size() >= (1ull << 31)) return FC_OK;
   FC_TRY(e->item_table.reserve(items.size() * sizeof(uint64_t)));
   e->item_host.swap(items);  // the copy is asynchronous: its source stays with the ensemble (no host wait here)
@@ -3217,16 +3241,16 @@ int prebuild_screen_items(fc_ensemble *e) {
 template <int NW, int TC, bool EIG>
 static int launch_complete_variant(fc_ensemble *e, dim3 grid, size_t lds_m, double A_small, int64_t rb, int64_t rank, int64_t world,
                                    unsigned long long *cnt, const uint64_t *item_table_dev, unsigned long long n_items,
-                                   double *rmsd_dev, double *maxdev_dev) {
+                                   double *rmsd_dev, double *maxdev_dev, uint64_t *timeline_dev) {
   if (lds_m > 64 * 1024) {
     hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma<NW, 2, TC, EIG>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
     if (err != hipSuccess) return set_error(FC_E_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
   }
   hipLaunchKernelGGL((k_simbits_screen_mfma<NW, 2, TC, EIG>), grid, dim3(NW * 64), lds_m, ctx().stream, e->Xs.as<double>(),
-                     e->G.as<double>(), e->N, e->Npad, (int)e->A, A_small, (int)rb, rank, world, nullptr, e->W, nullptr, cnt,
+                     e->G.as<double>(), e->N, e->Npad, (int)e->A, A_small, (int)rb, rank, world, timeline_dev, e->W, nullptr, cnt,
                      e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap, item_table_dev, n_items, rmsd_dev, nullptr,
-                     maxdev_dev);
+                     maxdev_dev);  // (bits: nullptr in the product build -- FC_TIMELINE builds pass their stamp buffer there)
   return FC_OK;
 }
 
@@ -3266,7 +3290,18 @@ int launch_rmsd_values(fc_ensemble *e, double small_rmsd, double *rmsd_dev, doub
   // the world == 1 layout with its own row block, so it keeps its own table
   const int64_t saved_rank = e->rank, saved_world = e->world, saved_rb = e->row_block;
   e->rank = rank; e->world = world; e->row_block = rb;
-  const int rc_tbl = screen_item_table(e, NT, n_lblocks, true, tc);
+  // Complete alignments: an item keeps its column tile for `chunk` row blocks.  Measured for
+  // the two-workgroups-per-CU kernel only (up to 52 atoms); the one-workgroup kernels stay on single row blocks unless
+  // asked.  FC_COMPLETE_ROW_CHUNK: 1 = single row blocks everywhere (read per call: the tests compare both forms);
+  // FC_COMPLETE_TAIL_ORDER=0: chunks up to the half items, ascending order (an arm of the measurement).
+  int64_t chunk = 0;
+  bool tail_order = true;
+  if (complete) {
+    chunk = two_blocks && !narrow ? kCompleteRowChunk : 1;
+    if (const char *v = getenv("FC_COMPLETE_ROW_CHUNK")) chunk = std::min<int64_t>(kItemChunkMax, std::max<int64_t>(1, std::strtoll(v, nullptr, 10)));
+    if (const char *v = getenv("FC_COMPLETE_TAIL_ORDER")) tail_order = atoi(v) != 0;
+  }
+  const int rc_tbl = screen_item_table(e, NT, n_lblocks, true, tc, chunk, tail_order);
   e->rank = saved_rank; e->world = saved_world; e->row_block = saved_rb;
   e->item_key[3] = -1;  // the table was built for rb, not for the ensemble's own sharding
   if (rc_tbl != FC_OK) return rc_tbl;
@@ -3276,6 +3311,16 @@ int launch_rmsd_values(fc_ensemble *e, double small_rmsd, double *rmsd_dev, doub
   const uint64_t *item_table_dev = compact ? e->item_table.as<uint64_t>() : nullptr;
   if (n_items >= (1ull << 31)) return set_error(FC_E_LIMIT, "too many value-kernel items for one launch");
   const dim3 grid((unsigned)n_items);
+  uint64_t *timeline_dev = nullptr;
+#ifdef FC_TIMELINE  // per item: start, fill done, end (100 MHz), index; FC_TIMELINE_OUT receives them, then the item table
+  static DevBuf tlbuf;
+  const bool timeline = complete && getenv("FC_TIMELINE_OUT") != nullptr;
+  if (timeline) {
+    FC_TRY(tlbuf.reserve(n_items * 4 * sizeof(uint64_t)));
+    FC_HIP_TRY(hipMemsetAsync(tlbuf.p, 0, n_items * 4 * sizeof(uint64_t), ctx().stream));
+    timeline_dev = tlbuf.as<uint64_t>();
+  }
+#endif
 #define FC_LAUNCH_VALUES(NW_, MODE_)                                                                      \
   hipLaunchKernelGGL((k_simbits_screen_mfma<NW_, MODE_>), grid, dim3(NW_ * 64), lds_m, ctx().stream,      \
                      e->Xs.as<double>(), e->G.as<double>(), e->N, e->Npad, (int)e->A, A_small, (int)rb,   \
@@ -3285,9 +3330,9 @@ int launch_rmsd_values(fc_ensemble *e, double small_rmsd, double *rmsd_dev, doub
   const bool eig = complete && !(eig_env && atoi(eig_env) == 0) && !explicit_sum;
 #define FC_LAUNCH_COMPLETE(NW_, TC_)                                                                                        \
   FC_TRY((eig ? launch_complete_variant<NW_, TC_, true>(e, grid, lds_m, A_small, rb, rank, world, cnt, item_table_dev, n_items, \
-                                                       rmsd_dev, maxdev_dev)                                               \
+                                                       rmsd_dev, maxdev_dev, timeline_dev)                                 \
               : launch_complete_variant<NW_, TC_, false>(e, grid, lds_m, A_small, rb, rank, world, cnt, item_table_dev,     \
-                                                        n_items, rmsd_dev, maxdev_dev)))
+                                                        n_items, rmsd_dev, maxdev_dev, timeline_dev)))
   if (narrow && tc == 32) {
     FC_LAUNCH_COMPLETE(8, 32);
   } else if (narrow) {
@@ -3302,6 +3347,20 @@ int launch_rmsd_values(fc_ensemble *e, double small_rmsd, double *rmsd_dev, doub
 #undef FC_LAUNCH_COMPLETE
 #undef FC_LAUNCH_VALUES
   FC_TRY(check_launch("k_simbits_screen_mfma<values>"));
+#ifdef FC_TIMELINE
+  if (timeline) {
+    std::vector<uint64_t> h(n_items * 4);
+    FC_HIP_TRY(hipMemcpyAsync(h.data(), tlbuf.p, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx().stream));
+    FC_HIP_TRY(hipStreamSynchronize(ctx().stream));
+    if (FILE *f = fopen(getenv("FC_TIMELINE_OUT"), "wb")) {
+      const uint64_t head[2] = {(uint64_t)n_items, compact ? 1ull : 0ull};  // items, "the item table follows the stamps"
+      fwrite(head, sizeof(uint64_t), 2, f);
+      fwrite(h.data(), sizeof(uint64_t), h.size(), f);
+      if (compact) fwrite(e->item_host.data(), sizeof(uint64_t), e->item_host.size(), f);
+      fclose(f);
+    }
+  }
+#endif
   if (ctx().mark_after_screen) (void)hipEventRecord(ctx().mark_after_screen, ctx().stream);  // bench hook: end of the tiled kernel
   hipLaunchKernelGGL(k_rmsd_fix_small, dim3((unsigned)(ctx().n_cu * 4)), dim3(256), 0, ctx().stream,
                      e->Xa.as<double>(), (int)e->A, e->N, e->pairq.as<uint64_t>(), cnt,

@@ -5,6 +5,8 @@
 // can slip into libfc_hip.so through an EXTRA left over in a shell.
 //
 //   timelines (s_memtime stamps into a side buffer; results unchanged, timing not):   FC_TIMELINE  FC_H2_TIMELINE  FC_RB_TIMELINE
+//     (FC_TIMELINE: the fp64 screen and the complete alignments, k_simbits_screen_mfma modes 0 and 2 -- start / fill done / end per
+//       item into FC_TIMELINE_OUT; tools/complete_items_timeline.py reads the complete alignments' file)
 //     FC_TFD_STAMPS (cfg3's three steps: fc_tfd_core.h -- cycles per phase of the largest TFD component, tools/ladder_stamps.py;
 //       fc_prune.hip -- phases of the first-match walk per workgroup, tools/fm_stamps.py; fc_torsion.hip -- per-node phases of the
 //       scan tree's last level, tools/ts_stamps.py; with FC_TFD_STAMPS_SMALL the components of 19 ... 76 nodes instead of the
