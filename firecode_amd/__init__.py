@@ -22,7 +22,7 @@ from firecode_amd._lib import (  # noqa: F401
 )
 from firecode_amd import (  # noqa: F401,E402
     algebra, embeds, ensemble, host_helpers, hypermolecule_class, operators, pruner, pt, refining, rmsd,
-    torsion_module, utils,
+    symmetry, torsion_module, utils,
 )
 
 __version__ = "0.1.0"

@@ -79,6 +79,11 @@ _SIGNATURES = {
     "fc_greedy_prune_from_bits": [_p_u64, _i64, _i64, _p_u8],
     "fc_rmsd_clusters": [_ens, _f64, _f64, _p_f64, _f64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_i64, _p_i64],
     "fc_rmsd_clusters_enant": [_ens, _f64, _f64, _p_f64, _f64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_i64, _p_i64],
+    "fc_ensemble_rmsd_pairs_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, _p_i64, _p_i64, _i64, _p_f64, _p_f64],
+    "fc_rmsd_simbits_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, _f64, _f64, _p_f64, _f64, _i64, _i64, _p_u64, _p_i64],
+    "fc_prune_rmsd_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, _f64, _f64, _p_f64, _f64, _i64, _p_u8, _p_i64],
+    "fc_rmsd_clusters_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, _f64, _f64, _p_f64, _f64, C.POINTER(C.c_int32), _p_i64,
+                              _p_i64, _p_i64, _p_i64],
     "fc_clusters_from_pairs": [_p_u64, _i64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_i64],
     "fc_clusters_from_bits": [_p_u64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_i64],
     "fc_prune_rmsd_begin": [_ens, _f64, _f64, _p_f64, _f64, _i64, _i64, _i64, _p_i64],
@@ -408,6 +413,7 @@ class DeviceEnsemble:
         m = None if atom_mask is None else u8(np.asarray(atom_mask, dtype=bool))
         if m is not None and m.shape != (self.A_all,):
             raise FirecodeHipInputError(FC_E_INVALID, "atom_mask must have one entry per atom")
+        self._atom_mask = None if m is None else m.astype(bool)
         self._h = _ens()
         call("fc_ensemble_create", pf(coords), self.N, self.A_all, pb(m), int(bool(center)), C.byref(self._h))
         self.W = (max(self.N, 1) + 63) // 64
@@ -435,10 +441,30 @@ class DeviceEnsemble:
             raise FirecodeHipInputError(FC_E_INVALID, "ensemble already destroyed")
         return self._h
 
-    def rmsd_pairs(self, pair_i, pair_j, inverted=False):
+    def _perm_args(self, symmetry, flag_name=None, flag=False):
+        """``symmetry=`` (a (K, A_all) table over all atoms; firecode_amd.symmetry) -> the leading arguments of the
+        ``_perm`` entry points in selected-atom indices, every check of the contract made before the handle is used"""
+        from firecode_amd import symmetry as S
+
+        table = S.resolve(symmetry, None, n_atoms=self.A_all)
+        if flag:
+            raise FirecodeHipInputError(
+                FC_E_INVALID, f"{flag_name}=True cannot be combined with symmetry=: the symmetry-aware forms have no such variant")
+        t = S.selected_table(table, self._atom_mask)
+        return t, (ptr(t, C.c_int32), int(t.shape[0]), int(t.shape[1]))
+
+    def rmsd_pairs(self, pair_i, pair_j, inverted=False, symmetry=None):
         """(rmsd, maxdev) of the pairs; ``inverted=True``: of (X_i, -X_j), the partner's mirror image
-        (fc_ensemble_rmsd_pairs_inv)."""
+        (fc_ensemble_rmsd_pairs_inv).  ``symmetry=`` a (K, A_all) table: both (P, K), the values of
+        (X_i, X_j[perms[k]]) for every k (fc_ensemble_rmsd_pairs_perm); choosing among them is the caller's."""
         inverted = check_flag("inverted", inverted)
+        if symmetry is not None:
+            keep, args = self._perm_args(symmetry, "inverted", inverted)
+            pi_, pj_ = i64(pair_i), i64(pair_j)
+            P = int(pi_.shape[0])
+            r, m = np.empty((P, args[1])), np.empty((P, args[1]))
+            call("fc_ensemble_rmsd_pairs_perm", self.handle, *args, pi(pi_), pi(pj_), P, pf(r), pf(m))
+            return r, m
         pi_, pj_ = i64(pair_i), i64(pair_j)
         P = int(pi_.shape[0])
         r, m = np.empty(P), np.empty(P)
@@ -519,40 +545,59 @@ class DeviceEnsemble:
              C.byref(k), C.byref(t), pi(stats))
         return k.value, t.value, stats, r, m
 
-    def simbits(self, max_rmsd, max_dev, energies=None, max_dE=0.0, row_begin=0, row_end=None, prune_enantiomers=False):
+    def simbits(self, max_rmsd, max_dev, energies=None, max_dE=0.0, row_begin=0, row_end=None, prune_enantiomers=False,
+                symmetry=None):
         """Similarity bits (fc_rmsd_simbits); ``prune_enantiomers=True``: a pair is also similar when it is so with one
-        partner inverted (fc_rmsd_simbits_enant; the contract is in include/fc_hip.h)."""
+        partner inverted (fc_rmsd_simbits_enant; the contract is in include/fc_hip.h).  ``symmetry=`` a (K, A_all)
+        table of atom permutations: similar under any of them (fc_rmsd_simbits_perm)."""
         enant = check_flag("prune_enantiomers", prune_enantiomers)
+        perm = None if symmetry is None else self._perm_args(symmetry, "prune_enantiomers", enant)
         row_end = self.N if row_end is None else int(row_end)
         bits = np.zeros((row_end - row_begin, self.W), dtype=np.uint64)
         grey = C.c_int64(0)
         en = None if energies is None else f64(energies)
+        if perm is not None:
+            call("fc_rmsd_simbits_perm", self.handle, *perm[1], float(max_rmsd), float(max_dev), pf(en), float(max_dE),
+                 int(row_begin), row_end, pw(bits), C.byref(grey))
+            return bits, grey.value
         call("fc_rmsd_simbits_enant" if enant else "fc_rmsd_simbits", self.handle, float(max_rmsd), float(max_dev), pf(en), float(max_dE),
              int(row_begin), row_end, pw(bits), C.byref(grey))
         return bits, grey.value
 
-    def prune(self, max_rmsd, max_dev, energies=None, max_dE=0.0, min_per_group=20, prune_enantiomers=False):
+    def prune(self, max_rmsd, max_dev, energies=None, max_dE=0.0, min_per_group=20, prune_enantiomers=False, symmetry=None):
         """The whole stage (fc_prune_rmsd) -> (mask, stats); ``prune_enantiomers=True``: mirror images count as
-        duplicates (fc_prune_rmsd_enant)."""
+        duplicates (fc_prune_rmsd_enant).  ``symmetry=`` a (K, A_all) table of atom permutations: relabelled copies
+        count as duplicates (fc_prune_rmsd_perm)."""
         enant = check_flag("prune_enantiomers", prune_enantiomers)
+        perm = None if symmetry is None else self._perm_args(symmetry, "prune_enantiomers", enant)
         mask = np.zeros(self.N, dtype=np.uint8)
         stats = np.zeros(6, dtype=np.int64)
         en = None if energies is None else f64(energies)
+        if perm is not None:
+            call("fc_prune_rmsd_perm", self.handle, *perm[1], float(max_rmsd), float(max_dev), pf(en), float(max_dE),
+                 int(min_per_group), pb(mask), pi(stats))
+            return mask.astype(bool), stats
         call("fc_prune_rmsd_enant" if enant else "fc_prune_rmsd", self.handle, float(max_rmsd), float(max_dev), pf(en), float(max_dE),
              int(min_per_group), pb(mask), pi(stats))
         return mask.astype(bool), stats
 
-    def clusters(self, max_rmsd, max_dev, energies=None, max_dE=0.0, prune_enantiomers=False):
+    def clusters(self, max_rmsd, max_dev, energies=None, max_dE=0.0, prune_enantiomers=False, symmetry=None):
         """Connected components of the prune's similarity graph (fc_rmsd_clusters; ``prune_enantiomers=True``:
         fc_rmsd_clusters_enant; the contract is in include/fc_hip.h) -> ``(labels (N,) int32, reps (K,) int64, sizes (K,)
         int64, stats)`` in processing order: clusters numbered by ascending smallest member, which is their
-        representative.  stats: pairs, refined, edges, grey, 1 if the bit-matrix path ran, K."""
+        representative.  stats: pairs, refined, edges, grey, 1 if the bit-matrix path ran, K.  ``symmetry=`` a
+        (K, A_all) table of atom permutations: the components of that graph (fc_rmsd_clusters_perm)."""
         enant = check_flag("prune_enantiomers", prune_enantiomers)
+        perm = None if symmetry is None else self._perm_args(symmetry, "prune_enantiomers", enant)
         labels = np.zeros(self.N, dtype=np.int32)
         reps, sizes = np.zeros(self.N, dtype=np.int64), np.zeros(self.N, dtype=np.int64)
         stats = np.zeros(6, dtype=np.int64)
         k = C.c_int64(0)
         en = None if energies is None else f64(energies)
+        if perm is not None:
+            call("fc_rmsd_clusters_perm", self.handle, *perm[1], float(max_rmsd), float(max_dev), pf(en), float(max_dE),
+                 ptr(labels, C.c_int32), pi(reps), pi(sizes), C.byref(k), pi(stats))
+            return labels, reps[:k.value].copy(), sizes[:k.value].copy(), stats
         call("fc_rmsd_clusters_enant" if enant else "fc_rmsd_clusters", self.handle, float(max_rmsd), float(max_dev), pf(en),
              float(max_dE), ptr(labels, C.c_int32), pi(reps), pi(sizes), C.byref(k), pi(stats))
         return labels, reps[:k.value].copy(), sizes[:k.value].copy(), stats
@@ -666,6 +711,9 @@ class _EnsembleView(DeviceEnsemble):
     def handle(self):
         self._parent.handle  # raises when the owner is gone
         return self._view_h
+
+    def _perm_args(self, symmetry, flag_name=None, flag=False):
+        raise FirecodeHipInputError(FC_E_INVALID, "symmetry= is not offered on a twin workspace: use the owning ensemble")
 
     def close(self):
         pass

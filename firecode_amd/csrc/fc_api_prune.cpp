@@ -1113,6 +1113,219 @@ int fc_rmsd_clusters_enant(fc_ensemble *ens, double max_rmsd, double max_dev, co
   return fc_rmsd_clusters(ens, max_rmsd, max_dev, energies, max_dE, labels_out, reps_out, sizes_out, n_clusters, stats);
 }
 
+// ---- symmetry-aware forms (include/fc_hip.h; the kernels: fc_symm.hip) -----------------------------------------------
+namespace {
+// every check the contract lists for the table, on the host; -> the table as the kernels take it (16-bit indices)
+int perm_table_check(const int32_t *perms, int64_t K, int64_t A_sel, std::vector<uint16_t> &table) {
+  FC_REQUIRE(perms != nullptr, "perms is NULL");
+  FC_REQUIRE(K >= 1, "K=%lld: the table holds at least the identity", (long long)K);
+  if (K > kPermMax)
+    return set_error(FC_E_LIMIT, "K=%lld permutations exceed FC_PERM_MAX=%lld", (long long)K, (long long)kPermMax);
+  FC_REQUIRE(A_sel >= 1 && A_sel <= 32767, "A_sel=%lld outside [1, 32767]", (long long)A_sel);
+  const size_t A = (size_t)A_sel;
+  std::vector<uint8_t> seen(A);
+  for (int64_t k = 0; k < K; ++k) {
+    std::fill(seen.begin(), seen.end(), (uint8_t)0);
+    for (size_t a = 0; a < A; ++a) {
+      const int32_t v = perms[(size_t)k * A + a];
+      FC_REQUIRE(v >= 0 && v < A_sel && !seen[(size_t)v], "row %lld of perms is not a permutation of 0..%lld", (long long)k,
+                 (long long)A_sel - 1);
+      seen[(size_t)v] = 1;
+    }
+  }
+  for (size_t a = 0; a < A; ++a) FC_REQUIRE(perms[a] == (int32_t)a, "row 0 of perms is not the identity");
+  std::vector<int32_t> inv(A);
+  for (int64_t k = 0; k < K; ++k) {
+    const int32_t *row = perms + (size_t)k * A;
+    for (size_t a = 0; a < A; ++a) inv[(size_t)row[a]] = (int32_t)a;
+    bool found = false;
+    for (int64_t l = 0; l < K && !found; ++l) found = std::equal(inv.begin(), inv.end(), perms + (size_t)l * A);
+    FC_REQUIRE(found, "perms is not closed under inverse: the inverse of row %lld is not in the table", (long long)k);
+  }
+  table.resize((size_t)K * A);
+  for (size_t t = 0; t < table.size(); ++t) table[t] = (uint16_t)perms[t];
+  return FC_OK;
+}
+
+// what the table and the ensemble have to satisfy together, still before any device use
+int perm_ensemble_check(const fc_ensemble *ens, int64_t K, int64_t A_sel, bool bit_matrix) {
+  FC_REQUIRE(ens != nullptr, "ens is NULL");
+  FC_REQUIRE(ens->epoch == ctx().epoch, "this ensemble was created before fc_shutdown / a device switch: create it again");
+  FC_REQUIRE(A_sel == ens->A, "A_sel=%lld, the ensemble has %lld selected atoms", (long long)A_sel, (long long)ens->A);
+  if (!bit_matrix) return FC_OK;
+  const size_t lds = symm_lds_bytes(A_sel, K);
+  if (lds > kLdsLimit)
+    return set_error(FC_E_LIMIT, "A_sel=%lld selected atoms with K=%lld permutations need %zu bytes of LDS per tile (limit %zu)",
+                     (long long)A_sel, (long long)K, lds, kLdsLimit);
+  const int64_t rb = default_row_block();
+  if ((uint64_t)(ceil_div(ens->N, rb) * rb) * (uint64_t)ens->W >= (1ull << 32))
+    return set_error(FC_E_LIMIT, "N=%lld: the bit matrix exceeds the 32-bit word index", (long long)ens->N);
+  return FC_OK;
+}
+
+// bits, similar-pair queue and counters of the whole ensemble under similar_sym; `dperm` lives until the caller's wait
+int symm_local(fc_ensemble *e, const std::vector<uint16_t> &table, int64_t K, DevBuf &dperm, double max_rmsd, double max_dev,
+               const double *energies, double max_dE) {
+  FC_TRY(ensemble_shard(e, 0, 1, default_row_block()));
+  e->lean = false;
+  const double *en_dev = nullptr;
+  if (energies != nullptr) {
+    FC_TRY(upload(e->energies, energies, (size_t)e->N));
+    en_dev = e->energies.as<double>();
+  }
+  FC_TRY(upload(dperm, table.data(), table.size()));
+  FC_HIP_TRY(hipMemsetAsync(e->counters.p, 0, kCounters * sizeof(uint64_t), ctx().stream));
+  FC_TRY(launch_symm_simbits(e, dperm.as<uint16_t>(), K, max_rmsd, max_dev, en_dev, max_dE));
+  e->bits_valid = true;
+  return FC_OK;
+}
+
+int prune_rmsd_perm_run(fc_ensemble *ens, const std::vector<uint16_t> &table, int64_t K, DevBuf &dperm, double max_rmsd,
+                        double max_dev, const double *energies, double max_dE, int64_t min_per_group, uint8_t *mask_out,
+                        int64_t *stats) {
+  FC_TRY(symm_local(ens, table, K, dperm, max_rmsd, max_dev, energies, max_dE));
+  // the pair ladder over the queue; it declines a queue that overflowed or is too long for it, and the bit-matrix levels
+  // take over from the matrix the same launch wrote
+  unsigned long long cnt[8];
+  int64_t levels = 0, survivors = 0;
+  LadderJob job;
+  job.pairs_dev = ens->simq.as<uint64_t>(), job.bits_dev = ens->bits.as<uint64_t>(), job.counters_zeroed = true;
+  job.mask_out = mask_out, job.levels = &levels, job.survivors = &survivors, job.counters_out = cnt;
+  FC_TRY(ladder_single(ens, min_per_group, job));
+  if (stats) fill_stats(stats, ens->N * (ens->N - 1) / 2, cnt, levels, survivors);
+  return FC_OK;
+}
+
+int rmsd_clusters_perm_run(fc_ensemble *ens, const std::vector<uint16_t> &table, int64_t K, DevBuf &dperm, DevBuf &work,
+                           double max_rmsd, double max_dev, const double *energies, double max_dE, int32_t *labels_out,
+                           int64_t *reps_out, int64_t *sizes_out, int64_t *n_clusters, int64_t *stats) {
+  const int64_t N = ens->N;
+  FC_TRY(symm_local(ens, table, K, dperm, max_rmsd, max_dev, energies, max_dE));
+  auto *cnt = reinterpret_cast<unsigned long long *>(ens->counters.p);
+  ClusterGraph g;
+  g.pairs_dev = ens->simq.as<uint64_t>(), g.n_pairs_dev = cnt + 2;
+  g.n_cand_dev = cnt + 6, g.cand_cap = (unsigned long long)ens->pairq_cap, g.redo_dev = cnt + 12;
+  ClusterResult res;
+  FC_TRY(clusters_run(g, N, work, cnt, &res));
+  int64_t from_bits = 0;
+  if (res.status()[kClStatusList] == 0ull) {  // the queue overflowed: the matrix of the same launch
+    ClusterGraph gb;
+    gb.bits_dev = ens->bits.as<uint64_t>(), gb.W = ens->W;
+    FC_TRY(clusters_run(gb, N, work, cnt, &res));
+    from_bits = 1;
+  }
+  clusters_unpack(res, N, labels_out, reps_out, sizes_out, n_clusters);
+  if (stats) fill_stats(stats, N * (N - 1) / 2, res.extra(), from_bits, *n_clusters);
+  return FC_OK;
+}
+}  // namespace
+
+int fc_ensemble_rmsd_pairs_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, const int64_t *pair_i,
+                                const int64_t *pair_j, int64_t P, double *rmsd_out, double *maxdev_out) {
+  FC_API_LOCK;
+  std::vector<uint16_t> table;
+  FC_TRY(perm_table_check(perms, K, A_sel, table));
+  FC_TRY(perm_ensemble_check(ens, K, A_sel, false));
+  FC_REQUIRE(P >= 0, "P < 0");
+  if (P == 0) return FC_OK;
+  FC_REQUIRE(pair_i && pair_j && rmsd_out && maxdev_out, "NULL pointer argument");
+  for (int64_t k = 0; k < P; ++k)
+    FC_REQUIRE(pair_i[k] >= 0 && pair_i[k] < ens->N && pair_j[k] >= 0 && pair_j[k] < ens->N,
+               "pair %lld = (%lld, %lld) out of range [0, %lld)", (long long)k, (long long)pair_i[k], (long long)pair_j[k],
+               (long long)ens->N);
+  FC_TRY(ensure_init());
+  DevBuf di, dj, dr, dm, dperm;
+  const auto run = [&]() -> int {
+    FC_TRY(upload(di, pair_i, (size_t)P));
+    FC_TRY(upload(dj, pair_j, (size_t)P));
+    FC_TRY(upload(dperm, table.data(), table.size()));
+    FC_TRY(dr.reserve((size_t)P * K * sizeof(double)));
+    FC_TRY(dm.reserve((size_t)P * K * sizeof(double)));
+    FC_TRY(launch_symm_pairs(ens, dperm.as<uint16_t>(), K, di.as<int64_t>(), dj.as<int64_t>(), P, dr.as<double>(),
+                             dm.as<double>()));
+    FC_TRY(d2h(rmsd_out, dr.p, (size_t)P * K * sizeof(double)));
+    FC_TRY(d2h(maxdev_out, dm.p, (size_t)P * K * sizeof(double)));
+    return sync();
+  };
+  const int rc = run();
+  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());  // nothing of the buffers may be in flight when they go
+  return rc;
+}
+
+int fc_rmsd_simbits_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
+                         const double *energies, double max_dE, int64_t row_begin, int64_t row_end, uint64_t *bits_out,
+                         int64_t *n_grey) {
+  FC_API_LOCK;
+  std::vector<uint16_t> table;
+  FC_TRY(perm_table_check(perms, K, A_sel, table));
+  FC_TRY(perm_ensemble_check(ens, K, A_sel, true));
+  FC_REQUIRE(bits_out != nullptr, "NULL pointer argument");
+  FC_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= ens->N, "bad row range");
+  FC_REQUIRE(max_rmsd > 0.0 && max_dev > 0.0, "thresholds must be positive");
+  FC_TRY(ensure_init());
+  if (ens->N == 0) return FC_OK;
+  DevBuf dperm;
+  const int64_t W = ens->W;
+  std::vector<uint64_t> all;
+  unsigned long long cnt[8];
+  const auto run = [&]() -> int {
+    FC_TRY(symm_local(ens, table, K, dperm, max_rmsd, max_dev, energies, max_dE));
+    all.resize((size_t)ens->rows_local * W);
+    FC_TRY(d2h(all.data(), ens->bits.p, all.size() * sizeof(uint64_t)));
+    FC_TRY(d2h(cnt, ens->counters.p, sizeof cnt));
+    return sync();
+  };
+  const int rc = run();
+  if (rc != FC_OK) {
+    (void)hipStreamSynchronize(cur_stream());
+    return rc;
+  }
+  for (int64_t i = row_begin; i < row_end; ++i)
+    for (int64_t w = 0; w < W; ++w) bits_out[(i - row_begin) * W + w] = all[(size_t)i * W + w];
+  if (n_grey) *n_grey = (int64_t)cnt[3];
+  return FC_OK;
+}
+
+int fc_prune_rmsd_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
+                       const double *energies, double max_dE, int64_t min_per_group, uint8_t *mask_out, int64_t *stats) {
+  FC_API_LOCK;
+  std::vector<uint16_t> table;
+  FC_TRY(perm_table_check(perms, K, A_sel, table));
+  FC_TRY(perm_ensemble_check(ens, K, A_sel, true));
+  FC_REQUIRE(mask_out != nullptr, "NULL pointer argument");
+  FC_REQUIRE(max_rmsd > 0.0 && max_dev > 0.0, "thresholds must be positive");
+  FC_REQUIRE(min_per_group >= 1, "min_per_group must be >= 1");
+  FC_TRY(ensure_init());
+  if (ens->N == 0) return FC_OK;
+  DevBuf dperm;
+  const int rc = prune_rmsd_perm_run(ens, table, K, dperm, max_rmsd, max_dev, energies, max_dE, min_per_group, mask_out, stats);
+  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());
+  return rc;
+}
+
+int fc_rmsd_clusters_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd,
+                          double max_dev, const double *energies, double max_dE, int32_t *labels_out, int64_t *reps_out,
+                          int64_t *sizes_out, int64_t *n_clusters, int64_t *stats) {
+  FC_API_LOCK;
+  std::vector<uint16_t> table;
+  FC_TRY(perm_table_check(perms, K, A_sel, table));
+  FC_TRY(perm_ensemble_check(ens, K, A_sel, true));
+  FC_REQUIRE(n_clusters != nullptr, "NULL pointer argument");
+  FC_REQUIRE(max_rmsd > 0.0 && max_dev > 0.0, "thresholds must be positive");
+  *n_clusters = 0;
+  if (stats) std::memset(stats, 0, 6 * sizeof(int64_t));
+  if (ens->N > (int64_t)INT32_MAX - 256)
+    return set_error(FC_E_LIMIT, "N=%lld: clusters index conformers with 32 bits", (long long)ens->N);
+  FC_TRY(ensure_init());
+  if (ens->N == 0) return FC_OK;
+  FC_REQUIRE(labels_out && reps_out && sizes_out, "NULL pointer argument");
+  DevBuf dperm, work;
+  const int rc = rmsd_clusters_perm_run(ens, table, K, dperm, work, max_rmsd, max_dev, energies, max_dE, labels_out, reps_out,
+                                        sizes_out, n_clusters, stats);
+  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());
+  return rc;
+}
+
 // a caller's graph: checks on the host, one upload, the same labelling
 static int clusters_from_graph(const uint64_t *pairs, int64_t n_pairs, const uint64_t *bits, int64_t N, int32_t *labels_out,
                                int64_t *reps_out, int64_t *sizes_out, int64_t *n_clusters) {

@@ -187,6 +187,14 @@ inline ClusterLayout cluster_layout(int64_t N) {
 }
 int launch_clusters(const ClusterGraph &g, int64_t N, DevBuf &work);
 int warm_clusters();
+// ---- fc_symm.hip -----------------------------------------------------------------------------------------
+constexpr int64_t kPermMax = FC_PERM_MAX;
+size_t symm_lds_bytes(int64_t A, int64_t K);  // dynamic LDS of a tile of k_symm_simbits: both coordinate tiles + the table
+int launch_symm_simbits(fc_ensemble *e, const uint16_t *perms_dev, int64_t K, double max_rmsd, double max_dev,
+                        const double *energies_dev, double max_dE);
+int launch_symm_pairs(const fc_ensemble *e, const uint16_t *perms_dev, int64_t K, const int64_t *pi_dev,
+                      const int64_t *pj_dev, int64_t P, double *rmsd_dev, double *maxdev_dev);  // (P, K) outputs
+int warm_symm();
 // ---- fc_tfd_ladder.hip -----------------------------------------------------------------------------------
 int tfd_ladder_device(const int64_t *fm_dev, const int64_t *fm_host, int64_t N, uint8_t *mask_out);
 int pyset_order_pairs_device(const int64_t *pairs_host, int64_t n, int64_t *order_out);

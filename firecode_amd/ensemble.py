@@ -129,19 +129,21 @@ class Ensemble:
                 f"{perf_counter() - t0:.3f} s)")
         return sel
 
-    def cluster_by_rmsd(self, max_rmsd=None, heavy_atoms_only=True, prune_enantiomers=False, verbose=True):
+    def cluster_by_rmsd(self, max_rmsd=None, heavy_atoms_only=True, prune_enantiomers=False, verbose=True, symmetry=None):
         """Which conformers belong together (``firecode_amd.pruner.cluster_by_rmsd``): the connected components of the
         graph the RMSD stage of ``similarity_pruning`` prunes, with its energies and window (``max_dE = 1.0`` when there is
-        one energy per conformer).  Returns the ``RmsdClusters``; the ensemble is not masked."""
+        one energy per conformer).  ``symmetry=``: as in ``similarity_pruning``.  Returns the ``RmsdClusters``; the ensemble is
+        not masked."""
         from firecode_amd.pruner import cluster_by_rmsd
 
         use_en = len(self.energies) == len(self.coords)
         return cluster_by_rmsd(self.coords, self.atoms, max_rmsd, energies=self.energies if use_en else None,
                                max_dE=1.0 if use_en else 0.0, debugfunction=self.logfunction if verbose else None,
-                               heavy_atoms_only=heavy_atoms_only, prune_enantiomers=prune_enantiomers)
+                               heavy_atoms_only=heavy_atoms_only, prune_enantiomers=prune_enantiomers, symmetry=symmetry)
 
     def similarity_pruning(self, moi=True, rmsd=True, rmsd_rot_corr=False, verbose=True, max_rmsd=None,
-                           symmetric_torsions=None, graph=None, rotation_masks=None, prune_enantiomers=False):
+                           symmetric_torsions=None, graph=None, rotation_masks=None, prune_enantiomers=False,
+                           symmetry=None):
         """firecode/ensemble.py:185-276: MOI prune, RMSD prune, then (``rmsd_rot_corr``, at
         most 1000 structures, :246-270) the symmetry-corrected RMSD prune; masks propagated to
         ``energies``.  Log messages as the reference words them, except the elapsed-time field: its
@@ -152,18 +154,27 @@ class Ensemble:
         torsions from it (``symmetric_torsions=`` / ``rotation_masks=`` override the perception).
         ``prune_enantiomers=True``: the RMSD stage (only that stage) counts mirror images as duplicates
         (``prune_by_rmsd(..., prune_enantiomers=True)``); its log line then reads "RMSD similarity (mirror images
-        included)"."""
+        included)".
+        ``symmetry=`` (a bond graph or a (K, A) table of atom permutations, ``prune_by_rmsd``): the RMSD stage (only that
+        stage) counts relabelled copies as duplicates; the MOI stage then runs as a call of its own, and the RMSD log line
+        reads "RMSD similarity (K atom permutations)"."""
         from firecode_amd import _lib as L
+        from firecode_amd import symmetry as S
 
         enant = L.check_flag("prune_enantiomers", prune_enantiomers)
+        table = S.resolve(symmetry, self.atoms, True)
+        S.refuse_with_enantiomers(table, enant)
         rmsd_label = "RMSD similarity (mirror images included)" if enant else "RMSD similarity"
+        if table is not None:
+            rmsd_label = f"RMSD similarity ({len(table)} atom permutations)"
         log = self.logfunction if verbose else None
         if log is not None:
             log("--> Similarity Processing")
         before = len(self.coords)
         use_en = len(self.energies) == len(self.coords)
         max_dE = 1.0
-        if moi and rmsd:
+        fused = moi and rmsd and table is None
+        if fused:
             # both stages on ONE upload of the coordinates (fc_prune_similarity): the MOI stage's survivors
             # are gathered on the device for the RMSD stage; same masks and the same two log lines as the
             # stage-by-stage calls of firecode/ensemble.py:205-244
@@ -180,7 +191,7 @@ class Ensemble:
                 log(f"Discarded {int(counts[1] - counts[2])} candidates for {rmsd_label} ({int(counts[2])} left, {dt:.3f} s)")
             self.coords = self.coords[m_both]
             self.apply_mask(("energies",), m_both)
-        elif moi:
+        if moi and not fused:
             n0, t0 = len(self.coords), perf_counter()
             self.coords, mask = prune_by_moment_of_inertia(
                 self.coords, self.atoms, energies=self.energies if use_en else None, max_dE=max_dE)
@@ -188,11 +199,12 @@ class Ensemble:
             if n0 > len(self.coords) and log is not None:
                 log(f"Discarded {n0 - len(self.coords)} candidates for MOI similarity "
                     f"({len(self.coords)} left, {perf_counter() - t0:.3f} s)")
-        elif rmsd:
+        if rmsd and not fused:
             n0, t0 = len(self.coords), perf_counter()
+            use_en = len(self.energies) == len(self.coords)
             self.coords, mask = prune_by_rmsd(
                 self.coords, self.atoms, max_rmsd, energies=self.energies if use_en else None, max_dE=max_dE,
-                prune_enantiomers=enant)
+                prune_enantiomers=enant, symmetry=table)
             self.apply_mask(("energies",), mask)
             if n0 > len(self.coords) and log is not None:
                 log(f"Discarded {n0 - len(self.coords)} candidates for {rmsd_label} "

@@ -67,14 +67,22 @@ def _unsort(mask_sorted, order):
 
 
 def prune_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None, max_dE=0.0,
-                  debugfunction=None, heavy_atoms_only=True, min_per_group=20, prune_enantiomers=False):
+                  debugfunction=None, heavy_atoms_only=True, min_per_group=20, prune_enantiomers=False, symmetry=None):
     """Heavy-atom Kabsch-RMSD pruning: a pair is similar when
     ``rmsd < max_rmsd and maxdev < max_dev`` (default ``2*max_rmsd``; ``max_rmsd`` defaults to
     ``CONVENTIONS["default_max_rmsd"]``, the case of firecode/ensemble.py:230 which passes none).
 
     ``prune_enantiomers=True``: mirror images count as duplicates -- a pair is also similar when it passes the same
     two tests with one partner inverted through its centroid (fc_prune_rmsd_enant; the contract is written out in
-    include/fc_hip.h).  Upstream's ``prune_enantiomers`` / ``ENANTIOMERS`` option, removed there for speed."""
+    include/fc_hip.h).  Upstream's ``prune_enantiomers`` / ``ENANTIOMERS`` option, removed there for speed.
+
+    ``symmetry=``: copies of one conformation with equivalent atoms relabelled count as duplicates -- a pair is also
+    similar when it passes the two tests under any of K atom permutations (fc_prune_rmsd_perm; the contract is written
+    out in include/fc_hip.h).  A networkx bond graph (its automorphisms are perceived,
+    ``firecode_amd.symmetry.graph_automorphisms``) or an explicit (K, A) table over all atoms; ``None``: the path as
+    it is.  Not combinable with ``prune_enantiomers``."""
+    from firecode_amd import symmetry as S
+
     t0 = perf_counter()
     enant = L.check_flag("prune_enantiomers", prune_enantiomers)
     structures = L.f64(structures)
@@ -83,14 +91,22 @@ def prune_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None,
     atoms = np.asarray(atoms)
     if atoms.shape[0] != structures.shape[1]:
         raise L.FirecodeHipInputError(L.FC_E_INVALID, "len(atoms) != number of atoms")
+    heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
+    table = S.resolve(symmetry, atoms, heavy_atoms_only)
+    S.refuse_with_enantiomers(table, enant)
+    if table is not None:
+        S.selected_table(table, heavy)  # (its checks, before any device use)
     max_rmsd, max_dev, max_dE = _thresholds(max_rmsd, max_dev, max_dE)
     N = structures.shape[0]
     if N == 0:
         return structures, np.ones(0, dtype=bool)
-    heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
     order, en_sorted = _sorted_by_energy(structures, energies)
     X = structures if order is None else np.ascontiguousarray(structures[order])
-    if enant:  # the resident form: the one-call host path stays the default's
+    if table is not None:  # the resident form, as below
+        with L.DeviceEnsemble(X, atom_mask=heavy, center=True) as ens:
+            m_sorted, stats = ens.prune(max_rmsd, max_dev, energies=en_sorted, max_dE=max_dE, min_per_group=min_per_group,
+                                        symmetry=table)
+    elif enant:  # the resident form: the one-call host path stays the default's
         with L.DeviceEnsemble(X, atom_mask=heavy, center=True) as ens:
             m_sorted, stats = ens.prune(max_rmsd, max_dev, energies=en_sorted, max_dE=max_dE, min_per_group=min_per_group,
                                         prune_enantiomers=True)
@@ -105,7 +121,8 @@ def prune_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None,
     mask = _unsort(m_sorted, order)
     if debugfunction is not None:
         debugfunction(
-            f"DEBUG: prune_by_rmsd [gfx950{', mirror images included' if enant else ''}] - {stats[0]} pairs screened, {stats[1]} refined, "
+            f"DEBUG: prune_by_rmsd [gfx950{', mirror images included' if enant else ''}"
+            f"{'' if table is None else f', {len(table)} atom permutations'}] - {stats[0]} pairs screened, {stats[1]} refined, "
             f"{stats[2]} similar, {stats[3]} grey, {stats[4]} ladder levels, "
             f"keeping {int(mask.sum())}/{N} in {perf_counter() - t0:.3f} s")
     return structures[mask], mask
@@ -161,10 +178,11 @@ RmsdClusters = namedtuple("RmsdClusters", ["labels", "representatives", "sizes"]
 
 
 def cluster_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None, max_dE=0.0, debugfunction=None,
-                    heavy_atoms_only=True, prune_enantiomers=False):
+                    heavy_atoms_only=True, prune_enantiomers=False, symmetry=None):
     """Which conformers belong together: the connected components of the similarity graph ``prune_by_rmsd`` prunes
     (an edge where ``rmsd < max_rmsd and maxdev < max_dev`` [and ``|dE| < max_dE``]; with ``prune_enantiomers=True``
-    also where that holds for the mirror image), on the GPU (fc_rmsd_clusters; the contract is written out in
+    also where that holds for the mirror image; with ``symmetry=``, as in ``prune_by_rmsd``, also where it holds under
+    one of the atom permutations: fc_rmsd_clusters_perm), on the GPU (fc_rmsd_clusters; the contract is written out in
     include/fc_hip.h).  Unlike the greedy mask the answer does not depend on the order of the conformers, on
     ``min_per_group`` or on ``CONVENTIONS["drop"]``.
 
@@ -172,6 +190,8 @@ def cluster_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=Non
     (K,) int64 indices into ``structures``; sizes (K,) int64.  A cluster's representative is its first member in
     processing order -- lowest energy (earliest on ties) when ``energies`` is usable, lowest index otherwise -- and
     clusters are numbered in the order of their representatives."""
+    from firecode_amd import symmetry as S
+
     t0 = perf_counter()
     enant = L.check_flag("prune_enantiomers", prune_enantiomers)
     structures = L.f64(structures)
@@ -180,6 +200,10 @@ def cluster_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=Non
     atoms = np.asarray(atoms)
     if atoms.shape[0] != structures.shape[1]:
         raise L.FirecodeHipInputError(L.FC_E_INVALID, "len(atoms) != number of atoms")
+    table = S.resolve(symmetry, atoms, heavy_atoms_only)
+    S.refuse_with_enantiomers(table, enant)
+    if table is not None:
+        S.selected_table(table, (atoms != "H") if heavy_atoms_only else None)
     max_rmsd, max_dev, max_dE = _thresholds(max_rmsd, max_dev, max_dE)
     N = structures.shape[0]
     if N == 0:
@@ -189,7 +213,7 @@ def cluster_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=Non
     X = structures if order is None else np.ascontiguousarray(structures[order])
     with L.DeviceEnsemble(X, atom_mask=heavy, center=True) as ens:
         labels_sorted, reps_sorted, sizes, stats = ens.clusters(max_rmsd, max_dev, energies=en_sorted, max_dE=max_dE,
-                                                                prune_enantiomers=enant)
+                                                                prune_enantiomers=enant, symmetry=table)
     if order is None:
         labels, reps = labels_sorted, reps_sorted
     else:
@@ -198,7 +222,8 @@ def cluster_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=Non
         reps = order[reps_sorted].astype(np.int64)
     if debugfunction is not None:
         debugfunction(
-            f"DEBUG: cluster_by_rmsd [gfx950{', mirror images included' if enant else ''}] - {stats[0]} pairs screened, "
+            f"DEBUG: cluster_by_rmsd [gfx950{', mirror images included' if enant else ''}"
+            f"{'' if table is None else f', {len(table)} atom permutations'}] - {stats[0]} pairs screened, "
             f"{stats[2]} similar, {len(sizes)} clusters, largest {int(sizes.max())}, in {perf_counter() - t0:.3f} s")
     return RmsdClusters(labels, reps, sizes)
 

@@ -6,15 +6,26 @@ import numpy as np
 from firecode_amd import _lib as L
 
 
-def rmsd_and_max_batch(structures, pair_i, pair_j, center=False, atom_mask=None, inverted=False):
+def rmsd_and_max_batch(structures, pair_i, pair_j, center=False, atom_mask=None, inverted=False, symmetry=None):
     """(rmsd, maxdev) of P conformer pairs of one (N, A, 3) block -- the batched
     form the one-pair name wraps (fc_kabsch_rmsd_pairs).  ``inverted=True``: the values of
     ``rmsd_and_max(p, -q, center)`` -- the partner inverted through the origin, its mirror image
-    (fc_kabsch_rmsd_pairs_inv): with ``center`` the centroids are removed first, then q is negated."""
+    (fc_kabsch_rmsd_pairs_inv): with ``center`` the centroids are removed first, then q is negated.
+    ``symmetry=`` a (K, A) table of atom permutations (firecode_amd.symmetry): both results are (P, K), the values
+    of ``rmsd_and_max(p, q[perms[k]], center)`` for every k (fc_ensemble_rmsd_pairs_perm)."""
     inverted = L.check_flag("inverted", inverted)
     X = L.f64(structures)
     if X.ndim != 3 or X.shape[2] != 3:
         raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {X.shape}")
+    if symmetry is not None:
+        from firecode_amd import symmetry as S
+
+        table = S.resolve(symmetry, None, n_atoms=X.shape[1])
+        if inverted:
+            raise L.FirecodeHipInputError(L.FC_E_INVALID, "inverted=True cannot be combined with symmetry=")
+        S.selected_table(table, atom_mask)
+        with L.DeviceEnsemble(X, atom_mask=atom_mask, center=center) as ens:
+            return ens.rmsd_pairs(pair_i, pair_j, symmetry=table)
     pi_, pj_ = L.i64(pair_i), L.i64(pair_j)
     P = int(pi_.shape[0])
     r, m = np.empty(P), np.empty(P)

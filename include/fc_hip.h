@@ -265,6 +265,48 @@ int fc_clusters_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, in
 int fc_clusters_from_bits(const uint64_t *bits, int64_t N, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
                           int64_t *n_clusters);
 
+/* ---- symmetry-aware forms: atom permutations of equivalent atoms ----
+ * The contract, once.  X = the prepared ensemble of the RMSD stage (atom selection applied, each conformer centred on the
+ * centroid of its selected atoms).  perms = a (K, A_sel) row-major table of permutations of the selected atoms, in
+ * selected-atom indices 0 .. A_sel-1: row 0 is the identity and the set is closed under inverse (the automorphisms of a
+ * bond graph are).  For i < j:
+ *
+ *   (r_k, m_k) = rmsd_and_max(X[i], X[j][perms[k]])            k = 0 .. K-1
+ *   similar_sym(i, j) = any_k (r_k < max_rmsd && m_k < max_dev)     [&& |E_i - E_j| < max_dE when energies != NULL]
+ *
+ * -- the OR of K complete tests, not "the smallest rmsd, then its max deviation".  Comparison operators, max_dev,
+ * conformer order, fc_prune_conventions and the k-ladder exactly as in fc_rmsd_simbits / fc_prune_rmsd; the clusters are
+ * the components of that graph, numbered as fc_rmsd_clusters numbers them.  Only the predicate changes.  A pair is grey
+ * when any of its r_k, or an m_k whose r_k passes, lies within 1e-9 of its threshold; it is counted once (n_grey,
+ * stats[3]).  (Values of k behind a pass that is itself clear of both thresholds are not looked at: they cannot turn
+ * the verdict.)  K = 1 gives the bits and the mask of the default forms, bit for bit.  Explicit entry points, no mode on
+ * the handle: every other entry point does what it did.
+ *
+ * One exact-fp64 all-pairs kernel (no screen: fc_screen_last_kind is not touched).  stats as the sibling's, with
+ * [1] = pairs whose polynomial test passed for at least one k; fc_rmsd_clusters_perm's [4] = 1 when the bit matrix
+ * produced the labels.  Refused before the device is touched -- FC_E_LIMIT: K > FC_PERM_MAX; an A_sel whose tile
+ * -- 2 x 16 conformers at ((3 A_sel) | 1) doubles each, the table of 2 K A_sel bytes rounded up to 8, and 8200 bytes of
+ * candidate queue -- exceeds the 160 KiB of LDS (A_sel <= 201 at K = 2); N beyond the 32-bit
+ * word index of the bit matrix (fc_rmsd_clusters_perm: N >= 2^31 - 256).  FC_E_INVALID: NULL perms, K < 1, A_sel
+ * that is not the ensemble's, a row that is not a permutation of 0 .. A_sel-1, row 0 not the identity, a row whose
+ * inverse is not in the table; then the sibling's own checks.  The table is checked before the handle is looked at.
+ * Not offered: sharded and multi-GPU forms, fc_prune_rmsd_many, the one-call host form, twin workspaces,
+ * fc_ensemble_select_diverse, fc_prune_rmsd_rot_corr, the MOI stage; no combination with the enantiomer-aware forms.
+ *
+ * fc_ensemble_rmsd_pairs_perm: all K values of each requested pair (any i, j), rmsd_out and maxdev_out (P, K)
+ * row-major: element (p, k) = rmsd_and_max(X[pair_i[p]], X[pair_j[p]][perms[k]]).  Choosing among them is the caller's. */
+#define FC_PERM_MAX 64
+int fc_ensemble_rmsd_pairs_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, const int64_t *pair_i,
+                                const int64_t *pair_j, int64_t P, double *rmsd_out, double *maxdev_out);
+int fc_rmsd_simbits_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
+                         const double *energies, double max_dE, int64_t row_begin, int64_t row_end, uint64_t *bits_out,
+                         int64_t *n_grey);
+int fc_prune_rmsd_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
+                       const double *energies, double max_dE, int64_t min_per_group, uint8_t *mask_out, int64_t *stats);
+int fc_rmsd_clusters_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd,
+                          double max_dev, const double *energies, double max_dE, int32_t *labels_out, int64_t *reps_out,
+                          int64_t *sizes_out, int64_t *n_clusters, int64_t *stats);
+
 /* sharded form (conformer rows dealt block-cyclically to ranks):
  * fc_prune_rmsd_begin computes this rank's rows of the bit matrix;
  * fc_prune_level applies one ladder level to this rank's rows given the
