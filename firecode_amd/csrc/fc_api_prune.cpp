@@ -876,7 +876,7 @@ int fc_ensemble_rmsd_values(fc_ensemble *ens, double *rmsd_out, double *ms_kerne
   }
   FC_TRY(sync());
   if (cnt[6] > (unsigned long long)ens->pairq_cap)
-    return set_error(FC_E_LIMIT, "%llu pairs closer than 0.02 A exceed the fix-up queue (%lld): "
+    return set_error(FC_E_LIMIT, "%llu pairs closer than 0.02 A or without a unique optimal rotation exceed the fix-up queue (%lld): "
                      "use fc_ensemble_rmsd_matrix", cnt[6], (long long)ens->pairq_cap);
   return elapsed_ms(c.ev0, c.ev1, ms_kernel);
 }

@@ -415,6 +415,16 @@ k_pairs_exact(const double *__restrict__ Xa, int A, const int64_t *__restrict__ 
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P) return;
   double r, m;
+  if (!INV && pi[p] == pj[p]) {
+    // a conformer against itself is exactly 0, as on the diagonal of the matrix forms: where the largest eigenvalue is
+    // degenerate (one atom, two atoms about their centroid, atoms on a line) the eigenvector taken need not be the
+    // identity's, and the rotated difference would come out as a few 1e-15 instead
+    rmsd[p] = 0.0;
+    maxdev[p] = 0.0;
+    if (Rout)
+      for (int k = 0; k < 9; ++k) Rout[p * 9 + k] = (k % 4 == 0) ? 1.0 : 0.0;
+    return;
+  }
   pair_exact_aos<INV>(Xa, A, pi[p], pj[p], r, m, Rout ? Rout + p * 9 : nullptr);
   rmsd[p] = r;
   maxdev[p] = m;
@@ -1159,11 +1169,15 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
 #pragma unroll
           for (int e = 0; e < 9; ++e) B9[e] = acc[t][e][r];
           if (VALUES) {
-            const double lam = kabsch_lambda_max(B9, Gp + Gq);
+            double slope;
+            const double lam = kabsch_lambda_max(B9, Gp + Gq, &slope);
             const double msdA = (Gp + Gq) - 2.0 * lam;
             const bool in = (j > i) && (j < n32) && (i < n32);
             if (in) rmsd_out[(int64_t)i * N + j] = sqrt(fmax(msdA, 0.0) / (double)A);
-            const bool redo = in && (msdA < A_thr2);
+            // the exact evaluation takes the pairs too close for the difference, and those whose largest eigenvalue is
+            // (nearly) double: Newton's iteration stalls ~sqrt(u) lambda short of such a root (4e-8 A in the rmsd of two
+            // single atoms)
+            const bool redo = in && (msdA < A_thr2 || !kabsch_lambda_is_sharp(lam, slope, (double)A, msdA));
             stage_pairs(__ballot(redo), redo, (unsigned)i, (unsigned)j, stageQ, stageN, pairq, Q, counters, lane);
             continue;
           }

@@ -358,7 +358,11 @@ inline KabschF32Bounds kabsch_h2_bounds(int64_t KS2) {
 // convergence from above; Theobald's QCP).  rmsd^2 = (Gp + Gq - 2 lambda) / A.
 // Used for all-pairs RMSD *values*: no eigenvector, no rotation.  The caller
 // re-evaluates pairs with a tiny rmsd exactly (cancellation in Gp+Gq-2*lambda).
-__host__ __device__ __forceinline__ double kabsch_lambda_max(const double (&B)[9], double GpGq) {
+// slope (may be NULL): P'(x) of the last step -- the product of the distances to the other three eigenvalues.  Where the
+// largest eigenvalue is (nearly) double -- a covariance of rank one: one atom, two atoms about their centroid, atoms on a
+// line -- P' vanishes with P, the iteration stalls where the rounding of P (a few u x^4) equals its quadratic, sqrt(u) x
+// away from the root, and the caller has to evaluate the pair another way (kabsch_lambda_is_sharp).
+__host__ __device__ __forceinline__ double kabsch_lambda_max(const double (&B)[9], double GpGq, double *slope = nullptr) {
 #pragma clang fp contract(fast)
   const double Sxx = B[0], Sxy = B[1], Sxz = B[2];
   const double Syx = B[3], Syy = B[4], Syz = B[5];
@@ -372,18 +376,29 @@ __host__ __device__ __forceinline__ double kabsch_lambda_max(const double (&B)[9
   const double e2 = c00 * c00 + c01 * c01 + c02 * c02 + c10 * c10 + c11 * c11 + c12 * c12 +
                     c20 * c20 + c21 * c21 + c22 * c22;
   const double C2 = -2.0 * n2, C1 = -8.0 * detB, C0 = n2 * n2 - 4.0 * e2;
-  double x = 0.5 * GpGq;
+  double x = 0.5 * GpGq, den = 0.0;
   for (int it = 0; it < 64; ++it) {
     const double x2 = x * x;
     const double b = (x2 + C2) * x;
     const double a = b + C1;
-    const double den = 2.0 * x2 * x + b + a;
+    den = 2.0 * x2 * x + b + a;
     if (den == 0.0) break;
     const double delta = (a * x + C0) / den;
     x -= delta;
     if (fabs(delta) <= 4e-16 * fabs(x)) break;
   }
+  if (slope) *slope = den;
   return x;
+}
+
+// Whether lambda = kabsch_lambda_max(..., &slope) carries the rmsd to ~1e-11: the rounding of P at the root, taken as
+// 4.5 u x^4 = 1e-15 x^4 (a margin of ten over its four terms of size x^4), moves the root by that over |P'|, the sum
+// A msd = (Gp + Gq) - 2 lambda by twice as much, and the rmsd by d(A msd) / (2 sqrt(A * A msd)):
+//     1e-15 x^4 / |slope| <= 1e-11 sqrt(A * A msd)   <=>   (1e-4 x^4)^2 <= slope^2 * A * A msd
+// False for a (nearly) double largest eigenvalue, whatever the iteration made of it, and for NaN.
+__host__ __device__ __forceinline__ bool kabsch_lambda_is_sharp(double lam, double slope, double A, double msdA) {
+  const double x2 = lam * lam, e = 1e-4 * x2 * x2;
+  return e * e <= slope * slope * A * msdA;
 }
 
 // Optimal rotation without the Jacobi sweeps, for pairs whose largest quaternion eigenvalue

@@ -131,7 +131,9 @@ int fc_ensemble_rmsd_matrix(fc_ensemble *ens, double *rmsd_out, double *maxdev_o
 int fc_ensemble_rmsd_and_max_all(fc_ensemble *ens, double *rmsd_out, double *maxdev_out, double *ms_kernel);
 /* all-pairs RMSD VALUES on the fp64 matrix pipe: covariance by MFMA, largest
  * quaternion eigenvalue by Newton (QCP), rmsd = sqrt((Gp+Gq-2*lambda)/A); pairs
- * below 0.02 A are re-evaluated with the explicit rotated difference.  No max
+ * below 0.02 A, and pairs whose largest eigenvalue is (nearly) double -- one atom, two atoms about their
+ * centroid, atoms on a line: the iteration stalls short of such a root -- are re-evaluated with the explicit
+ * rotated difference (FC_E_LIMIT when they outnumber the fix-up queue).  No max
  * deviation (that needs the rotation: fc_ensemble_rmsd_matrix).  rmsd_out (N, N)
  * symmetric, may be NULL (timing only); ms_kernel (may be NULL) = HIP-event time
  * of the two kernels. */

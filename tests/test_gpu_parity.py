@@ -67,6 +67,8 @@ def test_heavy_atom_mask(fc):
     r, m = fc.rmsd.rmsd_and_max_batch(X, iu, ju, center=True, atom_mask=hv)
     r0, m0 = o.rmsd_and_max_batch(X[iu][:, hv], X[ju][:, hv], center=True)
     assert np.abs(r - r0).max() < TOL
+    bound = o.rotation_error_bound_batch(X[iu][:, hv], X[ju][:, hv], center=True)
+    assert np.all(np.abs(m - m0) <= TOL + bound) and (bound < TOL).mean() > 0.95
 
 
 def test_alignment_matrix_and_align_vec_pair(fc, golden):
@@ -84,6 +86,32 @@ def test_alignment_matrix_and_align_vec_pair(fc, golden):
     assert np.abs(out - golden["avp_out"])[ok].max() < TOL
     one = fc.algebra.align_vec_pair(golden["avp_ref"][20], golden["avp_tgt"][20])
     assert np.abs(one - golden["avp_out"][20]).max() < TOL
+
+
+@pytest.mark.parametrize("A", [1, 2, 3, 4, 63, 64, 65, 300])
+def test_alignment_matrices_shapes(fc, A):
+    """fc_alignment_matrices at 1 ... 300 atoms and 1, 63, 64, 65 pairs (a wavefront of pairs, one less, one more):
+    partners are rotated copies with 0.05 A of noise.  The matrix within 1e-10 of the oracle's wherever the optimal
+    rotation is unique (a finite rotation_error_bound_batch); a proper rotation (det = 1 within 1e-12) everywhere; and
+    everywhere -- one atom, where any rotation about the atom's direction is as good, included -- as good a fit as the
+    oracle's: the RMSD after applying the matrix within 1e-10 of the RMSD after applying the oracle's."""
+    for n_pairs in (1, 63, 64, 65):
+        rng = np.random.default_rng(1000 * A + n_pairs)
+        P = rng.normal(scale=2.0, size=(n_pairs, A, 3))
+        Q = np.einsum("kij,kaj->kai", np.array([_rot(rng) for _ in range(n_pairs)]), P) + 0.05 * rng.normal(size=P.shape)
+        M = fc.rmsd.get_alignment_matrices(P, Q)
+        M0 = np.array([o.get_alignment_matrix(p, q) for p, q in zip(P, Q)])
+        assert M.shape == (n_pairs, 3, 3)
+        unique = np.isfinite(o.rotation_error_bound_batch(P, Q, center=False))
+        assert unique.all() == (A >= 2) and unique.any() == (A >= 2)  # (two atoms and the origin span a plane)
+        print(f"A={A} pairs={n_pairs}: matrix off by {np.abs(M - M0)[unique].max(initial=0.0):.2e}, "
+              f"det off by {np.abs(np.linalg.det(M) - 1).max():.2e}")
+        assert np.abs(M - M0)[unique].max(initial=0.0) < TOL
+        assert np.abs(np.linalg.det(M) - 1).max() < 1e-12
+        assert np.abs(np.einsum("kij,klj->kil", M, M) - np.eye(3)).max() < 1e-12
+        fit = np.sqrt(((P - np.einsum("kij,kaj->kai", M, Q)) ** 2).sum(axis=(1, 2)) / A)
+        fit0 = np.sqrt(((P - np.einsum("kij,kaj->kai", M0, Q)) ** 2).sum(axis=(1, 2)) / A)
+        assert np.abs(fit - fit0).max() < TOL
 
 
 def test_align_structures(fc):
@@ -1705,11 +1733,12 @@ def test_rmsd_and_max_all_pairs_tiled_kernel(fc):
     assert R[4, 5] < 1e-12 and R[8, 9] < 1e-7
 
 
-@pytest.mark.parametrize("n,a", [(140, 104), (130, 105), (120, 160), (100, 260), (90, 320)])
+@pytest.mark.parametrize("n,a", [(140, 104), (130, 105), (120, 160), (100, 260), (90, 320), (70, 416), (66, 417)])
 def test_rmsd_and_max_all_pairs_above_the_tiled_kernel(fc, n, a):
-    """the complete alignments of all pairs on both sides of the tiled kernel's last atom count (104: the 64-column
-    tile plus the kernel's own arrays fill the LDS) and at the sizes of docked poses -- k_matrix_exact takes over, same
-    1e-10 against the oracle"""
+    """the complete alignments of all pairs on both sides of the last atom count of the tiled kernel's 64-column tile
+    (104: the tile plus the kernel's own arrays fill the LDS; 105 ... 208 atoms take 32 columns, 209 ... 416 take 16), at
+    the sizes of docked poses, and on both sides of the tiled kernel's last size: 416 atoms is its widest structure, from
+    417 on k_matrix_exact takes over -- the same 1e-10 against the oracle everywhere"""
     X, atoms, _ = syn.synthetic_ensemble(n, a, seed=500 + a, cluster_size=3)
     with fc.DeviceEnsemble(X, center=True) as ens:
         R, D, _ = ens.rmsd_and_max_all()
