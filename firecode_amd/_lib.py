@@ -167,6 +167,10 @@ _SIGNATURES = {
     "fc_bench_prune_rmsd_sharded": [_ens, _f64, _f64, _i64, C.c_int, _p_f64, _p_f64, _p_u8, _p_i64],
     "fc_ensemble_select_diverse": [_ens, _i64, _i64, _f64, _p_i64, _p_f64, C.POINTER(C.c_int32), _p_f64, _p_i64],
     "fc_bench_select_diverse": [_ens, _i64, _i64, _f64, _i64, _p_f64, _p_f64, _p_i64, _p_i64, _p_i64],
+    "fc_ensemble_select_diverse_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, _i64, _i64, _f64, _p_i64, _p_f64,
+                                        C.POINTER(C.c_int32), _p_f64, _p_i64],
+    "fc_bench_select_diverse_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, _i64, _i64, _f64, _i64, _p_f64, _p_f64,
+                                     _p_i64, _p_i64, _p_i64],
     "fc_prune_rmsd_many": [C.POINTER(_ens), _i64, _f64, _f64, _i64, C.POINTER(_p_u8), _p_i64],
 }
 
@@ -472,10 +476,27 @@ class DeviceEnsemble:
              pf(r), pf(m))
         return r, m
 
-    def select_diverse(self, n_max, start=0, stop_rmsd=None):
+    def _diverse_perm_args(self, symmetry, prune_enantiomers):
+        """``symmetry=`` (a (K, A_all) table) and the mirror flag of the diverse selection -> None when neither is set,
+        else the leading arguments of the ``_perm`` entry points; every check made before the handle is used"""
+        from firecode_amd import symmetry as S
+
+        enant = check_flag("prune_enantiomers", prune_enantiomers)
+        if symmetry is None and not enant:
+            return None
+        # (a twin workspace refuses here; the identity table stands for "mirror images only")
+        keep, args = self._perm_args(np.arange(self.A_all, dtype=np.int64)[None] if symmetry is None else symmetry)
+        S.diverse_lds_check(args[1], args[2])
+        return keep, args + (int(enant),)
+
+    def select_diverse(self, n_max, start=0, stop_rmsd=None, symmetry=None, prune_enantiomers=False):
         """Greedy max-min selection under this ensemble's RMSD (fc_ensemble_select_diverse; the contract is in
         include/fc_hip.h) -> ``(indices (K,) int64 in selection order, labels (N,) int32 = position in ``indices``
-        of each conformer's representative, distances (N,) to it, radii (K,) nonincreasing, radii[0] = inf)``."""
+        of each conformer's representative, distances (N,) to it, radii (K,) nonincreasing, radii[0] = inf)``.
+        ``symmetry=`` a (K, A_all) table of atom permutations and / or ``prune_enantiomers=True``: under the smallest
+        RMSD over the permutations and, with the flag, over both handednesses (fc_ensemble_select_diverse_perm) --
+        relabelled copies and mirror images of a representative are at distance 0 from it."""
+        perm = self._diverse_perm_args(symmetry, prune_enantiomers)
         n_max, start = int(n_max), int(start)
         stop = -1.0 if stop_rmsd is None else float(stop_rmsd)
         if stop_rmsd is not None and not stop >= 0.0:
@@ -484,15 +505,28 @@ class DeviceEnsemble:
         idx, rad = np.empty(cap, dtype=np.int64), np.empty(cap)
         lab, dist = np.empty(self.N, dtype=np.int32), np.empty(self.N)
         k = C.c_int64(0)
-        call("fc_ensemble_select_diverse", self.handle, n_max, start, stop, pi(idx), pf(rad),
-             ptr(lab, C.c_int32), pf(dist), C.byref(k))
+        if perm is not None:
+            call("fc_ensemble_select_diverse_perm", self.handle, *perm[1], n_max, start, stop, pi(idx), pf(rad),
+                 ptr(lab, C.c_int32), pf(dist), C.byref(k))
+        else:
+            call("fc_ensemble_select_diverse", self.handle, n_max, start, stop, pi(idx), pf(rad),
+                 ptr(lab, C.c_int32), pf(dist), C.byref(k))
         return idx[:k.value], lab, dist, rad[:k.value]
 
-    def bench_select_diverse(self, n_max, start=0, stop_rmsd=None, reps=3):
-        """``reps`` selections -> (mean device ms, mean host ms, indices of the last, lanes per conformer used)."""
+    def bench_select_diverse(self, n_max, start=0, stop_rmsd=None, reps=3, symmetry=None, prune_enantiomers=False):
+        """``reps`` selections -> (mean device ms, mean host ms, indices of the last, lanes per conformer used); with
+        ``symmetry=`` / ``prune_enantiomers=True`` (fc_bench_select_diverse_perm) the last entry is instead
+        ``(k_h_formed, k_h_explicit)``: the (permutation, handedness) combinations whose eigenvalue was formed and
+        those that went on to the explicit pass, over one selection."""
+        perm = self._diverse_perm_args(symmetry, prune_enantiomers)
         stop = -1.0 if stop_rmsd is None else float(stop_rmsd)
         idx = np.empty(max(1, min(int(n_max), self.N)), dtype=np.int64)
         dev, host, k, lanes = C.c_double(0), C.c_double(0), C.c_int64(0), C.c_int64(0)
+        if perm is not None:
+            stats = np.zeros(2, dtype=np.int64)
+            call("fc_bench_select_diverse_perm", self.handle, *perm[1], int(n_max), int(start), stop, int(reps),
+                 C.byref(dev), C.byref(host), pi(idx), C.byref(k), pi(stats))
+            return dev.value, host.value, idx[:k.value], (int(stats[0]), int(stats[1]))
         call("fc_bench_select_diverse", self.handle, int(n_max), int(start), stop, int(reps), C.byref(dev),
              C.byref(host), pi(idx), C.byref(k), C.byref(lanes))
         return dev.value, host.value, idx[:k.value], lanes.value

@@ -4,6 +4,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <functional>
 #include <memory>
 
 #include "fc_internal.h"
@@ -779,9 +780,11 @@ static int bench_rmsd_and_max_all(fc_ensemble *ens, int64_t reps, double *ms_ker
 }
 
 // ---- RMSD-diverse selection (greedy max-min; the contract: include/fc_hip.h, fc_diverse.hip) ----------------------
+// prepare_sym (may be empty): the symmetry-aware form -- called behind the checks and ensure_init to put the table on the
+// device and fill the DiverseSym the steps then take
 static int select_diverse_checked(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
                                   double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected,
-                                  double *ms_device) {
+                                  double *ms_device, const std::function<int(DiverseSym &)> &prepare_sym = nullptr) {
   FC_REQUIRE(ens != nullptr, "ens is NULL");
   FC_REQUIRE(indices_out != nullptr && n_selected != nullptr, "indices_out / n_selected is NULL");
   FC_REQUIRE(n_max >= 1, "n_max=%lld < 1", (long long)n_max);
@@ -792,7 +795,10 @@ static int select_diverse_checked(fc_ensemble *ens, int64_t n_max, int64_t start
   FC_REQUIRE(start >= 0 && start < ens->N, "start=%lld outside [0, %lld)", (long long)start, (long long)ens->N);
   FC_REQUIRE(ens->N <= (int64_t)INT32_MAX - 256, "N=%lld: the selection indexes conformers with 32 bits", (long long)ens->N);
   FC_TRY(ensure_init());
-  return select_diverse(ens, n_max, start, stop_rmsd, indices_out, radii_out, labels_out, dist_out, n_selected, ms_device);
+  DiverseSym sym;
+  if (prepare_sym) FC_TRY(prepare_sym(sym));
+  return select_diverse(ens, n_max, start, stop_rmsd, indices_out, radii_out, labels_out, dist_out, n_selected, ms_device,
+                        prepare_sym ? &sym : nullptr);
 }
 
 int fc_ensemble_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
@@ -1324,6 +1330,77 @@ int fc_rmsd_clusters_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int
                                         sizes_out, n_clusters, stats);
   if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());
   return rc;
+}
+
+// ---- the diverse selection under d_sym (include/fc_hip.h; the kernel: k_diverse_step_sym, fc_diverse.hip) ---------------
+// stats (may be NULL): the two counters of DiverseSym::stats_dev after the selection
+static int select_diverse_perm_checked(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
+                                       int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out, double *radii_out,
+                                       int32_t *labels_out, double *dist_out, int64_t *n_selected, double *ms_device,
+                                       int64_t *stats) {
+  std::vector<uint16_t> table;
+  FC_TRY(perm_table_check(perms, K, A_sel, table));
+  const size_t lds = diverse_sym_lds_bytes(A_sel, K);
+  if (lds > kLdsLimit)
+    return set_error(FC_E_LIMIT, "A_sel=%lld selected atoms with K=%lld permutations need %zu bytes of LDS (limit %zu)",
+                     (long long)A_sel, (long long)K, lds, kLdsLimit);
+  FC_REQUIRE(mirror == 0 || mirror == 1, "mirror=%d: 0 or 1", mirror);
+  FC_TRY(perm_ensemble_check(ens, K, A_sel, false));
+  if (stats) stats[0] = stats[1] = 0;
+  if (K == 1 && !mirror)  // d_sym = d: the default's kernels, bit for bit
+    return select_diverse_checked(ens, n_max, start, stop_rmsd, indices_out, radii_out, labels_out, dist_out, n_selected,
+                                  ms_device);
+  DevBuf dperm, dstats;
+  // (behind the sibling's checks and ensure_init; the buffers live until select_diverse's last wait)
+  const auto run = [&](DiverseSym &sym) -> int {
+    FC_TRY(upload(dperm, table.data(), table.size()));
+    sym.perms_dev = dperm.as<uint16_t>(), sym.K = (int)K, sym.mirror = mirror != 0;
+    if (!stats) return FC_OK;
+    FC_TRY(dstats.reserve(2 * sizeof(unsigned long long)));
+    FC_HIP_TRY(hipMemsetAsync(dstats.p, 0, 2 * sizeof(unsigned long long), ctx().stream));
+    sym.stats_dev = reinterpret_cast<unsigned long long *>(dstats.p);
+    return FC_OK;
+  };
+  int rc = select_diverse_checked(ens, n_max, start, stop_rmsd, indices_out, radii_out, labels_out, dist_out, n_selected,
+                                  ms_device, run);
+  if (rc == FC_OK && stats && ens->N > 0) {
+    unsigned long long cnt[2] = {0, 0};
+    rc = d2h(cnt, dstats.p, sizeof cnt);
+    if (rc == FC_OK) rc = sync();
+    stats[0] = (int64_t)cnt[0], stats[1] = (int64_t)cnt[1];
+  }
+  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());  // nothing of the buffers may be in flight when they go
+  return rc;
+}
+
+int fc_ensemble_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
+                                    int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
+                                    double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected) {
+  FC_API_LOCK;
+  return select_diverse_perm_checked(ens, perms, K, A_sel, mirror, n_max, start, stop_rmsd, indices_out, radii_out,
+                                     labels_out, dist_out, n_selected, nullptr, nullptr);
+}
+
+int fc_bench_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
+                                 int64_t n_max, int64_t start, double stop_rmsd, int64_t reps, double *ms_device_mean,
+                                 double *ms_host_mean, int64_t *indices_out, int64_t *n_selected, int64_t *stats) {
+  FC_API_LOCK;
+  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
+  double dev = 0.0, host = 0.0;
+  for (int64_t r = 0; r < reps; ++r) {
+    double ms = 0.0;
+    const auto t0 = std::chrono::steady_clock::now();
+    FC_TRY(select_diverse_perm_checked(ens, perms, K, A_sel, mirror, n_max, start, stop_rmsd, indices_out, nullptr, nullptr,
+                                       nullptr, n_selected, &ms, nullptr));
+    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    dev += ms;
+  }
+  *ms_device_mean = dev / (double)reps;
+  *ms_host_mean = host / (double)reps;
+  if (stats)  // counted in a selection of its own: the timed ones run without the counters
+    FC_TRY(select_diverse_perm_checked(ens, perms, K, A_sel, mirror, n_max, start, stop_rmsd, indices_out, nullptr, nullptr,
+                                       nullptr, n_selected, nullptr, stats));
+  return FC_OK;
 }
 
 // a caller's graph: checks on the host, one upload, the same labelling

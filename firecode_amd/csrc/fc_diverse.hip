@@ -33,6 +33,9 @@
 //
 // Limits: the representative's A x 24 bytes are staged in LDS up to kDiverseLdsAtoms atoms (48 KiB); beyond that the
 // same kernel reads them from global memory (k_diverse_step<.., false>): no size limit of its own besides N < 2^31.
+//
+// k_diverse_step_sym (further down) is the same step under the smallest rmsd over a table of atom permutations and,
+// optionally, both handednesses (fc_ensemble_select_diverse_perm); the host loop is shared.
 #include "fc_internal.h"
 #include "fc_kabsch_math.h"
 
@@ -190,6 +193,167 @@ k_diverse_step(const double *__restrict__ Xs, const double *__restrict__ Xa, con
   }
 }
 
+// ---------------------------------------------------------------------------
+// k_diverse_step_sym: the step under d_sym (include/fc_hip.h, fc_ensemble_select_diverse_perm)
+//
+//   d_sym(s, j) = min over k < K, h in H of rmsd(X[s], h * X[j][perms[k]]),   H = {+1} or, MIRROR, {+1, -1}
+//
+// The three parts of k_diverse_step, with part 2 walking the table.  The representative AND the table (16-bit indices)
+// sit in LDS and the permutation is applied to the representative: sum_a p_a q_pi(a)^T = sum_b p_pi^-1(b) q_b^T and the
+// table is closed under inverse, so the minimum over "rows applied to s" is the minimum the contract names, a
+// permutation costs an LDS address, and the conformer is still read coalesced from the conformer-minor Xs.
+// Per conformer and row k: the covariance B_k (the only atom loop every (pair, k) pays), the Newton eigenvalue of B_k
+// and -- MIRROR -- of -B_k (kabsch_lambda_max_both), and for each h the rotation and the explicit deviation pass
+// UNLESS the eigenvalue form of its msd, (Gs + Gj - 2 lambda)/A, exceeds the smallest explicit msd seen so far for this
+// conformer by more than kScreenMargin (1e-6 A^2: the eigenvalue form is good to ~1e-12 of G/A, and the iteration
+// errs towards a SMALLER msd where it stalls).  A (k, h) left out is therefore not the minimum; the value kept is the
+// explicit sum of the winning (k, h), h = -1 as pair_exact_aos<INV> forms it: -B, p + R q.
+// The rows are taken in table order against a running best -- not sorted by eigenvalue: that would keep 2 K
+// eigenvalues per lane.  Row 0 is the identity, the winner for every conformer that was not relabelled.
+// stats (may be NULL): [0] += (k, h) whose eigenvalue was formed, [1] += those that reached the explicit pass.
+// ---------------------------------------------------------------------------
+constexpr size_t kDiverseSymStaticLds = 64;  // s_v, s_i, s_stop below: 52 bytes, rounded
+
+size_t diverse_sym_lds_bytes(int64_t A, int64_t K) {
+  return (size_t)A * 3 * sizeof(double) + (((size_t)K * (size_t)A * sizeof(uint16_t) + 7) & ~(size_t)7) + kDiverseSymStaticLds;
+}
+
+template <int LANES, bool MIRROR>
+__global__ void __launch_bounds__(kDivThreads)
+k_diverse_step_sym(const double *__restrict__ Xs, const double *__restrict__ Xa, const double *__restrict__ G, int N, int64_t Npad,
+                   int A, const uint16_t *__restrict__ perms, int K, int k, int start, double stop_rmsd, int n_steps,
+                   double *__restrict__ D, int32_t *__restrict__ L, uint8_t *__restrict__ is_rep, double *__restrict__ part_v,
+                   int32_t *__restrict__ part_i, int nb, int64_t *__restrict__ idx_out, double *__restrict__ rad_out,
+                   int64_t *__restrict__ state, unsigned long long *__restrict__ stats) {
+  static_assert(LANES == 1 || LANES == 8, "one or eight lanes per conformer");
+  extern __shared__ double s_sym[];  // [A][3] of the representative, then the table [K][A] as uint16_t
+  __shared__ double s_v[kDivThreads / 64];
+  __shared__ int s_i[kDivThreads / 64];
+  __shared__ int s_stop;
+  static_assert(sizeof s_v + sizeof s_i + sizeof s_stop <= kDiverseSymStaticLds, "diverse_sym_lds_bytes counts less");
+  const int tid = threadIdx.x;
+
+  // ---- 1. the representative of this step (as k_diverse_step, which says why the stop word is read once)
+  int s = start;
+  if (k > 0) {
+    if (tid == 0) s_stop = *(volatile int64_t *)state != 0;
+    __syncthreads();
+    if (s_stop) return;
+    const double *__restrict__ pv = part_v + (size_t)((k - 1) & 1) * nb;
+    const int32_t *__restrict__ pi = part_i + (size_t)((k - 1) & 1) * nb;
+    double m = -1.0;
+    int mi = INT_MAX;
+    for (int b = tid; b < nb; b += kDivThreads)
+      if (div_better(pv[b], pi[b], m, mi)) m = pv[b], mi = pi[b];
+    div_block_argmax(m, mi, s_v, s_i);
+    if (mi == INT_MAX || (stop_rmsd >= 0.0 && m <= stop_rmsd)) {
+      if (blockIdx.x == 0 && tid == 0) state[0] = 1, state[1] = k;
+      return;
+    }
+    if (blockIdx.x == 0 && tid == 0) idx_out[k] = mi, rad_out[k] = m;
+    s = mi;
+  } else if (blockIdx.x == 0 && tid == 0) {
+    idx_out[0] = start, rad_out[0] = INFINITY;
+    state[0] = 0, state[1] = n_steps;
+  }
+
+  // ---- 2. align s, under every row of the table and either handedness, against every conformer of this workgroup
+  uint16_t *pt = reinterpret_cast<uint16_t *>(s_sym + 3 * A);
+  {
+    const double *__restrict__ src = Xa + (int64_t)s * A * 3;
+    for (int t = tid; t < 3 * A; t += kDivThreads) s_sym[t] = src[t];
+    for (int t = tid; t < K * A; t += kDivThreads) pt[t] = perms[t];
+    __syncthreads();
+  }
+  const double *__restrict__ P = s_sym;
+  constexpr int kPerBlock = kDivThreads / LANES;
+  const int sub = LANES == 1 ? 0 : (tid & (LANES - 1));
+  const int j = blockIdx.x * kPerBlock + tid / LANES;
+  double cand = -1.0;
+  int cand_i = INT_MAX;
+  unsigned n_formed = 0, n_explicit = 0;
+  if (j < N) {  // (uniform over the LANES lanes of a conformer, and so is every branch below: xor sums are)
+    if (j == s) {
+      if (sub == 0) D[j] = 0.0, L[j] = k, is_rep[j] = 1;
+    } else if (k == 0 || !is_rep[j]) {
+      const double Gs = G[s] + G[j];
+      const double margin = (double)A * kScreenMargin;
+      double best = INFINITY;  // the smallest explicit sum of squares so far
+      for (int r = 0; r < K; ++r) {
+        const uint16_t *__restrict__ pr = pt + r * A;
+        double B[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int a = sub; a < A; a += LANES) {
+          const double *__restrict__ qa = Xs + (int64_t)(a * 3) * Npad + j;
+          const int b = (int)pr[a] * 3;
+          const double px = P[b], py = P[b + 1], pz = P[b + 2];
+          const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
+          B[0] = fma(px, qx, B[0]); B[1] = fma(px, qy, B[1]); B[2] = fma(px, qz, B[2]);
+          B[3] = fma(py, qx, B[3]); B[4] = fma(py, qy, B[4]); B[5] = fma(py, qz, B[5]);
+          B[6] = fma(pz, qx, B[6]); B[7] = fma(pz, qy, B[7]); B[8] = fma(pz, qz, B[8]);
+        }
+        if (LANES > 1) {
+#pragma unroll
+          for (int e = 0; e < 9; ++e) B[e] = div_group8_sum(B[e]);
+        }
+        double lam_p, lam_m = 0.0;
+        kabsch_lambda_max_both<MIRROR>(B, Gs, lam_p, lam_m);
+#pragma nounroll
+        for (int h = 0; h < (MIRROR ? 2 : 1); ++h) {
+          ++n_formed;
+          if (Gs - 2.0 * (h ? lam_m : lam_p) > best + margin) continue;  // (a NaN goes on to the explicit pass)
+          ++n_explicit;
+          const double sg = h ? -1.0 : 1.0;
+          double Bh[9], R[9];
+#pragma unroll
+          for (int e = 0; e < 9; ++e) Bh[e] = sg * B[e];
+          if (!kabsch_rotation_qcp(Bh, Gs, R)) (void)kabsch_rotation(Bh, R);
+          double ssq = 0.0;
+          for (int a = sub; a < A; a += LANES) {
+            const double *__restrict__ qa = Xs + (int64_t)(a * 3) * Npad + j;
+            const int b = (int)pr[a] * 3;
+            const double px = P[b], py = P[b + 1], pz = P[b + 2];
+            const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
+            const double dx = px - sg * (R[0] * qx + R[1] * qy + R[2] * qz);
+            const double dy = py - sg * (R[3] * qx + R[4] * qy + R[5] * qz);
+            const double dz = pz - sg * (R[6] * qx + R[7] * qy + R[8] * qz);
+            ssq += dx * dx + dy * dy + dz * dz;
+          }
+          if (LANES > 1) ssq = div_group8_sum(ssq);
+          if (!(ssq >= best)) best = ssq;
+        }
+      }
+      const double t = sqrt(best / (double)A);
+      if (sub == 0) {
+        double d = t;
+        if (k == 0) {
+          D[j] = t, L[j] = 0, is_rep[j] = 0;
+        } else {
+          d = D[j];
+          if (t < d) D[j] = t, L[j] = k, d = t;
+        }
+        cand = d, cand_i = j;
+      } else {
+        n_formed = n_explicit = 0;  // (counted once per conformer)
+      }
+    }
+  }
+  if (stats != nullptr) {  // (uniform: a bench hook's counters)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n_formed += __shfl_xor(n_formed, o), n_explicit += __shfl_xor(n_explicit, o);
+    if ((tid & 63) == 0 && n_formed) {
+      atomicAdd(&stats[0], (unsigned long long)n_formed);
+      atomicAdd(&stats[1], (unsigned long long)n_explicit);
+    }
+  }
+
+  // ---- 3. this workgroup's partial for the next step
+  div_block_argmax(cand, cand_i, s_v, s_i);
+  if (tid == 0) {
+    part_v[(size_t)(k & 1) * nb + blockIdx.x] = cand;
+    part_i[(size_t)(k & 1) * nb + blockIdx.x] = cand_i;
+  }
+}
+
 int diverse_lanes(int64_t N) {  // lanes per conformer of the step kernel at N conformers (fc_bench_select_diverse reports it)
   if (const char *v = getenv("FC_DIVERSE_LANES")) {  // a measurement of the two forms at one size (tools/bench_diverse.py)
     if (v[0] == '1' && v[1] == 0) return 1;
@@ -209,17 +373,45 @@ static int launch_step(const fc_ensemble *e, int k, int start, double stop, int 
   return check_launch("k_diverse_step");
 }
 
+template <int LANES, bool MIRROR>
+static const void *step_sym_kernel() {
+  return reinterpret_cast<const void *>(k_diverse_step_sym<LANES, MIRROR>);
+}
+
+template <int LANES, bool MIRROR>
+static int launch_step_sym(const fc_ensemble *e, const DiverseSym &sym, int k, int start, double stop, int n_steps, DevBuf &D,
+                           DevBuf &L, DevBuf &rep, DevBuf &pv, DevBuf &pi, int nb, DevBuf &idx, DevBuf &rad, DevBuf &state) {
+  const size_t lds = diverse_sym_lds_bytes(e->A, sym.K) - kDiverseSymStaticLds;
+  hipLaunchKernelGGL((k_diverse_step_sym<LANES, MIRROR>), dim3((unsigned)nb), dim3(kDivThreads), lds, ctx().stream,
+                     e->Xs.as<double>(), e->Xa.as<double>(), e->G.as<double>(), (int)e->N, e->Npad, (int)e->A, sym.perms_dev,
+                     sym.K, k, start, stop, n_steps, D.as<double>(), L.as<int32_t>(), rep.as<uint8_t>(), pv.as<double>(),
+                     pi.as<int32_t>(), nb, idx.as<int64_t>(), rad.as<double>(), state.as<int64_t>(), sym.stats_dev);
+  return check_launch("k_diverse_step_sym");
+}
+
 // The selection behind fc_ensemble_select_diverse (arguments checked there; N >= 1, 1 <= n_max, 0 <= start < N).
 // stop_rmsd < 0: n_max steps enqueued at once, one host wait at the end; otherwise batches of kDiverseBatch steps and
 // a read of the stop word behind each.  ms_device (may be NULL): HIP-event time from the first launch to the last.
+// sym (may be NULL): the steps are k_diverse_step_sym's (fc_ensemble_select_diverse_perm, which has checked that the
+// representative and the table fit the LDS).
 int select_diverse(fc_ensemble *e, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
-                   double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected, double *ms_device) {
+                   double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected, double *ms_device,
+                   const DiverseSym *sym) {
   constexpr int kDiverseBatch = 64;
   const int64_t N = e->N;
   const int n_steps = (int)std::min<int64_t>(n_max, N);
   const int lanes = diverse_lanes(N);
   const bool stage = e->A <= kDiverseLdsAtoms;
   const int nb = (int)ceil_div(N, kDivThreads / lanes);
+  if (sym) {
+    const size_t lds = diverse_sym_lds_bytes(e->A, sym->K);
+    if (lds > kLdsLimit)
+      return set_error(FC_E_LIMIT, "A_sel=%lld selected atoms with K=%lld permutations need %zu bytes of LDS (limit %zu)",
+                       (long long)e->A, (long long)sym->K, lds, kLdsLimit);
+    const void *fn = lanes == 8 ? (sym->mirror ? step_sym_kernel<8, true>() : step_sym_kernel<8, false>())
+                                : (sym->mirror ? step_sym_kernel<1, true>() : step_sym_kernel<1, false>());
+    FC_TRY(allow_dynamic_lds(fn, lds - kDiverseSymStaticLds, "k_diverse_step_sym"));
+  }
   DevBuf D, L, rep, pv, pi, idx, rad, state;
   FC_TRY(D.reserve((size_t)N * sizeof(double)));
   FC_TRY(L.reserve((size_t)N * sizeof(int32_t)));
@@ -236,7 +428,13 @@ int select_diverse(fc_ensemble *e, int64_t n_max, int64_t start, double stop_rms
     const int k_end = stop_rmsd < 0.0 ? n_steps : std::min(n_steps, k + kDiverseBatch);
     for (; k < k_end; ++k) {
       int rc;
-      if (lanes == 8)
+      if (sym && lanes == 8)
+        rc = sym->mirror ? launch_step_sym<8, true>(e, *sym, k, (int)start, stop_rmsd, n_steps, D, L, rep, pv, pi, nb, idx, rad, state)
+                         : launch_step_sym<8, false>(e, *sym, k, (int)start, stop_rmsd, n_steps, D, L, rep, pv, pi, nb, idx, rad, state);
+      else if (sym)
+        rc = sym->mirror ? launch_step_sym<1, true>(e, *sym, k, (int)start, stop_rmsd, n_steps, D, L, rep, pv, pi, nb, idx, rad, state)
+                         : launch_step_sym<1, false>(e, *sym, k, (int)start, stop_rmsd, n_steps, D, L, rep, pv, pi, nb, idx, rad, state);
+      else if (lanes == 8)
         rc = stage ? launch_step<8, true>(e, k, (int)start, stop_rmsd, n_steps, D, L, rep, pv, pi, nb, idx, rad, state)
                    : launch_step<8, false>(e, k, (int)start, stop_rmsd, n_steps, D, L, rep, pv, pi, nb, idx, rad, state);
       else

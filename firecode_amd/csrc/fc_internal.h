@@ -143,8 +143,17 @@ int launch_tri_embed(const double *const coords_dev[3], const int64_t *const rea
 int warm_embed3();
 // ---- fc_diverse.hip --------------------------------------------------------------------------------------
 int diverse_lanes(int64_t N);
+// the symmetry- and mirror-aware step (k_diverse_step_sym): the table on the device as 16-bit indices, K rows of e->A
+struct DiverseSym {
+  const uint16_t *perms_dev = nullptr;
+  int K = 1;
+  bool mirror = false;
+  unsigned long long *stats_dev = nullptr;  // two counters, or nullptr: (k, h) whose eigenvalue was formed / that went on to the explicit pass
+};
+size_t diverse_sym_lds_bytes(int64_t A, int64_t K);  // representative + table + the kernel's static LDS
 int select_diverse(fc_ensemble *e, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
-                   double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected, double *ms_device);
+                   double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected, double *ms_device,
+                   const DiverseSym *sym = nullptr);
 int warm_diverse();
 // ---- fc_clusters.hip -------------------------------------------------------------------------------------
 // the graph whose components are labelled: a device pair list OR a bit matrix

@@ -391,6 +391,45 @@ __host__ __device__ __forceinline__ double kabsch_lambda_max(const double (&B)[9
   return x;
 }
 
+// The Newton eigenvalue alone, of B and -- MIRROR -- of -B as well (one structure inverted through the origin): n2 and
+// |cof B|_F^2 are even in B, det B changes sign, so the second polynomial is the first with C1 negated (the lemma of
+// kabsch_may_be_below).  Both iterations start from the upper bound (Gp + Gq)/2 and come down monotonically: a value
+// returned is never below the eigenvalue by more than rounding, also where the iteration stalls short of a (nearly)
+// double root -- the side on which a screen that drops LARGE msd = (Gp + Gq - 2 lambda)/A needs it (k_diverse_step_sym).
+template <bool MIRROR>
+__host__ __device__ __forceinline__ void kabsch_lambda_max_both(const double (&B)[9], double GpGq, double &lam_plus,
+                                                                double &lam_minus) {
+#pragma clang fp contract(fast)
+  const double Sxx = B[0], Sxy = B[1], Sxz = B[2];
+  const double Syx = B[3], Syy = B[4], Syz = B[5];
+  const double Szx = B[6], Szy = B[7], Szz = B[8];
+  const double n2 = Sxx * Sxx + Sxy * Sxy + Sxz * Sxz + Syx * Syx + Syy * Syy + Syz * Syz +
+                    Szx * Szx + Szy * Szy + Szz * Szz;
+  const double c00 = Syy * Szz - Syz * Szy, c01 = Syz * Szx - Syx * Szz, c02 = Syx * Szy - Syy * Szx;
+  const double c10 = Sxz * Szy - Sxy * Szz, c11 = Sxx * Szz - Sxz * Szx, c12 = Sxy * Szx - Sxx * Szy;
+  const double c20 = Sxy * Syz - Sxz * Syy, c21 = Sxz * Syx - Sxx * Syz, c22 = Sxx * Syy - Sxy * Syx;
+  const double detB = Sxx * c00 + Sxy * c01 + Sxz * c02;
+  const double e2 = c00 * c00 + c01 * c01 + c02 * c02 + c10 * c10 + c11 * c11 + c12 * c12 +
+                    c20 * c20 + c21 * c21 + c22 * c22;
+  const double C2 = -2.0 * n2, C0 = n2 * n2 - 4.0 * e2;
+#pragma unroll
+  for (int h = 0; h < (MIRROR ? 2 : 1); ++h) {
+    const double C1 = h ? 8.0 * detB : -8.0 * detB;
+    double x = 0.5 * GpGq;
+    for (int it = 0; it < 64; ++it) {
+      const double x2 = x * x;
+      const double b = (x2 + C2) * x;
+      const double a = b + C1;
+      const double den = 2.0 * x2 * x + b + a;
+      if (den == 0.0) break;
+      const double delta = (a * x + C0) / den;
+      x -= delta;
+      if (fabs(delta) <= 4e-16 * fabs(x)) break;
+    }
+    (h ? lam_minus : lam_plus) = x;
+  }
+}
+
 // Whether lambda = kabsch_lambda_max(..., &slope) carries the rmsd to ~1e-11: the rounding of P at the root, taken as
 // 4.5 u x^4 = 1e-15 x^4 (a margin of ten over its four terms of size x^4), moves the root by that over |P'|, the sum
 // A msd = (Gp + Gq) - 2 lambda by twice as much, and the rmsd by d(A msd) / (2 sqrt(A * A msd)):

@@ -107,25 +107,33 @@ class Ensemble:
         self.energies = self.energies[order]
         self.coords = self.coords[order]
 
-    def diversity_selection(self, n=None, stop_rmsd=None, heavy_atoms_only=True, verbose=True):
+    def diversity_selection(self, n=None, stop_rmsd=None, heavy_atoms_only=True, verbose=True, symmetry=None,
+                            prune_enantiomers=False):
         """Keep the ``n`` most diverse structures, or representatives within ``stop_rmsd`` of every structure, by
         greedy max-min selection under the heavy-atom RMSD (``firecode_amd.pruner.select_diverse``; no reference
         counterpart: FIRECODE's ``most_diverse_conformers`` is a random draw).  Starts at the lowest energy when
         energies are known, else at the first structure; the kept structures stay in selection order and
-        ``energies`` follow them.  Returns the ``DiverseSelection`` of the ensemble as it was."""
+        ``energies`` follow them.  ``symmetry=`` / ``prune_enantiomers=True``: as in ``select_diverse`` -- relabelled
+        copies and mirror images count as the same structure.  Returns the ``DiverseSelection`` of the ensemble as it
+        was."""
+        from firecode_amd import symmetry as S
+        from firecode_amd._lib import check_flag
         from firecode_amd.pruner import select_diverse
 
+        enant = check_flag("prune_enantiomers", prune_enantiomers)
+        table = S.resolve(symmetry, np.asarray(self.atoms), heavy_atoms_only)
         log = self.logfunction if verbose else None
         n0, t0 = len(self.coords), perf_counter()
         use_en = len(self.energies) == n0 and n0 > 0
         sel = select_diverse(self.coords, self.atoms, n=n, stop_rmsd=stop_rmsd, heavy_atoms_only=heavy_atoms_only,
-                             energies=self.energies if use_en else None)
+                             energies=self.energies if use_en else None, symmetry=table, prune_enantiomers=enant)
         self.coords = self.coords[sel.indices]
         if use_en:
             self.apply_mask(("energies",), sel.indices)
         if log is not None:
             cover = float(sel.distances.max()) if n0 else 0.0
-            log(f"Kept {len(sel.indices)} of {n0} candidates for RMSD diversity (covering radius {cover:.3f} A, "
+            aware = ("" if table is None else f", {len(table)} atom permutations") + (", mirror images included" if enant else "")
+            log(f"Kept {len(sel.indices)} of {n0} candidates for RMSD diversity{aware} (covering radius {cover:.3f} A, "
                 f"{perf_counter() - t0:.3f} s)")
         return sel
 

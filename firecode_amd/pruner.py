@@ -131,7 +131,8 @@ def prune_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None,
 DiverseSelection = namedtuple("DiverseSelection", ["indices", "labels", "distances", "radii"])
 
 
-def select_diverse(structures, atoms, n=None, stop_rmsd=None, heavy_atoms_only=True, start=None, energies=None):
+def select_diverse(structures, atoms, n=None, stop_rmsd=None, heavy_atoms_only=True, start=None, energies=None,
+                   symmetry=None, prune_enantiomers=False):
     """RMSD-diverse selection: greedy max-min (farthest point, Gonzalez k-center) under the heavy-atom Kabsch RMSD
     ``prune_by_rmsd`` uses (centred, ``rmsd_and_max(...)[0]``), on the GPU (fc_ensemble_select_diverse; the contract
     is written out in include/fc_hip.h).  Either "the ``n`` most different conformers" (``n``) or "representatives
@@ -141,7 +142,15 @@ def select_diverse(structures, atoms, n=None, stop_rmsd=None, heavy_atoms_only=T
 
     Returns ``DiverseSelection(indices, labels, distances, radii)``: indices (K,) into ``structures`` in selection
     order; labels (N,) int32, the position in ``indices`` of each conformer's nearest representative; distances (N,)
-    to it; radii (K,) the covering radius just before each pick (nonincreasing, radii[0] = inf)."""
+    to it; radii (K,) the covering radius just before each pick (nonincreasing, radii[0] = inf).
+
+    ``symmetry=`` (a bond graph or a (K, A) table over all atoms, as in ``prune_by_rmsd``) and ``prune_enantiomers=True``
+    -- here the two combine -- make the distance the smallest RMSD over the atom permutations and, with the flag, over
+    both handednesses (fc_ensemble_select_diverse_perm): a relabelled copy or a mirror image of a representative is at
+    distance 0 from it and is not picked as "most different"."""
+    from firecode_amd import symmetry as S
+
+    enant = L.check_flag("prune_enantiomers", prune_enantiomers)
     structures = L.f64(structures)
     if structures.ndim != 3 or structures.shape[2] != 3:
         raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {structures.shape}")
@@ -164,6 +173,8 @@ def select_diverse(structures, atoms, n=None, stop_rmsd=None, heavy_atoms_only=T
     heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
     if not heavy.any():
         raise L.FirecodeHipInputError(L.FC_E_INVALID, "the atom selection is empty (no heavy atom)")
+    table = S.resolve(symmetry, atoms, heavy_atoms_only)
+    S.diverse_table(table, enant, heavy, len(atoms))  # (its checks, before any device use)
     if N == 0:
         empty = np.zeros(0, dtype=np.int64)
         return DiverseSelection(empty, np.zeros(0, dtype=np.int32), np.zeros(0), np.zeros(0))
@@ -171,7 +182,8 @@ def select_diverse(structures, atoms, n=None, stop_rmsd=None, heavy_atoms_only=T
         start = int(np.argmin(energies)) if energies is not None else 0  # (argmin: the first of equal minima)
     n_max = N if n is None else int(n)
     with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
-        return DiverseSelection(*ens.select_diverse(n_max, start=int(start), stop_rmsd=stop_rmsd))
+        return DiverseSelection(*ens.select_diverse(n_max, start=int(start), stop_rmsd=stop_rmsd, symmetry=table,
+                                                    prune_enantiomers=enant))
 
 
 RmsdClusters = namedtuple("RmsdClusters", ["labels", "representatives", "sizes"])

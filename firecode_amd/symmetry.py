@@ -109,6 +109,44 @@ def selected_table(table, atom_mask):
     return np.ascontiguousarray(position[images], dtype=np.int32)
 
 
+LDS_LIMIT = 160 * 1024  # kLdsLimit
+DIVERSE_STATIC_LDS = 64  # kDiverseSymStaticLds
+
+
+def diverse_lds_bytes(n_perms, n_selected):
+    """LDS of one workgroup of the symmetry-aware diverse selection (fc_ensemble_select_diverse_perm): the
+    representative, the table as 16-bit indices rounded up to 8 bytes, the kernel's own 64."""
+    return 24 * int(n_selected) + ((2 * int(n_perms) * int(n_selected) + 7) & ~7) + DIVERSE_STATIC_LDS
+
+
+def diverse_max_selected(n_perms):
+    """the largest number of selected atoms the symmetry-aware diverse selection takes with ``n_perms`` permutations"""
+    a = (LDS_LIMIT - DIVERSE_STATIC_LDS) // (24 + 2 * int(n_perms))
+    while diverse_lds_bytes(n_perms, a) > LDS_LIMIT:
+        a -= 1
+    return a
+
+
+def diverse_lds_check(n_perms, n_selected):
+    """FC_E_LIMIT, before any device use, where the library itself would refuse the selection for its LDS"""
+    need = diverse_lds_bytes(n_perms, n_selected)
+    if need > LDS_LIMIT:
+        raise L.FirecodeHipInputError(
+            L.FC_E_LIMIT, f"A_sel={int(n_selected)} selected atoms with K={int(n_perms)} permutations need {need} bytes of "
+            f"LDS (limit {LDS_LIMIT}): at most {diverse_max_selected(n_perms)} selected atoms")
+
+
+def diverse_table(symmetry, prune_enantiomers, atom_mask, n_atoms):
+    """``symmetry=`` (a checked table over all atoms, or None) and the mirror flag of the diverse selection -> the
+    (K, A_sel) int32 table the library takes, or None when neither is set; the LDS limit checked on the way"""
+    if symmetry is None and not prune_enantiomers:
+        return None
+    table = np.arange(int(n_atoms), dtype=np.int64)[None] if symmetry is None else symmetry
+    t = selected_table(table, atom_mask)
+    diverse_lds_check(t.shape[0], t.shape[1])
+    return t
+
+
 def refuse_with_enantiomers(table, prune_enantiomers):
     if table is not None and prune_enantiomers:
         raise L.FirecodeHipInputError(

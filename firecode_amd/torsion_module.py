@@ -167,7 +167,17 @@ def prune_conformers_tfd(structures, quadruplets, thresh=10, verbose=False):
     return structures[mask], mask
 
 
-def most_diverse_conformers(n, structures, seed=None, method="random", atoms=None):
+def _diversity_keywords(what, value, symmetry, prune_enantiomers):
+    """the two keywords of the RMSD-diverse selection on a call that can also draw at random: a real bool, and
+    nothing set with the random draw"""
+    enant = L.check_flag("prune_enantiomers", prune_enantiomers)
+    if value == "random" and (symmetry is not None or enant):
+        raise L.FirecodeHipInputError(
+            L.FC_E_INVALID, f"symmetry= / prune_enantiomers= belong to {what}='rmsd': the random draw compares nothing")
+    return enant
+
+
+def most_diverse_conformers(n, structures, seed=None, method="random", atoms=None, symmetry=None, prune_enantiomers=False):
     """firecode/torsion_module.py:574-586: everything when there are at most n structures (:581-582),
     else a RANDOM subsample of n (with replacement, sorted indices, :585-586).  The reference draws
     from the global, unseeded NumPy RNG; pass ``seed`` for a reproducible draw.
@@ -175,17 +185,25 @@ def most_diverse_conformers(n, structures, seed=None, method="random", atoms=Non
     ``method="rmsd"``: what the name promises and the reference's own comment says it no longer does (:579-580) --
     the n most diverse structures by greedy max-min selection under the Kabsch RMSD
     (``firecode_amd.pruner.select_diverse(..., n=n, start=0)``), in selection order -- also with at most n structures,
-    where that is all of them; ``atoms`` (one symbol per atom) makes it the heavy-atom RMSD, ``None`` aligns all atoms."""
+    where that is all of them; ``atoms`` (one symbol per atom) makes it the heavy-atom RMSD, ``None`` aligns all atoms.
+    ``symmetry=`` / ``prune_enantiomers=True``: as in ``select_diverse`` (a graph needs ``atoms``); an input error with
+    ``method="random"``."""
     if method not in ("random", "rmsd"):
         raise L.FirecodeHipInputError(L.FC_E_INVALID, f"method={method!r}: 'random' or 'rmsd'")
+    enant = _diversity_keywords("method", method, symmetry, prune_enantiomers)
     if len(structures) == 0 or (len(structures) <= n and method == "random"):
         return list(np.array(structures))
     if method == "rmsd":
         from firecode_amd.pruner import select_diverse
 
+        from firecode_amd import symmetry as S
+
         X = L.f64(np.array(structures))
+        table = S.resolve(symmetry, None if atoms is None else np.asarray(atoms), atoms is not None,
+                          n_atoms=X.shape[1] if X.ndim == 3 else None)
         sym = np.array(["C"] * X.shape[1]) if atoms is None else np.asarray(atoms)
-        sel = select_diverse(X, sym, n=n, start=0, heavy_atoms_only=atoms is not None)
+        sel = select_diverse(X, sym, n=n, start=0, heavy_atoms_only=atoms is not None, symmetry=table,
+                             prune_enantiomers=enant)
         return list(X[sel.indices])
     rng = np.random if seed is None else np.random.RandomState(seed)
     indices = np.sort(rng.choice(len(structures), size=n))
@@ -193,7 +211,7 @@ def most_diverse_conformers(n, structures, seed=None, method="random", atoms=Non
 
 
 def clustered_csearch_core(coords, torsions, rotation_masks, n_out=100, thresh=1.5, seed=None, logfunction=None,
-                           diversity="random", atoms=None):
+                           diversity="random", atoms=None, symmetry=None, prune_enantiomers=False):
     """Numeric core of ``clustered_csearch`` (torsion_module.py:726-891) for one
     torsion group: ``torsions`` = sequence of (i1, i2, i3, i4, n_fold),
     ``rotation_masks`` = the matching ``_get_rotation_mask`` arrays (graph
@@ -204,11 +222,13 @@ def clustered_csearch_core(coords, torsions, rotation_masks, n_out=100, thresh=1
     (``diversity="random"``) or the ``n_out`` most diverse by greedy max-min RMSD selection from the starting
     structure (``diversity="rmsd"``: FIRECODE's documented csearch mode 1, torsion_module.py:608-611) -- under the
     heavy-atom RMSD when ``atoms`` (one symbol per atom) is given, as ``prune_by_rmsd`` and ``select_diverse`` default
-    to, over all atoms otherwise (the core sees coordinates only)."""
+    to, over all atoms otherwise (the core sees coordinates only).  ``symmetry=`` / ``prune_enantiomers=True`` go to
+    that selection (``most_diverse_conformers``); an input error with ``diversity="random"``."""
     from firecode_amd.utils import cartesian_rows_at
 
     if diversity not in ("random", "rmsd"):
         raise L.FirecodeHipInputError(L.FC_E_INVALID, f"diversity={diversity!r}: 'random' or 'rmsd'")
+    enant = _diversity_keywords("diversity", diversity, symmetry, prune_enantiomers)
 
     n_fold_angles = {2: (0, 180), 3: (0, 120, 240), 4: (0, 90, 180, 270), 6: (0, 60, 120, 180, 240, 300)}
     quads = np.array([t[:4] for t in torsions], dtype=np.int64)
@@ -234,7 +254,8 @@ def clustered_csearch_core(coords, torsions, rotation_masks, n_out=100, thresh=1
     torsion_scan(base, quads, rotation_masks, cartesian_rows_at(values, rows), thresh=thresh, out=pruned[first:])
     if n_new > n_out:
         if diversity == "rmsd":  # index 0, the starting structure, first
-            return np.array(most_diverse_conformers(n_out, pruned, method="rmsd", atoms=atoms))
+            return np.array(most_diverse_conformers(n_out, pruned, method="rmsd", atoms=atoms, symmetry=symmetry,
+                                                    prune_enantiomers=enant))
         return np.array(most_diverse_conformers(n_out, list(pruned), seed=seed))
     return pruned
 
@@ -331,7 +352,7 @@ def _log_torsions(logfunction, atoms, torsions, with_symbols):
 
 def clustered_csearch(atoms, coords, torsions, graph, charge=0, mult=1, constrained_indices=None, n=100, n_out=100,
                       title="test", logfunction=print, interactive_print=True, write_torsions=False, debug=False,
-                      seed=None, diversity="random"):
+                      seed=None, diversity="random", symmetry=None, prune_enantiomers=False):
     """``clustered_csearch`` with the reference's signature (firecode/torsion_module.py:726-742; called at :697-710 with
     ``Torsion`` objects from the perception step): one torsion group, its n-fold angle grid in ``cartesian_product``
     order scanned on the GPU with the clash test and the 5-degree back-off, the starting structure plus every conformer
@@ -340,7 +361,7 @@ def clustered_csearch(atoms, coords, torsions, graph, charge=0, mult=1, constrai
     ``n`` only acts between torsion groups and the reference forms one group, :749).  ``write_torsions`` (VMD files)
     is outside the hot path: not supported here.  ``seed`` (extra, keyword only in practice) fixes the final draw;
     ``diversity="rmsd"`` (extra) replaces the draw with the greedy max-min selection under the heavy-atom RMSD of
-    ``atoms`` (csearch mode 1)."""
+    ``atoms`` (csearch mode 1); ``symmetry=`` / ``prune_enantiomers=True`` go to that selection."""
     import time
 
     if write_torsions:
@@ -352,7 +373,7 @@ def clustered_csearch(atoms, coords, torsions, graph, charge=0, mult=1, constrai
         logfunction(f"\n--> Clustered CSearch on {title}\n    - {len(torsions)} torsions in 1 group - {[len(torsions)]}")
     rows, masks = _torsion_rows(torsions, graph)
     out = clustered_csearch_core(coords, rows, masks, n_out=n_out, seed=seed, logfunction=logfunction,
-                                 diversity=diversity, atoms=atoms)
+                                 diversity=diversity, atoms=atoms, symmetry=symmetry, prune_enantiomers=prune_enantiomers)
     if logfunction is not None:
         share = len(out) / np.prod([int(t.n_fold) for t in torsions], dtype=float)
         logfunction(f"  Selected the most diverse {len(out)} conformers, corresponding\n"

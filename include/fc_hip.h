@@ -161,6 +161,25 @@ int fc_ensemble_rmsd_values(fc_ensemble *ens, double *rmsd_out, double *ms_kerne
 int fc_ensemble_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd,
                                int64_t *indices_out, double *radii_out, int32_t *labels_out, double *dist_out,
                                int64_t *n_selected);
+/* The symmetry- and mirror-aware form: the same selection under
+ *
+ *   d_sym(i, j) = min over k < K, h in H of rmsd_and_max(X[i], h * X[j][perms[k]])[0]
+ *   H = {+1}, or {+1, -1} when mirror != 0      (-1: the partner inverted through the origin, as in the
+ *                                                enantiomer-aware forms below)
+ *
+ * X = the prepared ensemble (atom selection applied, centred); perms = a (K, A_sel) table exactly as in the
+ * symmetry-aware forms below: row 0 the identity, closed under inverse (which makes d_sym symmetric), K <= FC_PERM_MAX.
+ * The greedy loop, its tie rules, start, stop_rmsd, every output and the argument checks are those of
+ * fc_ensemble_select_diverse with d replaced by d_sym; the value is the explicit rotated-difference rmsd of the winning
+ * (k, h).  K = 1 with mirror = 0 is fc_ensemble_select_diverse itself, bit for bit.  Refused before the device is
+ * touched, the table first (it is checked before the handle is looked at) -- FC_E_LIMIT: K > FC_PERM_MAX; the
+ * representative (24 A_sel bytes) + the table as 16-bit indices (2 K A_sel bytes, rounded up to 8) + 64 bytes of the
+ * kernel's own exceed the 160 KiB of LDS (A_sel <= 5 849 at K = 2, <= 1 077 at K = 64; no HBM fallback).  FC_E_INVALID:
+ * the table checks of fc_prune_rmsd_perm, A_sel that is not the ensemble's, mirror outside {0, 1}; then the sibling's
+ * own checks.  Not offered: sharded, multi-GPU and twin-workspace forms. */
+int fc_ensemble_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
+                                    int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
+                                    double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected);
 /* a9: get_alignment_matrix(p, q) -- prism_pruner.rmsd; call site
  * hypermolecule_class.py:77.  M (3,3) row-major, applied as (M @ q.T).T */
 int fc_alignment_matrices(const double *p, const double *q, int64_t n_pairs, int64_t A,
@@ -293,7 +312,8 @@ int fc_clusters_from_bits(const uint64_t *bits, int64_t N, int32_t *labels_out, 
  * that is not the ensemble's, a row that is not a permutation of 0 .. A_sel-1, row 0 not the identity, a row whose
  * inverse is not in the table; then the sibling's own checks.  The table is checked before the handle is looked at.
  * Not offered: sharded and multi-GPU forms, fc_prune_rmsd_many, the one-call host form, twin workspaces,
- * fc_ensemble_select_diverse, fc_prune_rmsd_rot_corr, the MOI stage; no combination with the enantiomer-aware forms.
+ * fc_prune_rmsd_rot_corr, the MOI stage; no combination with the enantiomer-aware forms on the prune and the clusters
+ * (the diverse selection has a form that takes both: fc_ensemble_select_diverse_perm).
  *
  * fc_ensemble_rmsd_pairs_perm: all K values of each requested pair (any i, j), rmsd_out and maxdev_out (P, K)
  * row-major: element (p, k) = rmsd_and_max(X[pair_i[p]], X[pair_j[p]][perms[k]]).  Choosing among them is the caller's. */
@@ -784,6 +804,12 @@ int fc_bench_rmsd_and_max_all_sampled(fc_ensemble *ens, int64_t reps, const int6
 int fc_bench_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd, int64_t reps,
                             double *ms_device_mean, double *ms_host_mean, int64_t *indices_out, int64_t *n_selected,
                             int64_t *lanes_out);
+/* the same for fc_ensemble_select_diverse_perm.  stats (2 values, may be NULL), summed over the steps of the last
+ * selection: [0] = (k, h) of a (representative, conformer) pair whose eigenvalue was formed, [1] = those of them that
+ * reached the rotation and the explicit deviation pass. */
+int fc_bench_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
+                                 int64_t n_max, int64_t start, double stop_rmsd, int64_t reps, double *ms_device_mean,
+                                 double *ms_host_mean, int64_t *indices_out, int64_t *n_selected, int64_t *stats);
 /* (fc_bench_prune_rmsd writes EIGHT stats: [6] = 16 x 32-pair units the subset stage of the lean fp32
  * screen queued for the full test in the last prune, [7] = 1 when its sample found similarity dense
  * and the single-stage kernel did the launch) */
