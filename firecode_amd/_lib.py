@@ -86,6 +86,14 @@ _SIGNATURES = {
                               _p_i64, _p_i64, _p_i64],
     "fc_clusters_from_pairs": [_p_u64, _i64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_i64],
     "fc_clusters_from_bits": [_p_u64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_i64],
+    "fc_rmsd_dbscan": [_ens, _f64, _f64, _i64, _p_f64, _f64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_u8, C.POINTER(C.c_int32),
+                       _p_i64, _p_i64],
+    "fc_rmsd_dbscan_enant": [_ens, _f64, _f64, _i64, _p_f64, _f64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_u8,
+                             C.POINTER(C.c_int32), _p_i64, _p_i64],
+    "fc_rmsd_dbscan_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, _f64, _f64, _i64, _p_f64, _f64, C.POINTER(C.c_int32), _p_i64,
+                            _p_i64, _p_u8, C.POINTER(C.c_int32), _p_i64, _p_i64],
+    "fc_dbscan_from_pairs": [_p_u64, _i64, _i64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_u8, C.POINTER(C.c_int32), _p_i64],
+    "fc_dbscan_from_bits": [_p_u64, _i64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_u8, C.POINTER(C.c_int32), _p_i64],
     "fc_prune_rmsd_begin": [_ens, _f64, _f64, _p_f64, _f64, _i64, _i64, _i64, _p_i64],
     "fc_prune_level": [_ens, _i64, _p_u8, _p_u8],
     "fc_prune_similar_pairs": [_ens, _p_u64, _i64, _p_i64],
@@ -406,6 +414,16 @@ def check_flag(name, value):
     return bool(value)
 
 
+def check_min_samples(value):
+    """``min_samples`` of the density-based clusters: a real integer >= 1, checked before any device use -- ``True`` or
+    ``2.5`` would otherwise be truncated into a different density."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or int(value) < 1:
+        raise FirecodeHipInputError(FC_E_INVALID, f"min_samples must be an integer >= 1, got {value!r}")
+    if int(value) >= 2 ** 63:
+        raise FirecodeHipInputError(FC_E_INVALID, f"min_samples={value!r} does not fit 64 bits")
+    return int(value)
+
+
 class DeviceEnsemble:
     """HBM-resident prepared ensemble (fc_ensemble)."""
 
@@ -635,6 +653,31 @@ class DeviceEnsemble:
         call("fc_rmsd_clusters_enant" if enant else "fc_rmsd_clusters", self.handle, float(max_rmsd), float(max_dev), pf(en),
              float(max_dE), ptr(labels, C.c_int32), pi(reps), pi(sizes), C.byref(k), pi(stats))
         return labels, reps[:k.value].copy(), sizes[:k.value].copy(), stats
+
+    def dbscan(self, max_rmsd, max_dev, min_samples, energies=None, max_dE=0.0, prune_enantiomers=False, symmetry=None):
+        """Density-based clusters of the prune's similarity graph (fc_rmsd_dbscan; ``prune_enantiomers=True``:
+        fc_rmsd_dbscan_enant; ``symmetry=`` a (K, A_all) table: fc_rmsd_dbscan_perm; the contract is in include/fc_hip.h)
+        -> ``(labels (N,) int32 with -1 for noise, reps (K,) int64, sizes (K,) int64, core (N,) bool, degrees (N,) int32,
+        stats)`` in processing order.  A conformer is core when it has at least ``min_samples - 1`` neighbours; clusters
+        are the components of the core points, numbered by ascending smallest core member, their representative; a
+        point that is not core joins the cluster of its smallest-index core neighbour, or is noise.  stats: as
+        ``clusters``, then the numbers of core and of noise points."""
+        enant = check_flag("prune_enantiomers", prune_enantiomers)
+        m = check_min_samples(min_samples)
+        perm = None if symmetry is None else self._perm_args(symmetry, "prune_enantiomers", enant)
+        labels, degrees = np.zeros(self.N, dtype=np.int32), np.zeros(self.N, dtype=np.int32)
+        reps, sizes = np.zeros(self.N, dtype=np.int64), np.zeros(self.N, dtype=np.int64)
+        core = np.zeros(self.N, dtype=np.uint8)
+        stats = np.zeros(8, dtype=np.int64)
+        k = C.c_int64(0)
+        en = None if energies is None else f64(energies)
+        outs = (ptr(labels, C.c_int32), pi(reps), pi(sizes), pb(core), ptr(degrees, C.c_int32), C.byref(k), pi(stats))
+        if perm is not None:
+            call("fc_rmsd_dbscan_perm", self.handle, *perm[1], float(max_rmsd), float(max_dev), m, pf(en), float(max_dE), *outs)
+        else:
+            call("fc_rmsd_dbscan_enant" if enant else "fc_rmsd_dbscan", self.handle, float(max_rmsd), float(max_dev), m, pf(en),
+                 float(max_dE), *outs)
+        return labels, reps[:k.value].copy(), sizes[:k.value].copy(), core.astype(bool), degrees, stats
 
     def prune_begin(self, max_rmsd, max_dev, rank, world, row_block=128, energies=None, max_dE=0.0):
         stats = np.zeros(6, dtype=np.int64)

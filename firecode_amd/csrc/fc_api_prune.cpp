@@ -1459,6 +1459,215 @@ int fc_clusters_from_bits(const uint64_t *bits, int64_t N, int32_t *labels_out, 
   return clusters_from_graph(nullptr, 0, bits, N, labels_out, reps_out, sizes_out, n_clusters);
 }
 
+// ---- density-based clusters (the contract: include/fc_hip.h; the kernels: fc_clusters.hip, k_db_*) ---------------------
+namespace {
+struct DbscanOut {
+  int32_t *labels;
+  int64_t *reps, *sizes;
+  uint8_t *core;
+  int32_t *degrees;
+  int64_t *n_clusters;
+  bool complete() const { return labels && reps && sizes && core && degrees; }
+};
+
+// clusters_run for the density-based form: enqueue, ONE copy chain into pinned memory, one wait
+int dbscan_run(const ClusterGraph &g, int64_t N, int64_t min_samples, DevBuf &work, const void *counters_dev,
+               ClusterResult *out) {
+  const ClusterLayout L = dbscan_layout(N);
+  FC_TRY(work.reserve(L.total));
+  FC_TRY(pinned_reserve(L.parent + 16 * sizeof(uint64_t)));
+  FC_TRY(launch_dbscan(g, N, min_samples, work));
+  char *host = static_cast<char *>(ctx().pinned);
+  FC_TRY(d2h(host, work.p, L.result_bytes));
+  if (counters_dev) FC_TRY(d2h(host + L.parent, counters_dev, 16 * sizeof(uint64_t)));
+  FC_TRY(sync());
+  out->host = host, out->L = L;
+  if (out->status()[kClStatusErr] != 0ull)
+    return set_error(FC_E_INTERNAL, "density-based clusters: a union exceeded its retry bound on the device");
+  return FC_OK;
+}
+
+// -> the caller's arrays; tail (may be NULL): [0] core points, [1] noise points
+void dbscan_unpack(const ClusterResult &r, int64_t N, const DbscanOut &o, int64_t *tail) {
+  const int64_t K = (int64_t)r.status()[kClStatusK];
+  std::memcpy(o.labels, r.host + r.L.labels, (size_t)N * sizeof(int32_t));
+  std::memcpy(o.reps, r.host + r.L.reps, (size_t)K * sizeof(int64_t));
+  std::memcpy(o.sizes, r.host + r.L.sizes, (size_t)K * sizeof(int64_t));
+  std::memcpy(o.core, r.host + r.L.core, (size_t)N * sizeof(uint8_t));
+  std::memcpy(o.degrees, r.host + r.L.degrees, (size_t)N * sizeof(int32_t));
+  *o.n_clusters = K;
+  if (tail == nullptr) return;
+  tail[0] = tail[1] = 0;
+  for (int64_t i = 0; i < N; ++i) tail[0] += o.core[i] != 0, tail[1] += o.labels[i] < 0;
+}
+
+// the body of fc_rmsd_dbscan behind its argument checks, as rmsd_clusters_run (the caller drains on error)
+int rmsd_dbscan_run(fc_ensemble *ens, double max_rmsd, double max_dev, int64_t min_samples, const double *energies,
+                    double max_dE, DevBuf &work, const DbscanOut &o, int64_t *stats) {
+  const int64_t N = ens->N;
+  FC_TRY(ensemble_shard(ens, 0, 1, default_row_block()));
+  auto *cnt = reinterpret_cast<unsigned long long *>(ens->counters.p);
+  FC_TRY(simbits_local(ens, max_rmsd, max_dev, energies, max_dE, true, /*lean=*/true));
+  ClusterGraph g;
+  g.pairs_dev = ens->simq.as<uint64_t>(), g.n_pairs_dev = cnt + 2;
+  g.n_cand_dev = cnt + 6, g.cand_cap = (unsigned long long)ens->pairq_cap, g.redo_dev = cnt + 12;
+  g.known_short = ens->last_similar >= 0 && ens->last_similar < kClShortList;
+  ClusterResult res;
+  FC_TRY(dbscan_run(g, N, min_samples, work, cnt, &res));
+  int64_t from_bits = 0;
+  if (res.status()[kClStatusList] == 0ull) {  // the degree pass declined the list: the bit matrix
+    FC_TRY(simbits_local(ens, max_rmsd, max_dev, energies, max_dE, true, /*lean=*/false));
+    ClusterGraph gb;
+    gb.bits_dev = ens->bits.as<uint64_t>(), gb.W = ens->W;
+    FC_TRY(dbscan_run(gb, N, min_samples, work, cnt, &res));
+    from_bits = 1;
+  }
+  const unsigned long long *c = res.extra();
+  note_candidates(ens, c[6], c[2]);
+  dbscan_unpack(res, N, o, stats ? stats + 6 : nullptr);
+  if (stats) fill_stats(stats, N * (N - 1) / 2, c, from_bits, *o.n_clusters);
+  return FC_OK;
+}
+
+int rmsd_dbscan_perm_run(fc_ensemble *ens, const std::vector<uint16_t> &table, int64_t K, DevBuf &dperm, DevBuf &work,
+                         double max_rmsd, double max_dev, int64_t min_samples, const double *energies, double max_dE,
+                         const DbscanOut &o, int64_t *stats) {
+  const int64_t N = ens->N;
+  FC_TRY(symm_local(ens, table, K, dperm, max_rmsd, max_dev, energies, max_dE));
+  auto *cnt = reinterpret_cast<unsigned long long *>(ens->counters.p);
+  ClusterGraph g;
+  g.pairs_dev = ens->simq.as<uint64_t>(), g.n_pairs_dev = cnt + 2;
+  g.n_cand_dev = cnt + 6, g.cand_cap = (unsigned long long)ens->pairq_cap, g.redo_dev = cnt + 12;
+  ClusterResult res;
+  FC_TRY(dbscan_run(g, N, min_samples, work, cnt, &res));
+  int64_t from_bits = 0;
+  if (res.status()[kClStatusList] == 0ull) {  // the queue overflowed: the matrix of the same launch
+    ClusterGraph gb;
+    gb.bits_dev = ens->bits.as<uint64_t>(), gb.W = ens->W;
+    FC_TRY(dbscan_run(gb, N, min_samples, work, cnt, &res));
+    from_bits = 1;
+  }
+  dbscan_unpack(res, N, o, stats ? stats + 6 : nullptr);
+  if (stats) fill_stats(stats, N * (N - 1) / 2, res.extra(), from_bits, *o.n_clusters);
+  return FC_OK;
+}
+
+// a caller's graph: one upload, the same labelling (the index checks are the entry points')
+int dbscan_from_graph(const uint64_t *pairs, int64_t n_pairs, const uint64_t *bits, int64_t N, int64_t min_samples,
+                      const DbscanOut &o) {
+  FC_TRY(ensure_init());
+  DevBuf graph, work;
+  ClusterGraph g;
+  ClusterResult res;
+  int rc = FC_OK;
+  if (bits != nullptr) {
+    const int64_t W = ceil_div(N, 64);
+    rc = upload(graph, bits, (size_t)N * (size_t)W);
+    g.bits_dev = graph.as<uint64_t>(), g.W = W;
+  } else {
+    rc = upload(graph, pairs, (size_t)n_pairs);  // (n_pairs == 0: an 8-byte block that is never read)
+    g.pairs_dev = graph.as<uint64_t>(), g.n_pairs_host = (unsigned long long)n_pairs;
+    g.known_short = n_pairs < kClShortList;
+  }
+  if (rc == FC_OK) rc = dbscan_run(g, N, min_samples, work, nullptr, &res);
+  if (rc != FC_OK) {
+    (void)hipStreamSynchronize(cur_stream());  // nothing of `graph` / `work` may be in flight when they go out of scope
+    return rc;
+  }
+  dbscan_unpack(res, N, o, nullptr);
+  return FC_OK;
+}
+}  // namespace
+
+int fc_rmsd_dbscan(fc_ensemble *ens, double max_rmsd, double max_dev, int64_t min_samples, const double *energies,
+                   double max_dE, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, uint8_t *core_out,
+                   int32_t *degrees_out, int64_t *n_clusters, int64_t *stats) {
+  FC_API_LOCK;
+  FC_REQUIRE(ens && n_clusters, "NULL pointer argument");
+  FC_REQUIRE(max_rmsd > 0.0 && max_dev > 0.0, "thresholds must be positive");
+  FC_REQUIRE(min_samples >= 1, "min_samples=%lld must be >= 1", (long long)min_samples);
+  *n_clusters = 0;
+  if (stats) std::memset(stats, 0, 8 * sizeof(int64_t));
+  FC_TRY(ensure_init());
+  if (ens->N == 0) return FC_OK;
+  const DbscanOut o{labels_out, reps_out, sizes_out, core_out, degrees_out, n_clusters};
+  FC_REQUIRE(o.complete(), "NULL pointer argument");
+  FC_REQUIRE(ens->N <= (int64_t)INT32_MAX - 256, "N=%lld: clusters index conformers with 32 bits", (long long)ens->N);
+  DevBuf work;
+  const int rc = rmsd_dbscan_run(ens, max_rmsd, max_dev, min_samples, energies, max_dE, work, o, stats);
+  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());  // nothing of `work` may be in flight when it goes out of scope
+  return rc;
+}
+
+int fc_rmsd_dbscan_enant(fc_ensemble *ens, double max_rmsd, double max_dev, int64_t min_samples, const double *energies,
+                         double max_dE, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, uint8_t *core_out,
+                         int32_t *degrees_out, int64_t *n_clusters, int64_t *stats) {
+  FC_API_LOCK;
+  FC_REQUIRE(ens && n_clusters, "NULL pointer argument");
+  EnantScope scope(ens);
+  return fc_rmsd_dbscan(ens, max_rmsd, max_dev, min_samples, energies, max_dE, labels_out, reps_out, sizes_out, core_out,
+                        degrees_out, n_clusters, stats);
+}
+
+int fc_rmsd_dbscan_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
+                        int64_t min_samples, const double *energies, double max_dE, int32_t *labels_out, int64_t *reps_out,
+                        int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out, int64_t *n_clusters, int64_t *stats) {
+  FC_API_LOCK;
+  std::vector<uint16_t> table;
+  FC_TRY(perm_table_check(perms, K, A_sel, table));
+  FC_TRY(perm_ensemble_check(ens, K, A_sel, true));
+  FC_REQUIRE(n_clusters != nullptr, "NULL pointer argument");
+  FC_REQUIRE(max_rmsd > 0.0 && max_dev > 0.0, "thresholds must be positive");
+  FC_REQUIRE(min_samples >= 1, "min_samples=%lld must be >= 1", (long long)min_samples);
+  *n_clusters = 0;
+  if (stats) std::memset(stats, 0, 8 * sizeof(int64_t));
+  if (ens->N > (int64_t)INT32_MAX - 256)
+    return set_error(FC_E_LIMIT, "N=%lld: clusters index conformers with 32 bits", (long long)ens->N);
+  FC_TRY(ensure_init());
+  if (ens->N == 0) return FC_OK;
+  const DbscanOut o{labels_out, reps_out, sizes_out, core_out, degrees_out, n_clusters};
+  FC_REQUIRE(o.complete(), "NULL pointer argument");
+  DevBuf dperm, work;
+  const int rc = rmsd_dbscan_perm_run(ens, table, K, dperm, work, max_rmsd, max_dev, min_samples, energies, max_dE, o, stats);
+  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());
+  return rc;
+}
+
+int fc_dbscan_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int64_t min_samples, int32_t *labels_out,
+                         int64_t *reps_out, int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out,
+                         int64_t *n_clusters) {
+  FC_API_LOCK;
+  FC_REQUIRE(n_clusters != nullptr, "n_clusters is NULL");
+  FC_REQUIRE(N >= 0 && n_pairs >= 0, "bad arguments N=%lld n_pairs=%lld", (long long)N, (long long)n_pairs);
+  FC_REQUIRE(min_samples >= 1, "min_samples=%lld must be >= 1", (long long)min_samples);
+  FC_REQUIRE(N <= (int64_t)INT32_MAX - 256, "N=%lld: clusters index conformers with 32 bits", (long long)N);
+  FC_REQUIRE(pairs != nullptr || n_pairs == 0, "pairs is NULL");
+  for (int64_t p = 0; p < n_pairs; ++p) {
+    const uint64_t i = pairs[p] >> 32, j = pairs[p] & 0xffffffffull;
+    FC_REQUIRE(i != j && i < (uint64_t)N && j < (uint64_t)N, "pair %lld = (%llu, %llu): i == j or an index outside [0, %lld)",
+               (long long)p, (unsigned long long)i, (unsigned long long)j, (long long)N);
+  }
+  *n_clusters = 0;
+  if (N == 0) return FC_OK;
+  const DbscanOut o{labels_out, reps_out, sizes_out, core_out, degrees_out, n_clusters};
+  FC_REQUIRE(o.complete(), "NULL pointer argument");
+  return dbscan_from_graph(pairs, n_pairs, nullptr, N, min_samples, o);
+}
+
+int fc_dbscan_from_bits(const uint64_t *bits, int64_t N, int64_t min_samples, int32_t *labels_out, int64_t *reps_out,
+                        int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out, int64_t *n_clusters) {
+  FC_API_LOCK;
+  FC_REQUIRE(n_clusters != nullptr, "n_clusters is NULL");
+  FC_REQUIRE(N >= 0, "N=%lld < 0", (long long)N);
+  FC_REQUIRE(min_samples >= 1, "min_samples=%lld must be >= 1", (long long)min_samples);
+  FC_REQUIRE(N <= (int64_t)INT32_MAX - 256, "N=%lld: clusters index conformers with 32 bits", (long long)N);
+  *n_clusters = 0;
+  if (N == 0) return FC_OK;
+  const DbscanOut o{labels_out, reps_out, sizes_out, core_out, degrees_out, n_clusters};
+  FC_REQUIRE(bits != nullptr && o.complete(), "NULL pointer argument");
+  return dbscan_from_graph(nullptr, 0, bits, N, min_samples, o);
+}
+
 int fc_prune_rmsd_begin(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies,
                         double max_dE, int64_t rank, int64_t world, int64_t row_block,
                         int64_t *stats) {

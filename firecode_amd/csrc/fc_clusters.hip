@@ -340,6 +340,327 @@ int launch_clusters(const ClusterGraph &g, int64_t N, DevBuf &work) {
   return check_launch("k_cl_label");
 }
 
+// ---- density-based clusters (include/fc_hip.h, "density-based clusters") ---------------------------
+// The same union-find restricted to the CORE vertices (degree + 1 >= min_samples): only core-core edges unite, an edge
+// with exactly one core end leaves that end in attach[the other] (the smallest one wins), and the labelling counts a root
+// only when it is core.  The kernels of the components above are not touched: every step that differs has a kernel of
+// its own here (k_db_*), the steps that do not (k_cl_init, k_cl_compress, k_cl_scan) are shared.
+// Launches: init -> degrees -> hook (the phases of the components; borders attached by the launch that sees every
+// entry) -> flatten + core flags -> scan -> label.  deg[] is complete when its launch has ended and attach[] is only
+// written (an agent-scope atomic that returns nothing) inside the hook launches: plain loads of both are enough
+// behind the kernel boundary.  parent[] inside the hook launches: as above, agent-scope atomics only.
+namespace {
+
+constexpr uint32_t kDbNone = 0xffffffffu;  // attach[i]: no core neighbour seen (hipMemsetAsync 0xff)
+
+__device__ __forceinline__ bool db_core(const int32_t *__restrict__ deg, uint32_t i, int64_t min_samples) {
+  return (int64_t)deg[i] + 1 >= min_samples;
+}
+
+// deg[dest] += 1 for every lane that is `on`, equal destinations of the wavefront added once: up to four distinct ones
+// through a ballot each (a hub, or the run of one row in the refine's list), the rest one by one.  The caller keeps
+// the wavefront converged.  Integer adds that return nothing: the order does not show.
+__device__ __forceinline__ void db_count(int32_t *deg, bool on, uint32_t dest, int lane) {
+  bool pending = on;
+  for (int round = 0; round < 4; ++round) {
+    const uint64_t mp = __ballot(pending);
+    if (mp == 0) return;  // wave-uniform
+    const int leader = __ffsll((unsigned long long)mp) - 1;
+    const uint32_t ld = __shfl(dest, leader);
+    const bool same = pending && dest == ld;
+    const uint64_t ms = __ballot(same);
+    if (lane == leader) (void)__hip_atomic_fetch_add(deg + ld, (int32_t)__popcll(ms), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    pending = pending && !same;
+  }
+  if (pending) (void)__hip_atomic_fetch_add(deg + dest, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the conditions on which k_cl_hook_pairs declines the refine's list, word for word
+__device__ __forceinline__ bool db_declined(unsigned long long P, const unsigned long long *__restrict__ n_cand_ptr,
+                                            unsigned long long cand_cap, const unsigned long long *__restrict__ redo_ptr) {
+  return (n_cand_ptr != nullptr && (*n_cand_ptr > cand_cap || P > cand_cap)) || (redo_ptr != nullptr && *redo_ptr != 0ull);
+}
+
+// Degrees from the pair list: every entry adds 1 to both of its ends (so an unordered pair must be listed once).  The
+// length is the device's word; a declined list counts nothing and clears status[kClStatusList].  deg[] zeroed by the launcher.
+__global__ void __launch_bounds__(kClThreads)
+k_db_degree_pairs(const uint64_t *__restrict__ pairs, const unsigned long long *__restrict__ n_pairs_ptr,
+                  const unsigned long long *__restrict__ n_cand_ptr, unsigned long long cand_cap,
+                  const unsigned long long *__restrict__ redo_ptr, int64_t N, int32_t *deg, unsigned long long *status) {
+  const unsigned long long P = *n_pairs_ptr;
+  if (db_declined(P, n_cand_ptr, cand_cap, redo_ptr)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) status[kClStatusList] = 0ull;
+    return;
+  }
+  const uint32_t n32 = (uint32_t)N;
+  const int lane = threadIdx.x & 63;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  // (the bound is the wavefront's first entry: all 64 lanes stay in the loop together)
+  for (unsigned long long p0 = (unsigned long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); p0 < P; p0 += stride) {
+    const unsigned long long p = p0 + (unsigned)lane;
+    uint32_t i = 0, j = 0;
+    bool on = p < P;
+    if (on) {
+      const uint64_t e = pairs[p];
+      i = (uint32_t)(e >> 32), j = (uint32_t)(e & 0xffffffffull);
+      on = i != j && i < n32 && j < n32;
+    }
+    db_count(deg, on, i, lane);
+    db_count(deg, on, j, lane);
+  }
+}
+
+// Degrees from the bit matrix, no atomics: workgroup c owns the 64 conformers of word column c.
+//   column part  the four wavefronts share the rows above the diagonal; all lanes read the same word (row i, word c)
+//                and lane l counts bit l, for i < 64 c + l only, in a register;
+//   row part     each wavefront takes 16 of the 64 rows: the popcount of the row's words from the diagonal word
+//                rightwards, masked as k_cl_hook_bits masks it and cut at N.
+// Each part reads the upper triangle once; the sum is exact and has no order.
+__global__ void __launch_bounds__(kClThreads)
+k_db_degree_bits(const uint64_t *__restrict__ bits, int64_t W, int64_t N, int32_t *__restrict__ deg) {
+  __shared__ int s_col[kClThreads / 64][64];
+  __shared__ int s_row[64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t c = blockIdx.x, Wn = (N + 63) >> 6;
+  const int64_t j = c * 64 + lane;
+  const int64_t rows = N < c * 64 + 64 ? N : c * 64 + 64;
+  int cnt = 0;
+#pragma unroll 8
+  for (int64_t i = wave; i < rows; i += kClThreads / 64) {
+    const uint64_t word = bits[i * W + c];
+    cnt += (int)((word >> lane) & 1ull) & (int)(i < j);
+  }
+  s_col[wave][lane] = cnt;
+  for (int r = 0; r < 16; ++r) {
+    const int64_t i = c * 64 + wave * 16 + r;  // (wave-uniform)
+    int rc = 0;
+    if (i < N) {
+      for (int64_t w = c + lane; w < Wn; w += 64) {
+        uint64_t word = bits[i * W + w];
+        if (w == c) word &= (i & 63) == 63 ? 0ull : ~0ull << ((i & 63) + 1);
+        if (w == Wn - 1 && (N & 63) != 0) word &= (1ull << (N & 63)) - 1ull;
+        rc += __popcll(word);
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) rc += __shfl_xor(rc, o);
+    if (lane == 0) s_row[wave * 16 + r] = rc;
+  }
+  __syncthreads();
+  if (tid < 64 && j < N) deg[j] = s_col[0][tid] + s_col[1][tid] + s_col[2][tid] + s_col[3][tid] + s_row[tid];
+}
+
+// one edge under the core rule.  unite: the hooking rule for a core-core edge (seed: its seed); attach: an edge with
+// exactly one core end offers that end to the other
+__device__ __forceinline__ void db_edge(uint32_t i, uint32_t j, const int32_t *__restrict__ deg, int64_t min_samples,
+                                        int32_t *parent, uint32_t *attach, bool seed, bool unite, bool do_attach,
+                                        int64_t retry_cap, unsigned long long *status) {
+  const bool ci = db_core(deg, i, min_samples), cj = db_core(deg, j, min_samples);
+  if (ci && cj) {
+    if (!unite) return;
+    if (seed)
+      cl_seed(parent, (int32_t)(i > j ? i : j), (int32_t)(i > j ? j : i));
+    else
+      cl_unite(parent, (int32_t)i, (int32_t)j, retry_cap, status);
+  } else if (do_attach && (ci || cj)) {
+    (void)__hip_atomic_fetch_min(attach + (ci ? j : i), ci ? i : j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// k_cl_hook_pairs under the core rule: the same phases, the same split decided from the device's length, the same
+// retry cap and error word.  Borders are attached by the one launch that visits every entry: the seed launch of a split
+// list, the last launch of a list that is not split.
+__global__ void __launch_bounds__(kClThreads)
+k_db_hook_pairs(const uint64_t *__restrict__ pairs, const unsigned long long *__restrict__ n_pairs_ptr,
+                const unsigned long long *__restrict__ n_cand_ptr, unsigned long long cand_cap,
+                const unsigned long long *__restrict__ redo_ptr, int64_t N, const int32_t *__restrict__ deg,
+                int64_t min_samples, int32_t *parent, uint32_t *attach, unsigned long long *status, bool seed, unsigned c_lo,
+                unsigned c_hi, unsigned long long split_min) {
+  const unsigned long long P = *n_pairs_ptr;
+  if (db_declined(P, n_cand_ptr, cand_cap, redo_ptr)) return;  // (k_db_degree_pairs has said so in status[])
+  const bool split = P >= split_min;
+  const bool last = !seed && c_hi == kClClasses;
+  if (!last && !split) return;
+  const bool do_attach = seed ? split : !split;
+  const uint32_t n32 = (uint32_t)N;
+  const int64_t retry_cap = 4 * N + 1024;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  for (unsigned long long p = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += stride) {
+    const bool mine = seed || !split || (cl_class(p) >= c_lo && cl_class(p) < c_hi);
+    if (!mine && !do_attach) continue;
+    const uint64_t e = pairs[p];
+    const uint32_t i = (uint32_t)(e >> 32), j = (uint32_t)(e & 0xffffffffull);
+    if (i == j || i >= n32 || j >= n32) continue;
+    db_edge(i, j, deg, min_samples, parent, attach, seed, mine, do_attach, retry_cap, status);
+  }
+}
+
+// k_cl_hook_bits under the core rule.  The seed launch walks every set bit (the borders are attached there) and seeds
+// each core row with its first core neighbour of the word.
+__global__ void __launch_bounds__(kClThreads)
+k_db_hook_bits(const uint64_t *__restrict__ bits, int64_t W, int64_t N, const int32_t *__restrict__ deg, int64_t min_samples,
+               int32_t *parent, uint32_t *attach, unsigned long long *status, bool seed, bool do_attach, unsigned c_lo,
+               unsigned c_hi) {
+  const int64_t total = N * W;
+  const int64_t retry_cap = 4 * N + 1024;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t i = t / W, w = t - i * W;
+    if (w < (i >> 6)) continue;
+    if (!seed && (cl_class((unsigned long long)t) < c_lo || cl_class((unsigned long long)t) >= c_hi)) continue;
+    uint64_t word = bits[t];
+    if (w == (i >> 6)) word &= (i & 63) == 63 ? 0ull : ~0ull << ((i & 63) + 1);
+    bool seeded = false;
+    while (word) {
+      const int b = __ffsll((unsigned long long)word) - 1;
+      word &= word - 1;
+      const int64_t j = w * 64 + b;
+      if (j >= N) break;  // (ascending: nothing behind it is a conformer)
+      const bool both = db_core(deg, (uint32_t)i, min_samples) && db_core(deg, (uint32_t)j, min_samples);
+      db_edge((uint32_t)i, (uint32_t)j, deg, min_samples, parent, attach, seed, !(seed && seeded), do_attach, retry_cap, status);
+      seeded = seeded || both;
+    }
+  }
+}
+
+// k_cl_flatten under the core rule: a vertex that is not core was never hooked and is its own root, so a root is
+// flagged only when it is core.  The core flags travel to the host from here.
+__global__ void __launch_bounds__(kClThreads)
+k_db_flatten(const int32_t *__restrict__ parent, int64_t N, const int32_t *__restrict__ deg, int64_t min_samples,
+             int32_t *__restrict__ root, uint64_t *__restrict__ flags, int64_t W, uint8_t *__restrict__ core) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool is_root = false;
+  if (i < N) {
+    int32_t x = (int32_t)i;
+    for (int32_t p = parent[x]; p != x; p = parent[x]) x = p;
+    root[i] = x;
+    const bool c = db_core(deg, (uint32_t)i, min_samples);
+    core[i] = c ? 1 : 0;
+    is_root = c && x == (int32_t)i;
+  }
+  const uint64_t m = __ballot(is_root);
+  if ((threadIdx.x & 63) == 0 && (i >> 6) < W) flags[i >> 6] = m;
+}
+
+// k_cl_label with noise: a core vertex takes the rank of its root, a border vertex that of the root of attach[i] (a
+// core vertex: its root is a flagged one), everything else -1.  sizes count both kinds, aggregated as in k_cl_label.
+__global__ void __launch_bounds__(kClThreads)
+k_db_label(const int32_t *__restrict__ root, int64_t N, const uint8_t *__restrict__ core, const uint32_t *__restrict__ attach,
+           const uint64_t *__restrict__ flags, const int32_t *__restrict__ prefix, int32_t *__restrict__ labels,
+           int64_t *__restrict__ reps, unsigned long long *__restrict__ sizes) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  bool pending = false;
+  int32_t rank = -1;
+  if (i < N) {
+    int32_t r = -1;
+    if (core[i])
+      r = root[i];
+    else if (attach[i] != kDbNone)
+      r = root[attach[i]];
+    if (r >= 0) {
+      rank = prefix[r >> 6] + __popcll(flags[r >> 6] & ((1ull << (r & 63)) - 1ull));
+      if ((int64_t)r == i) reps[rank] = i;
+      pending = true;
+    }
+    labels[i] = rank;
+  }
+  for (int round = 0; round < 4; ++round) {
+    const uint64_t mp = __ballot(pending);
+    if (mp == 0) break;  // wave-uniform
+    const int leader = __ffsll((unsigned long long)mp) - 1;
+    const int32_t lr = __shfl(rank, leader);
+    const bool same = pending && rank == lr;
+    const uint64_t ms = __ballot(same);
+    if (lane == leader) atomicAdd(&sizes[lr], (unsigned long long)__popcll(ms));
+    pending = pending && !same;
+  }
+  if (pending) atomicAdd(&sizes[rank], 1ull);
+}
+
+}  // namespace
+
+// launch_clusters under the core rule; `work` holds dbscan_layout(N).total bytes
+int launch_dbscan(const ClusterGraph &g, int64_t N, int64_t min_samples, DevBuf &work) {
+  const ClusterLayout L = dbscan_layout(N);
+  if (work.p == nullptr || work.bytes < L.total) return set_error(FC_E_INVALID, "cluster workspace too small");
+  if (N < 1 || N > (int64_t)INT32_MAX - 256) return set_error(FC_E_LIMIT, "N=%lld: clusters index conformers with 32 bits", (long long)N);
+  if (min_samples < 1) return set_error(FC_E_INVALID, "min_samples=%lld < 1", (long long)min_samples);
+  if ((g.pairs_dev != nullptr) == (g.bits_dev != nullptr)) return set_error(FC_E_INVALID, "one of pair list / bit matrix");
+  char *base = static_cast<char *>(work.p);
+  auto *labels = reinterpret_cast<int32_t *>(base + L.labels);
+  auto *reps = reinterpret_cast<int64_t *>(base + L.reps);
+  auto *sizes = reinterpret_cast<unsigned long long *>(base + L.sizes);
+  auto *core = reinterpret_cast<uint8_t *>(base + L.core);
+  auto *deg = reinterpret_cast<int32_t *>(base + L.degrees);
+  auto *status = reinterpret_cast<unsigned long long *>(base + L.status);
+  auto *parent = reinterpret_cast<int32_t *>(base + L.parent);
+  auto *root = reinterpret_cast<int32_t *>(base + L.root);
+  auto *flags = reinterpret_cast<uint64_t *>(base + L.flags);
+  auto *prefix = reinterpret_cast<int32_t *>(base + L.prefix);
+  auto *attach = reinterpret_cast<uint32_t *>(base + L.attach);
+  const int64_t W = ceil_div(N, 64);
+  hipStream_t st = cur_stream();
+  const unsigned per_n = (unsigned)ceil_div(N, kClThreads);
+  FC_HIP_TRY(hipMemsetAsync(sizes, 0, (size_t)N * sizeof(unsigned long long), st));
+  FC_HIP_TRY(hipMemsetAsync(deg, 0, (size_t)N * sizeof(int32_t), st));
+  FC_HIP_TRY(hipMemsetAsync(attach, 0xff, (size_t)N * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_cl_init, dim3(per_n), dim3(kClThreads), 0, st, parent, N, status, g.n_pairs_host);
+  FC_TRY(check_launch("k_cl_init"));
+  const auto compress = [&]() {
+    hipLaunchKernelGGL(k_cl_compress, dim3(per_n), dim3(kClThreads), 0, st, parent, N);
+    return check_launch("k_cl_compress");
+  };
+  if (g.pairs_dev != nullptr) {
+    const unsigned long long *n_pairs_dev = g.n_pairs_dev != nullptr ? g.n_pairs_dev : status + kClStatusPairs;
+    const dim3 grid((unsigned)(ctx().n_cu * 8));
+    const unsigned long long split_min = g.known_short ? kClNeverSplit : kClSplitMin;
+    hipLaunchKernelGGL(k_db_degree_pairs, grid, dim3(kClThreads), 0, st, g.pairs_dev, n_pairs_dev, g.n_cand_dev, g.cand_cap,
+                       g.redo_dev, N, deg, status);
+    FC_TRY(check_launch("k_db_degree_pairs"));
+    const auto hook = [&](bool seed, unsigned c_lo, unsigned c_hi) {
+      hipLaunchKernelGGL(k_db_hook_pairs, grid, dim3(kClThreads), 0, st, g.pairs_dev, n_pairs_dev, g.n_cand_dev, g.cand_cap,
+                         g.redo_dev, N, deg, min_samples, parent, attach, status, seed, c_lo, c_hi, split_min);
+      return check_launch("k_db_hook_pairs");
+    };
+    if (!g.known_short) {
+      FC_TRY(hook(true, 0, 0));
+      FC_TRY(compress());
+      FC_TRY(hook(false, 0, kClCoarse));
+      FC_TRY(compress());
+      FC_TRY(hook(false, kClCoarse, kClFine));
+      FC_TRY(compress());
+    }
+    FC_TRY(hook(false, kClFine, kClClasses));  // (all of a list that is not split)
+  } else {
+    if (g.W < W) return set_error(FC_E_INVALID, "bit rows of %lld words, %lld needed", (long long)g.W, (long long)W);
+    hipLaunchKernelGGL(k_db_degree_bits, dim3((unsigned)W), dim3(kClThreads), 0, st, g.bits_dev, g.W, N, deg);
+    FC_TRY(check_launch("k_db_degree_bits"));
+    const dim3 grid((unsigned)cl_blocks(N * g.W, 16));
+    const bool split = (unsigned long long)N * (unsigned long long)g.W >= 1024ull;
+    const auto hook = [&](bool seed, unsigned c_lo, unsigned c_hi) {
+      hipLaunchKernelGGL(k_db_hook_bits, grid, dim3(kClThreads), 0, st, g.bits_dev, g.W, N, deg, min_samples, parent, attach,
+                         status, seed, /*do_attach=*/seed || !split, c_lo, c_hi);
+      return check_launch("k_db_hook_bits");
+    };
+    if (split) {
+      FC_TRY(hook(true, 0, 0));
+      FC_TRY(compress());
+      FC_TRY(hook(false, 0, kClCoarse));
+      FC_TRY(compress());
+      FC_TRY(hook(false, kClCoarse, kClFine));
+      FC_TRY(compress());
+    }
+    FC_TRY(hook(false, split ? kClFine : 0u, kClClasses));
+  }
+  hipLaunchKernelGGL(k_db_flatten, dim3(per_n), dim3(kClThreads), 0, st, parent, N, deg, min_samples, root, flags, W, core);
+  FC_TRY(check_launch("k_db_flatten"));
+  hipLaunchKernelGGL(k_cl_scan, dim3(1), dim3(1024), 0, st, flags, W, prefix, status);
+  FC_TRY(check_launch("k_cl_scan"));
+  hipLaunchKernelGGL(k_db_label, dim3(per_n), dim3(kClThreads), 0, st, root, N, core, attach, flags, prefix, labels, reps, sizes);
+  return check_launch("k_db_label");
+}
+
 __global__ void k_warm_clusters() {}
 int warm_clusters() {
   hipLaunchKernelGGL(k_warm_clusters, dim3(1), dim3(64), 0, ctx().stream);

@@ -265,6 +265,11 @@ def clusters_from_pairs(pairs, n):
     (P, 2) integer array of (i, j); ``n`` vertices.  ``i == j`` or an index outside [0, n) is refused before any device
     use.  Returns ``RmsdClusters``: clusters numbered by ascending smallest member, which is their representative."""
     n = _vertex_count(n)
+    return _clusters_from_graph("fc_clusters_from_pairs", _pair_words(pairs, n), n)
+
+
+def _pair_words(pairs, n):
+    """a caller's pair list, (P,) words or (P, 2) indices -> (P,) uint64 words, every check made"""
     pairs = np.asarray(pairs)
     if pairs.ndim == 2 and pairs.shape[1] == 2:
         ij = pairs.astype(np.int64)
@@ -281,7 +286,7 @@ def clusters_from_pairs(pairs, n):
     hi, lo = pairs >> np.uint64(32), pairs & np.uint64(0xFFFFFFFF)
     if pairs.size and ((hi == lo).any() or hi.max() >= n or lo.max() >= n):
         raise L.FirecodeHipInputError(L.FC_E_INVALID, f"a pair with i == j or an index outside [0, {n})")
-    return _clusters_from_graph("fc_clusters_from_pairs", pairs, n)
+    return pairs
 
 
 def clusters_from_bits(bits, n):
@@ -294,6 +299,106 @@ def clusters_from_bits(bits, n):
         raise L.FirecodeHipInputError(
             L.FC_E_INVALID, f"bits must be ({n}, {(n + 63) // 64}) uint64, got {bits.shape} {bits.dtype}")
     return _clusters_from_graph("fc_clusters_from_bits", np.ascontiguousarray(bits), n)
+
+
+RmsdDbscan = namedtuple("RmsdDbscan", ["labels", "representatives", "sizes", "core", "degrees"])
+
+
+def _empty_dbscan():
+    return RmsdDbscan(np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64),
+                      np.zeros(0, dtype=bool), np.zeros(0, dtype=np.int32))
+
+
+def dbscan_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, min_samples=5, energies=None, max_dE=0.0,
+                   debugfunction=None, heavy_atoms_only=True, prune_enantiomers=False, symmetry=None):
+    """Which conformers form a populated region: density-based clusters (DBSCAN) on the similarity graph of
+    ``cluster_by_rmsd`` -- the same edges, the same options -- on the GPU (fc_rmsd_dbscan; the contract is written out
+    in include/fc_hip.h).  A conformer is a core point when it and its neighbours number at least ``min_samples``; the
+    clusters are the connected components of the core points, so a thin chain of intermediates does not weld two basins
+    together; a conformer that is not core joins the cluster of its first core neighbour in processing order (border),
+    or, with none, is noise.
+
+    Returns ``RmsdDbscan(labels, representatives, sizes, core, degrees)`` in the caller's order: labels (N,) int32, -1 for
+    noise; representatives (K,) int64 indices into ``structures``, the first core member of each cluster in processing
+    order -- lowest energy when ``energies`` is usable, lowest index otherwise -- with clusters numbered in that order;
+    sizes (K,) int64, core and border members; core (N,) bool; degrees (N,) int32, the number of neighbours of each
+    conformer: its local density at ``max_rmsd``.  ``min_samples=1`` gives the clusters of ``cluster_by_rmsd``."""
+    from firecode_amd import symmetry as S
+
+    t0 = perf_counter()
+    enant = L.check_flag("prune_enantiomers", prune_enantiomers)
+    min_samples = L.check_min_samples(min_samples)
+    structures = L.f64(structures)
+    if structures.ndim != 3 or structures.shape[2] != 3:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {structures.shape}")
+    atoms = np.asarray(atoms)
+    if atoms.shape[0] != structures.shape[1]:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "len(atoms) != number of atoms")
+    table = S.resolve(symmetry, atoms, heavy_atoms_only)
+    S.refuse_with_enantiomers(table, enant)
+    if table is not None:
+        S.selected_table(table, (atoms != "H") if heavy_atoms_only else None)
+    max_rmsd, max_dev, max_dE = _thresholds(max_rmsd, max_dev, max_dE)
+    N = structures.shape[0]
+    if N == 0:
+        return _empty_dbscan()
+    heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
+    order, en_sorted = _sorted_by_energy(structures, energies)
+    X = structures if order is None else np.ascontiguousarray(structures[order])
+    with L.DeviceEnsemble(X, atom_mask=heavy, center=True) as ens:
+        labels, reps, sizes, core, degrees, stats = ens.dbscan(max_rmsd, max_dev, min_samples, energies=en_sorted,
+                                                               max_dE=max_dE, prune_enantiomers=enant, symmetry=table)
+    if order is not None:
+        labels, core, degrees = _unsort(labels, order), _unsort(core, order), _unsort(degrees, order)
+        reps = order[reps].astype(np.int64)
+    if debugfunction is not None:
+        debugfunction(
+            f"DEBUG: dbscan_by_rmsd [gfx950{', mirror images included' if enant else ''}"
+            f"{'' if table is None else f', {len(table)} atom permutations'}] - {stats[0]} pairs screened, "
+            f"{stats[2]} similar, min_samples {min_samples}: {len(sizes)} clusters, {stats[6]} core, "
+            f"{N - int(stats[6]) - int(stats[7])} border, {stats[7]} noise, in {perf_counter() - t0:.3f} s")
+    return RmsdDbscan(labels, reps, sizes, core, degrees)
+
+
+def _dbscan_from_graph(name, graph, n, min_samples):
+    import ctypes as C
+
+    labels, degrees = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    reps, sizes = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    core = np.zeros(n, dtype=np.uint8)
+    k = C.c_int64(0)
+    head = (L.pw(graph), int(graph.shape[0]), n) if name == "fc_dbscan_from_pairs" else (L.pw(graph), n)
+    L.call(name, *head, min_samples, L.ptr(labels, C.c_int32), L.pi(reps), L.pi(sizes), L.pb(core), L.ptr(degrees, C.c_int32),
+           C.byref(k))
+    return RmsdDbscan(labels, reps[:k.value].copy(), sizes[:k.value].copy(), core.astype(bool), degrees)
+
+
+def dbscan_from_pairs(pairs, n, min_samples, assume_unique=False):
+    """The labelling of ``dbscan_by_rmsd`` on a caller's graph (fc_dbscan_from_pairs): ``pairs`` and ``n`` as
+    ``clusters_from_pairs`` takes them, with the same checks before any device use.  Degrees count list entries, so
+    every unordered pair must be listed once: the list is brought to (min, max) order and duplicates are removed here
+    unless ``assume_unique=True`` (the output of ``DeviceEnsemble.similar_pairs`` is), in which case a pair listed twice
+    counts twice.  Returns ``RmsdDbscan``."""
+    n = _vertex_count(n)
+    min_samples = L.check_min_samples(min_samples)
+    assume_unique = L.check_flag("assume_unique", assume_unique)
+    pairs = _pair_words(pairs, n)
+    if not assume_unique:
+        hi, lo = pairs >> np.uint64(32), pairs & np.uint64(0xFFFFFFFF)
+        pairs = np.unique((np.minimum(hi, lo) << np.uint64(32)) | np.maximum(hi, lo))
+    return _dbscan_from_graph("fc_dbscan_from_pairs", np.ascontiguousarray(pairs, dtype=np.uint64), n, min_samples)
+
+
+def dbscan_from_bits(bits, n, min_samples):
+    """The labelling of ``dbscan_by_rmsd`` on a caller's (n, ceil(n/64)) uint64 bit matrix (fc_dbscan_from_bits): the
+    layout and the checks of ``clusters_from_bits``; only bits j > i are read, so no pair can count twice."""
+    n = _vertex_count(n)
+    min_samples = L.check_min_samples(min_samples)
+    bits = np.asarray(bits)
+    if bits.dtype != np.uint64 or bits.ndim != 2 or bits.shape != (n, (n + 63) // 64):
+        raise L.FirecodeHipInputError(
+            L.FC_E_INVALID, f"bits must be ({n}, {(n + 63) // 64}) uint64, got {bits.shape} {bits.dtype}")
+    return _dbscan_from_graph("fc_dbscan_from_bits", np.ascontiguousarray(bits), n, min_samples)
 
 
 def rotation_mask(graph, torsion, n_atoms=None):

@@ -286,6 +286,50 @@ int fc_clusters_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, in
 int fc_clusters_from_bits(const uint64_t *bits, int64_t N, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
                           int64_t *n_clusters);
 
+/* ---- density-based clusters: core, border and noise on the prune's graph (DBSCAN) ----
+ * The contract, once.  G = exactly the graph of fc_rmsd_clusters on the N conformers in processing order (fc_rmsd_dbscan_enant:
+ * of fc_rmsd_clusters_enant; fc_rmsd_dbscan_perm: of fc_rmsd_clusters_perm): the same thresholds, "<", max_dev, energy
+ * window and grey handling.  fc_prune_conventions and min_per_group play no part.  With m = min_samples >= 1:
+ *
+ *   degree  d(i) = the number of neighbours of i in G: i itself excluded, every unordered pair counted once
+ *   core    i is a core point when d(i) + 1 >= m (the point counts itself: the usual DBSCAN convention)
+ *   cluster a connected component of the subgraph induced on the core points.  Its representative is its smallest core
+ *           member; clusters are numbered 0 .. K-1 by ascending representative
+ *   border  a point that is not core and has at least one core neighbour joins the cluster of its SMALLEST-INDEX core
+ *           neighbour (textbook DBSCAN leaves that choice to the visiting order; here the result is a function of G and
+ *           the processing order alone, never of launch order or of which internal path ran)
+ *   noise   a point that is not core and has no core neighbour: label -1
+ *
+ *   labels_out  (N, int32)              the cluster of each conformer, -1 for noise
+ *   reps_out    (N entries, K written)  the smallest core member of each cluster
+ *   sizes_out   (N entries, K written)  core and border members of each cluster
+ *   core_out    (N, uint8)              1 for a core point
+ *   degrees_out (N, int32)              d(i): the local density of a conformer at the prune's threshold
+ *   *n_clusters = K
+ *
+ * The host pre-sorts by energy as for fc_rmsd_clusters, so with usable energies the representative is the lowest-energy
+ * core member.  m = 1: labels, reps and sizes are those of fc_rmsd_clusters, exactly.  m = 2: the same, except that
+ * clusters of one become noise.  stats (8 values, may be NULL): [0 .. 5] as fc_rmsd_clusters, [6] core points, [7] noise
+ * points.  N = 0: K = 0.  Limit: N < 2^31 - 256.  FC_E_INVALID before any device use: min_samples < 1, NULL ens / outputs,
+ * thresholds <= 0 (fc_rmsd_dbscan_perm: first the table's checks, as fc_rmsd_clusters_perm).  FC_E_INTERNAL: as fc_rmsd_clusters.
+ *
+ * fc_dbscan_from_pairs / fc_dbscan_from_bits: the same labelling of a caller's graph, host arrays in the formats of
+ * fc_clusters_from_pairs / fc_clusters_from_bits with the same host-side index checks.  ONE DIFFERENCE from the components:
+ * degrees count list entries, so fc_dbscan_from_pairs requires every unordered pair AT MOST ONCE (in either order), as
+ * fc_prune_similar_pairs delivers it; a pair listed twice counts twice in both degrees.  The bit form cannot hold a pair
+ * twice: only bits j > i are read. */
+int fc_rmsd_dbscan(fc_ensemble *ens, double max_rmsd, double max_dev, int64_t min_samples, const double *energies,
+                   double max_dE, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, uint8_t *core_out,
+                   int32_t *degrees_out, int64_t *n_clusters, int64_t *stats);
+int fc_rmsd_dbscan_enant(fc_ensemble *ens, double max_rmsd, double max_dev, int64_t min_samples, const double *energies,
+                         double max_dE, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, uint8_t *core_out,
+                         int32_t *degrees_out, int64_t *n_clusters, int64_t *stats);
+int fc_dbscan_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int64_t min_samples, int32_t *labels_out,
+                         int64_t *reps_out, int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out,
+                         int64_t *n_clusters);
+int fc_dbscan_from_bits(const uint64_t *bits, int64_t N, int64_t min_samples, int32_t *labels_out, int64_t *reps_out,
+                        int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out, int64_t *n_clusters);
+
 /* ---- symmetry-aware forms: atom permutations of equivalent atoms ----
  * The contract, once.  X = the prepared ensemble of the RMSD stage (atom selection applied, each conformer centred on the
  * centroid of its selected atoms).  perms = a (K, A_sel) row-major table of permutations of the selected atoms, in
@@ -328,6 +372,10 @@ int fc_prune_rmsd_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_
 int fc_rmsd_clusters_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd,
                           double max_dev, const double *energies, double max_dE, int32_t *labels_out, int64_t *reps_out,
                           int64_t *sizes_out, int64_t *n_clusters, int64_t *stats);
+/* the density-based clusters (above) of the graph of fc_rmsd_clusters_perm */
+int fc_rmsd_dbscan_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
+                        int64_t min_samples, const double *energies, double max_dE, int32_t *labels_out, int64_t *reps_out,
+                        int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out, int64_t *n_clusters, int64_t *stats);
 
 /* sharded form (conformer rows dealt block-cyclically to ranks):
  * fc_prune_rmsd_begin computes this rank's rows of the bit matrix;
