@@ -348,6 +348,12 @@ static int embed_grid(const double *m1, int64_t n1, int64_t A1, const int64_t *r
   FC_TRY(check_embed_mol(m2, n2, A2, reactive2, nr2, ps2, pe2, angles2, na2));
   FC_REQUIRE(pass_out != nullptr && max_clashes >= 0, "bad arguments");
   if (A1 * 40 + 64 > 64 * 1024) return set_error(FC_E_LIMIT, "A1=%lld too large for the LDS stage", (long long)A1);
+  if (accept_out != nullptr) {  // refused before anything is launched
+    FC_REQUIRE(rmsd_thr > 0.0, "rmsd_thr must be positive");
+    if (na1 * na2 * 4 * (int64_t)sizeof(int) > 64 * 1024)
+      return set_error(FC_E_LIMIT, "na1*na2=%lld angle pairs per group exceed the 4096 of the LDS list",
+                       (long long)(na1 * na2));
+  }
   FC_TRY(ensure_init());
   Context &c = ctx();
   const int64_t P = n1 * n2 * 2 * na1 * na2;
@@ -390,7 +396,9 @@ static int embed_grid(const double *m1, int64_t n1, int64_t A1, const int64_t *r
   DevBuf X2a, dacc;
   if (accept_out != nullptr) {
     FC_REQUIRE(rmsd_thr > 0.0, "rmsd_thr must be positive");
-    FC_REQUIRE(na1 * na2 * 4 * (int64_t)sizeof(int) <= 64 * 1024, "too many angle pairs per group for the LDS list");
+    if (na1 * na2 * 4 * (int64_t)sizeof(int) > 64 * 1024)
+      return set_error(FC_E_LIMIT, "na1*na2=%lld angle pairs per group exceed the 4096 of the LDS list",
+                       (long long)(na1 * na2));
     FC_TRY(X2a.reserve(G2 * A2 * 3 * sizeof(double)));
     FC_TRY(dacc.reserve((size_t)P));
     FC_TRY(launch_embed_pretransform(d2.as<double>(), n2, A2, na2, R2.as<double>(), t2.as<double>(), 1, 0,

@@ -1319,7 +1319,9 @@ k_leader_vs_kept(const double *__restrict__ tf, int Q, int64_t chunk0, int64_t P
     const int64_t j = j0 + threadIdx.x;
     if (j < n && tfd_sum(ti, 1, accT + j, cap, Q) < thresh) found = 1;
     __syncthreads();
-    if (found) break;
+    const int stop = found;  // every thread reads the flag of THIS trip ...
+    __syncthreads();         // ... before any thread of the next trip may set it: the break is workgroup-uniform
+    if (stop) break;
   }
   if (threadIdx.x == 0) rejected[blockIdx.x] = (uint8_t)found;
 }

@@ -615,7 +615,13 @@ int fc_embed_poses_clash(const double *m1, int64_t n1, int64_t A1, const double 
  * angle); fc_embed_grid_clash tests every pose
  *   p = ((c2*n1 + c1)*2 + o)*(na1*na2) + (a2*na1 + a1)
  * (the reference's loop order) and writes pass_out[p] = count(d < thresh) <=
- * max_clashes; counts_out (may be NULL) saturates just above max_clashes. */
+ * max_clashes; counts_out (may be NULL) saturates just above max_clashes:
+ * molecule-2 atoms b are taken in order, the whole row b (all molecule-1 atoms)
+ * is added while the running count is <= max_clashes, then counting stops.
+ * Exact for any coordinates: NaN and +-inf distances never count (`<` is
+ * false), far-away coordinates only make the fp32 screen pass more pairs on to
+ * the fp64 recount.  Limit: A1 <= 1636 (A1*40 + 64 bytes of LDS <= 64 KiB),
+ * FC_E_LIMIT beyond. */
 int fc_embed_mol_transforms(const double *coords, int64_t n, int64_t A, const int64_t *reactive,
                             int64_t nr, const double *pivot_start, const double *pivot_end,
                             int64_t mol, const double *angles, int64_t na, double *R_out,
@@ -628,7 +634,9 @@ int fc_embed_grid_clash(const double *m1, int64_t n1, int64_t A1, const int64_t 
                         uint8_t *pass_out, int32_t *counts_out, double *ms_kernel);
 /* same grid followed by the in-group de-duplication of embeds.py:723
  * (rmsd_similarity(pose, poses kept so far in this (conformer pair, orientation)
- * group, rmsd_thr)): accept_out[p] = pass[p] && the pose is new. */
+ * group, rmsd_thr)): accept_out[p] = pass[p] && the pose is new.
+ * Limits: A1 as above; na1*na2 <= 4096 angle pairs per group (the LDS list of
+ * kept poses), FC_E_LIMIT beyond; rmsd_thr > 0 (FC_E_INVALID). */
 int fc_embed_grid_dedupe(const double *m1, int64_t n1, int64_t A1, const int64_t *reactive1,
                          int64_t nr1, const double *ps1, const double *pe1, const double *m2,
                          int64_t n2, int64_t A2, const int64_t *reactive2, int64_t nr2,
@@ -650,7 +658,9 @@ int fc_embed_grid_dedupe(const double *m1, int64_t n1, int64_t A1, const int64_t
  * fragment pairs <= max_clashes) and the rmsd_similarity(rmsd_thr) filter against the poses
  * already accepted in the group (:553-566).
  * Out: dirs_out (J,8,3,3) directions used by each orientation; Rt_out (J,8,3,U,12): R (9, row
- * major) and t (3) of molecule i at step angle u; pass_out / accept_out (J,8,S) uint8. */
+ * major) and t (3) of molecule i at step angle u; pass_out / accept_out (J,8,S) uint8.
+ * Limits (FC_E_LIMIT beyond): U <= 85; J*8*S < 2^31; the LDS of one group,
+ *   U*Atot*24 + 3*U*96 + 3*U*U*4 + S*5 bytes rounded up to 16, <= 160 KiB. */
 int fc_embed_trimolecular(const double *const coords[3], const int64_t n_conf[3], const int64_t n_atoms[3],
                           const int64_t *const reactive[3], const int64_t n_reactive[3], int64_t J,
                           const int64_t *conf, const double *piv_start, const double *piv_end,
@@ -667,7 +677,8 @@ int fc_embed_trimolecular(const double *const coords[3], const int64_t n_conf[3]
  * accept_out[p]: passed AND its torsion fingerprint over quads (Q,4; atom indices
  * in the concatenated pose) is not TFD-similar (tfd_thresh) to any pose accepted
  * before it.  R2_out (P,3,3) / t2_out (P,3) (may be NULL): molecule 2's transform
- * (molecule 1 is not moved). */
+ * (molecule 1 is not moved).  Limits (FC_E_LIMIT beyond): Q <= 128;
+ * A1 <= 1706 (four structures of A1*24 bytes in 160 KiB of LDS). */
 int fc_string_embed(const double *m1, int64_t n1, int64_t A1, const double *centers1,
                     const double *orbvecs1, int64_t K1, const double *m2, int64_t n2, int64_t A2,
                     const double *centers2, const double *orbvecs2, int64_t K2,
