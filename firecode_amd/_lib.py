@@ -475,6 +475,13 @@ class DeviceEnsemble:
         t = S.selected_table(table, self._atom_mask)
         return t, (ptr(t, C.c_int32), int(t.shape[0]), int(t.shape[1]))
 
+    def _form(self, name, perm, enant):
+        """the entry point ``name`` in the form the keywords ask for -> (its name, its leading arguments): ``_perm`` with
+        the table of ``_perm_args`` behind the handle, else ``_enant``, else plain"""
+        if perm is not None:
+            return name + "_perm", (self.handle, *perm[1])
+        return (name + "_enant" if enant else name), (self.handle,)
+
     def rmsd_pairs(self, pair_i, pair_j, inverted=False, symmetry=None):
         """(rmsd, maxdev) of the pairs; ``inverted=True``: of (X_i, -X_j), the partner's mirror image
         (fc_ensemble_rmsd_pairs_inv).  ``symmetry=`` a (K, A_all) table: both (P, K), the values of
@@ -608,12 +615,9 @@ class DeviceEnsemble:
         bits = np.zeros((row_end - row_begin, self.W), dtype=np.uint64)
         grey = C.c_int64(0)
         en = None if energies is None else f64(energies)
-        if perm is not None:
-            call("fc_rmsd_simbits_perm", self.handle, *perm[1], float(max_rmsd), float(max_dev), pf(en), float(max_dE),
-                 int(row_begin), row_end, pw(bits), C.byref(grey))
-            return bits, grey.value
-        call("fc_rmsd_simbits_enant" if enant else "fc_rmsd_simbits", self.handle, float(max_rmsd), float(max_dev), pf(en), float(max_dE),
-             int(row_begin), row_end, pw(bits), C.byref(grey))
+        name, head = self._form("fc_rmsd_simbits", perm, enant)
+        call(name, *head, float(max_rmsd), float(max_dev), pf(en), float(max_dE), int(row_begin), row_end, pw(bits),
+             C.byref(grey))
         return bits, grey.value
 
     def prune(self, max_rmsd, max_dev, energies=None, max_dE=0.0, min_per_group=20, prune_enantiomers=False, symmetry=None):
@@ -625,12 +629,8 @@ class DeviceEnsemble:
         mask = np.zeros(self.N, dtype=np.uint8)
         stats = np.zeros(6, dtype=np.int64)
         en = None if energies is None else f64(energies)
-        if perm is not None:
-            call("fc_prune_rmsd_perm", self.handle, *perm[1], float(max_rmsd), float(max_dev), pf(en), float(max_dE),
-                 int(min_per_group), pb(mask), pi(stats))
-            return mask.astype(bool), stats
-        call("fc_prune_rmsd_enant" if enant else "fc_prune_rmsd", self.handle, float(max_rmsd), float(max_dev), pf(en), float(max_dE),
-             int(min_per_group), pb(mask), pi(stats))
+        name, head = self._form("fc_prune_rmsd", perm, enant)
+        call(name, *head, float(max_rmsd), float(max_dev), pf(en), float(max_dE), int(min_per_group), pb(mask), pi(stats))
         return mask.astype(bool), stats
 
     def clusters(self, max_rmsd, max_dev, energies=None, max_dE=0.0, prune_enantiomers=False, symmetry=None):
@@ -646,12 +646,9 @@ class DeviceEnsemble:
         stats = np.zeros(6, dtype=np.int64)
         k = C.c_int64(0)
         en = None if energies is None else f64(energies)
-        if perm is not None:
-            call("fc_rmsd_clusters_perm", self.handle, *perm[1], float(max_rmsd), float(max_dev), pf(en), float(max_dE),
-                 ptr(labels, C.c_int32), pi(reps), pi(sizes), C.byref(k), pi(stats))
-            return labels, reps[:k.value].copy(), sizes[:k.value].copy(), stats
-        call("fc_rmsd_clusters_enant" if enant else "fc_rmsd_clusters", self.handle, float(max_rmsd), float(max_dev), pf(en),
-             float(max_dE), ptr(labels, C.c_int32), pi(reps), pi(sizes), C.byref(k), pi(stats))
+        name, head = self._form("fc_rmsd_clusters", perm, enant)
+        call(name, *head, float(max_rmsd), float(max_dev), pf(en), float(max_dE), ptr(labels, C.c_int32), pi(reps), pi(sizes),
+             C.byref(k), pi(stats))
         return labels, reps[:k.value].copy(), sizes[:k.value].copy(), stats
 
     def dbscan(self, max_rmsd, max_dev, min_samples, energies=None, max_dE=0.0, prune_enantiomers=False, symmetry=None):
@@ -672,11 +669,8 @@ class DeviceEnsemble:
         k = C.c_int64(0)
         en = None if energies is None else f64(energies)
         outs = (ptr(labels, C.c_int32), pi(reps), pi(sizes), pb(core), ptr(degrees, C.c_int32), C.byref(k), pi(stats))
-        if perm is not None:
-            call("fc_rmsd_dbscan_perm", self.handle, *perm[1], float(max_rmsd), float(max_dev), m, pf(en), float(max_dE), *outs)
-        else:
-            call("fc_rmsd_dbscan_enant" if enant else "fc_rmsd_dbscan", self.handle, float(max_rmsd), float(max_dev), m, pf(en),
-                 float(max_dE), *outs)
+        name, head = self._form("fc_rmsd_dbscan", perm, enant)
+        call(name, *head, float(max_rmsd), float(max_dev), m, pf(en), float(max_dE), *outs)
         return labels, reps[:k.value].copy(), sizes[:k.value].copy(), core.astype(bool), degrees, stats
 
     def prune_begin(self, max_rmsd, max_dev, rank, world, row_block=128, energies=None, max_dE=0.0):

@@ -265,78 +265,110 @@ int cl_blocks(int64_t items, int per_cu) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, kClThreads), (int64_t)ctx().n_cu * per_cu));
 }
 
-}  // namespace
+// what both launchers carve out of `work` (cluster_layout) and what every launch of theirs is sized by
+struct ClWork {
+  int32_t *labels;
+  int64_t *reps;
+  unsigned long long *sizes, *status;
+  int32_t *parent, *root;
+  uint64_t *flags;
+  int32_t *prefix;
+  uint8_t *core;     // core, deg, attach: the density-based form's
+  int32_t *deg;
+  uint32_t *attach;
+  int64_t W;
+  unsigned per_n;
+  hipStream_t st;
+};
 
-// Everything behind the graph: the caller has reserved `work` (cluster_layout(N).total bytes) and, for the pair form,
-// left the list where `g` says.  Enqueues only; the result region of `work` is complete when the stream has drained.
-int launch_clusters(const ClusterGraph &g, int64_t N, DevBuf &work) {
-  const ClusterLayout L = cluster_layout(N);
+// the head of both launchers: the argument checks, the carving, the memsets and k_cl_init.  density: launch_dbscan's
+int cl_begin(const ClusterGraph &g, int64_t N, bool density, int64_t min_samples, DevBuf &work, ClWork *w) {
+  const ClusterLayout L = cluster_layout(N, density);
   if (work.p == nullptr || work.bytes < L.total) return set_error(FC_E_INVALID, "cluster workspace too small");
   if (N < 1 || N > (int64_t)INT32_MAX - 256) return set_error(FC_E_LIMIT, "N=%lld: clusters index conformers with 32 bits", (long long)N);
+  if (density && min_samples < 1) return set_error(FC_E_INVALID, "min_samples=%lld < 1", (long long)min_samples);
   if ((g.pairs_dev != nullptr) == (g.bits_dev != nullptr)) return set_error(FC_E_INVALID, "one of pair list / bit matrix");
   char *base = static_cast<char *>(work.p);
-  auto *labels = reinterpret_cast<int32_t *>(base + L.labels);
-  auto *reps = reinterpret_cast<int64_t *>(base + L.reps);
-  auto *sizes = reinterpret_cast<unsigned long long *>(base + L.sizes);
-  auto *status = reinterpret_cast<unsigned long long *>(base + L.status);
-  auto *parent = reinterpret_cast<int32_t *>(base + L.parent);
-  auto *root = reinterpret_cast<int32_t *>(base + L.root);
-  auto *flags = reinterpret_cast<uint64_t *>(base + L.flags);
-  auto *prefix = reinterpret_cast<int32_t *>(base + L.prefix);
-  const int64_t W = ceil_div(N, 64);
-  hipStream_t st = cur_stream();
-  const unsigned per_n = (unsigned)ceil_div(N, kClThreads);
-  FC_HIP_TRY(hipMemsetAsync(sizes, 0, (size_t)N * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_cl_init, dim3(per_n), dim3(kClThreads), 0, st, parent, N, status, g.n_pairs_host);
-  FC_TRY(check_launch("k_cl_init"));
+  w->labels = reinterpret_cast<int32_t *>(base + L.labels);
+  w->reps = reinterpret_cast<int64_t *>(base + L.reps);
+  w->sizes = reinterpret_cast<unsigned long long *>(base + L.sizes);
+  w->core = reinterpret_cast<uint8_t *>(base + L.core);
+  w->deg = reinterpret_cast<int32_t *>(base + L.degrees);
+  w->status = reinterpret_cast<unsigned long long *>(base + L.status);
+  w->parent = reinterpret_cast<int32_t *>(base + L.parent);
+  w->root = reinterpret_cast<int32_t *>(base + L.root);
+  w->flags = reinterpret_cast<uint64_t *>(base + L.flags);
+  w->prefix = reinterpret_cast<int32_t *>(base + L.prefix);
+  w->attach = reinterpret_cast<uint32_t *>(base + L.attach);
+  w->W = ceil_div(N, 64);
+  w->st = cur_stream();
+  w->per_n = (unsigned)ceil_div(N, kClThreads);
+  FC_HIP_TRY(hipMemsetAsync(w->sizes, 0, (size_t)N * sizeof(unsigned long long), w->st));
+  if (density) {
+    FC_HIP_TRY(hipMemsetAsync(w->deg, 0, (size_t)N * sizeof(int32_t), w->st));
+    FC_HIP_TRY(hipMemsetAsync(w->attach, 0xff, (size_t)N * sizeof(uint32_t), w->st));
+  }
+  hipLaunchKernelGGL(k_cl_init, dim3(w->per_n), dim3(kClThreads), 0, w->st, w->parent, N, w->status, g.n_pairs_host);
+  return check_launch("k_cl_init");
+}
+
+// the hook launches of one graph, hook(seed, first class, end class).  phased: seed | [0, coarse) | [coarse, fine) with a
+// compression behind each, then the rest; else one launch over the classes from last_lo on
+template <class Hook>
+int hook_phases(const ClWork &w, int64_t N, bool phased, unsigned last_lo, const Hook &hook) {
   const auto compress = [&]() {
-    hipLaunchKernelGGL(k_cl_compress, dim3(per_n), dim3(kClThreads), 0, st, parent, N);
+    hipLaunchKernelGGL(k_cl_compress, dim3(w.per_n), dim3(kClThreads), 0, w.st, w.parent, N);
     return check_launch("k_cl_compress");
   };
-  if (g.pairs_dev != nullptr) {
-    const unsigned long long *n_pairs_dev = g.n_pairs_dev != nullptr ? g.n_pairs_dev : status + kClStatusPairs;
-    // the list's length is on the device only: the grid is sized for the chip, the kernels stride.  g.known_short: the
-    // caller has seen this list's length (or a recent one of these coordinates) -- the launches that would find
-    // nothing to do are left out; a list that is long after all is then hooked in one launch, slowly and correctly
-    const dim3 grid((unsigned)(ctx().n_cu * 8));
-    const unsigned long long split_min = g.known_short ? kClNeverSplit : kClSplitMin;
-    const auto hook = [&](bool seed, unsigned c_lo, unsigned c_hi) {
-      hipLaunchKernelGGL(k_cl_hook_pairs, grid, dim3(kClThreads), 0, st, g.pairs_dev, n_pairs_dev, g.n_cand_dev, g.cand_cap,
-                         g.redo_dev, N, parent, status, seed, c_lo, c_hi, split_min);
-      return check_launch("k_cl_hook_pairs");
-    };
-    if (!g.known_short) {
-      FC_TRY(hook(true, 0, 0));
-      FC_TRY(compress());
-      FC_TRY(hook(false, 0, kClCoarse));
-      FC_TRY(compress());
-      FC_TRY(hook(false, kClCoarse, kClFine));
-      FC_TRY(compress());
-    }
-    FC_TRY(hook(false, kClFine, kClClasses));  // (all of a list that is not split)
-  } else {
-    if (g.W < W) return set_error(FC_E_INVALID, "bit rows of %lld words, %lld needed", (long long)g.W, (long long)W);
-    const dim3 grid((unsigned)cl_blocks(N * g.W, 16));
-    const bool split = (unsigned long long)N * (unsigned long long)g.W >= 1024ull;  // (the bit matrix is the dense case)
-    const auto hook = [&](bool seed, unsigned c_lo, unsigned c_hi) {
-      hipLaunchKernelGGL(k_cl_hook_bits, grid, dim3(kClThreads), 0, st, g.bits_dev, g.W, N, parent, status, seed, c_lo, c_hi);
-      return check_launch("k_cl_hook_bits");
-    };
-    if (split) {
-      FC_TRY(hook(true, 0, 0));
-      FC_TRY(compress());
-      FC_TRY(hook(false, 0, kClCoarse));
-      FC_TRY(compress());
-      FC_TRY(hook(false, kClCoarse, kClFine));
-      FC_TRY(compress());
-    }
-    FC_TRY(hook(false, split ? kClFine : 0u, kClClasses));
+  if (phased) {
+    FC_TRY(hook(true, 0u, 0u));
+    FC_TRY(compress());
+    FC_TRY(hook(false, 0u, kClCoarse));
+    FC_TRY(compress());
+    FC_TRY(hook(false, kClCoarse, kClFine));
+    FC_TRY(compress());
   }
-  hipLaunchKernelGGL(k_cl_flatten, dim3(per_n), dim3(kClThreads), 0, st, parent, N, root, flags, W);
+  return hook(false, last_lo, kClClasses);
+}
+
+// the size of the pair-list launches (the list's length is on the device only: the grid is sized for the chip, the kernels
+// stride) and of the bit-matrix ones; the bit matrix is the dense case, split from 1024 words on
+dim3 cl_grid_pairs() { return dim3((unsigned)(ctx().n_cu * 8)); }
+dim3 cl_grid_bits(int64_t N, int64_t W) { return dim3((unsigned)cl_blocks(N * W, 16)); }
+bool cl_split_bits(int64_t N, int64_t W) { return (unsigned long long)N * (unsigned long long)W >= 1024ull; }
+
+}  // namespace
+
+// Everything behind the graph: the caller has reserved `work` (cluster_layout(N, false).total bytes) and, for the pair
+// form, left the list where `g` says.  Enqueues only; the result region of `work` is complete when the stream has drained.
+int launch_clusters(const ClusterGraph &g, int64_t N, DevBuf &work) {
+  ClWork w;
+  FC_TRY(cl_begin(g, N, /*density=*/false, 1, work, &w));
+  if (g.pairs_dev != nullptr) {
+    const unsigned long long *n_pairs_dev = g.n_pairs_dev != nullptr ? g.n_pairs_dev : w.status + kClStatusPairs;
+    // g.known_short: the caller has seen this list's length (or a recent one of these coordinates) -- the launches that
+    // would find nothing to do are left out; a list that is long after all is then hooked in one launch, slowly and correctly
+    const dim3 grid = cl_grid_pairs();
+    const unsigned long long split_min = g.known_short ? kClNeverSplit : kClSplitMin;
+    FC_TRY(hook_phases(w, N, !g.known_short, kClFine, [&](bool seed, unsigned c_lo, unsigned c_hi) {
+      hipLaunchKernelGGL(k_cl_hook_pairs, grid, dim3(kClThreads), 0, w.st, g.pairs_dev, n_pairs_dev, g.n_cand_dev, g.cand_cap,
+                         g.redo_dev, N, w.parent, w.status, seed, c_lo, c_hi, split_min);
+      return check_launch("k_cl_hook_pairs");
+    }));  // (the last launch: all of a list that is not split)
+  } else {
+    if (g.W < w.W) return set_error(FC_E_INVALID, "bit rows of %lld words, %lld needed", (long long)g.W, (long long)w.W);
+    const dim3 grid = cl_grid_bits(N, g.W);
+    const bool split = cl_split_bits(N, g.W);
+    FC_TRY(hook_phases(w, N, split, split ? kClFine : 0u, [&](bool seed, unsigned c_lo, unsigned c_hi) {
+      hipLaunchKernelGGL(k_cl_hook_bits, grid, dim3(kClThreads), 0, w.st, g.bits_dev, g.W, N, w.parent, w.status, seed, c_lo, c_hi);
+      return check_launch("k_cl_hook_bits");
+    }));
+  }
+  hipLaunchKernelGGL(k_cl_flatten, dim3(w.per_n), dim3(kClThreads), 0, w.st, w.parent, N, w.root, w.flags, w.W);
   FC_TRY(check_launch("k_cl_flatten"));
-  hipLaunchKernelGGL(k_cl_scan, dim3(1), dim3(1024), 0, st, flags, W, prefix, status);
+  hipLaunchKernelGGL(k_cl_scan, dim3(1), dim3(1024), 0, w.st, w.flags, w.W, w.prefix, w.status);
   FC_TRY(check_launch("k_cl_scan"));
-  hipLaunchKernelGGL(k_cl_label, dim3(per_n), dim3(kClThreads), 0, st, root, N, flags, prefix, labels, reps, sizes);
+  hipLaunchKernelGGL(k_cl_label, dim3(w.per_n), dim3(kClThreads), 0, w.st, w.root, N, w.flags, w.prefix, w.labels, w.reps, w.sizes);
   return check_launch("k_cl_label");
 }
 
@@ -580,84 +612,41 @@ k_db_label(const int32_t *__restrict__ root, int64_t N, const uint8_t *__restric
 
 }  // namespace
 
-// launch_clusters under the core rule; `work` holds dbscan_layout(N).total bytes
+// launch_clusters under the core rule; `work` holds cluster_layout(N, true).total bytes
 int launch_dbscan(const ClusterGraph &g, int64_t N, int64_t min_samples, DevBuf &work) {
-  const ClusterLayout L = dbscan_layout(N);
-  if (work.p == nullptr || work.bytes < L.total) return set_error(FC_E_INVALID, "cluster workspace too small");
-  if (N < 1 || N > (int64_t)INT32_MAX - 256) return set_error(FC_E_LIMIT, "N=%lld: clusters index conformers with 32 bits", (long long)N);
-  if (min_samples < 1) return set_error(FC_E_INVALID, "min_samples=%lld < 1", (long long)min_samples);
-  if ((g.pairs_dev != nullptr) == (g.bits_dev != nullptr)) return set_error(FC_E_INVALID, "one of pair list / bit matrix");
-  char *base = static_cast<char *>(work.p);
-  auto *labels = reinterpret_cast<int32_t *>(base + L.labels);
-  auto *reps = reinterpret_cast<int64_t *>(base + L.reps);
-  auto *sizes = reinterpret_cast<unsigned long long *>(base + L.sizes);
-  auto *core = reinterpret_cast<uint8_t *>(base + L.core);
-  auto *deg = reinterpret_cast<int32_t *>(base + L.degrees);
-  auto *status = reinterpret_cast<unsigned long long *>(base + L.status);
-  auto *parent = reinterpret_cast<int32_t *>(base + L.parent);
-  auto *root = reinterpret_cast<int32_t *>(base + L.root);
-  auto *flags = reinterpret_cast<uint64_t *>(base + L.flags);
-  auto *prefix = reinterpret_cast<int32_t *>(base + L.prefix);
-  auto *attach = reinterpret_cast<uint32_t *>(base + L.attach);
-  const int64_t W = ceil_div(N, 64);
-  hipStream_t st = cur_stream();
-  const unsigned per_n = (unsigned)ceil_div(N, kClThreads);
-  FC_HIP_TRY(hipMemsetAsync(sizes, 0, (size_t)N * sizeof(unsigned long long), st));
-  FC_HIP_TRY(hipMemsetAsync(deg, 0, (size_t)N * sizeof(int32_t), st));
-  FC_HIP_TRY(hipMemsetAsync(attach, 0xff, (size_t)N * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_cl_init, dim3(per_n), dim3(kClThreads), 0, st, parent, N, status, g.n_pairs_host);
-  FC_TRY(check_launch("k_cl_init"));
-  const auto compress = [&]() {
-    hipLaunchKernelGGL(k_cl_compress, dim3(per_n), dim3(kClThreads), 0, st, parent, N);
-    return check_launch("k_cl_compress");
-  };
+  ClWork w;
+  FC_TRY(cl_begin(g, N, /*density=*/true, min_samples, work, &w));
   if (g.pairs_dev != nullptr) {
-    const unsigned long long *n_pairs_dev = g.n_pairs_dev != nullptr ? g.n_pairs_dev : status + kClStatusPairs;
-    const dim3 grid((unsigned)(ctx().n_cu * 8));
+    const unsigned long long *n_pairs_dev = g.n_pairs_dev != nullptr ? g.n_pairs_dev : w.status + kClStatusPairs;
+    const dim3 grid = cl_grid_pairs();
     const unsigned long long split_min = g.known_short ? kClNeverSplit : kClSplitMin;
-    hipLaunchKernelGGL(k_db_degree_pairs, grid, dim3(kClThreads), 0, st, g.pairs_dev, n_pairs_dev, g.n_cand_dev, g.cand_cap,
-                       g.redo_dev, N, deg, status);
+    hipLaunchKernelGGL(k_db_degree_pairs, grid, dim3(kClThreads), 0, w.st, g.pairs_dev, n_pairs_dev, g.n_cand_dev, g.cand_cap,
+                       g.redo_dev, N, w.deg, w.status);
     FC_TRY(check_launch("k_db_degree_pairs"));
-    const auto hook = [&](bool seed, unsigned c_lo, unsigned c_hi) {
-      hipLaunchKernelGGL(k_db_hook_pairs, grid, dim3(kClThreads), 0, st, g.pairs_dev, n_pairs_dev, g.n_cand_dev, g.cand_cap,
-                         g.redo_dev, N, deg, min_samples, parent, attach, status, seed, c_lo, c_hi, split_min);
+    FC_TRY(hook_phases(w, N, !g.known_short, kClFine, [&](bool seed, unsigned c_lo, unsigned c_hi) {
+      hipLaunchKernelGGL(k_db_hook_pairs, grid, dim3(kClThreads), 0, w.st, g.pairs_dev, n_pairs_dev, g.n_cand_dev, g.cand_cap,
+                         g.redo_dev, N, w.deg, min_samples, w.parent, w.attach, w.status, seed, c_lo, c_hi, split_min);
       return check_launch("k_db_hook_pairs");
-    };
-    if (!g.known_short) {
-      FC_TRY(hook(true, 0, 0));
-      FC_TRY(compress());
-      FC_TRY(hook(false, 0, kClCoarse));
-      FC_TRY(compress());
-      FC_TRY(hook(false, kClCoarse, kClFine));
-      FC_TRY(compress());
-    }
-    FC_TRY(hook(false, kClFine, kClClasses));  // (all of a list that is not split)
+    }));
   } else {
-    if (g.W < W) return set_error(FC_E_INVALID, "bit rows of %lld words, %lld needed", (long long)g.W, (long long)W);
-    hipLaunchKernelGGL(k_db_degree_bits, dim3((unsigned)W), dim3(kClThreads), 0, st, g.bits_dev, g.W, N, deg);
+    if (g.W < w.W) return set_error(FC_E_INVALID, "bit rows of %lld words, %lld needed", (long long)g.W, (long long)w.W);
+    hipLaunchKernelGGL(k_db_degree_bits, dim3((unsigned)w.W), dim3(kClThreads), 0, w.st, g.bits_dev, g.W, N, w.deg);
     FC_TRY(check_launch("k_db_degree_bits"));
-    const dim3 grid((unsigned)cl_blocks(N * g.W, 16));
-    const bool split = (unsigned long long)N * (unsigned long long)g.W >= 1024ull;
-    const auto hook = [&](bool seed, unsigned c_lo, unsigned c_hi) {
-      hipLaunchKernelGGL(k_db_hook_bits, grid, dim3(kClThreads), 0, st, g.bits_dev, g.W, N, deg, min_samples, parent, attach,
-                         status, seed, /*do_attach=*/seed || !split, c_lo, c_hi);
+    const dim3 grid = cl_grid_bits(N, g.W);
+    const bool split = cl_split_bits(N, g.W);
+    FC_TRY(hook_phases(w, N, split, split ? kClFine : 0u, [&](bool seed, unsigned c_lo, unsigned c_hi) {
+      hipLaunchKernelGGL(k_db_hook_bits, grid, dim3(kClThreads), 0, w.st, g.bits_dev, g.W, N, w.deg, min_samples, w.parent,
+                         w.attach, w.status, seed, /*do_attach=*/seed || !split, c_lo, c_hi);
       return check_launch("k_db_hook_bits");
-    };
-    if (split) {
-      FC_TRY(hook(true, 0, 0));
-      FC_TRY(compress());
-      FC_TRY(hook(false, 0, kClCoarse));
-      FC_TRY(compress());
-      FC_TRY(hook(false, kClCoarse, kClFine));
-      FC_TRY(compress());
-    }
-    FC_TRY(hook(false, split ? kClFine : 0u, kClClasses));
+    }));
   }
-  hipLaunchKernelGGL(k_db_flatten, dim3(per_n), dim3(kClThreads), 0, st, parent, N, deg, min_samples, root, flags, W, core);
+  hipLaunchKernelGGL(k_db_flatten, dim3(w.per_n), dim3(kClThreads), 0, w.st, w.parent, N, w.deg, min_samples, w.root, w.flags,
+                     w.W, w.core);
   FC_TRY(check_launch("k_db_flatten"));
-  hipLaunchKernelGGL(k_cl_scan, dim3(1), dim3(1024), 0, st, flags, W, prefix, status);
+  hipLaunchKernelGGL(k_cl_scan, dim3(1), dim3(1024), 0, w.st, w.flags, w.W, w.prefix, w.status);
   FC_TRY(check_launch("k_cl_scan"));
-  hipLaunchKernelGGL(k_db_label, dim3(per_n), dim3(kClThreads), 0, st, root, N, core, attach, flags, prefix, labels, reps, sizes);
+  hipLaunchKernelGGL(k_db_label, dim3(w.per_n), dim3(kClThreads), 0, w.st, w.root, N, w.core, w.attach, w.flags, w.prefix,
+                     w.labels, w.reps, w.sizes);
   return check_launch("k_db_label");
 }
 

@@ -174,12 +174,12 @@ constexpr int kClStatusList = 1;   // 1: the pair list produced the result, 0: t
 constexpr int kClStatusK = 2;      // number of clusters
 constexpr int kClStatusPairs = 3;  // length of a list uploaded by the caller
 constexpr int64_t kClShortList = 1 << 16;  // pair lists below this are hooked in one launch (fc_clusters.hip)
-// one block: labels | reps | sizes | status (the part that travels to the host, result_bytes from offset 0) | scratch
-// (core, degrees, attach: the density-based form's, dbscan_layout below; 0 in cluster_layout)
+// one block: labels | reps | sizes [| core | degrees] | status (the part that travels to the host, result_bytes from
+// offset 0) | scratch [+ attach].  density: the density-based form, which adds the bracketed fields; they stay 0 without it
 struct ClusterLayout {
   size_t labels, reps, sizes, status, result_bytes, parent, root, flags, prefix, total, core, degrees, attach;
 };
-inline ClusterLayout cluster_layout(int64_t N) {
+inline ClusterLayout cluster_layout(int64_t N, bool density) {
   const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t n = (size_t)(N > 0 ? N : 1), w = (n + 63) / 64;
   ClusterLayout L{};
@@ -187,36 +187,27 @@ inline ClusterLayout cluster_layout(int64_t N) {
   L.reps = up(n * sizeof(int32_t));
   L.sizes = L.reps + up(n * sizeof(int64_t));
   L.status = L.sizes + up(n * sizeof(int64_t));
+  if (density) {
+    L.core = L.status;
+    L.degrees = L.core + up(n * sizeof(uint8_t));
+    L.status = L.degrees + up(n * sizeof(int32_t));
+  }
   L.result_bytes = L.status + 4 * sizeof(uint64_t);
   L.parent = up(L.result_bytes);
   L.root = L.parent + up(n * sizeof(int32_t));
   L.flags = L.root + up(n * sizeof(int32_t));
   L.prefix = L.flags + up(w * sizeof(uint64_t));
   L.total = L.prefix + up(w * sizeof(int32_t));
+  if (density) {
+    L.attach = L.total;
+    L.total = L.attach + up(n * sizeof(uint32_t));
+  }
   return L;
 }
+// `work` holds cluster_layout(N, false).total bytes
 int launch_clusters(const ClusterGraph &g, int64_t N, DevBuf &work);
-// the density-based form: labels | reps | sizes | core | degrees | status travel to the host | scratch (+ attach)
-inline ClusterLayout dbscan_layout(int64_t N) {
-  const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t n = (size_t)(N > 0 ? N : 1), w = (n + 63) / 64;
-  ClusterLayout L{};
-  L.labels = 0;
-  L.reps = up(n * sizeof(int32_t));
-  L.sizes = L.reps + up(n * sizeof(int64_t));
-  L.core = L.sizes + up(n * sizeof(int64_t));
-  L.degrees = L.core + up(n * sizeof(uint8_t));
-  L.status = L.degrees + up(n * sizeof(int32_t));
-  L.result_bytes = L.status + 4 * sizeof(uint64_t);
-  L.parent = up(L.result_bytes);
-  L.root = L.parent + up(n * sizeof(int32_t));
-  L.flags = L.root + up(n * sizeof(int32_t));
-  L.prefix = L.flags + up(w * sizeof(uint64_t));
-  L.attach = L.prefix + up(w * sizeof(int32_t));
-  L.total = L.attach + up(n * sizeof(uint32_t));
-  return L;
-}
-// the graph of launch_clusters under the core rule (degree + 1 >= min_samples); pair lists: each unordered pair once
+// the graph of launch_clusters under the core rule (degree + 1 >= min_samples); pair lists: each unordered pair once;
+// `work` holds cluster_layout(N, true).total bytes
 int launch_dbscan(const ClusterGraph &g, int64_t N, int64_t min_samples, DevBuf &work);
 int warm_clusters();
 // ---- fc_symm.hip -----------------------------------------------------------------------------------------

@@ -66,6 +66,38 @@ def _unsort(mask_sorted, order):
     return mask
 
 
+def _structures_and_atoms(structures, atoms):
+    """the two array arguments of every driver, checked against each other"""
+    structures = L.f64(structures)
+    if structures.ndim != 3 or structures.shape[2] != 3:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {structures.shape}")
+    atoms = np.asarray(atoms)
+    if atoms.shape[0] != structures.shape[1]:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "len(atoms) != number of atoms")
+    return structures, atoms
+
+
+def _graph_inputs(structures, atoms, max_rmsd, max_dev, energies, max_dE, heavy_atoms_only, enant, symmetry):
+    """What ``cluster_by_rmsd`` and ``dbscan_by_rmsd`` do in front of the device, in the order in which a bad argument
+    is reported: shapes, the symmetry table, the thresholds; then (not for an empty ensemble, whose caller returns at once)
+    the atom selection and the ascending-energy order
+    -> (structures, table, (max_rmsd, max_dev, max_dE), heavy, order, en_sorted, X = the structures in that order)"""
+    from firecode_amd import symmetry as S
+
+    structures, atoms = _structures_and_atoms(structures, atoms)
+    table = S.resolve(symmetry, atoms, heavy_atoms_only)
+    S.refuse_with_enantiomers(table, enant)
+    if table is not None:
+        S.selected_table(table, (atoms != "H") if heavy_atoms_only else None)
+    thresholds = _thresholds(max_rmsd, max_dev, max_dE)
+    if structures.shape[0] == 0:
+        return structures, table, thresholds, None, None, None, None
+    heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
+    order, en_sorted = _sorted_by_energy(structures, energies)
+    X = structures if order is None else np.ascontiguousarray(structures[order])
+    return structures, table, thresholds, heavy, order, en_sorted, X
+
+
 def prune_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None, max_dE=0.0,
                   debugfunction=None, heavy_atoms_only=True, min_per_group=20, prune_enantiomers=False, symmetry=None):
     """Heavy-atom Kabsch-RMSD pruning: a pair is similar when
@@ -85,12 +117,7 @@ def prune_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None,
 
     t0 = perf_counter()
     enant = L.check_flag("prune_enantiomers", prune_enantiomers)
-    structures = L.f64(structures)
-    if structures.ndim != 3 or structures.shape[2] != 3:
-        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {structures.shape}")
-    atoms = np.asarray(atoms)
-    if atoms.shape[0] != structures.shape[1]:
-        raise L.FirecodeHipInputError(L.FC_E_INVALID, "len(atoms) != number of atoms")
+    structures, atoms = _structures_and_atoms(structures, atoms)
     heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
     table = S.resolve(symmetry, atoms, heavy_atoms_only)
     S.refuse_with_enantiomers(table, enant)
@@ -151,12 +178,7 @@ def select_diverse(structures, atoms, n=None, stop_rmsd=None, heavy_atoms_only=T
     from firecode_amd import symmetry as S
 
     enant = L.check_flag("prune_enantiomers", prune_enantiomers)
-    structures = L.f64(structures)
-    if structures.ndim != 3 or structures.shape[2] != 3:
-        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {structures.shape}")
-    atoms = np.asarray(atoms)
-    if atoms.shape[0] != structures.shape[1]:
-        raise L.FirecodeHipInputError(L.FC_E_INVALID, "len(atoms) != number of atoms")
+    structures, atoms = _structures_and_atoms(structures, atoms)
     N = structures.shape[0]
     if n is None and stop_rmsd is None:
         raise L.FirecodeHipInputError(L.FC_E_INVALID, "select_diverse needs n, stop_rmsd or both")
@@ -202,27 +224,13 @@ def cluster_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=Non
     (K,) int64 indices into ``structures``; sizes (K,) int64.  A cluster's representative is its first member in
     processing order -- lowest energy (earliest on ties) when ``energies`` is usable, lowest index otherwise -- and
     clusters are numbered in the order of their representatives."""
-    from firecode_amd import symmetry as S
-
     t0 = perf_counter()
     enant = L.check_flag("prune_enantiomers", prune_enantiomers)
-    structures = L.f64(structures)
-    if structures.ndim != 3 or structures.shape[2] != 3:
-        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {structures.shape}")
-    atoms = np.asarray(atoms)
-    if atoms.shape[0] != structures.shape[1]:
-        raise L.FirecodeHipInputError(L.FC_E_INVALID, "len(atoms) != number of atoms")
-    table = S.resolve(symmetry, atoms, heavy_atoms_only)
-    S.refuse_with_enantiomers(table, enant)
-    if table is not None:
-        S.selected_table(table, (atoms != "H") if heavy_atoms_only else None)
-    max_rmsd, max_dev, max_dE = _thresholds(max_rmsd, max_dev, max_dE)
+    structures, table, (max_rmsd, max_dev, max_dE), heavy, order, en_sorted, X = _graph_inputs(
+        structures, atoms, max_rmsd, max_dev, energies, max_dE, heavy_atoms_only, enant, symmetry)
     N = structures.shape[0]
     if N == 0:
         return RmsdClusters(np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))
-    heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
-    order, en_sorted = _sorted_by_energy(structures, energies)
-    X = structures if order is None else np.ascontiguousarray(structures[order])
     with L.DeviceEnsemble(X, atom_mask=heavy, center=True) as ens:
         labels_sorted, reps_sorted, sizes, stats = ens.clusters(max_rmsd, max_dev, energies=en_sorted, max_dE=max_dE,
                                                                 prune_enantiomers=enant, symmetry=table)
@@ -240,15 +248,31 @@ def cluster_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=Non
     return RmsdClusters(labels, reps, sizes)
 
 
-def _clusters_from_graph(name, graph, n):
-    labels = np.zeros(n, dtype=np.int32)
-    reps, sizes = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+def _labels_from_graph(name, graph, n, min_samples=None):
+    """the C entry point ``name`` on a checked pair list or bit matrix; ``min_samples``: the density-based forms'"""
     import ctypes as C
 
+    dbscan = min_samples is not None
+    labels = np.zeros(n, dtype=np.int32)
+    reps, sizes = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
     k = C.c_int64(0)
-    args = (L.pw(graph), int(graph.shape[0]), n) if name == "fc_clusters_from_pairs" else (L.pw(graph), n)
-    L.call(name, *args, L.ptr(labels, C.c_int32), L.pi(reps), L.pi(sizes), C.byref(k))
-    return RmsdClusters(labels, reps[:k.value].copy(), sizes[:k.value].copy())
+    args = [L.pw(graph), int(graph.shape[0]), n] if name.endswith("_from_pairs") else [L.pw(graph), n]
+    args += [min_samples] * dbscan + [L.ptr(labels, C.c_int32), L.pi(reps), L.pi(sizes)]
+    if dbscan:
+        core, degrees = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int32)
+        args += [L.pb(core), L.ptr(degrees, C.c_int32)]
+    L.call(name, *args, C.byref(k))
+    reps, sizes = reps[:k.value].copy(), sizes[:k.value].copy()
+    return RmsdDbscan(labels, reps, sizes, core.astype(bool), degrees) if dbscan else RmsdClusters(labels, reps, sizes)
+
+
+def _bit_matrix(bits, n):
+    """a caller's (n, ceil(n/64)) uint64 bit matrix, checked -> contiguous"""
+    bits = np.asarray(bits)
+    if bits.dtype != np.uint64 or bits.ndim != 2 or bits.shape != (n, (n + 63) // 64):
+        raise L.FirecodeHipInputError(
+            L.FC_E_INVALID, f"bits must be ({n}, {(n + 63) // 64}) uint64, got {bits.shape} {bits.dtype}")
+    return np.ascontiguousarray(bits)
 
 
 def _vertex_count(n):
@@ -265,7 +289,7 @@ def clusters_from_pairs(pairs, n):
     (P, 2) integer array of (i, j); ``n`` vertices.  ``i == j`` or an index outside [0, n) is refused before any device
     use.  Returns ``RmsdClusters``: clusters numbered by ascending smallest member, which is their representative."""
     n = _vertex_count(n)
-    return _clusters_from_graph("fc_clusters_from_pairs", _pair_words(pairs, n), n)
+    return _labels_from_graph("fc_clusters_from_pairs", _pair_words(pairs, n), n)
 
 
 def _pair_words(pairs, n):
@@ -294,11 +318,7 @@ def clusters_from_bits(bits, n):
     ``greedy_prune_from_bits`` / ``DeviceEnsemble.simbits`` / ``fc_tfd_simbits`` (fc_clusters_from_bits): an edge
     (i, j) where bit j of row i is set; only bits j > i are read."""
     n = _vertex_count(n)
-    bits = np.asarray(bits)
-    if bits.dtype != np.uint64 or bits.ndim != 2 or bits.shape != (n, (n + 63) // 64):
-        raise L.FirecodeHipInputError(
-            L.FC_E_INVALID, f"bits must be ({n}, {(n + 63) // 64}) uint64, got {bits.shape} {bits.dtype}")
-    return _clusters_from_graph("fc_clusters_from_bits", np.ascontiguousarray(bits), n)
+    return _labels_from_graph("fc_clusters_from_bits", _bit_matrix(bits, n), n)
 
 
 RmsdDbscan = namedtuple("RmsdDbscan", ["labels", "representatives", "sizes", "core", "degrees"])
@@ -323,28 +343,14 @@ def dbscan_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, min_samples=5
     order -- lowest energy when ``energies`` is usable, lowest index otherwise -- with clusters numbered in that order;
     sizes (K,) int64, core and border members; core (N,) bool; degrees (N,) int32, the number of neighbours of each
     conformer: its local density at ``max_rmsd``.  ``min_samples=1`` gives the clusters of ``cluster_by_rmsd``."""
-    from firecode_amd import symmetry as S
-
     t0 = perf_counter()
     enant = L.check_flag("prune_enantiomers", prune_enantiomers)
     min_samples = L.check_min_samples(min_samples)
-    structures = L.f64(structures)
-    if structures.ndim != 3 or structures.shape[2] != 3:
-        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"structures must be (N, A, 3), got {structures.shape}")
-    atoms = np.asarray(atoms)
-    if atoms.shape[0] != structures.shape[1]:
-        raise L.FirecodeHipInputError(L.FC_E_INVALID, "len(atoms) != number of atoms")
-    table = S.resolve(symmetry, atoms, heavy_atoms_only)
-    S.refuse_with_enantiomers(table, enant)
-    if table is not None:
-        S.selected_table(table, (atoms != "H") if heavy_atoms_only else None)
-    max_rmsd, max_dev, max_dE = _thresholds(max_rmsd, max_dev, max_dE)
+    structures, table, (max_rmsd, max_dev, max_dE), heavy, order, en_sorted, X = _graph_inputs(
+        structures, atoms, max_rmsd, max_dev, energies, max_dE, heavy_atoms_only, enant, symmetry)
     N = structures.shape[0]
     if N == 0:
         return _empty_dbscan()
-    heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
-    order, en_sorted = _sorted_by_energy(structures, energies)
-    X = structures if order is None else np.ascontiguousarray(structures[order])
     with L.DeviceEnsemble(X, atom_mask=heavy, center=True) as ens:
         labels, reps, sizes, core, degrees, stats = ens.dbscan(max_rmsd, max_dev, min_samples, energies=en_sorted,
                                                                max_dE=max_dE, prune_enantiomers=enant, symmetry=table)
@@ -360,19 +366,6 @@ def dbscan_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, min_samples=5
     return RmsdDbscan(labels, reps, sizes, core, degrees)
 
 
-def _dbscan_from_graph(name, graph, n, min_samples):
-    import ctypes as C
-
-    labels, degrees = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
-    reps, sizes = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
-    core = np.zeros(n, dtype=np.uint8)
-    k = C.c_int64(0)
-    head = (L.pw(graph), int(graph.shape[0]), n) if name == "fc_dbscan_from_pairs" else (L.pw(graph), n)
-    L.call(name, *head, min_samples, L.ptr(labels, C.c_int32), L.pi(reps), L.pi(sizes), L.pb(core), L.ptr(degrees, C.c_int32),
-           C.byref(k))
-    return RmsdDbscan(labels, reps[:k.value].copy(), sizes[:k.value].copy(), core.astype(bool), degrees)
-
-
 def dbscan_from_pairs(pairs, n, min_samples, assume_unique=False):
     """The labelling of ``dbscan_by_rmsd`` on a caller's graph (fc_dbscan_from_pairs): ``pairs`` and ``n`` as
     ``clusters_from_pairs`` takes them, with the same checks before any device use.  Degrees count list entries, so
@@ -386,7 +379,7 @@ def dbscan_from_pairs(pairs, n, min_samples, assume_unique=False):
     if not assume_unique:
         hi, lo = pairs >> np.uint64(32), pairs & np.uint64(0xFFFFFFFF)
         pairs = np.unique((np.minimum(hi, lo) << np.uint64(32)) | np.maximum(hi, lo))
-    return _dbscan_from_graph("fc_dbscan_from_pairs", np.ascontiguousarray(pairs, dtype=np.uint64), n, min_samples)
+    return _labels_from_graph("fc_dbscan_from_pairs", np.ascontiguousarray(pairs, dtype=np.uint64), n, min_samples)
 
 
 def dbscan_from_bits(bits, n, min_samples):
@@ -394,11 +387,7 @@ def dbscan_from_bits(bits, n, min_samples):
     layout and the checks of ``clusters_from_bits``; only bits j > i are read, so no pair can count twice."""
     n = _vertex_count(n)
     min_samples = L.check_min_samples(min_samples)
-    bits = np.asarray(bits)
-    if bits.dtype != np.uint64 or bits.ndim != 2 or bits.shape != (n, (n + 63) // 64):
-        raise L.FirecodeHipInputError(
-            L.FC_E_INVALID, f"bits must be ({n}, {(n + 63) // 64}) uint64, got {bits.shape} {bits.dtype}")
-    return _dbscan_from_graph("fc_dbscan_from_bits", np.ascontiguousarray(bits), n, min_samples)
+    return _labels_from_graph("fc_dbscan_from_bits", _bit_matrix(bits, n), n, min_samples)
 
 
 def rotation_mask(graph, torsion, n_atoms=None):

@@ -12,6 +12,7 @@ import networkx as nx
 import numpy as np
 import pytest
 
+import dbscan_ref as dr
 import symm_ref as sr
 from firecode_amd import synthetic as syn
 from oracle import cpu_ref as o
@@ -267,6 +268,41 @@ def test_overflowed_pair_queue_takes_the_bit_matrix(fc, monkeypatch):
     assert np.array_equal(labels, l0) and np.array_equal(reps, r0) and np.array_equal(sizes, s0) and int(cstats[4]) == 1
     assert np.array_equal(mask_again, mask_sym) and np.array_equal(stats_again[:4], stats[:4])
     assert np.array_equal(mask0, mask_default)
+
+
+def test_overflowed_pair_queue_takes_the_bit_matrix_dbscan(fc, monkeypatch):
+    """the density-based twin of the test above: the degree pass declines the incomplete list on the device and the core
+    rule runs from the bit matrix the same launch wrote; without the cap the pair list gives the same answer"""
+    Y, atoms, table, _ = _case("blocks", 150, 13, 2)
+    mats, _, _ = _reference("blocks", 150, 13, 2)
+    # the case as worked out on the CPU: a graph that quietly stopped overflowing the cap of 64 fails here
+    assert int(np.triu(mats.S, 1).sum()) == 300 and int(np.triu(mats.S_default, 1).sum()) == 79 and mats.min_gap > 0.4
+    assert np.array_equal(mats.S.sum(axis=1) - np.diag(mats.S), np.full(150, 4))
+    want = {m: dr.dbscan_from_matrix(mats.S, m) for m in (1, 5, 6)}
+    for m in (1, 5):
+        assert len(want[m].representatives) == 30 and int(want[m].core.sum()) == 150
+    assert len(want[6].representatives) == 0 and int((want[6].labels < 0).sum()) == 150
+
+    def run(ens, from_bits):
+        got = {m: ens.dbscan(THR, 2 * THR, m, symmetry=table) for m in (1, 5, 6)}
+        for m, (labels, reps, sizes, core, degrees, stats) in got.items():
+            for field, have in zip(dr.RefDbscan._fields, (labels, reps, sizes, core, degrees)):
+                assert np.array_equal(have, getattr(want[m], field)), (from_bits, m, field)
+            assert int(stats[2]) == 300 and int(stats[3]) == 0 and int(stats[4]) == from_bits, (from_bits, m)
+            assert int(stats[5]) == len(reps) and int(stats[6]) == int(core.sum()), (from_bits, m)
+            assert int(stats[7]) == int((labels < 0).sum()), (from_bits, m)
+        return got
+
+    monkeypatch.setenv("FC_PAIRQ_CAP", "64")
+    with fc.DeviceEnsemble(Y, center=True) as ens:
+        capped = run(ens, 1)
+        components = ens.clusters(THR, 2 * THR, symmetry=table)
+        monkeypatch.delenv("FC_PAIRQ_CAP")
+        listed = run(ens, 0)
+    assert int(components[3][4]) == 1 and np.array_equal(capped[1][0], components[0])
+    for m in (1, 5, 6):
+        for a, b in zip(capped[m][:5], listed[m][:5]):
+            assert a.dtype == b.dtype and np.array_equal(a, b), m
 
 
 # ---- 3. the OR of complete tests -----------------------------------------------------------------------------------------

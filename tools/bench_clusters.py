@@ -83,7 +83,7 @@ def random_pairs(n_edges, seed):
 def measure_graph(n_edges, steps, windows):
     pairs = random_pairs(n_edges, seed=n_edges % 1000)
     def label():
-        return fc.pruner._clusters_from_graph("fc_clusters_from_pairs", pairs, GRAPH_N)
+        return fc.pruner._labels_from_graph("fc_clusters_from_pairs", pairs, GRAPH_N)
 
     label()  # warm-up
     times = []

@@ -85,8 +85,8 @@ def random_pairs(n_edges, seed):
 
 def measure_graph(n_edges, steps, windows):
     pairs = random_pairs(n_edges, seed=n_edges % 1000)
-    calls = {False: lambda: fc.pruner._clusters_from_graph("fc_clusters_from_pairs", pairs, GRAPH_N),
-             True: lambda: fc.pruner._dbscan_from_graph("fc_dbscan_from_pairs", pairs, GRAPH_N, M)}
+    calls = {False: lambda: fc.pruner._labels_from_graph("fc_clusters_from_pairs", pairs, GRAPH_N),
+             True: lambda: fc.pruner._labels_from_graph("fc_dbscan_from_pairs", pairs, GRAPH_N, M)}
     times = {False: [], True: []}
     got = {}
     for dbscan in (False, True):  # warm-up
