@@ -180,6 +180,8 @@ _SIGNATURES = {
     "fc_bench_select_diverse_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, _i64, _i64, _f64, _i64, _p_f64, _p_f64,
                                      _p_i64, _p_i64, _p_i64],
     "fc_prune_rmsd_many": [C.POINTER(_ens), _i64, _f64, _f64, _i64, C.POINTER(_p_u8), _p_i64],
+    "fc_ensemble_knn": [_ens, _i64, C.POINTER(C.c_int32), _p_f64],
+    "fc_bench_knn": [_ens, _i64, _i64, _p_f64, _p_f64, _p_i64],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("fc_last_error",)
@@ -424,6 +426,22 @@ def check_min_samples(value):
     return int(value)
 
 
+KNN_MAX = 64  # FC_KNN_MAX (include/fc_hip.h)
+
+
+def check_knn_k(value, limit=True):
+    """``k`` of the nearest-neighbour lists: a real integer >= 1, checked before any device use (``2.5`` or ``True``
+    would otherwise be truncated into another list length); above FC_KNN_MAX the refusal is FC_E_LIMIT -- made here
+    with ``limit``, left to the library (which makes it before any device use too) without."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or int(value) < 1:
+        raise FirecodeHipInputError(FC_E_INVALID, f"k must be an integer >= 1, got {value!r}")
+    if int(value) >= 2 ** 63:
+        raise FirecodeHipInputError(FC_E_INVALID, f"k={value!r} does not fit 64 bits")
+    if limit and int(value) > KNN_MAX:
+        raise FirecodeHipInputError(FC_E_LIMIT, f"k={value!r} neighbours: at most FC_KNN_MAX = {KNN_MAX}")
+    return int(value)
+
+
 class DeviceEnsemble:
     """HBM-resident prepared ensemble (fc_ensemble)."""
 
@@ -555,6 +573,22 @@ class DeviceEnsemble:
         call("fc_bench_select_diverse", self.handle, int(n_max), int(start), stop, int(reps), C.byref(dev),
              C.byref(host), pi(idx), C.byref(k), C.byref(lanes))
         return dev.value, host.value, idx[:k.value], lanes.value
+
+    def knn(self, k):
+        """The ``k`` nearest neighbours of every conformer under this ensemble's RMSD (fc_ensemble_knn; the contract is
+        in include/fc_hip.h) -> ``(indices (N, k) int32, distances (N, k) float64)``, each row in ascending order of
+        (distance, index), the conformer itself left out; rows longer than N - 1 end in -1 / +inf.  No N x N matrix."""
+        k = check_knn_k(k, limit=False)
+        shape = (self.N, k) if k <= KNN_MAX else (1, 1)  # (beyond the limit the library refuses before it writes)
+        idx, dist = np.empty(shape, dtype=np.int32), np.empty(shape)
+        call("fc_ensemble_knn", self.handle, k, ptr(idx, C.c_int32), pf(dist))
+        return idx, dist
+
+    def bench_knn(self, k, reps=3):
+        """``reps`` calls of ``knn(k)`` -> (mean device ms, mean host ms, column strips of the launch)"""
+        dev, host, strips = C.c_double(0), C.c_double(0), C.c_int64(0)
+        call("fc_bench_knn", self.handle, check_knn_k(k, limit=False), int(reps), C.byref(dev), C.byref(host), C.byref(strips))
+        return dev.value, host.value, strips.value
 
     def rmsd_matrix(self):
         r = np.zeros((self.N, self.N))

@@ -827,6 +827,49 @@ int fc_bench_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, doub
   return FC_OK;
 }
 
+// ---- k nearest neighbours under the RMSD (the contract: include/fc_hip.h; the kernels: fc_knn.hip) ------------------
+static int knn_checked(fc_ensemble *ens, int64_t k, int32_t *indices_out, double *dist_out, double *ms_device,
+                       int64_t *strips_out) {
+  FC_REQUIRE(ens != nullptr, "ens is NULL");
+  FC_REQUIRE(indices_out != nullptr && dist_out != nullptr, "indices_out / dist_out is NULL");
+  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
+  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
+  FC_REQUIRE(ens->epoch == ctx().epoch, "this ensemble was created before fc_shutdown / a device switch: create it again");
+  if (strips_out) *strips_out = 0;
+  if (ms_device) *ms_device = 0.0;
+  if (ens->N == 0) return FC_OK;
+  FC_REQUIRE(ens->N <= (int64_t)INT32_MAX - 256, "N=%lld: the lists index conformers with 32 bits", (long long)ens->N);
+  FC_TRY(ensure_init());
+  return knn(ens, k, indices_out, dist_out, ms_device, strips_out);
+}
+
+int fc_ensemble_knn(fc_ensemble *ens, int64_t k, int32_t *indices_out, double *dist_out) {
+  FC_API_LOCK;
+  return knn_checked(ens, k, indices_out, dist_out, nullptr, nullptr);
+}
+
+int fc_bench_knn(fc_ensemble *ens, int64_t k, int64_t reps, double *ms_device_mean, double *ms_host_mean,
+                 int64_t *strips_out) {
+  FC_API_LOCK;
+  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
+  FC_REQUIRE(ens != nullptr, "ens is NULL");
+  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
+  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
+  std::vector<int32_t> idx((size_t)ens->N * (size_t)k + 1);
+  std::vector<double> dist((size_t)ens->N * (size_t)k + 1);
+  double dev = 0.0, host = 0.0;
+  for (int64_t r = 0; r < reps; ++r) {
+    double ms = 0.0;
+    const auto t0 = std::chrono::steady_clock::now();
+    FC_TRY(knn_checked(ens, k, idx.data(), dist.data(), &ms, strips_out));
+    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    dev += ms;
+  }
+  *ms_device_mean = dev / (double)reps;
+  *ms_host_mean = host / (double)reps;
+  return FC_OK;
+}
+
 int fc_ensemble_rmsd_matrix(fc_ensemble *ens, double *rmsd_out, double *maxdev_out) {
   FC_API_LOCK;
   FC_REQUIRE(ens && rmsd_out && maxdev_out, "NULL pointer argument");

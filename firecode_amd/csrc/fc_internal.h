@@ -218,6 +218,10 @@ int launch_symm_simbits(fc_ensemble *e, const uint16_t *perms_dev, int64_t K, do
 int launch_symm_pairs(const fc_ensemble *e, const uint16_t *perms_dev, int64_t K, const int64_t *pi_dev,
                       const int64_t *pj_dev, int64_t P, double *rmsd_dev, double *maxdev_dev);  // (P, K) outputs
 int warm_symm();
+// ---- fc_knn.hip ------------------------------------------------------------------------------------------
+int knn_strips(int64_t N);  // column strips of the launch at N conformers (FC_KNN_STRIPS forces it)
+int knn(fc_ensemble *e, int64_t k, int32_t *indices_out, double *dist_out, double *ms_device, int64_t *strips_out);
+int warm_knn();
 // ---- fc_tfd_ladder.hip -----------------------------------------------------------------------------------
 int tfd_ladder_device(const int64_t *fm_dev, const int64_t *fm_host, int64_t N, uint8_t *mask_out);
 int pyset_order_pairs_device(const int64_t *pairs_host, int64_t n, int64_t *order_out);

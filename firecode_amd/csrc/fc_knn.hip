@@ -1,0 +1,295 @@
+// fc_knn.hip -- k nearest neighbours of every conformer under the ensemble's Kabsch RMSD, over a resident ensemble and
+// without an N x N matrix, for gfx950 (wave64, float64).
+//
+// The contract (include/fc_hip.h, fc_ensemble_knn) -- d(i, j) is the heavy-atom Kabsch RMSD of the
+// ensemble, the d of the diverse selection (fc_diverse.hip):
+//
+//   for every conformer i: the k conformers j != i with the smallest d(i, j), in ascending order of (d(i, j), j) --
+//   equal distances: the lower index first, inside the list and at its cut; slots beyond N - 1: index -1, distance +inf.
+//
+// k_knn_tile -- grid: row tiles x column strips.  A workgroup (4 wavefronts) takes kKnnTileRows = 16 rows, stages their
+// selected atoms (the centred conformer-major copy Xa, 24 B per atom) in LDS up to kKnnLdsAtoms atoms and reads them
+// from global memory beyond; each WAVEFRONT owns kKnnR = 4 of the rows and walks the strip's columns 64 at a time, one
+// lane per column conformer, the column's coordinates read from the conformer-minor Xs (coalesced over conformers):
+//   1. the covariances of the column with the 4 rows in one atom loop -- one load of the column's atom serves 4 rows,
+//      the row atoms are wave-uniform (LDS broadcasts);
+//   2. per row, the filter: the Newton eigenvalue of the covariance gives A msd = (Gi + Gj) - 2 lambda, never above the
+//      explicit sum by more than rounding (the iteration comes down from above, also where it stalls); when it exceeds
+//      A tau^2 -- tau the row's current k-th distance -- by more than the margin for EVERY column of the chunk, none of
+//      them can enter the row's list and the rest of the row is skipped (wave-uniform).  The eigenvalue decides nothing
+//      else: FC_KNN_FILTER=0 takes every pair through step 3 and gives the same bits;
+//   3. otherwise the rotation -- kabsch_rotation_qcp (Newton eigenvalue + adjugate eigenvector), the Jacobi sweeps of
+//      kabsch_rotation where the eigenvalue is not clearly simple, as k_diverse_step -- and the explicit rotated
+//      difference in a second atom loop, pair_exact_aos's sums: the value that is written out is never the eigenvalue
+//      form, which cancels for near neighbours;
+//   4. lanes whose (d, j) comes before the row's current k-th entry are found by a ballot and inserted one at a time
+//      into the row's running list.
+// The running list of a row is a sorted top-64 held ONE SLOT PER LANE in the registers of the wavefront that owns the
+// row (4 rows: 12 registers): an insertion is a ballot (the position), one shift by a lane and a select; the threshold
+// is slot k - 1.  A row's list within a strip has one owner, so nothing is shared between wavefronts: no atomics, no
+// order dependence.  The full square is computed, not the triangle -- d(i, j) is evaluated once as (row i, column j) and
+// once as (row j, column i), twice the arithmetic -- for exactly that reason: a triangular form would hand each distance to
+// two lists owned by different workgroups.
+// d(i, j) is one fixed instruction sequence over the atoms in order: it does not depend on the tile, the strip or the
+// lane a pair falls into (rows and columns past the end are computed as copies of conformer N - 1 and dropped), so two
+// columns with bitwise-identical coordinates give bitwise-identical distances in a row, and the outputs are the same
+// bits for every strip count.
+//
+// Each (row, strip) writes its sorted partial list; k_knn_merge -- one wavefront per row -- offers the S partial lists
+// of the row to one list by the same insertion and writes the outputs (-1 for the unfilled slots).  The entries of a
+// row are distinct in j, so the merged list does not depend on the order of the strips.
+#include "fc_internal.h"
+#include "fc_kabsch_math.h"
+
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+
+namespace fc {
+
+constexpr int kKnnThreads = 256;
+constexpr int kKnnR = 4;                                     // rows per wavefront
+constexpr int kKnnTileRows = (kKnnThreads / 64) * kKnnR;     // rows per workgroup
+constexpr int64_t kKnnLdsAtoms = 256;                        // 16 rows x A x 24 B = 96 KiB of LDS
+static_assert(FC_KNN_MAX == 64, "a row's list is one slot per lane of a wavefront");
+// The filter's margin on A * msd, beside A * kScreenMargin: the eigenvalue form (Gp + Gq) - 2 lambda and the explicit sum
+// differ by the rounding of G, of the covariance and of Newton's last step, a few (2 A + 10) u (Gp + Gq) -- 7e-12 of
+// (Gp + Gq) at the 32 767 atoms a conformer can have
+constexpr double kKnnFilterRel = 1e-10;
+
+// (d1, j1) comes before (d2, j2): smaller distance first, lower index on ties
+__device__ __forceinline__ bool knn_before(double d1, int j1, double d2, int j2) {
+  return d1 < d2 || (d1 == d2 && j1 < j2);
+}
+
+// Offer each lane's (d, j) -- where ok -- to a row's list: (ld, lj) is this lane's slot of the sorted top-64, (td, tj)
+// slot k - 1, the threshold.  Called by all 64 lanes.  Survivors are taken in lane order, each re-tested against the
+// threshold the insertions before it left.
+__device__ __forceinline__ void knn_offer(double &ld, int &lj, double &td, int &tj, double d, int j, bool ok, int k,
+                                          int lane) {
+  for (;;) {
+    const unsigned long long m = __ballot(ok && knn_before(d, j, td, tj));
+    if (m == 0) break;
+    const int src = __ffsll((long long)m) - 1;
+    const double nd = __shfl(d, src);
+    const int nj = __shfl(j, src);
+    const int pos = __popcll(__ballot(knn_before(ld, lj, nd, nj)));  // the list is sorted: entries before the new one
+    const double pd = __shfl_up(ld, 1);
+    const int pj = __shfl_up(lj, 1);
+    if (lane == pos) ld = nd, lj = nj;
+    else if (lane > pos) ld = pd, lj = pj;
+    if (lane == src) ok = false;
+    td = __shfl(ld, k - 1);
+    tj = __shfl(lj, k - 1);
+  }
+}
+
+template <bool STAGE>
+__global__ void __launch_bounds__(kKnnThreads)
+k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const double *__restrict__ G, int N, int64_t Npad, int A,
+           int k, int filter, int n_tiles, int n_chunks, double *__restrict__ part_d, int32_t *__restrict__ part_j) {
+  extern __shared__ double s_rows[];  // [kKnnTileRows][A][3] when STAGE
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int S = gridDim.y, s = blockIdx.y;
+  // the strip's chunks of 64 columns
+  const int c0 = (int)((int64_t)s * n_chunks / S), c1 = (int)((int64_t)(s + 1) * n_chunks / S);
+  const int A3 = 3 * A;
+  const double dA = (double)A;
+
+  for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int row0 = tile * kKnnTileRows;
+    if (STAGE) {
+      __syncthreads();  // (the previous tile's readers)
+      for (int r = w; r < kKnnTileRows; r += kKnnThreads / 64) {
+        const double *__restrict__ src = Xa + (int64_t)min(row0 + r, N - 1) * A3;
+        for (int t = lane; t < A3; t += 64) s_rows[r * A3 + t] = src[t];
+      }
+      __syncthreads();
+    }
+    const int wrow = row0 + w * kKnnR;
+    if (wrow < N) {  // (wave-uniform)
+      int row[kKnnR];
+      const double *__restrict__ P[kKnnR];
+      double Gi[kKnnR], ld[kKnnR], td[kKnnR];
+      int lj[kKnnR], tj[kKnnR];
+#pragma unroll
+      for (int r = 0; r < kKnnR; ++r) {
+        row[r] = wrow + r;
+        const int rl = min(row[r], N - 1);
+        P[r] = STAGE ? s_rows + (w * kKnnR + r) * A3 : Xa + (int64_t)rl * A3;
+        Gi[r] = G[rl];
+        ld[r] = td[r] = INFINITY;
+        lj[r] = tj[r] = INT_MAX;
+      }
+      for (int c = c0; c < c1; ++c) {
+        const int j = c * 64 + lane;
+        const int jl = min(j, N - 1);
+        const double *__restrict__ q0 = Xs + jl;
+        const int64_t step = 3 * Npad;
+        // ---- 1. covariances with the 4 rows
+        double B[kKnnR][9];
+#pragma unroll
+        for (int r = 0; r < kKnnR; ++r)
+#pragma unroll
+          for (int e = 0; e < 9; ++e) B[r][e] = 0.0;
+        {
+          const double *__restrict__ qa = q0;
+#pragma unroll 2
+          for (int a = 0; a < A; ++a, qa += step) {
+            const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
+#pragma unroll
+            for (int r = 0; r < kKnnR; ++r) {
+              const double px = P[r][a * 3], py = P[r][a * 3 + 1], pz = P[r][a * 3 + 2];
+              B[r][0] = fma(px, qx, B[r][0]); B[r][1] = fma(px, qy, B[r][1]); B[r][2] = fma(px, qz, B[r][2]);
+              B[r][3] = fma(py, qx, B[r][3]); B[r][4] = fma(py, qy, B[r][4]); B[r][5] = fma(py, qz, B[r][5]);
+              B[r][6] = fma(pz, qx, B[r][6]); B[r][7] = fma(pz, qy, B[r][7]); B[r][8] = fma(pz, qz, B[r][8]);
+            }
+          }
+        }
+        // ---- 2. per row: the filter, and where a lane passes it the rotation, the explicit rotated difference and the list
+        const double Gj = G[jl];
+#pragma unroll
+        for (int r = 0; r < kKnnR; ++r) {
+          const bool ok = j < N && j != row[r] && row[r] < N;  // the self-pair is left out by index
+          const double GG = Gi[r] + Gj;
+          bool may = ok;
+          if (filter) {  // (a NaN passes)
+            const double msdA = GG - 2.0 * kabsch_lambda_max(B[r], GG);
+            may = ok && !(msdA > dA * td[r] * td[r] + (dA * kScreenMargin + kKnnFilterRel * GG));
+          }
+          if (__ballot(may) == 0) continue;  // (wave-uniform) no column of this chunk can enter the row's list
+          double R[9];
+          if (!kabsch_rotation_qcp(B[r], GG, R)) (void)kabsch_rotation(B[r], R);
+          double ssq = 0.0;
+          const double *__restrict__ qa = q0;
+#pragma unroll 2
+          for (int a = 0; a < A; ++a, qa += step) {
+            const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
+            const double px = P[r][a * 3], py = P[r][a * 3 + 1], pz = P[r][a * 3 + 2];
+            const double dx = px - (R[0] * qx + R[1] * qy + R[2] * qz);
+            const double dy = py - (R[3] * qx + R[4] * qy + R[5] * qz);
+            const double dz = pz - (R[6] * qx + R[7] * qy + R[8] * qz);
+            ssq += dx * dx + dy * dy + dz * dz;
+          }
+          knn_offer(ld[r], lj[r], td[r], tj[r], sqrt(ssq / dA), j, ok, k, lane);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < kKnnR; ++r)
+        if (row[r] < N && lane < k) {
+          const int64_t at = ((int64_t)row[r] * S + s) * k + lane;
+          part_d[at] = ld[r];
+          part_j[at] = lj[r];
+        }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kKnnThreads)
+k_knn_merge(const double *__restrict__ part_d, const int32_t *__restrict__ part_j, int N, int S, int k,
+            int32_t *__restrict__ idx_out, double *__restrict__ dist_out) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  constexpr int kWaves = kKnnThreads / 64;
+  for (int64_t row = (int64_t)blockIdx.x * kWaves + w; row < N; row += (int64_t)gridDim.x * kWaves) {  // (wave-uniform)
+    double ld = INFINITY, td = INFINITY;
+    int lj = INT_MAX, tj = INT_MAX;
+    for (int s = 0; s < S; ++s) {
+      const int64_t at = (row * S + s) * k + lane;
+      const double d = lane < k ? part_d[at] : INFINITY;
+      const int j = lane < k ? part_j[at] : INT_MAX;
+      if (s == 0) {  // a sorted list as it is
+        ld = d, lj = j;
+        td = __shfl(ld, k - 1), tj = __shfl(lj, k - 1);
+      } else {
+        knn_offer(ld, lj, td, tj, d, j, j != INT_MAX, k, lane);
+      }
+    }
+    if (lane < k) {
+      idx_out[row * k + lane] = lj == INT_MAX ? -1 : lj;
+      dist_out[row * k + lane] = ld;
+    }
+  }
+}
+
+// column strips of a launch over N conformers: enough workgroups to fill the chip at small N; FC_KNN_STRIPS=<n> forces
+// it (speed only: the outputs are the same bits for every value)
+int knn_strips(int64_t N) {
+  const int64_t n_chunks = std::max<int64_t>(1, ceil_div(N, 64));
+  int64_t S = 0;
+  if (const char *v = getenv("FC_KNN_STRIPS")) {
+    char *end = nullptr;
+    const long long f = strtoll(v, &end, 10);
+    if (end != v && *end == 0 && f >= 1) S = std::min<long long>(f, kKnnMaxStrips);
+  }
+  if (S == 0) {
+    const int64_t tiles = std::max<int64_t>(1, ceil_div(N, kKnnTileRows));
+    S = std::min<int64_t>(kKnnMaxStrips, ceil_div((int64_t)kKnnWorkgroupsPerCu * std::max(1, ctx().n_cu), tiles));
+  }
+  return (int)std::max<int64_t>(1, std::min(S, n_chunks));
+}
+
+// FC_KNN_FILTER=0: the explicit pass for every pair (speed only: the outputs are the same bits either way)
+static int knn_filter() {
+  const char *v = getenv("FC_KNN_FILTER");
+  return !(v && v[0] == '0' && v[1] == 0);
+}
+
+template <bool STAGE>
+static int launch_knn_tile(const fc_ensemble *e, int k, int filter, int n_tiles, int n_chunks, int S, double *part_d, int32_t *part_j) {
+  const size_t lds = STAGE ? (size_t)kKnnTileRows * e->A * 3 * sizeof(double) : 0;
+  FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_knn_tile<STAGE>), lds, "k_knn_tile"));
+  const unsigned gx = (unsigned)std::min<int64_t>(n_tiles, (int64_t)1 << 20);
+  hipLaunchKernelGGL((k_knn_tile<STAGE>), dim3(gx, (unsigned)S), dim3(kKnnThreads), lds, ctx().stream, e->Xs.as<double>(),
+                     e->Xa.as<double>(), e->G.as<double>(), (int)e->N, e->Npad, (int)e->A, k, filter, n_tiles, n_chunks, part_d, part_j);
+  return check_launch("k_knn_tile");
+}
+
+static int knn_enqueue(fc_ensemble *e, int k, int S, int32_t *indices_out, double *dist_out, double *ms_device, DevBuf &pd,
+                       DevBuf &pj, DevBuf &oi, DevBuf &od) {
+  const int64_t N = e->N;
+  const int n_tiles = (int)ceil_div(N, kKnnTileRows), n_chunks = (int)ceil_div(N, 64);
+  const size_t entries = (size_t)N * (size_t)k;
+  FC_TRY(pd.reserve(entries * (size_t)S * sizeof(double)));
+  FC_TRY(pj.reserve(entries * (size_t)S * sizeof(int32_t)));
+  FC_TRY(oi.reserve(entries * sizeof(int32_t)));
+  FC_TRY(od.reserve(entries * sizeof(double)));
+  Context &c = ctx();
+  const int filter = knn_filter();
+  if (ms_device) FC_HIP_TRY(hipEventRecord(c.ev0, c.stream));
+  if (e->A <= kKnnLdsAtoms) FC_TRY(launch_knn_tile<true>(e, k, filter, n_tiles, n_chunks, S, pd.as<double>(), pj.as<int32_t>()));
+  else FC_TRY(launch_knn_tile<false>(e, k, filter, n_tiles, n_chunks, S, pd.as<double>(), pj.as<int32_t>()));
+  const unsigned gm = (unsigned)std::min<int64_t>(ceil_div(N, kKnnThreads / 64), (int64_t)1 << 20);
+  hipLaunchKernelGGL(k_knn_merge, dim3(gm), dim3(kKnnThreads), 0, c.stream, pd.as<double>(), pj.as<int32_t>(), (int)N, S, k,
+                     oi.as<int32_t>(), od.as<double>());
+  FC_TRY(check_launch("k_knn_merge"));
+  if (ms_device) FC_HIP_TRY(hipEventRecord(c.ev1, c.stream));
+  FC_TRY(d2h(indices_out, oi.p, entries * sizeof(int32_t)));
+  FC_TRY(d2h(dist_out, od.p, entries * sizeof(double)));
+  FC_TRY(sync());
+  if (ms_device) {
+    float ms = 0.0f;
+    FC_HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+    *ms_device = ms;
+  }
+  return FC_OK;
+}
+
+// The lists behind fc_ensemble_knn (arguments checked there; N >= 1, 1 <= k <= FC_KNN_MAX).  ms_device (may be NULL):
+// HIP-event time from the first launch to the end of the merge; strips_out (may be NULL): the strip count used.
+int knn(fc_ensemble *e, int64_t k, int32_t *indices_out, double *dist_out, double *ms_device, int64_t *strips_out) {
+  const int S = knn_strips(e->N);
+  if (strips_out) *strips_out = S;
+  DevBuf pd, pj, oi, od;
+  const int rc = knn_enqueue(e, (int)k, S, indices_out, dist_out, ms_device, pd, pj, oi, od);
+  // an error behind a launch: nothing of the four buffers may be in flight when they go back to the pool
+  if (rc != FC_OK && ctx().ready) (void)hipStreamSynchronize(cur_stream());
+  return rc;
+}
+
+__global__ void k_warm_knn() {}
+int warm_knn() {
+  hipLaunchKernelGGL(k_warm_knn, dim3(1), dim3(64), 0, ctx().stream);
+  return check_launch("k_warm_knn");
+}
+
+}  // namespace fc

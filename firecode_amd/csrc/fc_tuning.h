@@ -37,5 +37,10 @@ namespace fc {
 // us per step 1 lane / 8 lanes): 1 000: 14.9 / 10.7, 3 000: 15.2 / 11.1, 10 000: 15.5 / 15.4, 30 000: 22.9 / 24.9,
 // 100 000: 38.9 / 83.3.  FC_DIVERSE_LANES=1 / 8 forces either form at run time.
 constexpr int64_t kDiverseLanes8MaxN = 10000;
+// fc_knn.hip: the columns of a launch are cut into strips until the grid (row tiles of 16 conformers x strips) holds this
+// many workgroups per CU, at most kKnnMaxStrips and at most one strip per 64 columns.  FC_KNN_STRIPS=<n> forces the
+// strip count at run time; the outputs are the same bits for every value.
+constexpr int kKnnWorkgroupsPerCu = 4;
+constexpr int kKnnMaxStrips = 64;
 }  // namespace fc
 #endif

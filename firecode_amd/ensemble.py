@@ -137,6 +137,14 @@ class Ensemble:
                 f"{perf_counter() - t0:.3f} s)")
         return sel
 
+    def nearest_neighbours(self, k, heavy_atoms_only=True):
+        """The ``k`` nearest neighbours of every structure under the heavy-atom RMSD of the other RMSD stages
+        (``firecode_amd.pruner.knn_by_rmsd``).  Returns the ``RmsdNeighbours``, whose ``k_distances(min_samples - 1)`` is
+        the curve one reads the ``max_rmsd`` of ``dbscan_by_rmsd`` from; the ensemble is not masked."""
+        from firecode_amd.pruner import knn_by_rmsd
+
+        return knn_by_rmsd(self.coords, self.atoms, k, heavy_atoms_only=heavy_atoms_only)
+
     def cluster_by_rmsd(self, max_rmsd=None, heavy_atoms_only=True, prune_enantiomers=False, verbose=True, symmetry=None):
         """Which conformers belong together (``firecode_amd.pruner.cluster_by_rmsd``): the connected components of the
         graph the RMSD stage of ``similarity_pruning`` prunes, with its energies and window (``max_dE = 1.0`` when there is

@@ -208,6 +208,62 @@ def select_diverse(structures, atoms, n=None, stop_rmsd=None, heavy_atoms_only=T
                                                     prune_enantiomers=enant))
 
 
+class RmsdNeighbours(namedtuple("RmsdNeighbours", ["indices", "distances"])):
+    """The lists of ``knn_by_rmsd``: indices (N, k) int32 and distances (N, k) float64, each row in ascending order of
+    (distance, index); slots beyond N - 1 neighbours hold -1 / +inf.  The two methods are host-side NumPy."""
+
+    __slots__ = ()
+
+    def k_distances(self, k=None):
+        """The distance of every conformer to its ``k``-th neighbour (column ``k - 1``; default: the last), sorted in
+        descending order: the "k-distance" curve whose knee is the DBSCAN radius for ``min_samples = k + 1``."""
+        dist = np.asarray(self.distances)
+        width = dist.shape[1]
+        if k is None:
+            k = width
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= width:
+            raise L.FirecodeHipInputError(L.FC_E_INVALID, f"k={k!r}: an integer in [1, {width}], the lists' length")
+        return np.sort(dist[:, int(k) - 1])[::-1].copy()
+
+    def pairs(self, mutual=False):
+        """The neighbour graph as an undirected edge list (M, 2) int64 with ``i < j``, unique, sorted -- what
+        ``clusters_from_pairs`` / ``dbscan_from_pairs`` take: {i, j} is an edge when j is in i's list or i in j's;
+        ``mutual=True``: only when both hold.  Entries with index -1 are dropped."""
+        mutual = L.check_flag("mutual", mutual)
+        idx = np.asarray(self.indices).astype(np.int64)
+        n = idx.shape[0]
+        i = np.repeat(np.arange(n, dtype=np.int64), idx.shape[1])
+        j = idx.reshape(-1)
+        keep = j >= 0
+        i, j = i[keep], j[keep]
+        # (a row never names itself and names a conformer at most once: a word occurs once per direction)
+        words, counts = np.unique(np.minimum(i, j) * np.int64(n) + np.maximum(i, j), return_counts=True)
+        if mutual:
+            words = words[counts == 2]
+        return np.stack([words // max(n, 1), words % max(n, 1)], axis=1).astype(np.int64).reshape(-1, 2)
+
+
+def knn_by_rmsd(structures, atoms, k, heavy_atoms_only=True):
+    """The ``k`` nearest neighbours of every conformer under the heavy-atom Kabsch RMSD ``prune_by_rmsd`` uses (centred,
+    ``rmsd_and_max(...)[0]``), on the GPU (fc_ensemble_knn; the contract is written out in include/fc_hip.h), with no
+    N x N matrix: the top-k selection happens in the kernel that computes the distances.  1 <= k <= 64.
+
+    Returns ``RmsdNeighbours(indices, distances)``: (N, k) int32 and (N, k) float64, each row in ascending order of
+    (distance, index) -- on equal distances the lower index first -- the conformer itself left out by index (an exact
+    duplicate of it is its first neighbour, at distance ~1e-15); when ``k > N - 1`` the rows end in -1 / +inf.
+    ``.k_distances(min_samples - 1)`` is the curve one reads the ``max_rmsd`` of ``dbscan_by_rmsd`` from;
+    ``.pairs()`` / ``.pairs(mutual=True)`` is the (mutual) k-NN graph in the format of ``clusters_from_pairs``."""
+    structures, atoms = _structures_and_atoms(structures, atoms)
+    k = L.check_knn_k(k)
+    heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
+    if not heavy.any():
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "the atom selection is empty (no heavy atom)")
+    if structures.shape[0] == 0:
+        return RmsdNeighbours(np.zeros((0, k), dtype=np.int32), np.zeros((0, k)))
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
+        return RmsdNeighbours(*ens.knn(k))
+
+
 RmsdClusters = namedtuple("RmsdClusters", ["labels", "representatives", "sizes"])
 
 

@@ -180,6 +180,34 @@ int fc_ensemble_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, d
 int fc_ensemble_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
                                     int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
                                     double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected);
+/* k nearest neighbours of every conformer under the ensemble's Kabsch RMSD: what shows a sensible
+ * max_rmsd for fc_rmsd_dbscan (the sorted distance to the (min_samples - 1)-th neighbour, the "k-distance" curve) and
+ * feeds local density estimates, outlier scores and mutual-k-NN graphs (fc_clusters_from_pairs takes a caller's graph).
+ * No N x N matrix: the top-k selection happens in the kernel that computes the distances.  The contract:
+ *
+ *   d(i, j) = rmsd_and_max(X[i][sel], X[j][sel], center=True)[0] over the ensemble's atom selection -- the d of
+ *   fc_ensemble_select_diverse.  For every conformer i the list holds the k conformers j != i with the smallest d(i, j),
+ *   in ascending order of (d(i, j), j): on equal distances the lower index comes first, inside the list and at its cut.
+ *
+ * Outputs: indices_out (N, k) int32 and dist_out (N, k) float64, row-major.  1 <= k <= FC_KNN_MAX.  When k > N - 1 the
+ * trailing k - (N - 1) entries of every row are index -1 and distance +inf (N = 1: one row of them); N = 0: nothing is
+ * written.  The self-pair is left out by index, not by value: exact duplicates of i appear in its list.
+ * Determinism: d(i, j) is produced by one fixed instruction sequence over the atoms in order, whatever tile, strip,
+ * wavefront or launch the pair falls into, so two columns with bitwise-identical coordinates give bitwise-identical
+ * distances in a row, and the outputs are bit-identical for every strip count (FC_KNN_STRIPS=<n>, a speed-only knob);
+ * no floating-point atomics.  Bit symmetry d(i, j) == d(j, i) is NOT promised (the two are computed separately).
+ * Every value is the explicit rotated-difference rmsd (pair_exact_aos's sums; the rotation by Newton eigenvalue +
+ * adjugate eigenvector where the eigenvalue is clearly simple, the Jacobi sweeps otherwise, as the diverse selection):
+ * within a few ulp of fc_ensemble_rmsd_pairs, ~1e-15 for a duplicate pair where the eigenvalue form gives ~1e-8.  The
+ * eigenvalue serves only as a conservative filter -- the explicit pass is skipped for columns that provably cannot enter
+ * a row's current list (margin: DESIGN.md section 18) -- and decides no value and no order: FC_KNN_FILTER=0 (speed only)
+ * takes every pair through the explicit pass and gives the same bits.
+ * FC_E_INVALID before any device use: NULL ens or outputs, k < 1; FC_E_LIMIT before any device use: k > FC_KNN_MAX.
+ * Limits: N < 2^31 - 256; no atom limit (a workgroup's 16 row conformers are staged in LDS up to 256 selected atoms and
+ * read from HBM beyond).  Not offered: symmetry- and mirror-aware forms, queries of one ensemble against another,
+ * sharded, multi-GPU and twin-workspace forms. */
+#define FC_KNN_MAX 64
+int fc_ensemble_knn(fc_ensemble *ens, int64_t k, int32_t *indices_out, double *dist_out);
 /* a9: get_alignment_matrix(p, q) -- prism_pruner.rmsd; call site
  * hypermolecule_class.py:77.  M (3,3) row-major, applied as (M @ q.T).T */
 int fc_alignment_matrices(const double *p, const double *q, int64_t n_pairs, int64_t A,
@@ -869,6 +897,11 @@ int fc_bench_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, doub
 int fc_bench_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
                                  int64_t n_max, int64_t start, double stop_rmsd, int64_t reps, double *ms_device_mean,
                                  double *ms_host_mean, int64_t *indices_out, int64_t *n_selected, int64_t *stats);
+/* `reps` calls of fc_ensemble_knn (the same arguments; the lists are copied back each time) one after the other:
+ * ms_device_mean = HIP events on the library's stream from the first launch to the end of the merge, ms_host_mean =
+ * wall-clock time per call; strips_out (may be NULL) = the column strips of the launch. */
+int fc_bench_knn(fc_ensemble *ens, int64_t k, int64_t reps, double *ms_device_mean, double *ms_host_mean,
+                 int64_t *strips_out);
 /* (fc_bench_prune_rmsd writes EIGHT stats: [6] = 16 x 32-pair units the subset stage of the lean fp32
  * screen queued for the full test in the last prune, [7] = 1 when its sample found similarity dense
  * and the single-stage kernel did the launch) */

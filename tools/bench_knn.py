@@ -1,0 +1,136 @@
+#!/usr/bin/env python
+"""k nearest neighbours under the RMSD (fc_ensemble_knn) on one MI355X: one JSON line per workload.
+
+  python tools/bench_knn.py              # the sizes of DESIGN.md section 18: continuous and clustered ensembles at
+                                         # 10^4 x 50 and 10^5 x 50, k = 8 and 64; then, at 10^4 x 50, host arrays in ->
+                                         # lists out against the matrix route (rmsd_values + argpartition on the host)
+  python tools/bench_knn.py --small      # the 10^4 x 50 workloads and the comparison only
+  python tools/bench_knn.py --filter     # the eigenvalue filter against FC_KNN_FILTER=0, alternating, at both sizes
+  python tools/bench_knn.py --strips     # the strip count (FC_KNN_STRIPS) over N at k = 8
+  python tools/bench_knn.py --trace      # one 10^4 x 50 call at k = 8, for rocprofv3 --kernel-trace --stats
+
+Device time: HIP events on the library's stream from the first launch to the end of the merge (a warm-up call first,
+then 3 calls: mean and range).  Rates: ordered alignments (N (N - 1): the full square, whether or not a pair's explicit
+pass ran) per second; the fp64 flops an unfiltered kernel would spend on them at 2 400 per explicit alignment, the
+figure of DESIGN.md section 10, against the vector peak (the kernel's own only with FC_KNN_FILTER=0); first-pass bytes
+of the conformer-minor copy (N^2 A 24 / 4: one column load serves the 4 rows of a wavefront) against 8 TB/s.
+"""
+
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import firecode_amd as fc  # noqa: E402
+from firecode_amd import synthetic as syn  # noqa: E402
+
+A = 50
+FLOPS_PER_ALIGNMENT = 2400.0
+FP64_VECTOR_PEAK = 78.6e12
+HBM_PEAK = 8.0e12
+ROWS_PER_WAVE = 4
+
+
+def ensemble(kind, N, seed):
+    if kind == "clusters":
+        return syn.synthetic_ensemble(N, A, seed=seed)[0]
+    return syn.continuous_ensemble(N, A, seed=seed)
+
+
+def measure(name, X, k, reps=3):
+    N = X.shape[0]
+    with fc.DeviceEnsemble(X, atom_mask=np.ones(X.shape[1], bool), center=True) as ens:
+        ens.bench_knn(k, reps=1)  # warm-up: code objects, pool blocks
+        runs = [ens.bench_knn(k, reps=1) for _ in range(reps)]
+    dev = np.array([r[0] for r in runs])
+    aligned = N * (N - 1)
+    s = dev.mean() * 1e-3
+    out = {"workload": name, "N": N, "A": X.shape[1], "k": k, "strips": runs[0][2],
+           "ms_device_mean": round(float(dev.mean()), 3), "ms_device_min": round(float(dev.min()), 3),
+           "ms_device_max": round(float(dev.max()), 3), "ms_host_call_mean": round(float(np.mean([r[1] for r in runs])), 3),
+           "ordered_alignments": aligned, "alignments_per_s": aligned / s,
+           "unfiltered_fp64_share_of_vector_peak": aligned * FLOPS_PER_ALIGNMENT / s / FP64_VECTOR_PEAK,
+           "xs_first_pass_TBps": N * N * X.shape[1] * 24 / ROWS_PER_WAVE / s / 1e12}
+    out["xs_share_of_hbm_peak"] = out["xs_first_pass_TBps"] * 1e12 / HBM_PEAK
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def matrix_route(X, k):
+    """the only route without fc_ensemble_knn: the whole fp64 matrix to the host, argpartition + sort per row"""
+    with fc.DeviceEnsemble(X, atom_mask=np.ones(X.shape[1], bool), center=True) as ens:
+        R, _ = ens.rmsd_values()
+    np.fill_diagonal(R, np.inf)
+    part = np.argpartition(R, k - 1, axis=1)[:, :k]
+    d = np.take_along_axis(R, part, axis=1)
+    order = np.lexsort((part, d), axis=1)
+    return np.take_along_axis(part, order, axis=1).astype(np.int32), np.take_along_axis(d, order, axis=1)
+
+
+def end_to_end(X, k, reps=3):
+    """host arrays in -> lists out, the two routes alternating in one process"""
+    atoms = np.array(["C"] * X.shape[1])
+    fc.pruner.knn_by_rmsd(X, atoms, k), matrix_route(X, k)  # warm-up of both
+    t_new, t_old, same = [], [], True
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        nb = fc.pruner.knn_by_rmsd(X, atoms, k)
+        t_new.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        idx, _ = matrix_route(X, k)
+        t_old.append(time.perf_counter() - t0)
+        same = same and bool(np.array_equal(idx, nb.indices))
+    print(json.dumps({"workload": f"end to end, {X.shape[0]} x {X.shape[1]}, k = {k}",
+                      "knn_by_rmsd_ms": [round(1e3 * t, 2) for t in t_new],
+                      "matrix_route_ms": [round(1e3 * t, 2) for t in t_old],
+                      "knn_by_rmsd_ms_mean": round(1e3 * float(np.mean(t_new)), 2),
+                      "matrix_route_ms_mean": round(1e3 * float(np.mean(t_old)), 2),
+                      "same_indices": same}), flush=True)
+
+
+def main():
+    fc.init(0)
+    fc._lib.warmup()
+    if "--trace" in sys.argv:
+        with fc.DeviceEnsemble(ensemble("continuous", 10_000, 11), atom_mask=np.ones(A, bool), center=True) as ens:
+            ens.knn(8)
+        return
+    if "--strips" in sys.argv:
+        X5 = ensemble("continuous", 30_000, 12)
+        for N in (1000, 3000, 10_000, 30_000):
+            for strips in ("1", "2", "4", "8", "16", None):
+                if strips is None:
+                    os.environ.pop("FC_KNN_STRIPS", None)
+                else:
+                    os.environ["FC_KNN_STRIPS"] = strips
+                measure(f"strips {strips or 'default'}", X5[:N], 8)
+        return
+    if "--filter" in sys.argv:
+        for N in (10_000, 100_000):
+            X = ensemble("continuous", N, 11 if N == 10_000 else 12)
+            for k in (8, 64):
+                for flag in ("0", None):
+                    if flag is None:
+                        os.environ.pop("FC_KNN_FILTER", None)
+                    else:
+                        os.environ["FC_KNN_FILTER"] = flag
+                    measure(f"continuous {N} x {A}, k = {k}, filter {'off' if flag else 'on'}", X, k)
+        return
+    sizes = (10_000,) if "--small" in sys.argv else (10_000, 100_000)
+    for N in sizes:
+        for kind in ("continuous", "clusters"):
+            X = ensemble(kind, N, 11 if N == 10_000 else 12)
+            for k in (8, 64):
+                measure(f"{kind} {N} x {A}, k = {k}", X, k)
+    X4 = ensemble("continuous", 10_000, 11)
+    for k in (8, 64):
+        end_to_end(X4, k)
+
+
+if __name__ == "__main__":
+    main()
