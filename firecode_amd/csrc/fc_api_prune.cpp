@@ -441,6 +441,7 @@ static int ensemble_twin(fc_ensemble *ens, fc_ensemble **out) {
     t->N = ens->N, t->A = ens->A, t->Npad = ens->Npad, t->W = ens->W;
     t->Xs.alias(ens->Xs), t->Xa.alias(ens->Xa), t->G.alias(ens->G);
     if (ens->xsf_valid) t->Xsf.alias(ens->Xsf), t->sub.alias(ens->sub), t->xsf_valid = true;
+    if (ens->xt_valid) t->Xt.alias(ens->Xt), t->xt_valid = true;
     if (ens->xh_valid) t->Xh.alias(ens->Xh), t->xh_valid = true, t->xh_scale = ens->xh_scale;
     t->g_max = ens->g_max;
     t->head = ens->head ? ens->head : ens;

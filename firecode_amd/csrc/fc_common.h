@@ -356,6 +356,8 @@ struct fc_ensemble {
   fc::DevBuf sub;              // [Npad][8] floats: stage-1 subset statistics per conformer (made with Xsf)
   fc::DevBuf unitq;            // queue of the 16 x 32 units the subset stage could not rule out
   bool xsf_valid = false;
+  fc::DevBuf Xt;               // row-tile-major copy of Xs for the atom pass of the complete alignments (fc_items.h; made on first use)
+  bool xt_valid = false;
   fc::DevBuf Xh;               // split-half copy of Xs for the f16-matrix-pipe screen (made on first use)
   bool xh_valid = false;
   double xh_scale = 0.0;       // the power of two Xh was made with

@@ -1,6 +1,7 @@
 // fc_items.h -- the items of the tiled all-pairs kernels: which (row blocks, column tile) a workgroup takes, in which
 // order.  Pure host arithmetic apart from the two decoders the kernels share; it includes nothing of the GPU runtime, so
 // a host compiler builds it alone (tools/complete_items_check.cpp, tests/test_complete_items_cpu.py).
+// Also here: the layout of Xt, the row-tile-major copy of the ensemble (row_tile_offset; tools/row_tiles_check.cpp).
 #pragma once
 
 #include <algorithm>
@@ -39,6 +40,18 @@ constexpr int kItemChunkShift = 58, kItemChunkMax = 16;
 FC_ITEMS_HD inline int64_t item_tile(uint64_t it) { return (int64_t)(it & 0x7fffffffull); }
 FC_ITEMS_HD inline int64_t item_block(uint64_t it) { return (int64_t)((it >> 32) & 0x3ffffffull); }
 FC_ITEMS_HD inline int item_blocks(uint64_t it) { return (int)((it >> kItemChunkShift) & 15ull) + 1; }
+
+// Xt, the row-tile-major copy of the ensemble that the atom pass of the complete alignments reads its row conformer from
+// (fc_ensemble::Xt, made by k_row_tiles): doubles [t][u][c][r][h] -- t the tile of 16 consecutive conformers (row n lies
+// in tile n / 16), u the pair of atoms (2u, 2u + 1), c the coordinate, r the row inside the tile, h the atom inside the
+// pair.  A wave walks ONE stream of 768 bytes per pair of atoms for its 16 rows: lane r takes its two atoms of a
+// coordinate with one 16-byte load.  Rows n >= N are zero, and so is the second atom of the last pair of an odd A.
+FC_ITEMS_HD inline int64_t row_tile_pairs(int64_t A) { return (A + 1) / 2; }
+FC_ITEMS_HD inline int64_t row_tile_offset(int64_t n, int64_t a, int64_t c, int64_t A) {
+  return (((n >> 4) * row_tile_pairs(A) + (a >> 1)) * 3 + c) * 32 + (n & 15) * 2 + (a & 1);
+}
+// doubles of Xt for Npad (a multiple of 16) rows
+FC_ITEMS_HD inline int64_t row_tile_elems(int64_t Npad, int64_t A) { return (Npad >> 4) * row_tile_pairs(A) * 96; }
 
 struct ItemPlan {
   int64_t N = 0, rank = 0, world = 1;  // conformers; the rows are the row blocks dealt to `rank` of `world`

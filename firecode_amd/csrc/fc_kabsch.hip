@@ -717,7 +717,9 @@ typedef double d4_t __attribute__((ext_vector_type(4)));
 // difference).  The difference carries ~u (Gp + Gq) of rounding, so it holds 5e-11 in the rmsd only for pairs further
 // apart than ~1e-3 A (msd A > 2e-10 (Gp + Gq)^2 / A): closer pairs go to the fix-up kernel like the pairs whose rotation
 // was declined.  EIG = false (the launcher's retry when the fix-up queue overflowed: an ensemble of near-duplicates): the sum.
-template <int NW, int MODE = 0, int TC = 64, bool EIG = false, bool ENANT = false>
+// ROWT (MODE 2): the atom pass reads its row conformer from Xt, the row-tile-major copy (fc_items.h), instead of three rows
+// of Xs per atom; the K loop's row operands stay on Xs.  Same arithmetic in the same order: the outputs are bit-identical.
+template <int NW, int MODE = 0, int TC = 64, bool EIG = false, bool ENANT = false, bool ROWT = false>
 __global__ void __launch_bounds__(NW * 64, 2)
 k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ G, int64_t N,
                       int64_t Npad, int A, double A_thr2, int IB, int64_t rank, int64_t world,
@@ -725,8 +727,9 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
                       unsigned long long *__restrict__ counters, uint64_t *__restrict__ pairq,
                       unsigned long long Q, const uint64_t *__restrict__ item_table, unsigned long long n_items,
                       double *__restrict__ rmsd_out = nullptr, const unsigned long long *__restrict__ gate = nullptr,
-                      double *__restrict__ maxdev_out = nullptr) {
+                      double *__restrict__ maxdev_out = nullptr, const double *__restrict__ Xt = nullptr) {
   static_assert(!EIG || MODE == 2, "EIG: the complete alignments");
+  static_assert(!ROWT || MODE == 2, "ROWT: the complete alignments");
   static_assert(!ENANT || MODE == 0, "ENANT: the screen only");
   constexpr bool VALUES = MODE != 0;  // 1: rmsd values (Newton), 2: (rmsd, maxdev) by explicit difference
   // sub-tiles (16 columns) per unit: two share the row operands in the screens; the complete-alignment
@@ -1065,7 +1068,7 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
           // addressing mode of the load; the compiler takes it only when it can see that the offset is small)
           const double *__restrict__ pa0 = prow_u, *__restrict__ pa1 = prow_u + Npad, *__restrict__ pa2 = prow_u + 2 * Npad;
           const double *__restrict__ qg = qcol;    // the current k-group of the LDS tile
-          auto load_pq = [&](auto u_, double (&P)[3], d2_t (&Qv)[3][2]) {
+          auto load_q = [&](auto u_, d2_t (&Qv)[3][2]) {
             constexpr int u = decltype(u_)::value;  // position of the atom in its k-group
             const double *__restrict__ ql = qg + (u / KPR) * 128 + (u % KPR) * 16;
 #pragma unroll
@@ -1073,6 +1076,9 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
               Qv[c][0] = *reinterpret_cast<const d2_t *>(ql + c * CST);
               Qv[c][1] = *reinterpret_cast<const d2_t *>(ql + c * CST + 2);
             }
+          };
+          auto load_pq = [&](auto u_, double (&P)[3], d2_t (&Qv)[3][2]) {
+            load_q(u_, Qv);
             P[0] = pa0[l15u];
             P[1] = pa1[l15u];
             P[2] = pa2[l15u];
@@ -1080,14 +1086,14 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
             pa1 += Npad3;
             pa2 += Npad3;
           };
-          auto accumulate = [&](const double (&P)[3], const d2_t (&Qv)[3][2]) {
+          auto accumulate3 = [&](const double px, const double py, const double pz, const d2_t (&Qv)[3][2]) {
 #pragma clang fp contract(fast)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const double qx = Qv[0][r >> 1][r & 1], qy = Qv[1][r >> 1][r & 1], qz = Qv[2][r >> 1][r & 1];
-              const double dx = fma(nR[r][0], qx, fma(nR[r][1], qy, fma(nR[r][2], qz, P[0])));
-              const double dy = fma(nR[r][3], qx, fma(nR[r][4], qy, fma(nR[r][5], qz, P[1])));
-              const double dz = fma(nR[r][6], qx, fma(nR[r][7], qy, fma(nR[r][8], qz, P[2])));
+              const double dx = fma(nR[r][0], qx, fma(nR[r][1], qy, fma(nR[r][2], qz, px)));
+              const double dy = fma(nR[r][3], qx, fma(nR[r][4], qy, fma(nR[r][5], qz, py)));
+              const double dz = fma(nR[r][6], qx, fma(nR[r][7], qy, fma(nR[r][8], qz, pz)));
               const double s2 = fma(dz, dz, fma(dy, dy, dx * dx));
               if constexpr (!EIG) ssq[r] += s2;
               // (fmax() first re-quiets its loop-carried operand: one more instruction per pair and atom)
@@ -1098,37 +1104,117 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
           using U1 = std::integral_constant<int, 1>;
           using U2 = std::integral_constant<int, 2>;
           using U3 = std::integral_constant<int, 3>;
-          double PA[3], PB[3];
           d2_t QA[3][2], QB[3][2];
-          load_pq(U0{}, PA, QA);
-          // (the scheduling barriers keep the requests where they are written: the machine scheduler
-          // otherwise gathers the two sets' loads into one burst right in front of their first use)
-          for (int g = 0; g < n_groups; ++g) {
-            load_pq(U1{}, PB, QB);
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate(PA, QA);
-            __builtin_amdgcn_sched_barrier(0);
-            load_pq(U2{}, PA, QA);
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate(PB, QB);
-            __builtin_amdgcn_sched_barrier(0);
-            load_pq(U3{}, PB, QB);
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate(PA, QA);
-            __builtin_amdgcn_sched_barrier(0);
-            qg = TC == 16 ? qcol + koff(g + 1) : qg + 12 * TC;
-            if (g + 1 < n_groups || odd_round) load_pq(U0{}, PA, QA);  // wave-uniform: nothing is read past the last atom row
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate(PB, QB);
-            __builtin_amdgcn_sched_barrier(0);
+#define FC_SB __builtin_amdgcn_sched_barrier(0)
+          if constexpr (ROWT) {
+            // The row conformer from Xt: one wave-uniform base per row tile (advanced once per k-group, with qg), the
+            // lane's fixed offset 16 l15, compile-time offsets inside the k-group -- a 16-byte load per coordinate brings
+            // BOTH atoms of a round, so the register sets are per round (T0: atoms 0, 1 of a k-group, T1: atoms 2, 3), each
+            // requested two atoms ahead of its first use.  The request for the next k-group's T0 is unconditional: behind
+            // a conformer's last round it reads the next tile's first one (Xt ends in one spare round), which nothing uses.
+            const char *__restrict__ pt = reinterpret_cast<const char *>(Xt) + (ib >> 4) * ((int64_t)n_rounds * 768);
+            unsigned lo = l15u * 16u;
+            auto load_t = [&](auto rho_, d2_t (&T)[3]) {
+              constexpr int rho = decltype(rho_)::value;  // round inside the k-group
+              // (the offset passes through an empty asm, as in fetch_a_at: scalar base + 32-bit lane offset + immediate stays
+              // ONE addressing mode of the load instead of a running 64-bit vector pointer)
+              asm volatile("" : "+v"(lo));
+#pragma unroll
+              for (int c = 0; c < 3; ++c) T[c] = *reinterpret_cast<const d2_t *>(pt + lo + (rho * 768 + c * 256));
+            };
+            // ONE wait in front of an atom's arithmetic for everything it reads -- VM / LGKM: requests that may stay in
+            // flight behind the ones it needs (the compiler's own waits, one per operand as the chains reach it, then find
+            // nothing left to wait for).  s_waitcnt of gfx9: vmcnt [3:0] and [15:14], expcnt [6:4], lgkmcnt [11:8].
+            auto wait_for = [&](auto vm_, auto lgkm_) {
+              constexpr int vm = decltype(vm_)::value, lgkm = decltype(lgkm_)::value;
+              __builtin_amdgcn_s_waitcnt((vm & 15) | ((vm >> 4) << 14) | (7 << 4) | (lgkm << 8));
+              FC_SB;  // (the arithmetic does not depend on the wait itself: without the barrier it is scheduled in front of it)
+            };
+            auto accumulate = [&](auto h_, const d2_t (&T)[3], const d2_t (&Qv)[3][2]) {
+              constexpr int h = decltype(h_)::value;
+              accumulate3(T[0][h], T[1][h], T[2][h], Qv);
+            };
+            using W0 = std::integral_constant<int, 0>;
+            using W3 = std::integral_constant<int, 3>;
+            using W6 = std::integral_constant<int, 6>;
+            using WX = std::integral_constant<int, 63>;  // vmcnt: not waited for
+            d2_t T0[3], T1[3];
+            const int g_more = odd_round ? n_groups : n_groups - 1;  // k-groups with atoms behind them
+            load_q(U0{}, QA);
+            load_t(U0{}, T0);
+            for (int g = 0; g < n_groups; ++g) {
+              load_q(U1{}, QB);
+              load_t(U1{}, T1);
+              FC_SB;
+              wait_for(W3{}, W6{});
+              accumulate(U0{}, T0, QA);
+              FC_SB;
+              load_q(U2{}, QA);
+              FC_SB;
+              wait_for(WX{}, W6{});
+              accumulate(U1{}, T0, QB);
+              FC_SB;
+              load_q(U3{}, QB);
+              pt += 1536;
+              load_t(U0{}, T0);
+              FC_SB;
+              wait_for(W3{}, W6{});
+              accumulate(U0{}, T1, QA);
+              FC_SB;
+              // nothing is read past the last atom row: behind the conformer's last k-group the request repeats that group
+              // (unused) instead of branching round it -- a branch here also leaves the compiler two wait states to merge,
+              // which it does by waiting for everything
+              const int gn = g < g_more ? g + 1 : g;
+              qg = TC == 16 ? qcol + koff(gn) : qg + (gn - g) * (12 * TC);
+              load_q(U0{}, QA);
+              FC_SB;
+              wait_for(WX{}, W6{});
+              accumulate(U1{}, T1, QB);
+              FC_SB;
+            }
+            if (odd_round) {  // the last two atoms (the second one may be a zero row)
+              load_q(U1{}, QB);
+              FC_SB;
+              wait_for(W0{}, W6{});
+              accumulate(U0{}, T0, QA);
+              FC_SB;
+              wait_for(WX{}, W0{});
+              accumulate(U1{}, T0, QB);
+            }
+          } else {
+            auto accumulate = [&](const double (&P)[3], const d2_t (&Qv)[3][2]) { accumulate3(P[0], P[1], P[2], Qv); };
+            double PA[3], PB[3];
+            load_pq(U0{}, PA, QA);
+            // (the scheduling barriers keep the requests where they are written: the machine scheduler
+            // otherwise gathers the two sets' loads into one burst right in front of their first use)
+            for (int g = 0; g < n_groups; ++g) {
+              load_pq(U1{}, PB, QB);
+              FC_SB;
+              accumulate(PA, QA);
+              FC_SB;
+              load_pq(U2{}, PA, QA);
+              FC_SB;
+              accumulate(PB, QB);
+              FC_SB;
+              load_pq(U3{}, PB, QB);
+              FC_SB;
+              accumulate(PA, QA);
+              FC_SB;
+              qg = TC == 16 ? qcol + koff(g + 1) : qg + 12 * TC;
+              if (g + 1 < n_groups || odd_round) load_pq(U0{}, PA, QA);  // wave-uniform: nothing is read past the last atom row
+              FC_SB;
+              accumulate(PB, QB);
+              FC_SB;
+            }
+            if (odd_round) {  // the last two atoms (the second one may be a zero row)
+              load_pq(U1{}, PB, QB);
+              FC_SB;
+              accumulate(PA, QA);
+              FC_SB;
+              accumulate(PB, QB);
+            }
           }
-          if (odd_round) {  // the last two atoms (the second one may be a zero row)
-            load_pq(U1{}, PB, QB);
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate(PA, QA);
-            __builtin_amdgcn_sched_barrier(0);
-            accumulate(PB, QB);
-          }
+#undef FC_SB
           if constexpr (EIG) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) ssq[r] = msdA4[r];
@@ -3248,23 +3334,59 @@ int prebuild_screen_items(fc_ensemble *e) {
   return screen_item_table(e, e->Npad >> 6, n_lblocks, /*halves=*/true, 64);
 }
 
+// Xt from Xs (fc_items.h: [tile][atom pair][coordinate][row][atom of the pair]); one thread per double of Xt, the spare
+// round behind the last tile included (zeros: the atom pass requests it and uses nothing of it)
+__global__ void __launch_bounds__(256)
+k_row_tiles(const double *__restrict__ Xs, int64_t Npad, int A, int64_t n_elems, int64_t n_alloc, double *__restrict__ Xt) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n_alloc) return;
+  double v = 0.0;
+  if (idx < n_elems) {
+    const int64_t U = row_tile_pairs(A), q = idx >> 5, tu = q / 3;
+    const int64_t c = q - tu * 3, t = tu / U, u = tu - t * U;
+    const int64_t n = t * 16 + ((idx >> 1) & 15), a = 2 * u + (idx & 1);
+    if (a < A) v = Xs[(a * 3 + c) * Npad + n];  // (rows n >= N of Xs are zero)
+  }
+  Xt[idx] = v;
+}
+
+// e->Xt: the row-tile-major copy of Xs, unless the ensemble holds it already.  The kernel addresses a tile by a 64-bit
+// wave-uniform base; inside a tile it walks with the lane's 32-bit offset and immediates, so one tile must stay below 2^31 bytes
+// -- and the whole copy inside what one launch of k_row_tiles covers.
+static bool row_tiles_fit(int64_t Npad, int64_t A) {
+  const int64_t n_alloc = row_tile_elems(Npad, A) + 96;
+  return row_tile_pairs(A) * 768 < ((int64_t)1 << 31) && grid_x_fits(ceil_div(n_alloc, 256), 256);
+}
+static int make_row_tiles(fc_ensemble *e) {
+  if (e->xt_valid) return FC_OK;
+  if (!row_tiles_fit(e->Npad, e->A)) return set_error(FC_E_LIMIT, "ensemble too large for the row-tile copy");
+  const int64_t n_elems = row_tile_elems(e->Npad, e->A), n_alloc = n_elems + 96;
+  FC_TRY(e->Xt.reserve((size_t)n_alloc * sizeof(double)));
+  hipLaunchKernelGGL(k_row_tiles, dim3((unsigned)ceil_div(n_alloc, 256)), dim3(256), 0, ctx().stream, e->Xs.as<double>(), e->Npad,
+                     (int)e->A, n_elems, n_alloc, e->Xt.as<double>());
+  FC_TRY(check_launch("k_row_tiles"));
+  e->xt_valid = true;
+  return FC_OK;
+}
+
 // all-pairs RMSD values on the matrix pipe (world == 1 layout); rmsd_dev: (N, N), pre-zeroed.
 // maxdev_dev != nullptr: the complete alignment of every pair -- (rmsd, maxdev) from the explicit
 // rotated difference (MODE 2 of the kernel); pairs it could not rotate are redone by the fix-up.
 // one instantiation of the complete-alignment kernel: LDS attribute + launch
-template <int NW, int TC, bool EIG>
+template <int NW, int TC, bool EIG, bool ROWT>
 static int launch_complete_variant(fc_ensemble *e, dim3 grid, size_t lds_m, double A_small, int64_t rb, int64_t rank, int64_t world,
                                    unsigned long long *cnt, const uint64_t *item_table_dev, unsigned long long n_items,
                                    double *rmsd_dev, double *maxdev_dev, uint64_t *timeline_dev) {
   if (lds_m > 64 * 1024) {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma<NW, 2, TC, EIG>),
+    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma<NW, 2, TC, EIG, false, ROWT>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
     if (err != hipSuccess) return set_error(FC_E_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
   }
-  hipLaunchKernelGGL((k_simbits_screen_mfma<NW, 2, TC, EIG>), grid, dim3(NW * 64), lds_m, ctx().stream, e->Xs.as<double>(),
+  hipLaunchKernelGGL((k_simbits_screen_mfma<NW, 2, TC, EIG, false, ROWT>), grid, dim3(NW * 64), lds_m, ctx().stream, e->Xs.as<double>(),
                      e->G.as<double>(), e->N, e->Npad, (int)e->A, A_small, (int)rb, rank, world, timeline_dev, e->W, nullptr, cnt,
                      e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap, item_table_dev, n_items, rmsd_dev, nullptr,
-                     maxdev_dev);  // (bits: nullptr in the product build -- FC_TIMELINE builds pass their stamp buffer there)
+                     maxdev_dev,  // (bits: nullptr in the product build -- FC_TIMELINE builds pass their stamp buffer there)
+                     ROWT ? e->Xt.as<double>() : nullptr);
   return FC_OK;
 }
 
@@ -3342,11 +3464,17 @@ int launch_rmsd_values(fc_ensemble *e, double small_rmsd, double *rmsd_dev, doub
                      (unsigned long long)e->pairq_cap, item_table_dev, n_items, rmsd_dev, nullptr, maxdev_dev)
   const char *eig_env = getenv("FC_COMPLETE_EIG");  // 0: always the running sum (read per call: the tests compare both forms)
   const bool eig = complete && !(eig_env && atoi(eig_env) == 0) && !explicit_sum;
+  // FC_COMPLETE_ROW_TILES: 0 = the atom pass reads its row conformer from Xs, the form before Xt (read per call: the tests
+  // compare both forms bit for bit)
+  const char *rt_env = getenv("FC_COMPLETE_ROW_TILES");
+  const bool row_tiles = complete && !(rt_env && atoi(rt_env) == 0);
+  if (row_tiles) FC_TRY(make_row_tiles(e));
+#define FC_COMPLETE_ARGS e, grid, lds_m, A_small, rb, rank, world, cnt, item_table_dev, n_items, rmsd_dev, maxdev_dev, timeline_dev
 #define FC_LAUNCH_COMPLETE(NW_, TC_)                                                                                        \
-  FC_TRY((eig ? launch_complete_variant<NW_, TC_, true>(e, grid, lds_m, A_small, rb, rank, world, cnt, item_table_dev, n_items, \
-                                                       rmsd_dev, maxdev_dev, timeline_dev)                                 \
-              : launch_complete_variant<NW_, TC_, false>(e, grid, lds_m, A_small, rb, rank, world, cnt, item_table_dev,     \
-                                                        n_items, rmsd_dev, maxdev_dev, timeline_dev)))
+  FC_TRY((eig ? (row_tiles ? launch_complete_variant<NW_, TC_, true, true>(FC_COMPLETE_ARGS)                                  \
+                           : launch_complete_variant<NW_, TC_, true, false>(FC_COMPLETE_ARGS))                                \
+              : (row_tiles ? launch_complete_variant<NW_, TC_, false, true>(FC_COMPLETE_ARGS)                                 \
+                           : launch_complete_variant<NW_, TC_, false, false>(FC_COMPLETE_ARGS))))
   if (narrow && tc == 32) {
     FC_LAUNCH_COMPLETE(8, 32);
   } else if (narrow) {
@@ -3359,6 +3487,7 @@ int launch_rmsd_values(fc_ensemble *e, double small_rmsd, double *rmsd_dev, doub
     else FC_LAUNCH_VALUES(8, 1);
   }
 #undef FC_LAUNCH_COMPLETE
+#undef FC_COMPLETE_ARGS
 #undef FC_LAUNCH_VALUES
   FC_TRY(check_launch("k_simbits_screen_mfma<values>"));
 #ifdef FC_TIMELINE
@@ -3447,6 +3576,7 @@ int launch_prep_begin(fc_ensemble *e) {
   auto *gmax_bits = reinterpret_cast<unsigned long long *>(e->counters.p) + (kCounters - 1);
   FC_HIP_TRY(hipMemsetAsync(gmax_bits, 0, sizeof(unsigned long long), ctx().stream));
   e->xsf_valid = false;
+  e->xt_valid = false;
   e->xh_valid = false;
   e->g_max = -1.0;
   return FC_OK;
@@ -3983,7 +4113,7 @@ static int launch_fp64_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lbl
   hipLaunchKernelGGL(fn, dim3((unsigned)it.n), dim3(threads), p.lds64, ctx().stream, e->Xs.as<double>(), e->G.as<double>(), e->N,
                      e->Npad, (int)e->A, A_thr2, (int)e->row_block, e->rank, e->world, e->bits.as<uint64_t>(), e->W,
                      e->cand.as<uint32_t>(), reinterpret_cast<unsigned long long *>(e->counters.p), e->pairq.as<uint64_t>(),
-                     (unsigned long long)e->pairq_cap, it.table, it.n, dbg, gate, nullptr);
+                     (unsigned long long)e->pairq_cap, it.table, it.n, dbg, gate, nullptr, nullptr);
   FC_TRY(check_launch("k_simbits_screen_mfma"));
 #ifdef FC_TIMELINE
   if (p.timeline) {
