@@ -182,6 +182,8 @@ _SIGNATURES = {
     "fc_prune_rmsd_many": [C.POINTER(_ens), _i64, _f64, _f64, _i64, C.POINTER(_p_u8), _p_i64],
     "fc_ensemble_knn": [_ens, _i64, C.POINTER(C.c_int32), _p_f64],
     "fc_bench_knn": [_ens, _i64, _i64, _p_f64, _p_f64, _p_i64],
+    "fc_ensemble_knn_cross": [_ens, _ens, _i64, C.c_double, C.POINTER(C.c_int32), _p_f64],
+    "fc_bench_knn_cross": [_ens, _ens, _i64, C.c_double, _i64, _p_f64, _p_f64, _p_i64],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("fc_last_error",)
@@ -442,6 +444,18 @@ def check_knn_k(value, limit=True):
     return int(value)
 
 
+def check_max_rmsd_cap(value):
+    """``max_rmsd`` of the cross-ensemble lists: ``None`` (no cap: +inf) or a positive number, checked before any
+    device use -- a NaN, zero or a negative radius is refused, not read as "no cap"."""
+    if value is None:
+        return float("inf")
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise FirecodeHipInputError(FC_E_INVALID, f"max_rmsd must be a positive number or None, got {value!r}")
+    if not float(value) > 0.0:
+        raise FirecodeHipInputError(FC_E_INVALID, f"max_rmsd={value!r} must be positive")
+    return float(value)
+
+
 class DeviceEnsemble:
     """HBM-resident prepared ensemble (fc_ensemble)."""
 
@@ -588,6 +602,37 @@ class DeviceEnsemble:
         """``reps`` calls of ``knn(k)`` -> (mean device ms, mean host ms, column strips of the launch)"""
         dev, host, strips = C.c_double(0), C.c_double(0), C.c_int64(0)
         call("fc_bench_knn", self.handle, check_knn_k(k, limit=False), int(reps), C.byref(dev), C.byref(host), C.byref(strips))
+        return dev.value, host.value, strips.value
+
+    def _other(self, other):
+        """the reference ensemble of a cross-ensemble call: a live DeviceEnsemble with this one's atom selection"""
+        if not isinstance(other, DeviceEnsemble):
+            raise FirecodeHipInputError(FC_E_INVALID, f"the reference ensemble must be a DeviceEnsemble, got {type(other).__name__}")
+        mine = np.ones(self.A_all, dtype=bool) if self._atom_mask is None else self._atom_mask
+        theirs = np.ones(other.A_all, dtype=bool) if other._atom_mask is None else other._atom_mask
+        if mine.shape != theirs.shape or not np.array_equal(mine, theirs):
+            raise FirecodeHipInputError(FC_E_INVALID, "the two ensembles do not have the same atom selection")
+        return other.handle
+
+    def knn_against(self, other, k, max_rmsd=None):
+        """For every conformer of this ensemble its ``k`` nearest conformers of ``other`` under the RMSD
+        (fc_ensemble_knn_cross; the contract is in include/fc_hip.h) -> ``(indices (N, k) int32 into ``other``,
+        distances (N, k) float64)``, each row in ascending order of (distance, index), nothing left out (``other`` may
+        be this ensemble: a row then lists itself first).  ``max_rmsd``: only references with ``d < max_rmsd`` are
+        listed; rows with fewer than ``k`` of them end in -1 / +inf.  Both ensembles: centred, the same atom selection."""
+        k = check_knn_k(k, limit=False)
+        cap = check_max_rmsd_cap(max_rmsd)
+        ref = self._other(other)
+        shape = (self.N, k) if k <= KNN_MAX else (1, 1)  # (beyond the limit the library refuses before it writes)
+        idx, dist = np.empty(shape, dtype=np.int32), np.empty(shape)
+        call("fc_ensemble_knn_cross", self.handle, ref, k, cap, ptr(idx, C.c_int32), pf(dist))
+        return idx, dist
+
+    def bench_knn_against(self, other, k, max_rmsd=None, reps=3):
+        """``reps`` calls of ``knn_against(other, k, max_rmsd)`` -> (mean device ms, mean host ms, column strips)"""
+        dev, host, strips = C.c_double(0), C.c_double(0), C.c_int64(0)
+        call("fc_bench_knn_cross", self.handle, self._other(other), check_knn_k(k, limit=False), check_max_rmsd_cap(max_rmsd),
+             int(reps), C.byref(dev), C.byref(host), C.byref(strips))
         return dev.value, host.value, strips.value
 
     def rmsd_matrix(self):

@@ -841,7 +841,7 @@ static int knn_checked(fc_ensemble *ens, int64_t k, int32_t *indices_out, double
   if (ens->N == 0) return FC_OK;
   FC_REQUIRE(ens->N <= (int64_t)INT32_MAX - 256, "N=%lld: the lists index conformers with 32 bits", (long long)ens->N);
   FC_TRY(ensure_init());
-  return knn(ens, k, indices_out, dist_out, ms_device, strips_out);
+  return knn(ens, ens, false, k, INFINITY, indices_out, dist_out, ms_device, strips_out);
 }
 
 int fc_ensemble_knn(fc_ensemble *ens, int64_t k, int32_t *indices_out, double *dist_out) {
@@ -863,6 +863,62 @@ int fc_bench_knn(fc_ensemble *ens, int64_t k, int64_t reps, double *ms_device_me
     double ms = 0.0;
     const auto t0 = std::chrono::steady_clock::now();
     FC_TRY(knn_checked(ens, k, idx.data(), dist.data(), &ms, strips_out));
+    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    dev += ms;
+  }
+  *ms_device_mean = dev / (double)reps;
+  *ms_host_mean = host / (double)reps;
+  return FC_OK;
+}
+
+// the rows of `queries` against the columns of `refs` (the contract: include/fc_hip.h, fc_ensemble_knn_cross); the
+// scalar arguments are judged first, so that their refusals do not depend on the handles
+static int knn_cross_checked(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int32_t *indices_out,
+                             double *dist_out, double *ms_device, int64_t *strips_out) {
+  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
+  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
+  FC_REQUIRE(max_rmsd > 0.0, "max_rmsd=%g must be positive (+inf: no cap)", max_rmsd);  // (a NaN fails it)
+  FC_REQUIRE(queries != nullptr && refs != nullptr, "queries / refs is NULL");
+  FC_REQUIRE(indices_out != nullptr && dist_out != nullptr, "indices_out / dist_out is NULL");
+  FC_REQUIRE(queries->epoch == ctx().epoch && refs->epoch == ctx().epoch,
+             "an ensemble was created before fc_shutdown / a device switch: create it again");
+  FC_REQUIRE(queries->A == refs->A, "queries select %lld atoms, refs %lld: one atom selection for both", (long long)queries->A,
+             (long long)refs->A);
+  if (refs->N > (int64_t)INT32_MAX - 256 || queries->N > (int64_t)INT32_MAX - 256)
+    return set_error(FC_E_LIMIT, "Nq=%lld, Nr=%lld: the lists index conformers with 32 bits", (long long)queries->N,
+                     (long long)refs->N);
+  if (strips_out) *strips_out = 0;
+  if (ms_device) *ms_device = 0.0;
+  if (queries->N == 0) return FC_OK;
+  if (refs->N == 0) {  // no reference: every slot is empty, and no device is needed to say so
+    std::fill(indices_out, indices_out + queries->N * k, (int32_t)-1);
+    std::fill(dist_out, dist_out + queries->N * k, (double)INFINITY);
+    return FC_OK;
+  }
+  FC_TRY(ensure_init());
+  return knn(queries, refs, true, k, max_rmsd, indices_out, dist_out, ms_device, strips_out);
+}
+
+int fc_ensemble_knn_cross(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int32_t *indices_out,
+                          double *dist_out) {
+  FC_API_LOCK;
+  return knn_cross_checked(queries, refs, k, max_rmsd, indices_out, dist_out, nullptr, nullptr);
+}
+
+int fc_bench_knn_cross(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int64_t reps,
+                       double *ms_device_mean, double *ms_host_mean, int64_t *strips_out) {
+  FC_API_LOCK;
+  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
+  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
+  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
+  FC_REQUIRE(queries != nullptr && refs != nullptr, "queries / refs is NULL");
+  std::vector<int32_t> idx((size_t)queries->N * (size_t)k + 1);
+  std::vector<double> dist((size_t)queries->N * (size_t)k + 1);
+  double dev = 0.0, host = 0.0;
+  for (int64_t r = 0; r < reps; ++r) {
+    double ms = 0.0;
+    const auto t0 = std::chrono::steady_clock::now();
+    FC_TRY(knn_cross_checked(queries, refs, k, max_rmsd, idx.data(), dist.data(), &ms, strips_out));
     host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     dev += ms;
   }

@@ -219,8 +219,9 @@ int launch_symm_pairs(const fc_ensemble *e, const uint16_t *perms_dev, int64_t K
                       const int64_t *pj_dev, int64_t P, double *rmsd_dev, double *maxdev_dev);  // (P, K) outputs
 int warm_symm();
 // ---- fc_knn.hip ------------------------------------------------------------------------------------------
-int knn_strips(int64_t N);  // column strips of the launch at N conformers (FC_KNN_STRIPS forces it)
-int knn(fc_ensemble *e, int64_t k, int32_t *indices_out, double *dist_out, double *ms_device, int64_t *strips_out);
+int knn_strips(int64_t Nq, int64_t Nr);  // column strips of the launch of Nq rows against Nr columns (FC_KNN_STRIPS forces it)
+int knn(fc_ensemble *q, fc_ensemble *r, bool cross, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out,
+        double *ms_device, int64_t *strips_out);
 int warm_knn();
 // ---- fc_tfd_ladder.hip -----------------------------------------------------------------------------------
 int tfd_ladder_device(const int64_t *fm_dev, const int64_t *fm_host, int64_t N, uint8_t *mask_out);

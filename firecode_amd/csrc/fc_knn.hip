@@ -38,6 +38,14 @@
 // Each (row, strip) writes its sorted partial list; k_knn_merge -- one wavefront per row -- offers the S partial lists
 // of the row to one list by the same insertion and writes the outputs (-1 for the unfilled slots).  The entries of a
 // row are distinct in j, so the merged list does not depend on the order of the strips.
+//
+// The cross form (fc_ensemble_knn_cross) is the same kernel with its rows from one resident
+// ensemble Q (Xa, G, N) and its columns from another, R (Xs, G, N, Npad): for every conformer of Q its k nearest conformers
+// of R.  No pair is left out, every clamp is per side, the tiles come from Nq and the chunks and strips from Nr.  An
+// optional cap keeps only d < max_rmsd: the test is made on the value, beside the list, and the filter's tau is the
+// smaller of slot k - 1 and the cap from the first chunk on -- whole chunks are ruled out before any list has filled.
+// d(i, j) is the same instruction sequence in both forms: an ensemble against a bitwise copy of itself gives the
+// distance bits of the one-ensemble form for every i != j.
 #include "fc_internal.h"
 #include "fc_kabsch_math.h"
 
@@ -84,10 +92,29 @@ __device__ __forceinline__ void knn_offer(double &ld, int &lj, double &td, int &
   }
 }
 
-template <bool STAGE>
+// What the cross form (rows from an ensemble Q, columns from an ensemble R) passes beside the arguments of the
+// one-ensemble form, which then describe: Xs, Npad -- R; Xa, G, N -- Q.  The one-ensemble form passes an empty struct
+// at the end, so that its own arguments and its code stay as they were.
+template <bool CROSS>
+struct KnnCross {};
+template <>
+struct KnnCross<true> {
+  const double *Gr;  // R's sums of squares
+  int Nr;            // R's conformers
+  double cap;        // a list takes only d < cap; +inf: no cap
+};
+
+// CROSS = false: one ensemble, the self-pair left out by index.  CROSS = true: no pair left out, the cap.
+template <bool STAGE, bool CROSS>
 __global__ void __launch_bounds__(kKnnThreads)
-k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const double *__restrict__ G, int N, int64_t Npad, int A,
-           int k, int filter, int n_tiles, int n_chunks, double *__restrict__ part_d, int32_t *__restrict__ part_j) {
+k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const double *__restrict__ Gq, int Nq, int64_t Npad, int A,
+           int k, int filter, int n_tiles, int n_chunks, double *__restrict__ part_d, int32_t *__restrict__ part_j,
+           const KnnCross<CROSS> x) {
+  const double *__restrict__ Gr;
+  int Nr;
+  double cap;
+  if constexpr (CROSS) Gr = x.Gr, Nr = x.Nr, cap = x.cap;
+  else Gr = Gq, Nr = Nq, cap = INFINITY;
   extern __shared__ double s_rows[];  // [kKnnTileRows][A][3] when STAGE
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int S = gridDim.y, s = blockIdx.y;
@@ -101,13 +128,13 @@ k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const d
     if (STAGE) {
       __syncthreads();  // (the previous tile's readers)
       for (int r = w; r < kKnnTileRows; r += kKnnThreads / 64) {
-        const double *__restrict__ src = Xa + (int64_t)min(row0 + r, N - 1) * A3;
+        const double *__restrict__ src = Xa + (int64_t)min(row0 + r, Nq - 1) * A3;
         for (int t = lane; t < A3; t += 64) s_rows[r * A3 + t] = src[t];
       }
       __syncthreads();
     }
     const int wrow = row0 + w * kKnnR;
-    if (wrow < N) {  // (wave-uniform)
+    if (wrow < Nq) {  // (wave-uniform)
       int row[kKnnR];
       const double *__restrict__ P[kKnnR];
       double Gi[kKnnR], ld[kKnnR], td[kKnnR];
@@ -115,15 +142,15 @@ k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const d
 #pragma unroll
       for (int r = 0; r < kKnnR; ++r) {
         row[r] = wrow + r;
-        const int rl = min(row[r], N - 1);
+        const int rl = min(row[r], Nq - 1);
         P[r] = STAGE ? s_rows + (w * kKnnR + r) * A3 : Xa + (int64_t)rl * A3;
-        Gi[r] = G[rl];
+        Gi[r] = Gq[rl];
         ld[r] = td[r] = INFINITY;
         lj[r] = tj[r] = INT_MAX;
       }
       for (int c = c0; c < c1; ++c) {
         const int j = c * 64 + lane;
-        const int jl = min(j, N - 1);
+        const int jl = min(j, Nr - 1);
         const double *__restrict__ q0 = Xs + jl;
         const int64_t step = 3 * Npad;
         // ---- 1. covariances with the 4 rows
@@ -147,15 +174,16 @@ k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const d
           }
         }
         // ---- 2. per row: the filter, and where a lane passes it the rotation, the explicit rotated difference and the list
-        const double Gj = G[jl];
+        const double Gj = Gr[jl];
 #pragma unroll
         for (int r = 0; r < kKnnR; ++r) {
-          const bool ok = j < N && j != row[r] && row[r] < N;  // the self-pair is left out by index
+          const bool ok = j < Nr && (CROSS || j != row[r]) && row[r] < Nq;  // one ensemble: the self-pair is left out by index
           const double GG = Gi[r] + Gj;
           bool may = ok;
           if (filter) {  // (a NaN passes)
             const double msdA = GG - 2.0 * kabsch_lambda_max(B[r], GG);
-            may = ok && !(msdA > dA * td[r] * td[r] + (dA * kScreenMargin + kKnnFilterRel * GG));
+            const double tau = CROSS ? fmin(td[r], cap) : td[r];  // the cap: a smaller tau from the first chunk on
+            may = ok && !(msdA > dA * tau * tau + (dA * kScreenMargin + kKnnFilterRel * GG));
           }
           if (__ballot(may) == 0) continue;  // (wave-uniform) no column of this chunk can enter the row's list
           double R[9];
@@ -171,12 +199,14 @@ k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const d
             const double dz = pz - (R[6] * qx + R[7] * qy + R[8] * qz);
             ssq += dx * dx + dy * dy + dz * dz;
           }
-          knn_offer(ld[r], lj[r], td[r], tj[r], sqrt(ssq / dA), j, ok, k, lane);
+          const double d = sqrt(ssq / dA);
+          // (the cap is tested on the value itself, beside the list: slot k - 1, which knn_offer re-reads, never holds it)
+          knn_offer(ld[r], lj[r], td[r], tj[r], d, j, CROSS ? ok && d < cap : ok, k, lane);
         }
       }
 #pragma unroll
       for (int r = 0; r < kKnnR; ++r)
-        if (row[r] < N && lane < k) {
+        if (row[r] < Nq && lane < k) {
           const int64_t at = ((int64_t)row[r] * S + s) * k + lane;
           part_d[at] = ld[r];
           part_j[at] = lj[r];
@@ -211,10 +241,10 @@ k_knn_merge(const double *__restrict__ part_d, const int32_t *__restrict__ part_
   }
 }
 
-// column strips of a launch over N conformers: enough workgroups to fill the chip at small N; FC_KNN_STRIPS=<n> forces
-// it (speed only: the outputs are the same bits for every value)
-int knn_strips(int64_t N) {
-  const int64_t n_chunks = std::max<int64_t>(1, ceil_div(N, 64));
+// column strips of a launch of Nq rows against Nr columns: enough workgroups to fill the chip where the row tiles alone do
+// not; FC_KNN_STRIPS=<n> forces it (speed only: the outputs are the same bits for every value)
+int knn_strips(int64_t Nq, int64_t Nr) {
+  const int64_t n_chunks = std::max<int64_t>(1, ceil_div(Nr, 64));
   int64_t S = 0;
   if (const char *v = getenv("FC_KNN_STRIPS")) {
     char *end = nullptr;
@@ -222,7 +252,7 @@ int knn_strips(int64_t N) {
     if (end != v && *end == 0 && f >= 1) S = std::min<long long>(f, kKnnMaxStrips);
   }
   if (S == 0) {
-    const int64_t tiles = std::max<int64_t>(1, ceil_div(N, kKnnTileRows));
+    const int64_t tiles = std::max<int64_t>(1, ceil_div(Nq, kKnnTileRows));
     S = std::min<int64_t>(kKnnMaxStrips, ceil_div((int64_t)kKnnWorkgroupsPerCu * std::max(1, ctx().n_cu), tiles));
   }
   return (int)std::max<int64_t>(1, std::min(S, n_chunks));
@@ -234,32 +264,43 @@ static int knn_filter() {
   return !(v && v[0] == '0' && v[1] == 0);
 }
 
-template <bool STAGE>
-static int launch_knn_tile(const fc_ensemble *e, int k, int filter, int n_tiles, int n_chunks, int S, double *part_d, int32_t *part_j) {
-  const size_t lds = STAGE ? (size_t)kKnnTileRows * e->A * 3 * sizeof(double) : 0;
-  FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_knn_tile<STAGE>), lds, "k_knn_tile"));
-  const unsigned gx = (unsigned)std::min<int64_t>(n_tiles, (int64_t)1 << 20);
-  hipLaunchKernelGGL((k_knn_tile<STAGE>), dim3(gx, (unsigned)S), dim3(kKnnThreads), lds, ctx().stream, e->Xs.as<double>(),
-                     e->Xa.as<double>(), e->G.as<double>(), (int)e->N, e->Npad, (int)e->A, k, filter, n_tiles, n_chunks, part_d, part_j);
+// one launch: the rows of q against the columns of r (the self form: q == r, CROSS = false, cap = +inf)
+struct KnnLaunch {
+  const fc_ensemble *q, *r;
+  int k, filter, n_tiles, n_chunks, S;
+  double cap;
+};
+
+template <bool STAGE, bool CROSS>
+static int launch_knn_tile(const KnnLaunch &a, double *part_d, int32_t *part_j) {
+  const size_t lds = STAGE ? (size_t)kKnnTileRows * a.q->A * 3 * sizeof(double) : 0;
+  FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_knn_tile<STAGE, CROSS>), lds, "k_knn_tile"));
+  const unsigned gx = (unsigned)std::min<int64_t>(a.n_tiles, (int64_t)1 << 20);
+  KnnCross<CROSS> x;
+  if constexpr (CROSS) x = KnnCross<true>{a.r->G.as<double>(), (int)a.r->N, a.cap};
+  hipLaunchKernelGGL((k_knn_tile<STAGE, CROSS>), dim3(gx, (unsigned)a.S), dim3(kKnnThreads), lds, ctx().stream,
+                     a.r->Xs.as<double>(), a.q->Xa.as<double>(), a.q->G.as<double>(), (int)a.q->N, a.r->Npad, (int)a.q->A, a.k,
+                     a.filter, a.n_tiles, a.n_chunks, part_d, part_j, x);
   return check_launch("k_knn_tile");
 }
 
-static int knn_enqueue(fc_ensemble *e, int k, int S, int32_t *indices_out, double *dist_out, double *ms_device, DevBuf &pd,
-                       DevBuf &pj, DevBuf &oi, DevBuf &od) {
-  const int64_t N = e->N;
-  const int n_tiles = (int)ceil_div(N, kKnnTileRows), n_chunks = (int)ceil_div(N, 64);
-  const size_t entries = (size_t)N * (size_t)k;
+static int knn_enqueue(const fc_ensemble *q, const fc_ensemble *r, bool cross, int k, double cap, int S, int32_t *indices_out,
+                       double *dist_out, double *ms_device, DevBuf &pd, DevBuf &pj, DevBuf &oi, DevBuf &od) {
+  const int64_t Nq = q->N;
+  const KnnLaunch a{q, r, k, knn_filter(), (int)ceil_div(Nq, kKnnTileRows), (int)ceil_div(r->N, 64), S, cap};
+  const size_t entries = (size_t)Nq * (size_t)k;
   FC_TRY(pd.reserve(entries * (size_t)S * sizeof(double)));
   FC_TRY(pj.reserve(entries * (size_t)S * sizeof(int32_t)));
   FC_TRY(oi.reserve(entries * sizeof(int32_t)));
   FC_TRY(od.reserve(entries * sizeof(double)));
   Context &c = ctx();
-  const int filter = knn_filter();
   if (ms_device) FC_HIP_TRY(hipEventRecord(c.ev0, c.stream));
-  if (e->A <= kKnnLdsAtoms) FC_TRY(launch_knn_tile<true>(e, k, filter, n_tiles, n_chunks, S, pd.as<double>(), pj.as<int32_t>()));
-  else FC_TRY(launch_knn_tile<false>(e, k, filter, n_tiles, n_chunks, S, pd.as<double>(), pj.as<int32_t>()));
-  const unsigned gm = (unsigned)std::min<int64_t>(ceil_div(N, kKnnThreads / 64), (int64_t)1 << 20);
-  hipLaunchKernelGGL(k_knn_merge, dim3(gm), dim3(kKnnThreads), 0, c.stream, pd.as<double>(), pj.as<int32_t>(), (int)N, S, k,
+  const bool stage = q->A <= kKnnLdsAtoms;
+  const auto tile = cross ? (stage ? launch_knn_tile<true, true> : launch_knn_tile<false, true>)
+                         : (stage ? launch_knn_tile<true, false> : launch_knn_tile<false, false>);
+  FC_TRY(tile(a, pd.as<double>(), pj.as<int32_t>()));
+  const unsigned gm = (unsigned)std::min<int64_t>(ceil_div(Nq, kKnnThreads / 64), (int64_t)1 << 20);
+  hipLaunchKernelGGL(k_knn_merge, dim3(gm), dim3(kKnnThreads), 0, c.stream, pd.as<double>(), pj.as<int32_t>(), (int)Nq, S, k,
                      oi.as<int32_t>(), od.as<double>());
   FC_TRY(check_launch("k_knn_merge"));
   if (ms_device) FC_HIP_TRY(hipEventRecord(c.ev1, c.stream));
@@ -274,13 +315,16 @@ static int knn_enqueue(fc_ensemble *e, int k, int S, int32_t *indices_out, doubl
   return FC_OK;
 }
 
-// The lists behind fc_ensemble_knn (arguments checked there; N >= 1, 1 <= k <= FC_KNN_MAX).  ms_device (may be NULL):
-// HIP-event time from the first launch to the end of the merge; strips_out (may be NULL): the strip count used.
-int knn(fc_ensemble *e, int64_t k, int32_t *indices_out, double *dist_out, double *ms_device, int64_t *strips_out) {
-  const int S = knn_strips(e->N);
+// The lists behind fc_ensemble_knn (cross = false: q == r, max_rmsd = +inf) and fc_ensemble_knn_cross (cross = true: the
+// rows of q against the columns of r, which may be the same handle) -- arguments checked there; both N >= 1, the same A,
+// 1 <= k <= FC_KNN_MAX, max_rmsd > 0.  ms_device (may be NULL): HIP-event time from the first launch to the end of the
+// merge; strips_out (may be NULL): the strip count used.
+int knn(fc_ensemble *q, fc_ensemble *r, bool cross, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out,
+        double *ms_device, int64_t *strips_out) {
+  const int S = knn_strips(q->N, r->N);
   if (strips_out) *strips_out = S;
   DevBuf pd, pj, oi, od;
-  const int rc = knn_enqueue(e, (int)k, S, indices_out, dist_out, ms_device, pd, pj, oi, od);
+  const int rc = knn_enqueue(q, r, cross, (int)k, max_rmsd, S, indices_out, dist_out, ms_device, pd, pj, oi, od);
   // an error behind a launch: nothing of the four buffers may be in flight when they go back to the pool
   if (rc != FC_OK && ctx().ready) (void)hipStreamSynchronize(cur_stream());
   return rc;

@@ -145,6 +145,35 @@ class Ensemble:
 
         return knn_by_rmsd(self.coords, self.atoms, k, heavy_atoms_only=heavy_atoms_only)
 
+    def _same_atoms(self, other):
+        from firecode_amd._lib import FC_E_INVALID, FirecodeHipInputError
+
+        if not isinstance(other, Ensemble):
+            raise FirecodeHipInputError(FC_E_INVALID, f"the other ensemble must be an Ensemble, got {type(other).__name__}")
+        mine, theirs = np.asarray(self.atoms), np.asarray(other.atoms)
+        if mine.shape != theirs.shape or not np.array_equal(mine, theirs):
+            raise FirecodeHipInputError(FC_E_INVALID, "the two ensembles do not have the same atoms")
+
+    def nearest_in(self, other, k=1, max_rmsd=None, heavy_atoms_only=True):
+        """For every structure its ``k`` nearest structures of ``other`` -- an ensemble of the same molecule, same
+        ``atoms`` -- under the heavy-atom RMSD (``firecode_amd.pruner.knn_by_rmsd_against``); ``max_rmsd``: only those
+        with ``rmsd < max_rmsd``.  Returns the ``RmsdCrossNeighbours`` (indices into ``other``); neither ensemble is
+        masked.  RMSD only: no max-deviation or energy test."""
+        from firecode_amd.pruner import knn_by_rmsd_against
+
+        self._same_atoms(other)
+        return knn_by_rmsd_against(self.coords, other.coords, self.atoms, k, max_rmsd=max_rmsd,
+                                   heavy_atoms_only=heavy_atoms_only)
+
+    def novel_against(self, other, max_rmsd, heavy_atoms_only=True):
+        """(N,) bool: the structures with NO structure of ``other`` within ``max_rmsd`` of them
+        (``firecode_amd.pruner.novel_conformers``); the ensemble is not masked.  RMSD only: the max-deviation and
+        energy-window tests of ``similarity_pruning`` are not applied."""
+        from firecode_amd.pruner import novel_conformers
+
+        self._same_atoms(other)
+        return novel_conformers(self.coords, other.coords, self.atoms, max_rmsd, heavy_atoms_only=heavy_atoms_only)
+
     def cluster_by_rmsd(self, max_rmsd=None, heavy_atoms_only=True, prune_enantiomers=False, verbose=True, symmetry=None):
         """Which conformers belong together (``firecode_amd.pruner.cluster_by_rmsd``): the connected components of the
         graph the RMSD stage of ``similarity_pruning`` prunes, with its energies and window (``max_dE = 1.0`` when there is

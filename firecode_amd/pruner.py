@@ -264,6 +264,103 @@ def knn_by_rmsd(structures, atoms, k, heavy_atoms_only=True):
         return RmsdNeighbours(*ens.knn(k))
 
 
+class RmsdCrossNeighbours(namedtuple("RmsdCrossNeighbours", ["indices", "distances"])):
+    """The lists of ``knn_by_rmsd_against``: indices (Nq, k) int32 into the REFERENCE set and distances (Nq, k) float64,
+    each row in ascending order of (distance, index); slots for which no reference qualifies hold -1 / +inf.  Rows and
+    entries belong to different sets, so this is not an ``RmsdNeighbours`` (no graph, no k-distance curve).  The two
+    methods are host-side NumPy."""
+
+    __slots__ = ()
+
+    def nearest(self):
+        """``(indices[:, 0], distances[:, 0])``: every query's closest listed reference (-1 / +inf where none)"""
+        return np.asarray(self.indices)[:, 0], np.asarray(self.distances)[:, 0]
+
+    def novel(self, max_rmsd):
+        """(Nq,) bool: true where NO listed reference has ``d < max_rmsd`` (strict, like the prune's ``rmsd < max_rmsd``).
+        Lists made with a cap answer for radii up to that cap only.  RMSD alone: no max-deviation or energy test."""
+        max_rmsd = L.check_max_rmsd_cap(max_rmsd)
+        return ~(np.asarray(self.distances) < max_rmsd).any(axis=1)
+
+
+def _cross_inputs(structures, references, atoms):
+    """the three array arguments of the cross-ensemble drivers, checked against one another"""
+    structures, atoms = _structures_and_atoms(structures, atoms)
+    references = L.f64(references)
+    if references.ndim != 3 or references.shape[1:] != structures.shape[1:]:
+        raise L.FirecodeHipInputError(
+            L.FC_E_INVALID, f"references must be (N, {structures.shape[1]}, 3) like structures, got {references.shape}")
+    return structures, references, atoms
+
+
+def knn_by_rmsd_against(structures, references, atoms, k, max_rmsd=None, heavy_atoms_only=True):
+    """For every conformer of ``structures`` its ``k`` nearest conformers of ``references`` -- a second set of
+    conformers of the same molecule, same ``atoms`` -- under the heavy-atom Kabsch RMSD ``prune_by_rmsd`` uses (centred,
+    ``rmsd_and_max(...)[0]``), on the GPU (fc_ensemble_knn_cross; the contract is written out in include/fc_hip.h): the
+    kernel of ``knn_by_rmsd`` with its rows from one resident ensemble and its columns from another, no matrix of the
+    union on the host.  1 <= k <= 64.  ``max_rmsd``: only references with ``d < max_rmsd`` are listed.
+
+    Returns ``RmsdCrossNeighbours(indices, distances)``: (Nq, k) int32 indices into ``references`` and (Nq, k) float64,
+    each row in ascending order of (distance, index) -- on equal distances the lower index first.  Nothing is left out:
+    a query that is a copy of a reference lists it first, at ~1e-15.  Rows with fewer than ``k`` qualifying references
+    (``k > len(references)``, or the cap) end in -1 / +inf.  ``.nearest()`` is column 0; ``.novel(r)`` the queries with
+    no listed reference within ``r``.  RMSD only: the max-deviation and energy-window tests of the prune play no part."""
+    structures, references, atoms = _cross_inputs(structures, references, atoms)
+    k = L.check_knn_k(k)
+    cap = None if max_rmsd is None else L.check_max_rmsd_cap(max_rmsd)
+    heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
+    if not heavy.any():
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "the atom selection is empty (no heavy atom)")
+    Nq, Nr = structures.shape[0], references.shape[0]
+    if Nq == 0 or Nr == 0:  # nothing to list, or nothing to list from: no device needed
+        return RmsdCrossNeighbours(np.full((Nq, k), -1, dtype=np.int32), np.full((Nq, k), np.inf))
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as q, \
+            L.DeviceEnsemble(references, atom_mask=heavy, center=True) as r:
+        return RmsdCrossNeighbours(*q.knn_against(r, k, max_rmsd=cap))
+
+
+def novel_conformers(structures, references, atoms, max_rmsd, heavy_atoms_only=True):
+    """Which conformers of ``structures`` are new against ``references``: (Nq,) bool, true where NO reference is within
+    ``max_rmsd`` of the conformer (``rmsd < max_rmsd``, the RMSD test of ``prune_by_rmsd``).  One call of
+    ``knn_by_rmsd_against`` with ``k = 1`` and the cap, which lets the kernel's filter rule out whole blocks of
+    references from the start.  RMSD only: the max-deviation and energy-window tests of the prune are not applied, so
+    this is not "would ``prune_by_rmsd`` of the union drop it"."""
+    if max_rmsd is None:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "novel_conformers needs max_rmsd")
+    nb = knn_by_rmsd_against(structures, references, atoms, 1, max_rmsd=max_rmsd, heavy_atoms_only=heavy_atoms_only)
+    return nb.indices[:, 0] < 0
+
+
+class EnsembleCoverage(namedtuple("EnsembleCoverage", ["covered", "fraction", "nearest", "distances"])):
+    """The answer of ``ensemble_coverage``: covered (Nr,) bool, fraction = covered.mean() (nan for an empty reference
+    set), nearest (Nr,) int32 = the closest conformer of ``structures`` to each reference (-1 where there is none),
+    distances (Nr,) to it (+inf where there is none)."""
+
+    __slots__ = ()
+
+    @classmethod
+    def from_neighbours(cls, nb, max_rmsd):
+        """from the lists of the references against the structures (``k >= 1``, no cap below ``max_rmsd``)"""
+        max_rmsd = L.check_max_rmsd_cap(max_rmsd)
+        nearest, dist = nb.nearest()
+        covered = dist < max_rmsd
+        return cls(covered, float(covered.mean()) if len(covered) else float("nan"), nearest, dist)
+
+
+def ensemble_coverage(structures, references, atoms, max_rmsd, heavy_atoms_only=True):
+    """Does ``structures`` contain every conformer of ``references`` to within ``max_rmsd`` -- the coverage (recall)
+    figure of conformer-generator benchmarks: for every reference, is there a conformer of ``structures`` with
+    ``rmsd < max_rmsd``?  ``knn_by_rmsd_against`` with the roles swapped (the references are the rows), ``k = 1`` and no
+    cap, so that the distance to the closest conformer is reported for the uncovered references too.
+
+    Returns ``EnsembleCoverage(covered, fraction, nearest, distances)``.  RMSD only, as ``novel_conformers``."""
+    if max_rmsd is None:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "ensemble_coverage needs max_rmsd")
+    max_rmsd = L.check_max_rmsd_cap(max_rmsd)
+    nb = knn_by_rmsd_against(references, structures, atoms, 1, heavy_atoms_only=heavy_atoms_only)
+    return EnsembleCoverage.from_neighbours(nb, max_rmsd)
+
+
 RmsdClusters = namedtuple("RmsdClusters", ["labels", "representatives", "sizes"])
 
 

@@ -204,10 +204,41 @@ int fc_ensemble_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int6
  * takes every pair through the explicit pass and gives the same bits.
  * FC_E_INVALID before any device use: NULL ens or outputs, k < 1; FC_E_LIMIT before any device use: k > FC_KNN_MAX.
  * Limits: N < 2^31 - 256; no atom limit (a workgroup's 16 row conformers are staged in LDS up to 256 selected atoms and
- * read from HBM beyond).  Not offered: symmetry- and mirror-aware forms, queries of one ensemble against another,
- * sharded, multi-GPU and twin-workspace forms. */
+ * read from HBM beyond).  Not offered: symmetry- and mirror-aware forms, sharded, multi-GPU and twin-workspace forms
+ * (queries of one ensemble against another: fc_ensemble_knn_cross, below). */
 #define FC_KNN_MAX 64
 int fc_ensemble_knn(fc_ensemble *ens, int64_t k, int32_t *indices_out, double *dist_out);
+/* The same lists across two ensembles: for every conformer of `queries` its k nearest conformers
+ * of `refs` -- what answers "which of these conformers are not in the ensemble I hold" (novelty: k = 1 with max_rmsd at
+ * the duplicate threshold), "does my ensemble contain every conformer of a reference set to within max_rmsd" (coverage:
+ * the roles swapped) and "which conformer of B is closest to each conformer of A".  The kernels, the arithmetic and the
+ * determinism promises are those of fc_ensemble_knn: the rows come from `queries`, the columns from `refs`.  The contract:
+ *
+ *   d(i, j) = rmsd_and_max(Q[i][sel], R[j][sel], center=True)[0], Q = queries, R = refs.  For every i < Nq the list holds
+ *   the k conformers j < Nr with the smallest d(i, j) among those with d(i, j) < max_rmsd (strict, like the prune's
+ *   rmsd < max_rmsd; max_rmsd = +inf: no cap), in ascending order of (d(i, j), j): on equal distances the lower index
+ *   comes first, inside the list and at its cut.  NO pair is left out: a query that is a bitwise copy of a reference
+ *   lists that reference first, at ~1e-15.
+ *
+ * Outputs: indices_out (Nq, k) int32, indices into `refs`, and dist_out (Nq, k) float64, row-major.  1 <= k <= FC_KNN_MAX.
+ * Where fewer than k references qualify -- k > Nr, or the cap -- the trailing entries of the row are index -1 and
+ * distance +inf.  Nq = 0: nothing is written.  Nr = 0: every slot is -1 / +inf, written without any device use.
+ * queries == refs (the same handle) is allowed: a row then lists itself first.
+ * Both ensembles must belong to the current context epoch and have the same number of selected atoms A; like
+ * fc_ensemble_knn the distances mean what the contract says only when both hold CENTRED coordinates (center != 0 at
+ * fc_ensemble_create) of the SAME atom selection: the library checks A, the selection and the centring are the caller's
+ * (firecode_amd.pruner.knn_by_rmsd_against guarantees both).  Nq and Nr are independent.
+ * Determinism: as fc_ensemble_knn -- one fixed instruction sequence per d(i, j), bit-identical outputs for every strip
+ * count (strips are chosen from the row tiles of Nq and the 64-column chunks of Nr; FC_KNN_STRIPS=<n>) and with
+ * FC_KNN_FILTER=0.  An ensemble against a bitwise copy of itself gives, for every i != j, the distance bits of
+ * fc_ensemble_knn.  With a cap the eigenvalue filter starts from tau = max_rmsd instead of an empty list's +inf -- a
+ * smaller tau under the same margins, never a different value or order -- which is what makes a novelty query cheap.
+ * Refused before any device use -- FC_E_INVALID: k < 1, max_rmsd NaN or <= 0, NULL queries, refs or outputs, an ensemble
+ * of an earlier context epoch, different A; FC_E_LIMIT: k > FC_KNN_MAX, Nq or Nr >= 2^31 - 256.  k and max_rmsd are
+ * judged first, then the pointers.  No atom limit (LDS stage as fc_ensemble_knn).  Not offered: symmetry- and
+ * mirror-aware forms, max-deviation or energy criteria, sharded, multi-GPU and twin-workspace forms. */
+int fc_ensemble_knn_cross(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int32_t *indices_out,
+                          double *dist_out);
 /* a9: get_alignment_matrix(p, q) -- prism_pruner.rmsd; call site
  * hypermolecule_class.py:77.  M (3,3) row-major, applied as (M @ q.T).T */
 int fc_alignment_matrices(const double *p, const double *q, int64_t n_pairs, int64_t A,
@@ -902,6 +933,9 @@ int fc_bench_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int64_t
  * wall-clock time per call; strips_out (may be NULL) = the column strips of the launch. */
 int fc_bench_knn(fc_ensemble *ens, int64_t k, int64_t reps, double *ms_device_mean, double *ms_host_mean,
                  int64_t *strips_out);
+/* the same for fc_ensemble_knn_cross (its arguments and refusals) */
+int fc_bench_knn_cross(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int64_t reps,
+                       double *ms_device_mean, double *ms_host_mean, int64_t *strips_out);
 /* (fc_bench_prune_rmsd writes EIGHT stats: [6] = 16 x 32-pair units the subset stage of the lean fp32
  * screen queued for the full test in the last prune, [7] = 1 when its sample found similarity dense
  * and the single-stage kernel did the launch) */

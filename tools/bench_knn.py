@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""k nearest neighbours under the RMSD (fc_ensemble_knn) on one MI355X: one JSON line per workload.
+"""k nearest neighbours under the RMSD (fc_ensemble_knn, fc_ensemble_knn_cross) on one MI355X: one JSON line per workload.
 
   python tools/bench_knn.py              # the sizes of DESIGN.md section 18: continuous and clustered ensembles at
                                          # 10^4 x 50 and 10^5 x 50, k = 8 and 64; then, at 10^4 x 50, host arrays in ->
@@ -8,6 +8,12 @@
   python tools/bench_knn.py --filter     # the eigenvalue filter against FC_KNN_FILTER=0, alternating, at both sizes
   python tools/bench_knn.py --strips     # the strip count (FC_KNN_STRIPS) over N at k = 8
   python tools/bench_knn.py --trace      # one 10^4 x 50 call at k = 8, for rocprofv3 --kernel-trace --stats
+  python tools/bench_knn.py --cross      # fc_ensemble_knn_cross: queries x references at
+                                         # 10^4 x 10^4, 10^3 x 10^5 and 10^2 x 10^6, k = 1 and 8, without a cap and with
+                                         # the cap at the duplicate threshold; the self form at 10^4, k = 8 beside it;
+                                         # then host arrays in -> lists out at 5 000 x 5 000 against the matrix of the
+                                         # concatenated 10 000 on the host
+  python tools/bench_knn.py --cross --small   # without the 10^2 x 10^6 workload
 
 Device time: HIP events on the library's stream from the first launch to the end of the merge (a warm-up call first,
 then 3 calls: mean and range).  Rates: ordered alignments (N (N - 1): the full square, whether or not a pair's explicit
@@ -93,9 +99,86 @@ def end_to_end(X, k, reps=3):
                       "same_indices": same}), flush=True)
 
 
+def split(N_q, N_r, seed):
+    """queries and references drawn from one continuous ensemble, shuffled"""
+    X = ensemble("continuous", N_q + N_r, seed)
+    p = np.random.default_rng(seed).permutation(N_q + N_r)
+    return np.ascontiguousarray(X[p[:N_q]]), np.ascontiguousarray(X[p[N_q:]])
+
+
+def measure_cross(name, q, r, Nq, Nr, k, cap, reps=3):
+    q.bench_knn_against(r, k, max_rmsd=cap, reps=1)  # warm-up: code objects, pool blocks
+    runs = [q.bench_knn_against(r, k, max_rmsd=cap, reps=1) for _ in range(reps)]
+    dev = np.array([x[0] for x in runs])
+    s = dev.mean() * 1e-3
+    idx, _ = q.knn_against(r, k, max_rmsd=cap)
+    out = {"workload": name, "Nq": Nq, "Nr": Nr, "A": A, "k": k, "max_rmsd": cap, "strips": runs[0][2],
+           "ms_device_mean": round(float(dev.mean()), 3), "ms_device_min": round(float(dev.min()), 3),
+           "ms_device_max": round(float(dev.max()), 3), "ms_host_call_mean": round(float(np.mean([x[1] for x in runs])), 3),
+           "ordered_alignments": Nq * Nr, "alignments_per_s": Nq * Nr / s,
+           "rows_with_an_entry": int((idx[:, 0] >= 0).sum()), "entries": int((idx >= 0).sum())}
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def matrix_route_cross(Q, R, k):
+    """the one route without fc_ensemble_knn_cross: the fp64 matrix of the concatenated sets to the host, the block of
+    the queries against the references cut out of it, argpartition + sort per row"""
+    X = np.concatenate([Q, R])
+    with fc.DeviceEnsemble(X, atom_mask=np.ones(X.shape[1], bool), center=True) as ens:
+        M, _ = ens.rmsd_values()
+    B = M[:len(Q), len(Q):]
+    part = np.argpartition(B, k - 1, axis=1)[:, :k]
+    d = np.take_along_axis(B, part, axis=1)
+    order = np.lexsort((part, d), axis=1)
+    return np.take_along_axis(part, order, axis=1).astype(np.int32), np.take_along_axis(d, order, axis=1)
+
+
+def end_to_end_cross(Q, R, k, reps=3):
+    """host arrays in -> lists out, the two routes alternating in one process"""
+    atoms = np.array(["C"] * Q.shape[1])
+    fc.pruner.knn_by_rmsd_against(Q, R, atoms, k), matrix_route_cross(Q, R, k)  # warm-up of both
+    t_new, t_old, same = [], [], True
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        nb = fc.pruner.knn_by_rmsd_against(Q, R, atoms, k)
+        t_new.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        idx, _ = matrix_route_cross(Q, R, k)
+        t_old.append(time.perf_counter() - t0)
+        same = same and bool(np.array_equal(idx, nb.indices))
+    print(json.dumps({"workload": f"end to end, {len(Q)} x {len(R)} x {Q.shape[1]}, k = {k}",
+                      "knn_by_rmsd_against_ms": [round(1e3 * t, 2) for t in t_new],
+                      "matrix_route_ms": [round(1e3 * t, 2) for t in t_old],
+                      "knn_by_rmsd_against_ms_mean": round(1e3 * float(np.mean(t_new)), 2),
+                      "matrix_route_ms_mean": round(1e3 * float(np.mean(t_old)), 2),
+                      "same_indices": same}), flush=True)
+
+
+def cross():
+    dup = fc.pruner.CONVENTIONS["default_max_rmsd"]  # the duplicate threshold of prune_by_rmsd
+    sizes = [(10_000, 10_000), (1_000, 100_000)] + ([] if "--small" in sys.argv else [(100, 1_000_000)])
+    mask = np.ones(A, bool)
+    for Nq, Nr in sizes:
+        Q, R = split(Nq, Nr, 13)
+        with fc.DeviceEnsemble(Q, atom_mask=mask, center=True) as q, fc.DeviceEnsemble(R, atom_mask=mask, center=True) as r:
+            for k in (1, 8):
+                for cap in (None, dup):
+                    measure_cross(f"cross {Nq} x {Nr} x {A}, k = {k}, {'no cap' if cap is None else f'cap {cap}'}", q, r,
+                                  Nq, Nr, k, cap)
+        if (Nq, Nr) == (10_000, 10_000):  # the self form on the references, in the same process: N (N - 1) against N^2
+            measure(f"self form, continuous {Nr} x {A}, k = 8", R, 8)
+        del Q, R
+    Q, R = split(5_000, 5_000, 14)
+    end_to_end_cross(Q, R, 8)
+
+
 def main():
     fc.init(0)
     fc._lib.warmup()
+    if "--cross" in sys.argv:
+        cross()
+        return
     if "--trace" in sys.argv:
         with fc.DeviceEnsemble(ensemble("continuous", 10_000, 11), atom_mask=np.ones(A, bool), center=True) as ens:
             ens.knn(8)
