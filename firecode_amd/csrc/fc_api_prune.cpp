@@ -241,7 +241,11 @@ static int simbits_local(fc_ensemble *e, double max_rmsd, double max_dev, const 
 // duration of the last screen kernel enqueued by simbits_local, after a sync
 static int64_t last_screen_ns() {
   float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ctx().ev2, ctx().ev3) != hipSuccess) return 0;
+  if (hipEventElapsedTime(&ms, ctx().ev2, ctx().ev3) != hipSuccess) {
+    (void)hipGetLastError();  // (no screen has run in this process, the events were never recorded: the refusal must not
+                              // stay behind for the next launch's check to find)
+    return 0;
+  }
   return (int64_t)(ms * 1e6);
 }
 
@@ -277,6 +281,10 @@ struct LadderJob {
   const uint64_t *pairs_dev = nullptr;  // device list of the exactly-similar pairs (see ladder_single)
   bool pairs_are_final = false;         // the list's length is counters[2] alone (uploaded or gathered by the caller)
   bool counters_zeroed = false;         // counters[8 ..) are already zero on the stream
+  // which device form of the ladder runs: -1 the prune's own choice (below); 0 the bit-matrix levels, 1 the one-workgroup
+  // pair ladder, 2 the launch-per-level pair ladder -- exactly that one or FC_E_LIMIT (fc_debug_ladder_from_pairs)
+  int form = -1;
+  unsigned many_grid = 0;               // workgroups per level launch of form 2 (0: ladder_many_grid())
   int64_t defer_slot = -1, slot_stride = 0;
   uint8_t *mask_out = nullptr;
   int64_t *levels = nullptr, *survivors = nullptr;
@@ -321,7 +329,11 @@ static int ladder_single(fc_ensemble *e, int64_t min_per_group, const LadderJob 
   uint64_t *words = slot_words(std::max<int64_t>(defer_slot, 0), W, job.slot_stride);
   uint64_t *cnt_host = words + W;
   bool have_mask = false;
-  if (pairs_dev != nullptr && fits_pair_ladder(W)) {
+  const bool pair_form_asked = job.form == 1 || job.form == 2;
+  if (pair_form_asked && (pairs_dev == nullptr || !fits_pair_ladder(W)))
+    return set_error(FC_E_LIMIT, "N = %lld: the pair ladder keeps two masks of %lld words in LDS, 3840 words at the most",
+                     (long long)N, (long long)W);
+  if (pairs_dev != nullptr && fits_pair_ladder(W) && job.form != 0) {
     // sparse similarity (the usual case): the whole ladder is ONE launch over the pair list
     // the values that can run at this N are a suffix of kLadder: they sit on the device once per context (a launch of
     // k_store_ladder_ks per fresh ensemble -- every drop-in call -- was 5 us of an otherwise empty device)
@@ -371,20 +383,27 @@ static int ladder_single(fc_ensemble *e, int64_t min_per_group, const LadderJob 
       const char *v = getenv("FC_LADDER_MANY");  // 0: always the one-workgroup ladder
       return !(v && atoi(v) == 0);
     }();
-    if (many_ok && n_lv >= 2 && e->last_similar > ((int64_t)1 << 17))
+    const bool many = pair_form_asked ? job.form == 2 : many_ok && n_lv >= 2 && e->last_similar > ((int64_t)1 << 17);
+    // (the two masks of the launch-per-level form sit in the first 2 W words: its result goes behind them also when k = 1
+    // is the only level, which the prunes never send there)
+    uint64_t *const result_dev = mb + (size_t)std::max(n_lv, 2) * W;
+    if (many)
       FC_TRY(launch_ladder_pairs_many(pairs_dev, e->levelmask.as<uint64_t>(), cnt + 2, job.pairs_are_final ? nullptr : cnt + 6,
                                       (unsigned long long)e->pairq_cap, ladder_cap, N, W, min_per_group,
-                                      ks_dev ? ks_dev : e->ladder_k.as<int64_t>(), ks.data(), n_lv, mb, mb + (size_t)n_lv * W, cnt));
+                                      ks_dev ? ks_dev : e->ladder_k.as<int64_t>(), ks.data(), n_lv, mb, result_dev, cnt,
+                                      job.many_grid ? job.many_grid : ladder_many_grid()));
     else
       FC_TRY(launch_ladder_pairs(pairs_dev, e->levelmask.as<uint64_t>(), cnt + 2,
                                  job.pairs_are_final ? nullptr : cnt + 6,
                                  (unsigned long long)e->pairq_cap, ladder_cap, N, W, min_per_group,
-                                 ks_dev ? ks_dev : e->ladder_k.as<int64_t>(), n_lv, mb + (size_t)n_lv * W, cnt));
+                                 ks_dev ? ks_dev : e->ladder_k.as<int64_t>(), n_lv, result_dev, cnt));
     // mask words and the 16 counters behind them (written by the kernel): one copy
-    FC_TRY(d2h(words, mb + (size_t)n_lv * W, (size_t)(W + 16) * sizeof(uint64_t)));
+    FC_TRY(d2h(words, result_dev, (size_t)(W + 16) * sizeof(uint64_t)));
     if (defer_slot >= 0) return FC_OK;
     FC_TRY(sync());
     have_mask = cnt_host[9] != 0;
+    if (pair_form_asked && !have_mask)
+      return set_error(FC_E_LIMIT, "the pair ladder declined the list: more than %llu entries", ladder_cap);
   }
   if (defer_slot >= 0) return set_error(FC_E_INVALID, "deferred ladder needs the pair list");
   if (!have_mask) {
@@ -471,7 +490,8 @@ static void fill_stats(int64_t *stats, int64_t pairs, const unsigned long long *
 }
 
 // the bare ladder workspace over a bit matrix that is not the RMSD screen's (the caller's bits, MOI, rot-corr)
-static int ladder_workspace(fc_ensemble *e, int64_t N, size_t *bits_bytes = nullptr) {
+// (with_bits = false: the pair ladders alone, which need no bit matrix)
+static int ladder_workspace(fc_ensemble *e, int64_t N, size_t *bits_bytes = nullptr, bool with_bits = true) {
   e->N = N, e->Npad = ceil_div(N, 64) * 64, e->W = e->Npad / 64;
   e->row_block = 64;
   FC_TRY(e->maskA.reserve((size_t)e->Npad));
@@ -482,7 +502,7 @@ static int ladder_workspace(fc_ensemble *e, int64_t N, size_t *bits_bytes = null
   const int64_t rows = ceil_div(N, e->row_block) * e->row_block;
   const size_t bytes = (size_t)rows * e->W * sizeof(uint64_t);
   if (bits_bytes) *bits_bytes = bytes;
-  return e->bits.reserve(bytes);
+  return with_bits ? e->bits.reserve(bytes) : FC_OK;
 }
 
 // principal moments of coordinates that are already on the device
@@ -1120,6 +1140,36 @@ int fc_greedy_prune_from_bits(const uint64_t *bits, int64_t N, int64_t min_per_g
   FC_TRY(h2d(e.bits.p, bits, (size_t)N * e.W * sizeof(uint64_t)));
   LadderJob job;
   job.bits_dev = e.bits.as<uint64_t>(), job.mask_out = mask_out;
+  return ladder_single(&e, min_per_group, job);
+}
+
+// test hook: the ladder over a caller's pair list in ONE chosen device form (include/fc_hip.h)
+int fc_debug_ladder_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int64_t min_per_group, int form,
+                               int64_t grid, uint8_t *mask_out, int64_t *levels_out) {
+  FC_API_LOCK;
+  FC_REQUIRE(N >= 1 && N <= (int64_t)INT32_MAX && n_pairs >= 0 && min_per_group >= 1, "bad arguments");
+  FC_REQUIRE(mask_out && (pairs || n_pairs == 0), "NULL pointer argument");
+  FC_REQUIRE(form >= 0 && form <= 2, "form %d: 0 (bit-matrix levels), 1 (one-workgroup pair ladder) or 2 (launch per level)", form);
+  FC_REQUIRE(form != 2 || (grid >= 1 && grid <= kLadderManyGridMax), "grid %lld outside [1, %ld]", (long long)grid,
+             kLadderManyGridMax);
+  FC_TRY(ensure_init());
+  fc_ensemble e;
+  size_t bits_bytes = 0;
+  FC_TRY(ladder_workspace(&e, N, &bits_bytes, /*with_bits=*/form == 0));
+  auto *cnt = reinterpret_cast<unsigned long long *>(e.counters.p);
+  DevBuf dp;
+  FC_TRY(upload(dp, pairs, (size_t)n_pairs));
+  LadderJob job;
+  job.mask_out = mask_out, job.levels = levels_out, job.form = form, job.many_grid = (unsigned)grid;
+  if (form == 0) {
+    FC_HIP_TRY(hipMemsetAsync(e.bits.p, 0, bits_bytes, ctx().stream));
+    FC_TRY(launch_scatter_pairs(dp.as<uint64_t>(), n_pairs, N, e.W, e.bits.as<uint64_t>()));
+    job.bits_dev = e.bits.as<uint64_t>();
+  } else {
+    const unsigned long long np = (unsigned long long)n_pairs;
+    FC_TRY(h2d(cnt + 2, &np, sizeof np));  // (the pair ladders read the list's length from counters[2])
+    job.pairs_dev = dp.as<uint64_t>(), job.pairs_are_final = true;
+  }
   return ladder_single(&e, min_per_group, job);
 }
 

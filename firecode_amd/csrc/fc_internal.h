@@ -55,7 +55,9 @@ int launch_ladder_pairs_many(const uint64_t *pairs_dev, uint64_t *buckets_dev, c
                              const unsigned long long *n_cand_dev, unsigned long long cand_cap, unsigned long long cap,
                              int64_t N, int64_t W, int64_t min_per_group, const int64_t *ladder_dev,
                              const int64_t *ladder_host, int n_ladder, uint64_t *mask_bufs_dev, uint64_t *mask_out_dev,
-                             unsigned long long *counters_dev);
+                             unsigned long long *counters_dev, unsigned grid);
+constexpr long kLadderManyGridMax = 4096;
+unsigned ladder_many_grid();
 int launch_ladder_pairs(const uint64_t *pairs_dev, uint64_t *buckets_dev, const unsigned long long *n_pairs_dev,
                         const unsigned long long *n_cand_dev, unsigned long long cand_cap, unsigned long long cap,
                         int64_t N, int64_t W, int64_t min_per_group, const int64_t *ladder_dev, int n_ladder,

@@ -1571,10 +1571,22 @@ k_pair_buckets_many(const uint64_t *__restrict__ pairs, const unsigned long long
   }
 }
 
+// workgroups per level launch of the prunes (tuning knob FC_LADDER_MANY_GRID, read once per process)
+unsigned ladder_many_grid() {
+  static const unsigned many_grid = [] {
+    const char *v = getenv("FC_LADDER_MANY_GRID");
+    const long g = v ? std::strtol(v, nullptr, 10) : 16;  // (2 .. 256 measured at 7.6e5 pairs: 16-32 best; many workgroups pay in global atomics and tickets)
+    return (unsigned)(g >= 1 && g <= kLadderManyGridMax ? g : 16);
+  }();
+  return many_grid;
+}
+
+// grid: workgroups per level launch, 1 .. kLadderManyGridMax (the caller's check)
 int launch_ladder_pairs_many(const uint64_t *pairs_dev, uint64_t *buckets_dev, const unsigned long long *n_pairs_dev,
                              const unsigned long long *n_cand_dev, unsigned long long cand_cap, unsigned long long cap,
                              int64_t N, int64_t W, int64_t min_per_group, const int64_t *ladder_dev, const int64_t *ladder_host,
-                             int n_ladder, uint64_t *mask_bufs_dev, uint64_t *mask_out_dev, unsigned long long *counters_dev) {
+                             int n_ladder, uint64_t *mask_bufs_dev, uint64_t *mask_out_dev, unsigned long long *counters_dev,
+                             unsigned grid) {
   hipStream_t st = ctx().stream;
   hipLaunchKernelGGL(k_pair_buckets_many, dim3((unsigned)ctx().n_cu), dim3(1024), 0, st, pairs_dev, n_pairs_dev, cap, N,
                      ladder_dev, n_ladder, buckets_dev, counters_dev + kCntLevel, n_cand_dev, cand_cap);
@@ -1587,12 +1599,7 @@ int launch_ladder_pairs_many(const uint64_t *pairs_dev, uint64_t *buckets_dev, c
     const int64_t k = ladder_host[l];
     const uint64_t *src = k == 1 ? pairs_dev : buckets_dev + (unsigned long long)l * cap;
     const unsigned long long *n_src = k == 1 ? n_pairs_dev : counters_dev + kCntLevel + kCntLevelStride * l;
-    static const unsigned many_grid = [] {
-      const char *v = getenv("FC_LADDER_MANY_GRID");  // workgroups per level launch (tuning knob)
-      const long g = v ? std::strtol(v, nullptr, 10) : 16;  // (2 .. 256 measured at 7.6e5 pairs: 16-32 best; many workgroups pay in global atomics and tickets)
-      return (unsigned)(g >= 1 && g <= 4096 ? g : 16);
-    }();
-    hipLaunchKernelGGL(k_ladder_many_level, dim3(many_grid), dim3(kLadderManyThreads), lds, st, src, n_src, k, N, W, min_per_group,
+    hipLaunchKernelGGL(k_ladder_many_level, dim3(grid), dim3(kLadderManyThreads), lds, st, src, n_src, k, N, W, min_per_group,
                        buf_a, buf_b, counters_dev, g_drop_later, n_pairs_dev, n_cand_dev, cand_cap, cap);
     FC_TRY(check_launch("k_ladder_many_level"));
   }

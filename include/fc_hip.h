@@ -814,6 +814,21 @@ int fc_debug_pyset_order_pairs_device(const int64_t *pairs, int64_t n, int64_t *
 /* the device ladder's per-chunk and per-component routines (fc_tfd_core.h) run on the CPU by one host thread standing
  * for a wavefront: same mask as fc_tfd_ladder_from_first_match.  Pure host code.  Test hook. */
 int fc_debug_tfd_ladder_emulate(const int64_t *first_match, int64_t N, uint8_t *mask_out);
+/* The greedy k-ladder of the RMSD prunes over a caller's list of similar pairs ((i << 32) | j; entries with j <= i or
+ * j >= N never act, duplicates are harmless), in ONE chosen device form -- the prunes pick a form from the list's
+ * length and the ensemble's history, so a test cannot otherwise drive a given form from a given graph:
+ *   form 0  the list scattered into an N x ceil(N/64) bit matrix, then one launch per level over it (what a prune
+ *           runs on dense similarity or a list the pair ladder declines);
+ *   form 1  the one-workgroup pair ladder: the whole ladder in one launch (what every ordinary prune runs);
+ *   form 2  the launch-per-level pair ladder with `grid` workgroups per level, 1 .. 4096 (what a prune runs, with
+ *           FC_LADDER_MANY_GRID = 16 workgroups by default, once more than 2^17 similar pairs were seen).
+ * Exactly the requested form runs, or the call returns FC_E_LIMIT: forms 1 and 2 when N > 245 760 (two masks of
+ * ceil(N/64) words in 60 KB of LDS) or n_pairs > min(2^20, max(1024, N (N - 1) / 2)).  fc_prune_conventions is
+ * honoured as by the prunes: forms 1 and 2 implement drop_later, form 0 returns FC_E_INVALID under it.
+ * mask_out: N bytes; levels_out (may be NULL): the number of ladder levels that ran (counters[8] of the prunes).
+ * `grid` is read by form 2 only.  Test hook. */
+int fc_debug_ladder_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int64_t min_per_group, int form,
+                               int64_t grid, uint8_t *mask_out, int64_t *levels_out);
 
 /* ---- a1: the .xyz wire format (host code; firecode/ensemble.py:58-98, 284-297;
  * firecode/utils.py:105-116).  atoms: A C strings.  mode 0 = Ensemble.to_xyz text
