@@ -185,6 +185,12 @@ _SIGNATURES = {
     "fc_bench_knn": [_ens, _i64, _i64, _p_f64, _p_f64, _p_i64],
     "fc_ensemble_knn_cross": [_ens, _ens, _i64, C.c_double, C.POINTER(C.c_int32), _p_f64],
     "fc_bench_knn_cross": [_ens, _ens, _i64, C.c_double, _i64, _p_f64, _p_f64, _p_i64],
+    "fc_ensemble_knn_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, _i64, C.POINTER(C.c_int32), _p_f64],
+    "fc_ensemble_knn_cross_perm": [_ens, _ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, _i64, C.c_double,
+                                   C.POINTER(C.c_int32), _p_f64],
+    "fc_bench_knn_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, _i64, _i64, _p_f64, _p_f64, _p_i64, _p_i64],
+    "fc_bench_knn_cross_perm": [_ens, _ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, _i64, C.c_double, _i64, _p_f64, _p_f64,
+                                _p_i64, _p_i64],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("fc_last_error",)
@@ -589,19 +595,48 @@ class DeviceEnsemble:
              C.byref(host), pi(idx), C.byref(k), C.byref(lanes))
         return dev.value, host.value, idx[:k.value], lanes.value
 
-    def knn(self, k):
+    def _knn_perm_args(self, symmetry, prune_enantiomers):
+        """``symmetry=`` (a (K, A_all) table) and the mirror flag of the nearest-neighbour lists -> None when neither is
+        set, else the arguments of the ``_perm`` entry points behind the handles; every check made before a handle is used"""
+        from firecode_amd import symmetry as S
+
+        enant = check_flag("prune_enantiomers", prune_enantiomers)
+        if symmetry is None and not enant:
+            return None
+        # (a twin workspace refuses here; the identity table stands for "mirror images only")
+        keep, args = self._perm_args(np.arange(self.A_all, dtype=np.int64)[None] if symmetry is None else symmetry)
+        S.knn_lds_check(args[1], args[2])
+        return keep, args + (int(enant),)
+
+    def knn(self, k, symmetry=None, prune_enantiomers=False):
         """The ``k`` nearest neighbours of every conformer under this ensemble's RMSD (fc_ensemble_knn; the contract is
         in include/fc_hip.h) -> ``(indices (N, k) int32, distances (N, k) float64)``, each row in ascending order of
-        (distance, index), the conformer itself left out; rows longer than N - 1 end in -1 / +inf.  No N x N matrix."""
+        (distance, index), the conformer itself left out; rows longer than N - 1 end in -1 / +inf.  No N x N matrix.
+        ``symmetry=`` a (K, A_all) table of atom permutations and / or ``prune_enantiomers=True``: under the smallest
+        RMSD over the permutations and, with the flag, over both handednesses (fc_ensemble_knn_perm) -- a relabelled
+        copy or a mirror image of a conformer is its first neighbour, at distance 0."""
+        perm = self._knn_perm_args(symmetry, prune_enantiomers)
         k = check_knn_k(k, limit=False)
         shape = (self.N, k) if k <= KNN_MAX else (1, 1)  # (beyond the limit the library refuses before it writes)
         idx, dist = np.empty(shape, dtype=np.int32), np.empty(shape)
-        call("fc_ensemble_knn", self.handle, k, ptr(idx, C.c_int32), pf(dist))
+        if perm is not None:
+            call("fc_ensemble_knn_perm", self.handle, *perm[1], k, ptr(idx, C.c_int32), pf(dist))
+        else:
+            call("fc_ensemble_knn", self.handle, k, ptr(idx, C.c_int32), pf(dist))
         return idx, dist
 
-    def bench_knn(self, k, reps=3):
-        """``reps`` calls of ``knn(k)`` -> (mean device ms, mean host ms, column strips of the launch)"""
+    def bench_knn(self, k, reps=3, symmetry=None, prune_enantiomers=False):
+        """``reps`` calls of ``knn(k)`` -> (mean device ms, mean host ms, column strips of the launch); with
+        ``symmetry=`` / ``prune_enantiomers=True`` (fc_bench_knn_perm) a fourth entry ``(formed, explicit)``: the
+        (pair, permutation, handedness) combinations whose eigenvalue was formed and those taken through the explicit
+        pass, over one call."""
+        perm = self._knn_perm_args(symmetry, prune_enantiomers)
         dev, host, strips = C.c_double(0), C.c_double(0), C.c_int64(0)
+        if perm is not None:
+            stats = np.zeros(2, dtype=np.int64)
+            call("fc_bench_knn_perm", self.handle, *perm[1], check_knn_k(k, limit=False), int(reps), C.byref(dev), C.byref(host),
+                 C.byref(strips), pi(stats))
+            return dev.value, host.value, strips.value, (int(stats[0]), int(stats[1]))
         call("fc_bench_knn", self.handle, check_knn_k(k, limit=False), int(reps), C.byref(dev), C.byref(host), C.byref(strips))
         return dev.value, host.value, strips.value
 
@@ -615,23 +650,37 @@ class DeviceEnsemble:
             raise FirecodeHipInputError(FC_E_INVALID, "the two ensembles do not have the same atom selection")
         return other.handle
 
-    def knn_against(self, other, k, max_rmsd=None):
+    def knn_against(self, other, k, max_rmsd=None, symmetry=None, prune_enantiomers=False):
         """For every conformer of this ensemble its ``k`` nearest conformers of ``other`` under the RMSD
         (fc_ensemble_knn_cross; the contract is in include/fc_hip.h) -> ``(indices (N, k) int32 into ``other``,
         distances (N, k) float64)``, each row in ascending order of (distance, index), nothing left out (``other`` may
         be this ensemble: a row then lists itself first).  ``max_rmsd``: only references with ``d < max_rmsd`` are
-        listed; rows with fewer than ``k`` of them end in -1 / +inf.  Both ensembles: centred, the same atom selection."""
+        listed; rows with fewer than ``k`` of them end in -1 / +inf.  Both ensembles: centred, the same atom selection.
+        ``symmetry=`` / ``prune_enantiomers=True``: as in ``knn`` (fc_ensemble_knn_cross_perm); the one table serves
+        both ensembles."""
+        perm = self._knn_perm_args(symmetry, prune_enantiomers)
         k = check_knn_k(k, limit=False)
         cap = check_max_rmsd_cap(max_rmsd)
         ref = self._other(other)
         shape = (self.N, k) if k <= KNN_MAX else (1, 1)  # (beyond the limit the library refuses before it writes)
         idx, dist = np.empty(shape, dtype=np.int32), np.empty(shape)
-        call("fc_ensemble_knn_cross", self.handle, ref, k, cap, ptr(idx, C.c_int32), pf(dist))
+        if perm is not None:
+            call("fc_ensemble_knn_cross_perm", self.handle, ref, *perm[1], k, cap, ptr(idx, C.c_int32), pf(dist))
+        else:
+            call("fc_ensemble_knn_cross", self.handle, ref, k, cap, ptr(idx, C.c_int32), pf(dist))
         return idx, dist
 
-    def bench_knn_against(self, other, k, max_rmsd=None, reps=3):
-        """``reps`` calls of ``knn_against(other, k, max_rmsd)`` -> (mean device ms, mean host ms, column strips)"""
+    def bench_knn_against(self, other, k, max_rmsd=None, reps=3, symmetry=None, prune_enantiomers=False):
+        """``reps`` calls of ``knn_against(other, k, max_rmsd)`` -> (mean device ms, mean host ms, column strips); with
+        ``symmetry=`` / ``prune_enantiomers=True`` (fc_bench_knn_cross_perm) a fourth entry ``(formed, explicit)`` as
+        ``bench_knn``"""
+        perm = self._knn_perm_args(symmetry, prune_enantiomers)
         dev, host, strips = C.c_double(0), C.c_double(0), C.c_int64(0)
+        if perm is not None:
+            stats = np.zeros(2, dtype=np.int64)
+            call("fc_bench_knn_cross_perm", self.handle, self._other(other), *perm[1], check_knn_k(k, limit=False),
+                 check_max_rmsd_cap(max_rmsd), int(reps), C.byref(dev), C.byref(host), C.byref(strips), pi(stats))
+            return dev.value, host.value, strips.value, (int(stats[0]), int(stats[1]))
         call("fc_bench_knn_cross", self.handle, self._other(other), check_knn_k(k, limit=False), check_max_rmsd_cap(max_rmsd),
              int(reps), C.byref(dev), C.byref(host), C.byref(strips))
         return dev.value, host.value, strips.value

@@ -849,8 +849,45 @@ int fc_bench_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, doub
 }
 
 // ---- k nearest neighbours under the RMSD (the contract: include/fc_hip.h; the kernels: fc_knn.hip) ------------------
+// a checked table for the forms under d_sym (fc_ensemble_knn_perm, fc_ensemble_knn_cross_perm, further down)
+struct KnnPerm {
+  std::vector<uint16_t> table;  // (K, A_sel), as perm_table_check leaves it
+  int K = 1;
+  bool mirror = false;
+  int64_t *stats = nullptr;  // (may be NULL) the two counters of KnnSym::stats_dev after the call
+};
+
+// knn() behind the checks and ensure_init; perm (may be NULL): under d_sym -- the table goes up first and lives, like the
+// counters, until knn()'s last wait
+static int knn_run(fc_ensemble *q, fc_ensemble *r, bool cross, int64_t k, double max_rmsd, int32_t *indices_out,
+                   double *dist_out, double *ms_device, int64_t *strips_out, const KnnPerm *perm) {
+  if (!perm) return knn(q, r, cross, k, max_rmsd, indices_out, dist_out, ms_device, strips_out);
+  DevBuf dperm, dstats;
+  const auto run = [&]() -> int {
+    KnnSym sym;
+    FC_TRY(upload(dperm, perm->table.data(), perm->table.size()));
+    sym.perms_dev = dperm.as<uint16_t>(), sym.K = perm->K, sym.mirror = perm->mirror;
+    if (perm->stats) {
+      FC_TRY(dstats.reserve(2 * sizeof(unsigned long long)));
+      FC_HIP_TRY(hipMemsetAsync(dstats.p, 0, 2 * sizeof(unsigned long long), ctx().stream));
+      sym.stats_dev = reinterpret_cast<unsigned long long *>(dstats.p);
+    }
+    FC_TRY(knn(q, r, cross, k, max_rmsd, indices_out, dist_out, ms_device, strips_out, &sym));
+    if (perm->stats) {
+      unsigned long long cnt[2] = {0, 0};
+      FC_TRY(d2h(cnt, dstats.p, sizeof cnt));
+      FC_TRY(sync());
+      perm->stats[0] = (int64_t)cnt[0], perm->stats[1] = (int64_t)cnt[1];
+    }
+    return FC_OK;
+  };
+  const int rc = run();
+  if (rc != FC_OK && ctx().ready) (void)hipStreamSynchronize(cur_stream());  // nothing of the buffers may be in flight when they go
+  return rc;
+}
+
 static int knn_checked(fc_ensemble *ens, int64_t k, int32_t *indices_out, double *dist_out, double *ms_device,
-                       int64_t *strips_out) {
+                       int64_t *strips_out, const KnnPerm *perm = nullptr) {
   FC_REQUIRE(ens != nullptr, "ens is NULL");
   FC_REQUIRE(indices_out != nullptr && dist_out != nullptr, "indices_out / dist_out is NULL");
   FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
@@ -861,7 +898,7 @@ static int knn_checked(fc_ensemble *ens, int64_t k, int32_t *indices_out, double
   if (ens->N == 0) return FC_OK;
   FC_REQUIRE(ens->N <= (int64_t)INT32_MAX - 256, "N=%lld: the lists index conformers with 32 bits", (long long)ens->N);
   FC_TRY(ensure_init());
-  return knn(ens, ens, false, k, INFINITY, indices_out, dist_out, ms_device, strips_out);
+  return knn_run(ens, ens, false, k, INFINITY, indices_out, dist_out, ms_device, strips_out, perm);
 }
 
 int fc_ensemble_knn(fc_ensemble *ens, int64_t k, int32_t *indices_out, double *dist_out) {
@@ -894,7 +931,7 @@ int fc_bench_knn(fc_ensemble *ens, int64_t k, int64_t reps, double *ms_device_me
 // the rows of `queries` against the columns of `refs` (the contract: include/fc_hip.h, fc_ensemble_knn_cross); the
 // scalar arguments are judged first, so that their refusals do not depend on the handles
 static int knn_cross_checked(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int32_t *indices_out,
-                             double *dist_out, double *ms_device, int64_t *strips_out) {
+                             double *dist_out, double *ms_device, int64_t *strips_out, const KnnPerm *perm = nullptr) {
   FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
   if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
   FC_REQUIRE(max_rmsd > 0.0, "max_rmsd=%g must be positive (+inf: no cap)", max_rmsd);  // (a NaN fails it)
@@ -916,7 +953,7 @@ static int knn_cross_checked(fc_ensemble *queries, fc_ensemble *refs, int64_t k,
     return FC_OK;
   }
   FC_TRY(ensure_init());
-  return knn(queries, refs, true, k, max_rmsd, indices_out, dist_out, ms_device, strips_out);
+  return knn_run(queries, refs, true, k, max_rmsd, indices_out, dist_out, ms_device, strips_out, perm);
 }
 
 int fc_ensemble_knn_cross(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int32_t *indices_out,
@@ -1606,6 +1643,116 @@ int fc_bench_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int64_t
   if (stats)  // counted in a selection of its own: the timed ones run without the counters
     FC_TRY(select_diverse_perm_checked(ens, perms, K, A_sel, mirror, n_max, start, stop_rmsd, indices_out, nullptr, nullptr,
                                        nullptr, n_selected, nullptr, stats));
+  return FC_OK;
+}
+
+// ---- nearest neighbours under d_sym (include/fc_hip.h; the kernel: k_knn_tile_sym, fc_knn.hip) --------------------------
+namespace {
+// what both forms refuse first, in the order of select_diverse_perm_checked: the table, its LDS, the flag
+int knn_perm_table(const int32_t *perms, int64_t K, int64_t A_sel, int mirror, std::vector<uint16_t> &table) {
+  FC_TRY(perm_table_check(perms, K, A_sel, table));
+  const size_t lds = knn_sym_lds_bytes(A_sel, K);
+  if (lds > kLdsLimit)
+    return set_error(FC_E_LIMIT, "A_sel=%lld selected atoms with K=%lld permutations need %zu bytes of LDS (limit %zu)",
+                     (long long)A_sel, (long long)K, lds, kLdsLimit);
+  FC_REQUIRE(mirror == 0 || mirror == 1, "mirror=%d: 0 or 1", mirror);
+  return FC_OK;
+}
+
+int knn_perm_checked(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, int64_t k,
+                     int32_t *indices_out, double *dist_out, double *ms_device, int64_t *strips_out, int64_t *stats) {
+  KnnPerm perm;
+  FC_TRY(knn_perm_table(perms, K, A_sel, mirror, perm.table));
+  FC_TRY(perm_ensemble_check(ens, K, A_sel, false));
+  if (stats) stats[0] = stats[1] = 0;
+  if (K == 1 && !mirror)  // d_sym = d: the default's kernels, bit for bit
+    return knn_checked(ens, k, indices_out, dist_out, ms_device, strips_out);
+  perm.K = (int)K, perm.mirror = mirror != 0, perm.stats = stats;
+  return knn_checked(ens, k, indices_out, dist_out, ms_device, strips_out, &perm);
+}
+
+int knn_cross_perm_checked(fc_ensemble *queries, fc_ensemble *refs, const int32_t *perms, int64_t K, int64_t A_sel,
+                           int mirror, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out,
+                           double *ms_device, int64_t *strips_out, int64_t *stats) {
+  KnnPerm perm;
+  FC_TRY(knn_perm_table(perms, K, A_sel, mirror, perm.table));
+  FC_REQUIRE(queries != nullptr && refs != nullptr, "queries / refs is NULL");
+  FC_TRY(perm_ensemble_check(queries, K, A_sel, false));
+  FC_TRY(perm_ensemble_check(refs, K, A_sel, false));
+  if (stats) stats[0] = stats[1] = 0;
+  if (K == 1 && !mirror)
+    return knn_cross_checked(queries, refs, k, max_rmsd, indices_out, dist_out, ms_device, strips_out);
+  perm.K = (int)K, perm.mirror = mirror != 0, perm.stats = stats;
+  return knn_cross_checked(queries, refs, k, max_rmsd, indices_out, dist_out, ms_device, strips_out, &perm);
+}
+}  // namespace
+
+int fc_ensemble_knn_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, int64_t k,
+                         int32_t *indices_out, double *dist_out) {
+  FC_API_LOCK;
+  return knn_perm_checked(ens, perms, K, A_sel, mirror, k, indices_out, dist_out, nullptr, nullptr, nullptr);
+}
+
+int fc_ensemble_knn_cross_perm(fc_ensemble *queries, fc_ensemble *refs, const int32_t *perms, int64_t K, int64_t A_sel,
+                               int mirror, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out) {
+  FC_API_LOCK;
+  return knn_cross_perm_checked(queries, refs, perms, K, A_sel, mirror, k, max_rmsd, indices_out, dist_out, nullptr, nullptr,
+                                nullptr);
+}
+
+int fc_bench_knn_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, int64_t k, int64_t reps,
+                      double *ms_device_mean, double *ms_host_mean, int64_t *strips_out, int64_t *stats) {
+  FC_API_LOCK;
+  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
+  std::vector<uint16_t> table;
+  FC_TRY(knn_perm_table(perms, K, A_sel, mirror, table));
+  FC_TRY(perm_ensemble_check(ens, K, A_sel, false));
+  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
+  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
+  std::vector<int32_t> idx((size_t)ens->N * (size_t)k + 1);
+  std::vector<double> dist((size_t)ens->N * (size_t)k + 1);
+  double dev = 0.0, host = 0.0;
+  for (int64_t r = 0; r < reps; ++r) {
+    double ms = 0.0;
+    const auto t0 = std::chrono::steady_clock::now();
+    FC_TRY(knn_perm_checked(ens, perms, K, A_sel, mirror, k, idx.data(), dist.data(), &ms, strips_out, nullptr));
+    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    dev += ms;
+  }
+  *ms_device_mean = dev / (double)reps;
+  *ms_host_mean = host / (double)reps;
+  if (stats)  // counted in a call of its own: the timed ones run without the counters
+    FC_TRY(knn_perm_checked(ens, perms, K, A_sel, mirror, k, idx.data(), dist.data(), nullptr, nullptr, stats));
+  return FC_OK;
+}
+
+int fc_bench_knn_cross_perm(fc_ensemble *queries, fc_ensemble *refs, const int32_t *perms, int64_t K, int64_t A_sel,
+                            int mirror, int64_t k, double max_rmsd, int64_t reps, double *ms_device_mean,
+                            double *ms_host_mean, int64_t *strips_out, int64_t *stats) {
+  FC_API_LOCK;
+  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
+  std::vector<uint16_t> table;
+  FC_TRY(knn_perm_table(perms, K, A_sel, mirror, table));
+  FC_REQUIRE(queries != nullptr && refs != nullptr, "queries / refs is NULL");
+  FC_TRY(perm_ensemble_check(queries, K, A_sel, false));
+  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
+  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
+  std::vector<int32_t> idx((size_t)queries->N * (size_t)k + 1);
+  std::vector<double> dist((size_t)queries->N * (size_t)k + 1);
+  double dev = 0.0, host = 0.0;
+  for (int64_t r = 0; r < reps; ++r) {
+    double ms = 0.0;
+    const auto t0 = std::chrono::steady_clock::now();
+    FC_TRY(knn_cross_perm_checked(queries, refs, perms, K, A_sel, mirror, k, max_rmsd, idx.data(), dist.data(), &ms, strips_out,
+                                  nullptr));
+    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    dev += ms;
+  }
+  *ms_device_mean = dev / (double)reps;
+  *ms_host_mean = host / (double)reps;
+  if (stats)
+    FC_TRY(knn_cross_perm_checked(queries, refs, perms, K, A_sel, mirror, k, max_rmsd, idx.data(), dist.data(), nullptr, nullptr,
+                                  stats));
   return FC_OK;
 }
 

@@ -222,8 +222,16 @@ int launch_symm_pairs(const fc_ensemble *e, const uint16_t *perms_dev, int64_t K
 int warm_symm();
 // ---- fc_knn.hip ------------------------------------------------------------------------------------------
 int knn_strips(int64_t Nq, int64_t Nr);  // column strips of the launch of Nq rows against Nr columns (FC_KNN_STRIPS forces it)
+// the tile kernel under d_sym (k_knn_tile_sym): the table on the device, K rows of the ensembles' A selected atoms
+struct KnnSym {
+  const uint16_t *perms_dev = nullptr;
+  int K = 1;
+  bool mirror = false;
+  unsigned long long *stats_dev = nullptr;  // two counters, or nullptr: (pair, p, h) whose eigenvalue was formed / that made the explicit pass
+};
+size_t knn_sym_lds_bytes(int64_t A, int64_t K);  // the workgroup's 16 row conformers + the table
 int knn(fc_ensemble *q, fc_ensemble *r, bool cross, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out,
-        double *ms_device, int64_t *strips_out);
+        double *ms_device, int64_t *strips_out, const KnnSym *sym = nullptr);
 int warm_knn();
 // ---- fc_tfd_ladder.hip -----------------------------------------------------------------------------------
 int tfd_ladder_device(const int64_t *fm_dev, const int64_t *fm_host, int64_t N, uint8_t *mask_out);

@@ -46,6 +46,22 @@
 // smaller of slot k - 1 and the cap from the first chunk on -- whole chunks are ruled out before any list has filled.
 // d(i, j) is the same instruction sequence in both forms: an ensemble against a bitwise copy of itself gives the
 // distance bits of the one-ensemble form for every i != j.
+//
+// The symmetry- and mirror-aware forms (fc_ensemble_knn_perm, fc_ensemble_knn_cross_perm) are
+// k_knn_tile_sym, further down: the same tiles, strips, lists and merge under
+//   d_sym(i, j) = min over p < K, h in H of rmsd(Q[i], h * R[j][perms[p]]),   H = {+1} or {+1, -1}
+// with a (pair, p, h) taken through the explicit pass unless its eigenvalue rules it out -- by tau as above, or by the
+// pair's smallest explicit sum so far.
+// Why the outputs are the same bits with the filter on or off and for every strip count.  The explicit sum of a
+// (pair, p, h) is one fixed instruction sequence, so the pair has a fixed smallest explicit sum, that of its argmin
+// (p*, h*); the value offered is the minimum over the explicit sums that were VISITED, hence that sum whenever (p*, h*)
+// is visited.  (1) The eigenvalue form of (p*, h*) never exceeds its explicit sum by more than rounding (the iteration
+// comes down from above; the margins cover the rounding), and every other explicit sum of the pair is at least as
+// large: (p*, h*) is never above the running best, so only tau can rule it out.  (2) When tau rules it out,
+// d_sym > tau; whatever else of the pair was visited has an explicit sum >= that of (p*, h*), so the value offered is
+// above tau as well and is not inserted (nor under the cap) -- and tau only shrinks, so the pair is in no final list.
+// (3) A pair that belongs in the final list has d_sym <= every tau its row ever had in any strip, so (p*, h*) is
+// visited and the exact bits are offered.  Visiting MORE (other lanes of the ballot, the filter off) changes no minimum.
 #include "fc_internal.h"
 #include "fc_kabsch_math.h"
 
@@ -241,6 +257,183 @@ k_knn_merge(const double *__restrict__ part_d, const int32_t *__restrict__ part_
   }
 }
 
+// ---------------------------------------------------------------------------
+// k_knn_tile_sym: the tile kernel under d_sym (include/fc_hip.h, fc_ensemble_knn_perm / fc_ensemble_knn_cross_perm;
+// DESIGN.md section 21)
+//
+//   d_sym(i, j) = min over p < K, h in H of rmsd(Q[i], h * R[j][perms[p]]),   H = {+1} or, MIRROR, {+1, -1}
+//
+// k_knn_tile with its chunk walking the table, as k_diverse_step_sym does for its step.  The workgroup's 16 row
+// conformers AND the table (16-bit indices) sit in LDS -- this form is staged only -- and the permutation is applied to
+// the row side: sum_a p_a q_pi(a)^T = sum_b p_pi^-1(b) q_b^T and the table is closed under inverse, so the minimum over
+// "rows of the table applied to the row conformer" is the minimum the contract names, a permutation costs one LDS
+// address per atom (shared by the rows of the wavefront), and the column conformer is still read coalesced from Xs.
+// Per chunk of 64 columns and table row p: the covariances of kKnnSymR of the wavefront's rows with the column in one atom loop; per
+// row the Newton eigenvalue of B and -- MIRROR -- of -B (kabsch_lambda_max_both); a (p, h) goes on to the rotation and
+// the explicit pass (h = -1 as pair_exact_aos<INV> forms it: -B, p + R q) unless its eigenvalue form of A msd rules it
+// out for EVERY lane of the wavefront (a ballot, as k_knn_tile) -- by tau, the smaller of the row's slot k - 1 and the
+// cap under k_knn_tile's margins, or by the pair's smallest explicit sum so far plus A kScreenMargin (the rule of
+// k_diverse_step_sym).  After the K rows each lane offers (sqrt(best / A), j) once, if it made any explicit pass.
+//
+// Why the outputs are the same bits with the filter on or off and for every strip count: the head of this file.
+//
+// stats (may be NULL): [0] += (pair, p, h) whose eigenvalue was formed, [1] += those taken through the explicit pass
+// (the lanes of a wavefront that made the pass: a pair rides along when another lane of its chunk needs it).
+// ---------------------------------------------------------------------------
+size_t knn_sym_lds_bytes(int64_t A, int64_t K) {
+  return (size_t)kKnnTileRows * (size_t)A * 3 * sizeof(double) + (((size_t)K * (size_t)A * sizeof(uint16_t) + 7) & ~(size_t)7);
+}
+
+#ifdef FC_KNN_SYM_ROWS  // (a tuning build: fc_tuning.h)
+constexpr int kKnnSymR = FC_KNN_SYM_ROWS;
+#else
+// rows of a wavefront that share an atom loop.  4 (k_knn_tile's) holds 72 covariance registers beside the two eigenvalues
+// and the running best: 256 VGPRs + 6 ... 29 AGPRs, one wavefront per SIMD; 2 compiles to 193 / 213 VGPRs (MIRROR), two
+// wavefronts per SIMD, and measured 1.2 ... 1.5 x faster at 10 000 x 50 although a column load then serves 2 rows
+// instead of 4.  The outputs do not depend on it.
+constexpr int kKnnSymR = 2;
+#endif
+static_assert(kKnnR % kKnnSymR == 0, "a wavefront's rows in whole groups");
+
+template <bool CROSS, bool MIRROR>
+__global__ void __launch_bounds__(kKnnThreads)
+k_knn_tile_sym(const double *__restrict__ Xs, const double *__restrict__ Xa, const double *__restrict__ Gq, int Nq, int64_t Npad,
+               int A, const uint16_t *__restrict__ perms, int K, int k, int filter, int n_tiles, int n_chunks,
+               double *__restrict__ part_d, int32_t *__restrict__ part_j, unsigned long long *__restrict__ stats,
+               const KnnCross<CROSS> x) {
+  const double *__restrict__ Gr;
+  int Nr;
+  double cap;
+  if constexpr (CROSS) Gr = x.Gr, Nr = x.Nr, cap = x.cap;
+  else Gr = Gq, Nr = Nq, cap = INFINITY;
+  extern __shared__ double s_rows[];  // [kKnnTileRows][A][3], then the table [K][A] as uint16_t
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int S = gridDim.y, s = blockIdx.y;
+  const int c0 = (int)((int64_t)s * n_chunks / S), c1 = (int)((int64_t)(s + 1) * n_chunks / S);
+  const int A3 = 3 * A;
+  const double dA = (double)A;
+  const double margin = dA * kScreenMargin;
+  uint16_t *pt = reinterpret_cast<uint16_t *>(s_rows + kKnnTileRows * A3);
+  for (int t = tid; t < K * A; t += kKnnThreads) pt[t] = perms[t];  // (the first tile's barrier covers it)
+  unsigned long long n_formed = 0, n_explicit = 0;  // (wave-uniform: ballots)
+
+  for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int row0 = tile * kKnnTileRows;
+    __syncthreads();  // (the previous tile's readers)
+    for (int r = w; r < kKnnTileRows; r += kKnnThreads / 64) {
+      const double *__restrict__ src = Xa + (int64_t)min(row0 + r, Nq - 1) * A3;
+      for (int t = lane; t < A3; t += 64) s_rows[r * A3 + t] = src[t];
+    }
+    __syncthreads();
+    // the wavefront's kKnnR rows, kKnnSymR at a time (each group walks the strip: the outputs do not depend on the split)
+    for (int wrow = row0 + w * kKnnR; wrow < min(row0 + (w + 1) * kKnnR, Nq); wrow += kKnnSymR) {  // (wave-uniform)
+      int row[kKnnSymR];
+      const double *__restrict__ P[kKnnSymR];
+      double Gi[kKnnSymR], ld[kKnnSymR], td[kKnnSymR];
+      int lj[kKnnSymR], tj[kKnnSymR];
+#pragma unroll
+      for (int r = 0; r < kKnnSymR; ++r) {
+        row[r] = wrow + r;
+        P[r] = s_rows + (wrow - row0 + r) * A3;
+        Gi[r] = Gq[min(row[r], Nq - 1)];
+        ld[r] = td[r] = INFINITY;
+        lj[r] = tj[r] = INT_MAX;
+      }
+      for (int c = c0; c < c1; ++c) {
+        const int j = c * 64 + lane;
+        const int jl = min(j, Nr - 1);
+        const double *__restrict__ q0 = Xs + jl;
+        const int64_t step = 3 * Npad;
+        const double Gj = Gr[jl];
+        double best[kKnnSymR];  // the pair's smallest explicit sum of squares so far
+#pragma unroll
+        for (int r = 0; r < kKnnSymR; ++r) best[r] = INFINITY;
+#pragma nounroll
+        for (int p = 0; p < K; ++p) {
+          const uint16_t *__restrict__ pr = pt + p * A;
+          // ---- 1. covariances of the column with the rows under row p of the table
+          double B[kKnnSymR][9];
+#pragma unroll
+          for (int r = 0; r < kKnnSymR; ++r)
+#pragma unroll
+            for (int e = 0; e < 9; ++e) B[r][e] = 0.0;
+          {
+            const double *__restrict__ qa = q0;
+#pragma unroll 2
+            for (int a = 0; a < A; ++a, qa += step) {
+              const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
+              const int b = (int)pr[a] * 3;
+#pragma unroll
+              for (int r = 0; r < kKnnSymR; ++r) {
+                const double px = P[r][b], py = P[r][b + 1], pz = P[r][b + 2];
+                B[r][0] = fma(px, qx, B[r][0]); B[r][1] = fma(px, qy, B[r][1]); B[r][2] = fma(px, qz, B[r][2]);
+                B[r][3] = fma(py, qx, B[r][3]); B[r][4] = fma(py, qy, B[r][4]); B[r][5] = fma(py, qz, B[r][5]);
+                B[r][6] = fma(pz, qx, B[r][6]); B[r][7] = fma(pz, qy, B[r][7]); B[r][8] = fma(pz, qz, B[r][8]);
+              }
+            }
+          }
+          // ---- 2. per row and handedness: the filter, and where a lane passes it the rotation and the explicit pass
+#pragma unroll
+          for (int r = 0; r < kKnnSymR; ++r) {
+            const bool ok = j < Nr && (CROSS || j != row[r]) && row[r] < Nq;
+            const double GG = Gi[r] + Gj;
+            double lam_p = 0.0, lam_m = 0.0;
+            if (filter) kabsch_lambda_max_both<MIRROR>(B[r], GG, lam_p, lam_m);
+            n_formed += (unsigned long long)((MIRROR ? 2 : 1) * __popcll(__ballot(ok)));
+#pragma nounroll
+            for (int h = 0; h < (MIRROR ? 2 : 1); ++h) {
+              bool may = ok;
+              if (filter) {  // (a NaN passes)
+                const double msdA = GG - 2.0 * (h ? lam_m : lam_p);
+                const double tau = CROSS ? fmin(td[r], cap) : td[r];
+                may = ok && !(msdA > dA * tau * tau + (margin + kKnnFilterRel * GG)) && !(msdA > best[r] + margin);
+              }
+              if (__ballot(may) == 0) continue;  // (wave-uniform) this (p, h) is ruled out for every column of the chunk
+              n_explicit += (unsigned long long)__popcll(__ballot(ok));
+              const double sg = h ? -1.0 : 1.0;
+              double Bh[9], R[9];
+#pragma unroll
+              for (int e = 0; e < 9; ++e) Bh[e] = sg * B[r][e];
+              if (!kabsch_rotation_qcp(Bh, GG, R)) (void)kabsch_rotation(Bh, R);
+              double ssq = 0.0;
+              const double *__restrict__ qa = q0;
+#pragma unroll 2
+              for (int a = 0; a < A; ++a, qa += step) {
+                const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
+                const int b = (int)pr[a] * 3;
+                const double px = P[r][b], py = P[r][b + 1], pz = P[r][b + 2];
+                const double dx = px - sg * (R[0] * qx + R[1] * qy + R[2] * qz);
+                const double dy = py - sg * (R[3] * qx + R[4] * qy + R[5] * qz);
+                const double dz = pz - sg * (R[6] * qx + R[7] * qy + R[8] * qz);
+                ssq += dx * dx + dy * dy + dz * dz;
+              }
+              if (!(ssq >= best[r])) best[r] = ssq;
+            }
+          }
+        }
+        // ---- 3. one offer per pair: the smallest explicit sum, where any was formed
+#pragma unroll
+        for (int r = 0; r < kKnnSymR; ++r) {
+          const bool ok = j < Nr && (CROSS || j != row[r]) && row[r] < Nq && best[r] != INFINITY;
+          const double d = sqrt(best[r] / dA);
+          knn_offer(ld[r], lj[r], td[r], tj[r], d, j, CROSS ? ok && d < cap : ok, k, lane);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < kKnnSymR; ++r)
+        if (row[r] < Nq && lane < k) {
+          const int64_t at = ((int64_t)row[r] * S + s) * k + lane;
+          part_d[at] = ld[r];
+          part_j[at] = lj[r];
+        }
+    }
+  }
+  if (stats != nullptr && lane == 0 && n_formed) {  // (a bench hook's counters)
+    atomicAdd(&stats[0], n_formed);
+    atomicAdd(&stats[1], n_explicit);
+  }
+}
+
 // column strips of a launch of Nq rows against Nr columns: enough workgroups to fill the chip where the row tiles alone do
 // not; FC_KNN_STRIPS=<n> forces it (speed only: the outputs are the same bits for every value)
 int knn_strips(int64_t Nq, int64_t Nr) {
@@ -284,8 +477,22 @@ static int launch_knn_tile(const KnnLaunch &a, double *part_d, int32_t *part_j) 
   return check_launch("k_knn_tile");
 }
 
+template <bool CROSS, bool MIRROR>
+static int launch_knn_tile_sym(const KnnLaunch &a, const KnnSym &sym, double *part_d, int32_t *part_j) {
+  const size_t lds = knn_sym_lds_bytes(a.q->A, sym.K);
+  FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_knn_tile_sym<CROSS, MIRROR>), lds, "k_knn_tile_sym"));
+  const unsigned gx = (unsigned)std::min<int64_t>(a.n_tiles, (int64_t)1 << 20);
+  KnnCross<CROSS> x;
+  if constexpr (CROSS) x = KnnCross<true>{a.r->G.as<double>(), (int)a.r->N, a.cap};
+  hipLaunchKernelGGL((k_knn_tile_sym<CROSS, MIRROR>), dim3(gx, (unsigned)a.S), dim3(kKnnThreads), lds, ctx().stream,
+                     a.r->Xs.as<double>(), a.q->Xa.as<double>(), a.q->G.as<double>(), (int)a.q->N, a.r->Npad, (int)a.q->A,
+                     sym.perms_dev, sym.K, a.k, a.filter, a.n_tiles, a.n_chunks, part_d, part_j, sym.stats_dev, x);
+  return check_launch("k_knn_tile_sym");
+}
+
 static int knn_enqueue(const fc_ensemble *q, const fc_ensemble *r, bool cross, int k, double cap, int S, int32_t *indices_out,
-                       double *dist_out, double *ms_device, DevBuf &pd, DevBuf &pj, DevBuf &oi, DevBuf &od) {
+                       double *dist_out, double *ms_device, DevBuf &pd, DevBuf &pj, DevBuf &oi, DevBuf &od,
+                       const KnnSym *sym) {
   const int64_t Nq = q->N;
   const KnnLaunch a{q, r, k, knn_filter(), (int)ceil_div(Nq, kKnnTileRows), (int)ceil_div(r->N, 64), S, cap};
   const size_t entries = (size_t)Nq * (size_t)k;
@@ -298,7 +505,13 @@ static int knn_enqueue(const fc_ensemble *q, const fc_ensemble *r, bool cross, i
   const bool stage = q->A <= kKnnLdsAtoms;
   const auto tile = cross ? (stage ? launch_knn_tile<true, true> : launch_knn_tile<false, true>)
                          : (stage ? launch_knn_tile<true, false> : launch_knn_tile<false, false>);
-  FC_TRY(tile(a, pd.as<double>(), pj.as<int32_t>()));
+  if (sym) {
+    const auto tile_sym = cross ? (sym->mirror ? launch_knn_tile_sym<true, true> : launch_knn_tile_sym<true, false>)
+                                : (sym->mirror ? launch_knn_tile_sym<false, true> : launch_knn_tile_sym<false, false>);
+    FC_TRY(tile_sym(a, *sym, pd.as<double>(), pj.as<int32_t>()));
+  } else {
+    FC_TRY(tile(a, pd.as<double>(), pj.as<int32_t>()));
+  }
   const unsigned gm = (unsigned)std::min<int64_t>(ceil_div(Nq, kKnnThreads / 64), (int64_t)1 << 20);
   hipLaunchKernelGGL(k_knn_merge, dim3(gm), dim3(kKnnThreads), 0, c.stream, pd.as<double>(), pj.as<int32_t>(), (int)Nq, S, k,
                      oi.as<int32_t>(), od.as<double>());
@@ -318,13 +531,17 @@ static int knn_enqueue(const fc_ensemble *q, const fc_ensemble *r, bool cross, i
 // The lists behind fc_ensemble_knn (cross = false: q == r, max_rmsd = +inf) and fc_ensemble_knn_cross (cross = true: the
 // rows of q against the columns of r, which may be the same handle) -- arguments checked there; both N >= 1, the same A,
 // 1 <= k <= FC_KNN_MAX, max_rmsd > 0.  ms_device (may be NULL): HIP-event time from the first launch to the end of the
-// merge; strips_out (may be NULL): the strip count used.
+// merge; strips_out (may be NULL): the strip count used.  sym (may be NULL): the tiles are k_knn_tile_sym's
+// (fc_ensemble_knn_perm / fc_ensemble_knn_cross_perm, which have checked that the rows and the table fit the LDS).
 int knn(fc_ensemble *q, fc_ensemble *r, bool cross, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out,
-        double *ms_device, int64_t *strips_out) {
+        double *ms_device, int64_t *strips_out, const KnnSym *sym) {
   const int S = knn_strips(q->N, r->N);
   if (strips_out) *strips_out = S;
+  if (sym && knn_sym_lds_bytes(q->A, sym->K) > kLdsLimit)
+    return set_error(FC_E_LIMIT, "A_sel=%lld selected atoms with K=%d permutations need %zu bytes of LDS (limit %zu)",
+                     (long long)q->A, sym->K, knn_sym_lds_bytes(q->A, sym->K), kLdsLimit);
   DevBuf pd, pj, oi, od;
-  const int rc = knn_enqueue(q, r, cross, (int)k, max_rmsd, S, indices_out, dist_out, ms_device, pd, pj, oi, od);
+  const int rc = knn_enqueue(q, r, cross, (int)k, max_rmsd, S, indices_out, dist_out, ms_device, pd, pj, oi, od, sym);
   // an error behind a launch: nothing of the four buffers may be in flight when they go back to the pool
   if (rc != FC_OK && ctx().ready) (void)hipStreamSynchronize(cur_stream());
   return rc;

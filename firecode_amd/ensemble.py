@@ -137,13 +137,15 @@ class Ensemble:
                 f"{perf_counter() - t0:.3f} s)")
         return sel
 
-    def nearest_neighbours(self, k, heavy_atoms_only=True):
+    def nearest_neighbours(self, k, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
         """The ``k`` nearest neighbours of every structure under the heavy-atom RMSD of the other RMSD stages
         (``firecode_amd.pruner.knn_by_rmsd``).  Returns the ``RmsdNeighbours``, whose ``k_distances(min_samples - 1)`` is
-        the curve one reads the ``max_rmsd`` of ``dbscan_by_rmsd`` from; the ensemble is not masked."""
+        the curve one reads the ``max_rmsd`` of ``dbscan_by_rmsd`` from; the ensemble is not masked.  ``symmetry=`` /
+        ``prune_enantiomers=True``: as in ``knn_by_rmsd`` -- relabelled copies and mirror images are at distance 0."""
         from firecode_amd.pruner import knn_by_rmsd
 
-        return knn_by_rmsd(self.coords, self.atoms, k, heavy_atoms_only=heavy_atoms_only)
+        return knn_by_rmsd(self.coords, self.atoms, k, heavy_atoms_only=heavy_atoms_only, symmetry=symmetry,
+                           prune_enantiomers=prune_enantiomers)
 
     def _same_atoms(self, other):
         from firecode_amd._lib import FC_E_INVALID, FirecodeHipInputError
@@ -154,25 +156,28 @@ class Ensemble:
         if mine.shape != theirs.shape or not np.array_equal(mine, theirs):
             raise FirecodeHipInputError(FC_E_INVALID, "the two ensembles do not have the same atoms")
 
-    def nearest_in(self, other, k=1, max_rmsd=None, heavy_atoms_only=True):
+    def nearest_in(self, other, k=1, max_rmsd=None, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
         """For every structure its ``k`` nearest structures of ``other`` -- an ensemble of the same molecule, same
         ``atoms`` -- under the heavy-atom RMSD (``firecode_amd.pruner.knn_by_rmsd_against``); ``max_rmsd``: only those
         with ``rmsd < max_rmsd``.  Returns the ``RmsdCrossNeighbours`` (indices into ``other``); neither ensemble is
-        masked.  RMSD only: no max-deviation or energy test."""
+        masked.  RMSD only: no max-deviation or energy test.  ``symmetry=`` / ``prune_enantiomers=True``: as in
+        ``knn_by_rmsd``."""
         from firecode_amd.pruner import knn_by_rmsd_against
 
         self._same_atoms(other)
         return knn_by_rmsd_against(self.coords, other.coords, self.atoms, k, max_rmsd=max_rmsd,
-                                   heavy_atoms_only=heavy_atoms_only)
+                                   heavy_atoms_only=heavy_atoms_only, symmetry=symmetry, prune_enantiomers=prune_enantiomers)
 
-    def novel_against(self, other, max_rmsd, heavy_atoms_only=True):
+    def novel_against(self, other, max_rmsd, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
         """(N,) bool: the structures with NO structure of ``other`` within ``max_rmsd`` of them
         (``firecode_amd.pruner.novel_conformers``); the ensemble is not masked.  RMSD only: the max-deviation and
-        energy-window tests of ``similarity_pruning`` are not applied."""
+        energy-window tests of ``similarity_pruning`` are not applied.  ``symmetry=`` / ``prune_enantiomers=True``: as
+        in ``knn_by_rmsd`` -- a relabelled copy or a mirror image of a structure of ``other`` is not new."""
         from firecode_amd.pruner import novel_conformers
 
         self._same_atoms(other)
-        return novel_conformers(self.coords, other.coords, self.atoms, max_rmsd, heavy_atoms_only=heavy_atoms_only)
+        return novel_conformers(self.coords, other.coords, self.atoms, max_rmsd, heavy_atoms_only=heavy_atoms_only,
+                                symmetry=symmetry, prune_enantiomers=prune_enantiomers)
 
     def cluster_by_rmsd(self, max_rmsd=None, heavy_atoms_only=True, prune_enantiomers=False, verbose=True, symmetry=None):
         """Which conformers belong together (``firecode_amd.pruner.cluster_by_rmsd``): the connected components of the

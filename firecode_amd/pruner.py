@@ -243,7 +243,18 @@ class RmsdNeighbours(namedtuple("RmsdNeighbours", ["indices", "distances"])):
         return np.stack([words // max(n, 1), words % max(n, 1)], axis=1).astype(np.int64).reshape(-1, 2)
 
 
-def knn_by_rmsd(structures, atoms, k, heavy_atoms_only=True):
+def _knn_symmetry(symmetry, prune_enantiomers, atoms, heavy, heavy_atoms_only):
+    """``symmetry=`` (a bond graph or a table) and ``prune_enantiomers=`` of the nearest-neighbour drivers -> (the checked
+    table over all atoms or None, the flag); every check, the LDS limit included, made before any device use"""
+    from firecode_amd import symmetry as S
+
+    enant = L.check_flag("prune_enantiomers", prune_enantiomers)
+    table = S.resolve(symmetry, atoms, heavy_atoms_only)
+    S.knn_table(table, enant, heavy, len(atoms))
+    return table, enant
+
+
+def knn_by_rmsd(structures, atoms, k, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
     """The ``k`` nearest neighbours of every conformer under the heavy-atom Kabsch RMSD ``prune_by_rmsd`` uses (centred,
     ``rmsd_and_max(...)[0]``), on the GPU (fc_ensemble_knn; the contract is written out in include/fc_hip.h), with no
     N x N matrix: the top-k selection happens in the kernel that computes the distances.  1 <= k <= 64.
@@ -252,16 +263,22 @@ def knn_by_rmsd(structures, atoms, k, heavy_atoms_only=True):
     (distance, index) -- on equal distances the lower index first -- the conformer itself left out by index (an exact
     duplicate of it is its first neighbour, at distance ~1e-15); when ``k > N - 1`` the rows end in -1 / +inf.
     ``.k_distances(min_samples - 1)`` is the curve one reads the ``max_rmsd`` of ``dbscan_by_rmsd`` from;
-    ``.pairs()`` / ``.pairs(mutual=True)`` is the (mutual) k-NN graph in the format of ``clusters_from_pairs``."""
+    ``.pairs()`` / ``.pairs(mutual=True)`` is the (mutual) k-NN graph in the format of ``clusters_from_pairs``.
+
+    ``symmetry=`` (a bond graph or a (K, A) table over all atoms, as in ``prune_by_rmsd``) and ``prune_enantiomers=True``
+    -- the two combine, as in ``select_diverse`` -- make the distance the smallest RMSD over the atom permutations and,
+    with the flag, over both handednesses (fc_ensemble_knn_perm): a relabelled copy or a mirror image of a conformer is
+    its first neighbour, at distance 0, instead of sitting far away."""
     structures, atoms = _structures_and_atoms(structures, atoms)
     k = L.check_knn_k(k)
     heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
     if not heavy.any():
         raise L.FirecodeHipInputError(L.FC_E_INVALID, "the atom selection is empty (no heavy atom)")
+    table, enant = _knn_symmetry(symmetry, prune_enantiomers, atoms, heavy, heavy_atoms_only)
     if structures.shape[0] == 0:
         return RmsdNeighbours(np.zeros((0, k), dtype=np.int32), np.zeros((0, k)))
     with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
-        return RmsdNeighbours(*ens.knn(k))
+        return RmsdNeighbours(*ens.knn(k, symmetry=table, prune_enantiomers=enant))
 
 
 class RmsdCrossNeighbours(namedtuple("RmsdCrossNeighbours", ["indices", "distances"])):
@@ -293,7 +310,8 @@ def _cross_inputs(structures, references, atoms):
     return structures, references, atoms
 
 
-def knn_by_rmsd_against(structures, references, atoms, k, max_rmsd=None, heavy_atoms_only=True):
+def knn_by_rmsd_against(structures, references, atoms, k, max_rmsd=None, heavy_atoms_only=True, symmetry=None,
+                        prune_enantiomers=False):
     """For every conformer of ``structures`` its ``k`` nearest conformers of ``references`` -- a second set of
     conformers of the same molecule, same ``atoms`` -- under the heavy-atom Kabsch RMSD ``prune_by_rmsd`` uses (centred,
     ``rmsd_and_max(...)[0]``), on the GPU (fc_ensemble_knn_cross; the contract is written out in include/fc_hip.h): the
@@ -304,30 +322,36 @@ def knn_by_rmsd_against(structures, references, atoms, k, max_rmsd=None, heavy_a
     each row in ascending order of (distance, index) -- on equal distances the lower index first.  Nothing is left out:
     a query that is a copy of a reference lists it first, at ~1e-15.  Rows with fewer than ``k`` qualifying references
     (``k > len(references)``, or the cap) end in -1 / +inf.  ``.nearest()`` is column 0; ``.novel(r)`` the queries with
-    no listed reference within ``r``.  RMSD only: the max-deviation and energy-window tests of the prune play no part."""
+    no listed reference within ``r``.  RMSD only: the max-deviation and energy-window tests of the prune play no part.
+
+    ``symmetry=`` / ``prune_enantiomers=True``: as in ``knn_by_rmsd`` (fc_ensemble_knn_cross_perm); the one table serves
+    both sets, which are conformers of the same molecule."""
     structures, references, atoms = _cross_inputs(structures, references, atoms)
     k = L.check_knn_k(k)
     cap = None if max_rmsd is None else L.check_max_rmsd_cap(max_rmsd)
     heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
     if not heavy.any():
         raise L.FirecodeHipInputError(L.FC_E_INVALID, "the atom selection is empty (no heavy atom)")
+    table, enant = _knn_symmetry(symmetry, prune_enantiomers, atoms, heavy, heavy_atoms_only)
     Nq, Nr = structures.shape[0], references.shape[0]
     if Nq == 0 or Nr == 0:  # nothing to list, or nothing to list from: no device needed
         return RmsdCrossNeighbours(np.full((Nq, k), -1, dtype=np.int32), np.full((Nq, k), np.inf))
     with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as q, \
             L.DeviceEnsemble(references, atom_mask=heavy, center=True) as r:
-        return RmsdCrossNeighbours(*q.knn_against(r, k, max_rmsd=cap))
+        return RmsdCrossNeighbours(*q.knn_against(r, k, max_rmsd=cap, symmetry=table, prune_enantiomers=enant))
 
 
-def novel_conformers(structures, references, atoms, max_rmsd, heavy_atoms_only=True):
+def novel_conformers(structures, references, atoms, max_rmsd, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
     """Which conformers of ``structures`` are new against ``references``: (Nq,) bool, true where NO reference is within
     ``max_rmsd`` of the conformer (``rmsd < max_rmsd``, the RMSD test of ``prune_by_rmsd``).  One call of
     ``knn_by_rmsd_against`` with ``k = 1`` and the cap, which lets the kernel's filter rule out whole blocks of
     references from the start.  RMSD only: the max-deviation and energy-window tests of the prune are not applied, so
-    this is not "would ``prune_by_rmsd`` of the union drop it"."""
+    this is not "would ``prune_by_rmsd`` of the union drop it".  ``symmetry=`` / ``prune_enantiomers=True``: as in
+    ``knn_by_rmsd`` -- a relabelled copy or a mirror image of a reference is not new."""
     if max_rmsd is None:
         raise L.FirecodeHipInputError(L.FC_E_INVALID, "novel_conformers needs max_rmsd")
-    nb = knn_by_rmsd_against(structures, references, atoms, 1, max_rmsd=max_rmsd, heavy_atoms_only=heavy_atoms_only)
+    nb = knn_by_rmsd_against(structures, references, atoms, 1, max_rmsd=max_rmsd, heavy_atoms_only=heavy_atoms_only,
+                             symmetry=symmetry, prune_enantiomers=prune_enantiomers)
     return nb.indices[:, 0] < 0
 
 
@@ -346,18 +370,28 @@ class EnsembleCoverage(namedtuple("EnsembleCoverage", ["covered", "fraction", "n
         covered = dist < max_rmsd
         return cls(covered, float(covered.mean()) if len(covered) else float("nan"), nearest, dist)
 
+    def mean_distance(self):
+        """The mean of the finite nearest distances -- the MAT figure quoted beside the coverage; nan when no distance is
+        finite (no reference, or no structure)."""
+        dist = np.asarray(self.distances, dtype=np.float64)
+        finite = dist[np.isfinite(dist)]
+        return float(finite.mean()) if finite.size else float("nan")
 
-def ensemble_coverage(structures, references, atoms, max_rmsd, heavy_atoms_only=True):
+
+def ensemble_coverage(structures, references, atoms, max_rmsd, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
     """Does ``structures`` contain every conformer of ``references`` to within ``max_rmsd`` -- the coverage (recall)
     figure of conformer-generator benchmarks: for every reference, is there a conformer of ``structures`` with
     ``rmsd < max_rmsd``?  ``knn_by_rmsd_against`` with the roles swapped (the references are the rows), ``k = 1`` and no
     cap, so that the distance to the closest conformer is reported for the uncovered references too.
 
-    Returns ``EnsembleCoverage(covered, fraction, nearest, distances)``.  RMSD only, as ``novel_conformers``."""
+    Returns ``EnsembleCoverage(covered, fraction, nearest, distances)``; its ``.mean_distance()`` is the companion
+    figure (MAT).  RMSD only, as ``novel_conformers``.  ``symmetry=`` / ``prune_enantiomers=True``: as in
+    ``knn_by_rmsd`` -- the symmetry-corrected RMSD on which the benchmarks define the two figures."""
     if max_rmsd is None:
         raise L.FirecodeHipInputError(L.FC_E_INVALID, "ensemble_coverage needs max_rmsd")
     max_rmsd = L.check_max_rmsd_cap(max_rmsd)
-    nb = knn_by_rmsd_against(references, structures, atoms, 1, heavy_atoms_only=heavy_atoms_only)
+    nb = knn_by_rmsd_against(references, structures, atoms, 1, heavy_atoms_only=heavy_atoms_only, symmetry=symmetry,
+                             prune_enantiomers=prune_enantiomers)
     return EnsembleCoverage.from_neighbours(nb, max_rmsd)
 
 

@@ -147,6 +147,43 @@ def diverse_table(symmetry, prune_enantiomers, atom_mask, n_atoms):
     return t
 
 
+KNN_TILE_ROWS = 16  # kKnnTileRows
+
+
+def knn_lds_bytes(n_perms, n_selected):
+    """LDS of one workgroup of the symmetry-aware nearest-neighbour lists (fc_ensemble_knn_perm, fc_ensemble_knn_cross_perm):
+    its 16 row conformers and the table as 16-bit indices rounded up to 8 bytes."""
+    return KNN_TILE_ROWS * 24 * int(n_selected) + ((2 * int(n_perms) * int(n_selected) + 7) & ~7)
+
+
+def knn_max_selected(n_perms):
+    """the largest number of selected atoms the symmetry-aware nearest-neighbour lists take with ``n_perms`` permutations"""
+    a = LDS_LIMIT // (KNN_TILE_ROWS * 24 + 2 * int(n_perms)) + 1
+    while knn_lds_bytes(n_perms, a) > LDS_LIMIT:
+        a -= 1
+    return a
+
+
+def knn_lds_check(n_perms, n_selected):
+    """FC_E_LIMIT, before any device use, where the library itself would refuse the lists for their LDS"""
+    need = knn_lds_bytes(n_perms, n_selected)
+    if need > LDS_LIMIT:
+        raise L.FirecodeHipInputError(
+            L.FC_E_LIMIT, f"A_sel={int(n_selected)} selected atoms with K={int(n_perms)} permutations need {need} bytes of "
+            f"LDS (limit {LDS_LIMIT}): at most {knn_max_selected(n_perms)} selected atoms")
+
+
+def knn_table(symmetry, prune_enantiomers, atom_mask, n_atoms):
+    """``symmetry=`` (a checked table over all atoms, or None) and the mirror flag of the nearest-neighbour lists -> the
+    (K, A_sel) int32 table the library takes, or None when neither is set; the LDS limit checked on the way"""
+    if symmetry is None and not prune_enantiomers:
+        return None
+    table = np.arange(int(n_atoms), dtype=np.int64)[None] if symmetry is None else symmetry
+    t = selected_table(table, atom_mask)
+    knn_lds_check(t.shape[0], t.shape[1])
+    return t
+
+
 def refuse_with_enantiomers(table, prune_enantiomers):
     if table is not None and prune_enantiomers:
         raise L.FirecodeHipInputError(

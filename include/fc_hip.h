@@ -204,8 +204,8 @@ int fc_ensemble_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int6
  * takes every pair through the explicit pass and gives the same bits.
  * FC_E_INVALID before any device use: NULL ens or outputs, k < 1; FC_E_LIMIT before any device use: k > FC_KNN_MAX.
  * Limits: N < 2^31 - 256; no atom limit (a workgroup's 16 row conformers are staged in LDS up to 256 selected atoms and
- * read from HBM beyond).  Not offered: symmetry- and mirror-aware forms, sharded, multi-GPU and twin-workspace forms
- * (queries of one ensemble against another: fc_ensemble_knn_cross, below). */
+ * read from HBM beyond).  Not offered: sharded, multi-GPU and twin-workspace forms (queries of one ensemble against
+ * another: fc_ensemble_knn_cross; symmetry- and mirror-aware forms: fc_ensemble_knn_perm, both below). */
 #define FC_KNN_MAX 64
 int fc_ensemble_knn(fc_ensemble *ens, int64_t k, int32_t *indices_out, double *dist_out);
 /* The same lists across two ensembles: for every conformer of `queries` its k nearest conformers
@@ -235,10 +235,40 @@ int fc_ensemble_knn(fc_ensemble *ens, int64_t k, int32_t *indices_out, double *d
  * smaller tau under the same margins, never a different value or order -- which is what makes a novelty query cheap.
  * Refused before any device use -- FC_E_INVALID: k < 1, max_rmsd NaN or <= 0, NULL queries, refs or outputs, an ensemble
  * of an earlier context epoch, different A; FC_E_LIMIT: k > FC_KNN_MAX, Nq or Nr >= 2^31 - 256.  k and max_rmsd are
- * judged first, then the pointers.  No atom limit (LDS stage as fc_ensemble_knn).  Not offered: symmetry- and
- * mirror-aware forms, max-deviation or energy criteria, sharded, multi-GPU and twin-workspace forms. */
+ * judged first, then the pointers.  No atom limit (LDS stage as fc_ensemble_knn).  Not offered: max-deviation or
+ * energy criteria, sharded, multi-GPU and twin-workspace forms (symmetry- and mirror-aware: fc_ensemble_knn_cross_perm). */
 int fc_ensemble_knn_cross(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int32_t *indices_out,
                           double *dist_out);
+/* The symmetry- and mirror-aware forms of the two: the same lists under
+ *
+ *   d_sym(i, j) = min over p < K, h in H of rmsd_and_max(Q[i], h * R[j][perms[p]])[0]       (Q = R = X in the self form)
+ *   H = {+1}, or {+1, -1} when mirror != 0      (-1: the partner inverted through the origin, as in
+ *                                                fc_ensemble_select_diverse_perm and the enantiomer-aware forms below)
+ *
+ * X, Q, R = prepared ensembles (atom selection applied, centred); perms = a (K, A_sel) table exactly as in
+ * fc_ensemble_select_diverse_perm: row 0 the identity, closed under inverse, K <= FC_PERM_MAX; the cross form applies
+ * the one table to both ensembles (the same molecule, the same atom selection: the caller's, as in fc_ensemble_knn_cross).
+ * The table and the flag combine: a minimum over both.  Everything else of fc_ensemble_knn / fc_ensemble_knn_cross
+ * holds with d replaced by d_sym: ascending order of (d_sym, j), the lower index first on ties; the self form leaves
+ * j == i out by index (a relabelled or mirrored copy of i is its first neighbour, at ~1e-15); the cross form leaves
+ * nothing out and keeps the strict cap d_sym < max_rmsd; -1 / +inf padding; N = 0, Nr = 0 and 1 <= k <= FC_KNN_MAX as
+ * there.  The value written out is the explicit rotated-difference rmsd of the winning (p, h) (h = -1: -B, p + R q),
+ * never the eigenvalue form.
+ * Determinism: one fixed instruction sequence per (pair, p, h); the value of a pair is the minimum over the explicit
+ * sums that were formed, and the winning (p, h) of a pair that belongs in a list is always among them (fc_knn.hip says
+ * why), so the outputs are the same bits for every strip count (FC_KNN_STRIPS) and with FC_KNN_FILTER=0, and an
+ * ensemble against a bitwise copy of itself gives, for every i != j, the distance bits of the self form.  K = 1 with
+ * mirror = 0 is fc_ensemble_knn / fc_ensemble_knn_cross itself, bit for bit.
+ * Refused before any device use, in this order: the table (FC_E_INVALID: the table checks of fc_prune_rmsd_perm;
+ * FC_E_LIMIT: K > FC_PERM_MAX, or the LDS limit: a workgroup keeps its 16 row conformers (16 x 24 A_sel bytes) and the
+ * table as 16-bit indices (2 K A_sel bytes, rounded up to 8) in the 160 KiB of LDS -- A_sel <= 422 at K = 2,
+ * <= 413 at K = 6, <= 320 at K = 64; no HBM fallback); mirror outside {0, 1} (FC_E_INVALID); an A_sel that is not the
+ * ensemble's -- either ensemble's -- or a NULL handle (FC_E_INVALID); then the sibling's own checks in its own order.
+ * Not offered: max-deviation or energy criteria, sharded, multi-GPU and twin-workspace forms. */
+int fc_ensemble_knn_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, int64_t k,
+                         int32_t *indices_out, double *dist_out);
+int fc_ensemble_knn_cross_perm(fc_ensemble *queries, fc_ensemble *refs, const int32_t *perms, int64_t K, int64_t A_sel,
+                               int mirror, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out);
 /* a9: get_alignment_matrix(p, q) -- prism_pruner.rmsd; call site
  * hypermolecule_class.py:77.  M (3,3) row-major, applied as (M @ q.T).T */
 int fc_alignment_matrices(const double *p, const double *q, int64_t n_pairs, int64_t A,
@@ -951,6 +981,15 @@ int fc_bench_knn(fc_ensemble *ens, int64_t k, int64_t reps, double *ms_device_me
 /* the same for fc_ensemble_knn_cross (its arguments and refusals) */
 int fc_bench_knn_cross(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int64_t reps,
                        double *ms_device_mean, double *ms_host_mean, int64_t *strips_out);
+/* the same for fc_ensemble_knn_perm and fc_ensemble_knn_cross_perm (their arguments and refusals).  stats (2 values, may be
+ * NULL), over one further call made without the clock: [0] = (pair, p, h) whose eigenvalue was formed, [1] = those that
+ * were taken through the rotation and the explicit pass (a pair rides along when another column of its 64-column chunk
+ * needs the pass: the figure is the work done). */
+int fc_bench_knn_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, int64_t k, int64_t reps,
+                      double *ms_device_mean, double *ms_host_mean, int64_t *strips_out, int64_t *stats);
+int fc_bench_knn_cross_perm(fc_ensemble *queries, fc_ensemble *refs, const int32_t *perms, int64_t K, int64_t A_sel,
+                            int mirror, int64_t k, double max_rmsd, int64_t reps, double *ms_device_mean,
+                            double *ms_host_mean, int64_t *strips_out, int64_t *stats);
 /* (fc_bench_prune_rmsd writes EIGHT stats: [6] = 16 x 32-pair units the subset stage of the lean fp32
  * screen queued for the full test in the last prune, [7] = 1 when its sample found similarity dense
  * and the single-stage kernel did the launch) */

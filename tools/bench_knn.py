@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""k nearest neighbours under the RMSD (fc_ensemble_knn, fc_ensemble_knn_cross) on one MI355X: one JSON line per workload.
+"""k nearest neighbours under the RMSD (fc_ensemble_knn, fc_ensemble_knn_cross and their symmetry-aware forms) on one MI355X: one JSON line per workload.
 
   python tools/bench_knn.py              # the sizes of DESIGN.md section 18: continuous and clustered ensembles at
                                          # 10^4 x 50 and 10^5 x 50, k = 8 and 64; then, at 10^4 x 50, host arrays in ->
@@ -14,6 +14,14 @@
                                          # then host arrays in -> lists out at 5 000 x 5 000 against the matrix of the
                                          # concatenated 10 000 on the host
   python tools/bench_knn.py --cross --small   # without the 10^2 x 10^6 workload
+  python tools/bench_knn.py --symmetry K [--mirror] [--cross]
+                                         # fc_ensemble_knn_perm / fc_ensemble_knn_cross_perm at
+                                         # 10^4 x 50 (--cross: 10^4 x 10^4 x 50) under a table of K permutations
+                                         # (1, 2, 6 or a power of two up to 64) and, --mirror, both handednesses, k = 1 and
+                                         # 8 (--cross: without a cap and with the cap at the duplicate threshold): the
+                                         # device ms, the default form's ms from the same run alternating on one handle,
+                                         # K H times that (the cost of the covariance loops alone), the ratio, and the
+                                         # share of (pair, p, h) taken through the explicit pass
 
 Device time: HIP events on the library's stream from the first launch to the end of the merge (a warm-up call first,
 then 3 calls: mean and range).  Rates: ordered alignments (N (N - 1): the full square, whether or not a pair's explicit
@@ -155,6 +163,86 @@ def end_to_end_cross(Q, R, k, reps=3):
                       "same_indices": same}), flush=True)
 
 
+def sym_table(K):
+    """K permutations of the 50 atoms, the identity first, closed under inverse: the reversal (2), three runs of 16 atoms
+    behind atom 0 permuted as wholes (6), or the group of log2 K disjoint transpositions"""
+    import itertools
+
+    ident = np.arange(A)
+    if K == 1:
+        return ident[None]
+    if K == 2:
+        return np.stack([ident, ident[::-1]])
+    if K == 6:
+        rows = []
+        for order in itertools.permutations(range(3)):
+            row = ident.copy()
+            for m, src in enumerate(order):
+                row[1 + 16 * m:1 + 16 * (m + 1)] = np.arange(1 + 16 * src, 1 + 16 * (src + 1))
+            rows.append(row)
+        return np.stack(rows)
+    n = K.bit_length() - 1
+    if K != 1 << n or K > 64:
+        raise SystemExit("--symmetry K: 1, 2, 6 or a power of two up to 64")
+    rows = []
+    for bits in itertools.product((0, 1), repeat=n):
+        row = ident.copy()
+        for m, on in enumerate(bits):
+            if on:
+                row[[2 * m, 2 * m + 1]] = row[[2 * m + 1, 2 * m]]
+        rows.append(row)
+    return np.stack(rows)
+
+
+def sym_ensemble(N, table, mirror, seed):
+    """a continuous ensemble with a random half relabelled by a random row of the table and -- mirror -- a random half
+    reflected: the ensembles the aware forms are for"""
+    X = ensemble("continuous", N, seed)
+    rng = np.random.default_rng(seed)
+    rows = np.where(rng.random(N) < 0.5, rng.integers(0, len(table), size=N), 0)
+    X = np.take_along_axis(X, table[rows][:, :, None], axis=1)
+    if mirror:
+        X[rng.random(N) < 0.5, :, 0] *= -1.0
+    return np.ascontiguousarray(X)
+
+
+def symmetry(K, mirror, crossed, reps=3):
+    table, H = sym_table(K), 2 if mirror else 1
+    dup = fc.pruner.CONVENTIONS["default_max_rmsd"]
+    N = 10_000
+    X = sym_ensemble(2 * N if crossed else N, table, mirror, 21)
+    mask = np.ones(A, bool)
+    kw = dict(symmetry=table, prune_enantiomers=mirror)
+    with fc.DeviceEnsemble(X[:N], atom_mask=mask, center=True) as q, fc.DeviceEnsemble(X[-N:], atom_mask=mask, center=True) as r:
+        for k in (1, 8):
+            for cap in ((None, dup) if crossed else (None,)):
+                if crossed:
+                    aware = lambda: q.bench_knn_against(r, k, max_rmsd=cap, reps=1, **kw)  # noqa: E731
+                    plain = lambda: q.bench_knn_against(r, k, max_rmsd=cap, reps=1)  # noqa: E731
+                else:
+                    aware = lambda: q.bench_knn(k, reps=1, **kw)  # noqa: E731
+                    plain = lambda: q.bench_knn(k, reps=1)  # noqa: E731
+                aware(), plain()  # warm-up of both: code objects, pool blocks
+                a, b = [], []
+                for _ in range(reps):  # alternating on one handle
+                    a.append(aware())
+                    b.append(plain())
+                ms, ms0 = np.array([x[0] for x in a]), np.array([x[0] for x in b])
+                formed, explicit = (a[-1][3] if len(a[-1]) > 3 else (0, 0))  # (K = 1 without the flag is the default form)
+                out = {"workload": f"{'cross' if crossed else 'self'} {N}{f' x {N}' if crossed else ''} x {A}, K = {K}, "
+                                   f"mirror = {int(mirror)}, k = {k}, {'no cap' if cap is None else f'cap {cap}'}",
+                       "K": K, "H": H, "k": k, "max_rmsd": cap, "strips": a[0][2],
+                       "ms_device_mean": round(float(ms.mean()), 3), "ms_device_min": round(float(ms.min()), 3),
+                       "ms_device_max": round(float(ms.max()), 3),
+                       "default_ms_device_mean": round(float(ms0.mean()), 3), "default_ms_device_min": round(float(ms0.min()), 3),
+                       "default_ms_device_max": round(float(ms0.max()), 3),
+                       "default_ms_times_KH": round(float(ms0.mean()) * K * H, 3),
+                       "ratio_to_default_times_KH": round(float(ms.mean() / (ms0.mean() * K * H)), 3),
+                       "p_h_formed": int(formed), "p_h_explicit": int(explicit),
+                       "explicit_share": round(explicit / formed, 4) if formed else None}
+                print(json.dumps(out), flush=True)
+
+
 def cross():
     dup = fc.pruner.CONVENTIONS["default_max_rmsd"]  # the duplicate threshold of prune_by_rmsd
     sizes = [(10_000, 10_000), (1_000, 100_000)] + ([] if "--small" in sys.argv else [(100, 1_000_000)])
@@ -176,6 +264,9 @@ def cross():
 def main():
     fc.init(0)
     fc._lib.warmup()
+    if "--symmetry" in sys.argv:
+        symmetry(int(sys.argv[sys.argv.index("--symmetry") + 1]), "--mirror" in sys.argv, "--cross" in sys.argv)
+        return
     if "--cross" in sys.argv:
         cross()
         return
