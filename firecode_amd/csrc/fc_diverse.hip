@@ -205,9 +205,11 @@ k_diverse_step(const double *__restrict__ Xs, const double *__restrict__ Xa, con
 // Per conformer and row k: the covariance B_k (the only atom loop every (pair, k) pays), the Newton eigenvalue of B_k
 // and -- MIRROR -- of -B_k (kabsch_lambda_max_both), and for each h the rotation and the explicit deviation pass
 // UNLESS the eigenvalue form of its msd, (Gs + Gj - 2 lambda)/A, exceeds the smallest explicit msd seen so far for this
-// conformer by more than kScreenMargin (1e-6 A^2: the eigenvalue form is good to ~1e-12 of G/A, and the iteration
-// errs towards a SMALLER msd where it stalls).  A (k, h) left out is therefore not the minimum; the value kept is the
-// explicit sum of the winning (k, h), h = -1 as pair_exact_aos<INV> forms it: -B, p + R q.
+// conformer by more than kScreenMargin (1e-6 A^2: the eigenvalue form is good to ~1e-11 of G/A where the iteration
+// has settled on its largest root, a simple one; on a (nearly) double root it may end anywhere, and
+// kabsch_lambda_max_both then gives the upper bound (Gs + Gj)/2 -- an msd of 0, which leaves nothing out).  A (k, h)
+// left out is therefore not the minimum; the value kept is the explicit sum of the winning (k, h), h = -1 as
+// pair_exact_aos<INV> forms it: -B, p + R q.
 // The rows are taken in table order against a running best -- not sorted by eigenvalue: that would keep 2 K
 // eigenvalues per lane.  Row 0 is the identity, the winner for every conformer that was not relabelled.
 // stats (may be NULL): [0] += (k, h) whose eigenvalue was formed, [1] += those that reached the explicit pass.

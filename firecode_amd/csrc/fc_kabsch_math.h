@@ -361,8 +361,13 @@ inline KabschF32Bounds kabsch_h2_bounds(int64_t KS2) {
 // slope (may be NULL): P'(x) of the last step -- the product of the distances to the other three eigenvalues.  Where the
 // largest eigenvalue is (nearly) double -- a covariance of rank one: one atom, two atoms about their centroid, atoms on a
 // line -- P' vanishes with P, the iteration stalls where the rounding of P (a few u x^4) equals its quadratic, sqrt(u) x
-// away from the root, and the caller has to evaluate the pair another way (kabsch_lambda_is_sharp).
-__host__ __device__ __forceinline__ double kabsch_lambda_max(const double (&B)[9], double GpGq, double *slope = nullptr) {
+// away from the root ON EITHER SIDE of it (below the stall P / P' is rounding noise over a vanishing slope: a step can
+// throw the iterate far past the root, and 64 steps may end before it is back), and the caller has to evaluate the pair
+// another way (kabsch_lambda_is_sharp, kabsch_lambda_is_settled).
+// step (may be NULL): the last Newton step taken, +inf when none was (den == 0 at the start: an all-zero covariance).
+// norm2 (may be NULL): |B|_F^2 = -C2 / 2, which places the inflection points of P (kabsch_lambda_is_settled).
+__host__ __device__ __forceinline__ double kabsch_lambda_max(const double (&B)[9], double GpGq, double *slope = nullptr,
+                                                             double *step = nullptr, double *norm2 = nullptr) {
 #pragma clang fp contract(fast)
   const double Sxx = B[0], Sxy = B[1], Sxz = B[2];
   const double Syx = B[3], Syy = B[4], Syz = B[5];
@@ -376,7 +381,7 @@ __host__ __device__ __forceinline__ double kabsch_lambda_max(const double (&B)[9
   const double e2 = c00 * c00 + c01 * c01 + c02 * c02 + c10 * c10 + c11 * c11 + c12 * c12 +
                     c20 * c20 + c21 * c21 + c22 * c22;
   const double C2 = -2.0 * n2, C1 = -8.0 * detB, C0 = n2 * n2 - 4.0 * e2;
-  double x = 0.5 * GpGq, den = 0.0;
+  double x = 0.5 * GpGq, den = 0.0, last = INFINITY;
   for (int it = 0; it < 64; ++it) {
     const double x2 = x * x;
     const double b = (x2 + C2) * x;
@@ -385,17 +390,55 @@ __host__ __device__ __forceinline__ double kabsch_lambda_max(const double (&B)[9
     if (den == 0.0) break;
     const double delta = (a * x + C0) / den;
     x -= delta;
+    last = delta;
     if (fabs(delta) <= 4e-16 * fabs(x)) break;
   }
   if (slope) *slope = den;
+  if (step) *step = last;
+  if (norm2) *norm2 = n2;
   return x;
+}
+
+// Whether a Newton eigenvalue may be used ONE-SIDEDLY, by a screen that drops pairs whose eigenvalue form of A msd,
+// (Gp + Gq) - 2 lambda, is LARGE: lambda must not lie below the LARGEST root by more than rounding.  A small last step
+// on a simple root is not enough: on a (nearly) double largest root -- one atom, two atoms, atoms on a line, a symmetric
+// top against its mirror image -- a step over the vanishing slope can throw the iterate below the critical points of P,
+// from where the iteration converges cleanly on the third or the fourth root.  The test certifies the largest root:
+//   * the iteration has settled: its last step is at most kLambdaSettledStep |x|;
+//   * x > 0 and 3 x^2 > |B|_F^2, i.e. P'' = 12 x^2 - 4 |B|_F^2 > 0: x lies to the right of both inflection points, where
+//     P is convex and P' increasing (the third derivative is 24 x > 0).  The largest root always does: it is at least
+//     the largest singular value s1 of B, and |B|_F^2 <= 3 s1^2;
+//   * the slope of that step is POSITIVE and at least kLambdaSettledSlope x^3.  P' increases from x on, so no critical
+//     point and hence no second root of P lies to the right of x: the root the iteration settled on is the largest, and
+//     it is simple.  By convexity it is at most P(x) / P'(x) to the right of x.
+// Then x is below the largest root by at most |step| + (rounding of P) / slope: with the rounding of P taken as
+// 1e-14 x^4 (its terms reach 9 x^4; 6.7e-15 x^4 measured without fused arithmetic, tests/test_knn_filter_bound_cpu.py)
+// that is 1.1e-11 x, and 1.1e-11 (Gp + Gq) on A msd.  (The slope is that of the iterate before the last step, 1e-12 x
+// away: P' moves by at most 1.2e-11 x^3 over that.)  Elsewhere the value is not to be used on this side: DESIGN.md
+// section 18 has what the iteration does there.  False for NaN.
+constexpr double kLambdaSettledStep = 1e-12;
+constexpr double kLambdaSettledSlope = 1e-3;
+__host__ __device__ __forceinline__ bool kabsch_lambda_is_settled(double lam, double slope, double step, double norm2) {
+  return lam > 0.0 && fabs(step) <= kLambdaSettledStep * lam && 3.0 * (lam * lam) > norm2 &&
+         slope >= kLambdaSettledSlope * (lam * lam * lam);
+}
+
+// An UPPER bound of the largest eigenvalue for such a screen: the Newton value where kabsch_lambda_is_settled certifies
+// it, (Gp + Gq)/2 -- the iteration's start, which no eigenvalue exceeds: A msd >= 0 -- elsewhere, so that
+// (Gp + Gq) - 2 * (the value returned) is not above the explicit sum by more than rounding and a pair with an
+// eigenvalue that cannot be trusted is simply not ruled out.
+__host__ __device__ __forceinline__ double kabsch_lambda_upper(const double (&B)[9], double GpGq) {
+  double slope, step, n2;
+  const double lam = kabsch_lambda_max(B, GpGq, &slope, &step, &n2);
+  return kabsch_lambda_is_settled(lam, slope, step, n2) ? lam : 0.5 * GpGq;
 }
 
 // The Newton eigenvalue alone, of B and -- MIRROR -- of -B as well (one structure inverted through the origin): n2 and
 // |cof B|_F^2 are even in B, det B changes sign, so the second polynomial is the first with C1 negated (the lemma of
-// kabsch_may_be_below).  Both iterations start from the upper bound (Gp + Gq)/2 and come down monotonically: a value
-// returned is never below the eigenvalue by more than rounding, also where the iteration stalls short of a (nearly)
-// double root -- the side on which a screen that drops LARGE msd = (Gp + Gq - 2 lambda)/A needs it (k_diverse_step_sym).
+// kabsch_may_be_below).  Both iterations start from the upper bound (Gp + Gq)/2; each value returned is an UPPER bound
+// in the sense of kabsch_lambda_upper -- the Newton value where kabsch_lambda_is_settled certifies it as the largest
+// root, (Gp + Gq)/2 where it does not (a (nearly) double root, where the iteration may end anywhere) -- the side a
+// screen that drops LARGE msd = (Gp + Gq - 2 lambda)/A needs (k_diverse_step_sym, k_knn_tile_sym).
 template <bool MIRROR>
 __host__ __device__ __forceinline__ void kabsch_lambda_max_both(const double (&B)[9], double GpGq, double &lam_plus,
                                                                 double &lam_minus) {
@@ -415,18 +458,19 @@ __host__ __device__ __forceinline__ void kabsch_lambda_max_both(const double (&B
 #pragma unroll
   for (int h = 0; h < (MIRROR ? 2 : 1); ++h) {
     const double C1 = h ? 8.0 * detB : -8.0 * detB;
-    double x = 0.5 * GpGq;
+    double x = 0.5 * GpGq, den = 0.0, last = INFINITY;
     for (int it = 0; it < 64; ++it) {
       const double x2 = x * x;
       const double b = (x2 + C2) * x;
       const double a = b + C1;
-      const double den = 2.0 * x2 * x + b + a;
+      den = 2.0 * x2 * x + b + a;
       if (den == 0.0) break;
       const double delta = (a * x + C0) / den;
       x -= delta;
+      last = delta;
       if (fabs(delta) <= 4e-16 * fabs(x)) break;
     }
-    (h ? lam_minus : lam_plus) = x;
+    (h ? lam_minus : lam_plus) = kabsch_lambda_is_settled(x, den, last, n2) ? x : 0.5 * GpGq;
   }
 }
 

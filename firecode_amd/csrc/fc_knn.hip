@@ -14,10 +14,13 @@
 //   1. the covariances of the column with the 4 rows in one atom loop -- one load of the column's atom serves 4 rows,
 //      the row atoms are wave-uniform (LDS broadcasts);
 //   2. per row, the filter: the Newton eigenvalue of the covariance gives A msd = (Gi + Gj) - 2 lambda, never above the
-//      explicit sum by more than rounding (the iteration comes down from above, also where it stalls); when it exceeds
-//      A tau^2 -- tau the row's current k-th distance -- by more than the margin for EVERY column of the chunk, none of
-//      them can enter the row's list and the rest of the row is skipped (wave-uniform).  The eigenvalue decides nothing
-//      else: FC_KNN_FILTER=0 takes every pair through step 3 and gives the same bits;
+//      explicit sum by more than rounding WHERE THE ITERATION HAS SETTLED ON ITS LARGEST ROOT, A SIMPLE ONE
+//      (kabsch_lambda_is_settled certifies that); on a (nearly) double root -- atoms on a line, two atoms, a symmetric
+//      top against its mirror image -- it ends on either side of the root, or on another root altogether, and such a
+//      pair is not ruled out (kabsch_lambda_upper gives A msd = 0 for it).  When A msd exceeds A tau^2 -- tau the
+//      row's current k-th distance -- by more than the margin for EVERY column of the chunk, none of them can enter
+//      the row's list and the rest of the row is skipped (wave-uniform).  The eigenvalue decides nothing else: FC_KNN_FILTER=0 takes every pair through step 3 and gives
+//      the same bits;
 //   3. otherwise the rotation -- kabsch_rotation_qcp (Newton eigenvalue + adjugate eigenvector), the Jacobi sweeps of
 //      kabsch_rotation where the eigenvalue is not clearly simple, as k_diverse_step -- and the explicit rotated
 //      difference in a second atom loop, pair_exact_aos's sums: the value that is written out is never the eigenvalue
@@ -55,9 +58,10 @@
 // Why the outputs are the same bits with the filter on or off and for every strip count.  The explicit sum of a
 // (pair, p, h) is one fixed instruction sequence, so the pair has a fixed smallest explicit sum, that of its argmin
 // (p*, h*); the value offered is the minimum over the explicit sums that were VISITED, hence that sum whenever (p*, h*)
-// is visited.  (1) The eigenvalue form of (p*, h*) never exceeds its explicit sum by more than rounding (the iteration
-// comes down from above; the margins cover the rounding), and every other explicit sum of the pair is at least as
-// large: (p*, h*) is never above the running best, so only tau can rule it out.  (2) When tau rules it out,
+// is visited.  (1) The eigenvalue form of (p*, h*) never exceeds its explicit sum by more than rounding (it is used only
+// where it is certified as the largest root, and is 0 elsewhere: kabsch_lambda_max_both; the margins cover the
+// rounding), and every other explicit sum of the pair is at least as large: (p*, h*) is never above the running best,
+// so only tau can rule it out.  (2) When tau rules it out,
 // d_sym > tau; whatever else of the pair was visited has an explicit sum >= that of (p*, h*), so the value offered is
 // above tau as well and is not inserted (nor under the cap) -- and tau only shrinks, so the pair is in no final list.
 // (3) A pair that belongs in the final list has d_sym <= every tau its row ever had in any strip, so (p*, h*) is
@@ -78,7 +82,8 @@ constexpr int64_t kKnnLdsAtoms = 256;                        // 16 rows x A x 24
 static_assert(FC_KNN_MAX == 64, "a row's list is one slot per lane of a wavefront");
 // The filter's margin on A * msd, beside A * kScreenMargin: the eigenvalue form (Gp + Gq) - 2 lambda and the explicit sum
 // differ by the rounding of G, of the covariance and of Newton's last step, a few (2 A + 10) u (Gp + Gq) -- 7e-12 of
-// (Gp + Gq) at the 32 767 atoms a conformer can have
+// (Gp + Gq) at the 32 767 atoms a conformer can have -- and by what a settled iteration can be away from its root,
+// 1.1e-11 (Gp + Gq) (kabsch_lambda_is_settled)
 constexpr double kKnnFilterRel = 1e-10;
 
 // (d1, j1) comes before (d2, j2): smaller distance first, lower index on ties
@@ -197,7 +202,7 @@ k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const d
           const double GG = Gi[r] + Gj;
           bool may = ok;
           if (filter) {  // (a NaN passes)
-            const double msdA = GG - 2.0 * kabsch_lambda_max(B[r], GG);
+            const double msdA = GG - 2.0 * kabsch_lambda_upper(B[r], GG);  // (0 where the eigenvalue cannot be trusted)
             const double tau = CROSS ? fmin(td[r], cap) : td[r];  // the cap: a smaller tau from the first chunk on
             may = ok && !(msdA > dA * tau * tau + (dA * kScreenMargin + kKnnFilterRel * GG));
           }
