@@ -144,6 +144,7 @@ _SIGNATURES = {
     "fc_torsion_fingerprint": [_p_f64, _i64, _i64, _p_i64, _i64, _p_f64],
     "fc_tfd_simbits": [_p_f64, _i64, _i64, _f64, _i64, _i64, _p_u64],
     "fc_tfd_first_match": [_p_f64, _i64, _i64, _f64, _p_i64],
+    "fc_tfd_last_form": [_p_i64],
     "fc_tfd_ladder_from_first_match": [_p_i64, _i64, _p_u8],
     "fc_tfd_prune": [_p_f64, _i64, _i64, _f64, _p_u8],
     "fc_debug_pyset_order_ints": [_p_i64, _i64, _p_i64, _p_i64],
@@ -352,6 +353,14 @@ def stream_use(hip_stream):
 def screen_last_kind():
     """32 / 64 / 1: arithmetic of the all-pairs screen the last prune launched (fc_screen_last_kind)."""
     return int(load().fc_screen_last_kind())
+
+
+def tfd_last_form():
+    """(form, n_open) of the last TFD first match (fc_tfd_last_form): form bits 1 = one-phase fp32, 2 = fp32 look-ahead +
+    chunks, 4 = 16-bit dense, 8 = 16-bit walk launched, 16 = 16-bit path refused and redone; n_open = rows left open
+    after the first phase."""
+    n_open = C.c_int64(0)
+    return int(load().fc_tfd_last_form(C.byref(n_open))), int(n_open.value)
 
 
 def screen_select(kind=0):

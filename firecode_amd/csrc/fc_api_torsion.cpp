@@ -317,6 +317,7 @@ int fc_tfd_simbits(const double *tf, int64_t N, int64_t Q, double thresh, int64_
   FC_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= N, "bad row range");
   if (row_end == row_begin) return FC_OK;
   FC_REQUIRE(bits_out && (tf || Q == 0), "NULL pointer argument");
+  if (Q > 128) return set_error(FC_E_LIMIT, "Q=%lld fingerprints exceed 128 (NumPy's summation order changes there)", (long long)Q);
   FC_TRY(ensure_init());
   const int64_t W = ceil_div(N, 64);
   DevBuf dtf, dbits;
@@ -335,6 +336,10 @@ int fc_tfd_first_match(const double *tf, int64_t N, int64_t Q, double thresh, in
   if (N == 0) return FC_OK;
   FC_REQUIRE(first_out && (tf || Q == 0), "NULL pointer argument");
   if (Q > 128) return set_error(FC_E_LIMIT, "Q=%lld fingerprints exceed 128 (NumPy's summation order changes there)", (long long)Q);
+  if (Q == 0) {  // NumPy's empty sum is 0: every structure is similar to its successor for thresh > 0, to none otherwise
+    for (int64_t i = 0; i < N; ++i) first_out[i] = (thresh > 0.0 && i + 1 < N) ? i + 1 : -1;
+    return FC_OK;  // (nothing to launch: there is no fingerprint to upload, and tf may be NULL)
+  }
   FC_TRY(ensure_init());
   const int64_t Npad = ceil_div(N, 64) * 64;
   // fingerprint-major copy so that consecutive columns are contiguous: made on the device (on the
@@ -350,6 +355,8 @@ int fc_tfd_first_match(const double *tf, int64_t N, int64_t Q, double thresh, in
   FC_TRY(d2h(first_out, dfm.p, (size_t)N * sizeof(int64_t)));
   return sync();
 }
+
+int fc_tfd_last_form(int64_t *n_open_out) { return tfd_last_form(n_open_out); }
 
 int fc_tfd_ladder_from_first_match(const int64_t *first_match, int64_t N, uint8_t *mask_out) {
   FC_API_LOCK;

@@ -76,6 +76,7 @@ int launch_gather_transpose_pad(const double *in_dev, const double *first_dev, c
                                 int64_t Q, int64_t Npad, double *out_dev);
 int launch_tfd_first_match(const double *tfT_dev, int64_t N, int64_t Npad, int64_t Q, double thresh, int64_t *fm_dev,
                            float *tfF_scratch);
+int tfd_last_form(int64_t *n_open_out);
 int launch_tfd_simbits(const double *tf_dev, int64_t N, int64_t Q, double thresh, int64_t row_begin, int64_t row_end,
                        uint64_t *bits_dev, int64_t W);
 int warm_prune();

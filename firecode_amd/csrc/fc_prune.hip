@@ -1708,10 +1708,22 @@ k_tfd_prefilter_copy(const double *__restrict__ tfT, int64_t n, float *__restric
   if (i < n) tfF[i] = (float)tfT[i];
 }
 
+// Which device form the last launch_tfd_first_match took (fc_tfd_last_form): bit 0 one-phase fp32, bit 1 fp32 look-ahead
+// + column chunks, bit 2 16-bit dense phase, bit 3 16-bit walk launched, bit 4 the 16-bit path refused its angles and
+// the fp32 kernels redid the array; and the rows still open after phase 1.  Host bookkeeping only.
+static int g_tfd_last_form = 0;
+static int64_t g_tfd_last_open = 0;
+int tfd_last_form(int64_t *n_open_out) {
+  if (n_open_out != nullptr) *n_open_out = g_tfd_last_open;
+  return g_tfd_last_form;
+}
+
 // tfF_scratch: min(Q, 8) * Npad floats owned by the caller until the stream has run the kernel (nullptr, or
 // FC_TFD_F32_COPY=0: the kernel reads the fp64 columns for its pre-filter as well)
 int launch_tfd_first_match(const double *tfT_dev, int64_t N, int64_t Npad, int64_t Q, double thresh,
                            int64_t *fm_dev, float *tfF_scratch) {
+  g_tfd_last_form = 0;
+  g_tfd_last_open = 0;
   if (N == 0) return FC_OK;
   const dim3 grid((unsigned)ceil_div(N, 64)), block(256);
   const size_t lds = (size_t)64 * Q * sizeof(double);
@@ -1803,7 +1815,10 @@ int launch_tfd_first_match(const double *tfT_dev, int64_t N, int64_t Npad, int64
       fprintf(stderr, "[fc] tfd first match (16-bit angles%s): %llu of %lld rows open after the dense phase of %lld columns\n",
               head[kFmShards] ? ": REFUSED, angles beyond +-270 or not finite" : "", n_left, (long long)N, (long long)ahead);
     if (head[kFmShards] == 0ull) {
+      g_tfd_last_form = 4;
+      g_tfd_last_open = (int64_t)n_left;
       if (n_left == 0) return FC_OK;
+      g_tfd_last_form |= 8;
       const dim3 rgrid(sh.wg_begin[kFmShards]);
 #define FC_FMW(QT)                                                                                                      \
   case QT:                                                                                                              \
@@ -1820,6 +1835,7 @@ int launch_tfd_first_match(const double *tfT_dev, int64_t N, int64_t Npad, int64
       return check_launch("k_tfd_first_match_walk_u16");
     }
     // refused: the fp32 kernels below redo the whole array
+    g_tfd_last_form = 16;
     FC_HIP_TRY(hipMemsetAsync(left_count, 0, kHead * sizeof(unsigned long long), ctx().stream));
   }
   if (use_copy && tfF_scratch != nullptr) {
@@ -1843,10 +1859,12 @@ int launch_tfd_first_match(const double *tfT_dev, int64_t N, int64_t Npad, int64
   }
 #undef FC_FM
   FC_TRY(check_launch("k_tfd_first_match"));
+  g_tfd_last_form |= two_phase ? 2 : 1;
   if (!two_phase) return FC_OK;
   unsigned long long n_left = 0;
   FC_TRY(d2h(&n_left, left_count, sizeof n_left));
   FC_TRY(sync());
+  g_tfd_last_open = (int64_t)n_left;
   if (getenv("FC_DEBUG")) fprintf(stderr, "[fc] tfd first match: %llu of %lld rows open after a look-ahead of %lld columns\n", n_left, (long long)N, (long long)max_ahead);
   if (n_left == 0) return FC_OK;
   FC_HIP_TRY(hipMemsetAsync(best_dev, 0xff, (size_t)n_left * sizeof(unsigned long long), ctx().stream));

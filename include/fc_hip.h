@@ -831,6 +831,11 @@ int fc_tfd_simbits(const double *tf, int64_t N, int64_t Q, double thresh, int64_
  * pure host code (no device needed);
  * fc_tfd_prune = both. */
 int fc_tfd_first_match(const double *tf, int64_t N, int64_t Q, double thresh, int64_t *first_out);
+/* The device form the last first-match took (fc_tfd_first_match, fc_tfd_prune, fc_torsion_scan_tfd*), as bits:
+ * 1 = one-phase fp32 kernel, 2 = fp32 look-ahead + column chunks, 4 = 16-bit dense phase, 8 = 16-bit walk launched
+ * (rows were left open), 16 = the 16-bit path refused the angles and the fp32 kernels redid the array; 0 = none yet
+ * (or N = 0, or Q = 0, which launches nothing).  n_open_out (may be NULL): the rows still open after the first phase.  Results do not depend on it. */
+int fc_tfd_last_form(int64_t *n_open_out);
 int fc_tfd_ladder_from_first_match(const int64_t *first_match, int64_t N, uint8_t *mask_out);
 int fc_tfd_prune(const double *tf, int64_t N, int64_t Q, double thresh, uint8_t *mask_out);
 /* test hooks for the CPython set-order emulation used by the ladder: iteration

@@ -159,3 +159,30 @@ def test_rot_corr_refuses_sizes_its_launch_cannot_take():
     assert "1707" in _limit(lambda: call(3, 1707))  # 4 structures of 1707 atoms do not fit the 160 KiB of LDS
     msg = _limit(lambda: call(65536, 3))  # one grid row per structure: 65 535 is what every device guarantees
     assert "65535" in msg and "FC_ROTCORR_MAX_ROWS" in msg
+
+
+def test_tfd_entry_points_refuse_more_than_128_angles():
+    """np.sum adds more than 128 elements pairwise and the kernels' order would no longer be NumPy's: every TFD entry
+    point says so before it touches a device (fc_tfd_simbits, and through it tfd_similarity, included)"""
+    tf = np.zeros((3, 129))
+    fm, bits, mask = np.zeros(3, dtype=np.int64), np.zeros((3, 1), dtype=np.uint64), np.zeros(3, dtype=np.uint8)
+    msgs = [_limit(lambda: L.call("fc_tfd_first_match", L.pf(tf), 3, 129, 10.0, L.pi(fm))),
+            _limit(lambda: L.call("fc_tfd_simbits", L.pf(tf), 3, 129, 10.0, 0, 3, L.pw(bits))),
+            _limit(lambda: L.call("fc_tfd_simbits", L.pf(tf), 3, 129, 10.0, 1, 2, L.pw(bits))),
+            _limit(lambda: L.call("fc_tfd_prune", L.pf(tf), 3, 129, 10.0, L.pb(mask))),
+            _limit(lambda: fc.torsion_module.tfd_simbits(tf, 10.0)),
+            _limit(lambda: fc.torsion_module.tfd_similarity(tf[0], tf[1])),
+            _limit(lambda: fc.torsion_module.prune_tfd_from_tf_mat(tf))]
+    assert all("Q=129" in m and "128" in m for m in msgs) and len(set(msgs)) == 1  # (the same wording everywhere)
+
+
+def test_tfd_first_match_without_angles_needs_no_device():
+    """Q = 0: NumPy's empty sum is 0, below every positive threshold -- answered on the host, tf may be NULL"""
+    fm = np.full(4, -7, dtype=np.int64)
+    L.call("fc_tfd_first_match", None, 4, 0, 10.0, L.pi(fm))
+    assert fm.tolist() == [1, 2, 3, -1]
+    for thresh in (0.0, -1.0, float("nan")):
+        L.call("fc_tfd_first_match", None, 4, 0, thresh, L.pi(fm))
+        assert fm.tolist() == [-1] * 4
+    form = L.tfd_last_form()
+    assert isinstance(form[0], int) and form[1] >= 0

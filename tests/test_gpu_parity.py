@@ -792,6 +792,11 @@ def test_tfd_first_match_two_phases(fc, monkeypatch, q):
             fm = np.zeros(n, dtype=np.int64)
             L.call("fc_tfd_first_match", L.pf(np.ascontiguousarray(tf)), n, q, 10.0, L.pi(fm))
             assert np.array_equal(fm, ref), (u16, look)
+            # the form that ran (fc_tfd_last_form): one phase without a look-ahead (None: N < 65 536), else the fp32
+            # chunks or the 16-bit dense phase and, with rows left open, its walk
+            form, n_open = L.tfd_last_form()
+            assert form == (1 if look in ("0", None) else 2 if u16 == "0" else 4 | (8 if n_open else 0)), (u16, look, form)
+            assert look in ("0", None) or n_open > 0
 
 
 def _first_match_numpy(tf, thresh):
