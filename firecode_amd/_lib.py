@@ -94,6 +94,14 @@ _SIGNATURES = {
                             _p_i64, _p_u8, C.POINTER(C.c_int32), _p_i64, _p_i64],
     "fc_dbscan_from_pairs": [_p_u64, _i64, _i64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_u8, C.POINTER(C.c_int32), _p_i64],
     "fc_dbscan_from_bits": [_p_u64, _i64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, _p_u8, C.POINTER(C.c_int32), _p_i64],
+    "fc_rmsd_butina": [_ens, _f64, _f64, _p_f64, _f64, C.POINTER(C.c_int32), _p_i64, _p_i64, C.POINTER(C.c_int32), _p_i64,
+                       _p_i64],
+    "fc_rmsd_butina_enant": [_ens, _f64, _f64, _p_f64, _f64, C.POINTER(C.c_int32), _p_i64, _p_i64, C.POINTER(C.c_int32),
+                             _p_i64, _p_i64],
+    "fc_rmsd_butina_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, _f64, _f64, _p_f64, _f64, C.POINTER(C.c_int32), _p_i64,
+                            _p_i64, C.POINTER(C.c_int32), _p_i64, _p_i64],
+    "fc_butina_from_pairs": [_p_u64, _i64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, C.POINTER(C.c_int32), _p_i64],
+    "fc_butina_from_bits": [_p_u64, _i64, C.POINTER(C.c_int32), _p_i64, _p_i64, C.POINTER(C.c_int32), _p_i64],
     "fc_prune_rmsd_begin": [_ens, _f64, _f64, _p_f64, _f64, _i64, _i64, _i64, _p_i64],
     "fc_prune_level": [_ens, _i64, _p_u8, _p_u8],
     "fc_prune_similar_pairs": [_ens, _p_u64, _i64, _p_i64],
@@ -810,6 +818,25 @@ class DeviceEnsemble:
         name, head = self._form("fc_rmsd_dbscan", perm, enant)
         call(name, *head, float(max_rmsd), float(max_dev), m, pf(en), float(max_dE), *outs)
         return labels, reps[:k.value].copy(), sizes[:k.value].copy(), core.astype(bool), degrees, stats
+
+    def butina(self, max_rmsd, max_dev, energies=None, max_dE=0.0, prune_enantiomers=False, symmetry=None):
+        """Sphere-exclusion (Butina) clusters of the prune's similarity graph (fc_rmsd_butina; ``prune_enantiomers=True``:
+        fc_rmsd_butina_enant; ``symmetry=`` a (K, A_all) table: fc_rmsd_butina_perm; the contract is in include/fc_hip.h)
+        -> ``(labels (N,) int32, centroids (K,) int64, sizes (K,) int64, degrees (N,) int32, stats)`` in processing order.
+        Conformers are ranked by degree (more neighbours first, the smaller index on ties); the first unassigned one
+        becomes a centroid and takes its unassigned neighbours; clusters are numbered by ascending centroid.  stats: as
+        ``clusters``, then the rounds the device needed and the conformers its grid-wide rounds left to the finish."""
+        enant = check_flag("prune_enantiomers", prune_enantiomers)
+        perm = None if symmetry is None else self._perm_args(symmetry, "prune_enantiomers", enant)
+        labels, degrees = np.zeros(self.N, dtype=np.int32), np.zeros(self.N, dtype=np.int32)
+        reps, sizes = np.zeros(self.N, dtype=np.int64), np.zeros(self.N, dtype=np.int64)
+        stats = np.zeros(8, dtype=np.int64)
+        k = C.c_int64(0)
+        en = None if energies is None else f64(energies)
+        outs = (ptr(labels, C.c_int32), pi(reps), pi(sizes), ptr(degrees, C.c_int32), C.byref(k), pi(stats))
+        name, head = self._form("fc_rmsd_butina", perm, enant)
+        call(name, *head, float(max_rmsd), float(max_dev), pf(en), float(max_dE), *outs)
+        return labels, reps[:k.value].copy(), sizes[:k.value].copy(), degrees, stats
 
     def prune_begin(self, max_rmsd, max_dev, rank, world, row_block=128, energies=None, max_dE=0.0):
         stats = np.zeros(6, dtype=np.int64)

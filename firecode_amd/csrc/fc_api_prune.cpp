@@ -1213,27 +1213,36 @@ int fc_debug_ladder_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N
 // ---- similarity clusters and density-based clusters (the contract: include/fc_hip.h; the kernels: fc_clusters.hip) ----
 // Two axes, each said once: WHICH labelling runs on the graph (Labelling) and WHO makes the graph (a graph source, below).
 namespace {
-// the components of the graph, or its density-based clusters with min_samples bound
+// the components of the graph, its density-based clusters with min_samples bound, or its sphere-exclusion clusters
 struct Labelling {
   bool density;
   int64_t min_samples;
   const char *what;  // (in the error text)
+  bool butina = false;
+  ClKind kind() const { return density ? kClDensity : butina ? kClButina : kClComponents; }
+  ClusterLayout layout(const ClusterGraph &g, int64_t N) const {
+    return cluster_layout(N, kind(), butina ? butina_live_cap(g, N) : 0);
+  }
   int launch(const ClusterGraph &g, int64_t N, DevBuf &work) const {
+    if (butina) return launch_butina(g, N, work);
     return density ? launch_dbscan(g, N, min_samples, work) : launch_clusters(g, N, work);
   }
-  int n_stats() const { return density ? 8 : 6; }
+  int n_stats() const { return density || butina ? 8 : 6; }
 };
 Labelling components() { return {false, 1, "cluster labelling"}; }
 Labelling density_based(int64_t min_samples) { return {true, min_samples, "density-based clusters"}; }
+Labelling sphere_exclusion() { return {false, 1, "sphere-exclusion clusters", true}; }
 
-// the caller's arrays; core and degrees: the density-based form's
+// the caller's arrays; core: the density-based form's; degrees: its and the sphere-exclusion form's
 struct LabelOut {
   int32_t *labels;
   int64_t *reps, *sizes;
   uint8_t *core;
   int32_t *degrees;
   int64_t *n_clusters;
-  bool complete(const Labelling &lab) const { return labels && reps && sizes && (!lab.density || (core && degrees)); }
+  bool complete(const Labelling &lab) const {
+    return labels && reps && sizes && (!lab.density || core) && (!(lab.density || lab.butina) || degrees);
+  }
 };
 
 // what one labelling left in the pinned staging area: the result region of the workspace, then `extra` counter words
@@ -1248,7 +1257,7 @@ struct ClusterResult {
 // counters_dev (may be null): 16 counter words of the prune that travel behind the result.
 int label_run(const Labelling &lab, const ClusterGraph &g, int64_t N, DevBuf &work, const void *counters_dev,
               ClusterResult *out) {
-  const ClusterLayout L = cluster_layout(N, lab.density);
+  const ClusterLayout L = lab.layout(g, N);
   FC_TRY(work.reserve(L.total));
   FC_TRY(pinned_reserve(L.parent + 16 * sizeof(uint64_t)));
   FC_TRY(lab.launch(g, N, work));
@@ -1258,11 +1267,13 @@ int label_run(const Labelling &lab, const ClusterGraph &g, int64_t N, DevBuf &wo
   FC_TRY(sync());
   out->host = host, out->L = L;
   if (out->status()[kClStatusErr] != 0ull)
-    return set_error(FC_E_INTERNAL, "%s: a union exceeded its retry bound on the device", lab.what);
+    return set_error(FC_E_INTERNAL, "%s: %s on the device", lab.what,
+                     lab.butina ? "the rounds ended with conformers undecided" : "a union exceeded its retry bound");
   return FC_OK;
 }
 
-// -> the caller's arrays; tail (may be NULL; the density-based form's): [0] core points, [1] noise points
+// -> the caller's arrays; tail (may be NULL): the density-based form's [0] core points, [1] noise points; the
+// sphere-exclusion form's [0] rounds, [1] conformers that went to the finish
 void label_unpack(const ClusterResult &r, int64_t N, const LabelOut &o, int64_t *tail) {
   const int64_t K = (int64_t)r.status()[kClStatusK];
   std::memcpy(o.labels, r.host + r.L.labels, (size_t)N * sizeof(int32_t));
@@ -1271,9 +1282,15 @@ void label_unpack(const ClusterResult &r, int64_t N, const LabelOut &o, int64_t 
   if (r.L.core != 0) {  // (the density-based layout)
     std::memcpy(o.core, r.host + r.L.core, (size_t)N * sizeof(uint8_t));
     std::memcpy(o.degrees, r.host + r.L.degrees, (size_t)N * sizeof(int32_t));
+  } else if (r.L.degrees != 0) {  // (the sphere-exclusion layout)
+    std::memcpy(o.degrees, r.host + r.L.degrees, (size_t)N * sizeof(int32_t));
   }
   *o.n_clusters = K;
   if (tail == nullptr) return;
+  if (r.L.core == 0) {
+    tail[0] = (int64_t)r.status()[kBuStatusRounds], tail[1] = (int64_t)r.status()[kBuStatusLeft];
+    return;
+  }
   tail[0] = tail[1] = 0;
   for (int64_t i = 0; i < N; ++i) tail[0] += o.core[i] != 0, tail[1] += o.labels[i] < 0;
 }
@@ -1308,7 +1325,7 @@ int label_resident(fc_ensemble *ens, const Source &make, const Labelling &lab, D
   }
   const unsigned long long *c = res.extra();
   if (Source::screened) note_candidates(ens, c[6], c[2]);
-  label_unpack(res, N, o, stats && lab.density ? stats + 6 : nullptr);
+  label_unpack(res, N, o, stats && lab.n_stats() == 8 ? stats + 6 : nullptr);
   if (stats) fill_stats(stats, N * (N - 1) / 2, c, from_bits, *o.n_clusters);
   return FC_OK;
 }
@@ -1864,6 +1881,45 @@ int fc_dbscan_from_bits(const uint64_t *bits, int64_t N, int64_t min_samples, in
                         int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out, int64_t *n_clusters) {
   FC_API_LOCK;
   return label_from_bits(bits, N, density_based(min_samples), {labels_out, reps_out, sizes_out, core_out, degrees_out, n_clusters});
+}
+
+// ---- sphere-exclusion clusters (the contract: include/fc_hip.h; the kernels: fc_clusters.hip, k_bu_*) ------------------
+int fc_rmsd_butina(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                   int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int32_t *degrees_out, int64_t *n_clusters,
+                   int64_t *stats) {
+  FC_API_LOCK;
+  return rmsd_label(ens, max_rmsd, max_dev, energies, max_dE, sphere_exclusion(),
+                    {labels_out, reps_out, sizes_out, nullptr, degrees_out, n_clusters}, stats);
+}
+
+int fc_rmsd_butina_enant(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                         int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int32_t *degrees_out,
+                         int64_t *n_clusters, int64_t *stats) {
+  FC_API_LOCK;
+  FC_REQUIRE(ens && n_clusters, "NULL pointer argument");
+  EnantScope scope(ens);
+  return fc_rmsd_butina(ens, max_rmsd, max_dev, energies, max_dE, labels_out, reps_out, sizes_out, degrees_out, n_clusters,
+                        stats);
+}
+
+int fc_rmsd_butina_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
+                        const double *energies, double max_dE, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
+                        int32_t *degrees_out, int64_t *n_clusters, int64_t *stats) {
+  FC_API_LOCK;
+  return rmsd_label_perm(ens, perms, K, A_sel, max_rmsd, max_dev, energies, max_dE, sphere_exclusion(),
+                         {labels_out, reps_out, sizes_out, nullptr, degrees_out, n_clusters}, stats);
+}
+
+int fc_butina_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int32_t *labels_out, int64_t *reps_out,
+                         int64_t *sizes_out, int32_t *degrees_out, int64_t *n_clusters) {
+  FC_API_LOCK;
+  return label_from_pairs(pairs, n_pairs, N, sphere_exclusion(), {labels_out, reps_out, sizes_out, nullptr, degrees_out, n_clusters});
+}
+
+int fc_butina_from_bits(const uint64_t *bits, int64_t N, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
+                        int32_t *degrees_out, int64_t *n_clusters) {
+  FC_API_LOCK;
+  return label_from_bits(bits, N, sphere_exclusion(), {labels_out, reps_out, sizes_out, nullptr, degrees_out, n_clusters});
 }
 
 int fc_prune_rmsd_begin(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies,

@@ -265,7 +265,7 @@ int cl_blocks(int64_t items, int per_cu) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, kClThreads), (int64_t)ctx().n_cu * per_cu));
 }
 
-// what both launchers carve out of `work` (cluster_layout) and what every launch of theirs is sized by
+// what the launchers carve out of `work` (cluster_layout) and what every launch of theirs is sized by
 struct ClWork {
   int32_t *labels;
   int64_t *reps;
@@ -274,16 +274,21 @@ struct ClWork {
   uint64_t *flags;
   int32_t *prefix;
   uint8_t *core;     // core, deg, attach: the density-based form's
-  int32_t *deg;
+  int32_t *deg;      // (and the sphere-exclusion form's)
   uint32_t *attach;
+  uint64_t *key, *owner;  // from here to live_e: the sphere-exclusion form's
+  int32_t *state, *claim, *stamp, *live_v;
+  unsigned long long *und;
+  uint64_t *live_e;
   int64_t W;
   unsigned per_n;
   hipStream_t st;
 };
 
-// the head of both launchers: the argument checks, the carving, the memsets and k_cl_init.  density: launch_dbscan's
-int cl_begin(const ClusterGraph &g, int64_t N, bool density, int64_t min_samples, DevBuf &work, ClWork *w) {
-  const ClusterLayout L = cluster_layout(N, density);
+// the head of every launcher: the argument checks, the carving, the memsets and k_cl_init.  kind: whose block it is
+int cl_begin(const ClusterGraph &g, int64_t N, ClKind kind, int64_t min_samples, DevBuf &work, ClWork *w, size_t live_cap = 0) {
+  const bool density = kind == kClDensity;
+  const ClusterLayout L = cluster_layout(N, kind, live_cap);
   if (work.p == nullptr || work.bytes < L.total) return set_error(FC_E_INVALID, "cluster workspace too small");
   if (N < 1 || N > (int64_t)INT32_MAX - 256) return set_error(FC_E_LIMIT, "N=%lld: clusters index conformers with 32 bits", (long long)N);
   if (density && min_samples < 1) return set_error(FC_E_INVALID, "min_samples=%lld < 1", (long long)min_samples);
@@ -300,14 +305,20 @@ int cl_begin(const ClusterGraph &g, int64_t N, bool density, int64_t min_samples
   w->flags = reinterpret_cast<uint64_t *>(base + L.flags);
   w->prefix = reinterpret_cast<int32_t *>(base + L.prefix);
   w->attach = reinterpret_cast<uint32_t *>(base + L.attach);
+  w->key = reinterpret_cast<uint64_t *>(base + L.bu_key);
+  w->owner = reinterpret_cast<uint64_t *>(base + L.bu_owner);
+  w->state = reinterpret_cast<int32_t *>(base + L.bu_state);
+  w->claim = reinterpret_cast<int32_t *>(base + L.bu_claim);
+  w->stamp = reinterpret_cast<int32_t *>(base + L.bu_stamp);
+  w->live_v = reinterpret_cast<int32_t *>(base + L.bu_live_v);
+  w->und = reinterpret_cast<unsigned long long *>(base + L.bu_words);
+  w->live_e = reinterpret_cast<uint64_t *>(base + L.bu_live_e);
   w->W = ceil_div(N, 64);
   w->st = cur_stream();
   w->per_n = (unsigned)ceil_div(N, kClThreads);
   FC_HIP_TRY(hipMemsetAsync(w->sizes, 0, (size_t)N * sizeof(unsigned long long), w->st));
-  if (density) {
-    FC_HIP_TRY(hipMemsetAsync(w->deg, 0, (size_t)N * sizeof(int32_t), w->st));
-    FC_HIP_TRY(hipMemsetAsync(w->attach, 0xff, (size_t)N * sizeof(uint32_t), w->st));
-  }
+  if (kind != kClComponents) FC_HIP_TRY(hipMemsetAsync(w->deg, 0, (size_t)N * sizeof(int32_t), w->st));
+  if (density) FC_HIP_TRY(hipMemsetAsync(w->attach, 0xff, (size_t)N * sizeof(uint32_t), w->st));
   hipLaunchKernelGGL(k_cl_init, dim3(w->per_n), dim3(kClThreads), 0, w->st, w->parent, N, w->status, g.n_pairs_host);
   return check_launch("k_cl_init");
 }
@@ -339,11 +350,11 @@ bool cl_split_bits(int64_t N, int64_t W) { return (unsigned long long)N * (unsig
 
 }  // namespace
 
-// Everything behind the graph: the caller has reserved `work` (cluster_layout(N, false).total bytes) and, for the pair
+// Everything behind the graph: the caller has reserved `work` (cluster_layout(N, kClComponents).total bytes) and, for the pair
 // form, left the list where `g` says.  Enqueues only; the result region of `work` is complete when the stream has drained.
 int launch_clusters(const ClusterGraph &g, int64_t N, DevBuf &work) {
   ClWork w;
-  FC_TRY(cl_begin(g, N, /*density=*/false, 1, work, &w));
+  FC_TRY(cl_begin(g, N, kClComponents, 1, work, &w));
   if (g.pairs_dev != nullptr) {
     const unsigned long long *n_pairs_dev = g.n_pairs_dev != nullptr ? g.n_pairs_dev : w.status + kClStatusPairs;
     // g.known_short: the caller has seen this list's length (or a recent one of these coordinates) -- the launches that
@@ -612,10 +623,10 @@ k_db_label(const int32_t *__restrict__ root, int64_t N, const uint8_t *__restric
 
 }  // namespace
 
-// launch_clusters under the core rule; `work` holds cluster_layout(N, true).total bytes
+// launch_clusters under the core rule; `work` holds cluster_layout(N, kClDensity).total bytes
 int launch_dbscan(const ClusterGraph &g, int64_t N, int64_t min_samples, DevBuf &work) {
   ClWork w;
-  FC_TRY(cl_begin(g, N, /*density=*/true, min_samples, work, &w));
+  FC_TRY(cl_begin(g, N, kClDensity, min_samples, work, &w));
   if (g.pairs_dev != nullptr) {
     const unsigned long long *n_pairs_dev = g.n_pairs_dev != nullptr ? g.n_pairs_dev : w.status + kClStatusPairs;
     const dim3 grid = cl_grid_pairs();
@@ -648,6 +659,405 @@ int launch_dbscan(const ClusterGraph &g, int64_t N, int64_t min_samples, DevBuf 
   hipLaunchKernelGGL(k_db_label, dim3(w.per_n), dim3(kClThreads), 0, w.st, w.root, N, w.core, w.attach, w.flags, w.prefix,
                      w.labels, w.reps, w.sizes);
   return check_launch("k_db_label");
+}
+
+// ---- sphere-exclusion clusters (include/fc_hip.h, "sphere-exclusion clusters") --------------------
+// Butina's walk in its fixed order is the lexicographically-first maximal independent set of the graph under the
+// priority key[v] = ((0x7fffffff - d(v)) << 32) | v (smaller first): v is a centroid exactly when none of its neighbours
+// with a smaller key is one.  It is decided in synchronous rounds over state[N] (undecided, centroid, member).  Round r:
+//   edge pass    for an edge (a, b), key[a] < key[b]: a centroid and b undecided -> claim[b] = 1; both undecided ->
+//                stamp[b] = r ("blocked in round r": an earlier neighbour may still become a centroid);
+//   vertex pass  an undecided v that is claimed becomes a member; one that is not stamped r has only members before it
+//                and becomes a centroid; the rest is counted into und[r].
+// Two launches, so that nothing one workgroup writes is read by another in the same launch: the edge pass reads key[]
+// and state[] and writes claim[] and stamp[] (plain stores: every writer of a word writes the same value), the vertex
+// pass reads those and writes state[i] from thread i alone.  A round that finds und[r - 1] == 0 returns at once.  The
+// first undecided vertex in key order is never stamped, so every round decides at least one vertex.
+// Launches: init -> degrees (the density-based form's two kernels, unchanged) -> keys -> R rounds -> one more round that
+// also writes down the live subgraph (the vertices it leaves undecided; the edges it found with two undecided ends,
+// which are all the edges the remaining rounds can act on) -> finish: ONE workgroup goes on with the same two passes
+// over the live lists, __syncthreads() between them, until nothing is undecided -> owners -> roots + centroid flags ->
+// k_cl_scan -> k_cl_label (both unchanged).  No thread waits for another workgroup anywhere.
+// The live-edge list has live_cap entries.  When the graph left more than that, the list is not used and the finish
+// walks the graph itself (the caller's list or the bit matrix): slower, the same rounds.
+namespace {
+
+constexpr int32_t kBuUndecided = 0, kBuCentroid = 1, kBuMember = 2;
+constexpr int kBuLiveE = kBuRoundsMax + 2;  // und[kBuLiveE]: edges offered to the live list (more than live_cap: not used)
+constexpr int kBuFinishThreads = 1024;
+
+// The edge sources.  each(first, stride, f) calls f(on, i, j) with the wavefront CONVERGED (the loop bounds are the
+// wavefront's, a lane without an edge passes on = false), so that f may ballot.  first: the thread's index in the launch.
+
+// the edges of a pair list whose length is a device word; declined on k_db_degree_pairs' conditions (no edges then)
+struct BuPairs {
+  const uint64_t *pairs;
+  const unsigned long long *n_pairs_ptr, *n_cand_ptr;
+  unsigned long long cand_cap;
+  const unsigned long long *redo_ptr;
+  uint32_t n32;
+  template <class F>
+  __device__ __forceinline__ void each(unsigned long long first, unsigned long long stride, const F &f) const {
+    const unsigned long long P = *n_pairs_ptr;
+    if (db_declined(P, n_cand_ptr, cand_cap, redo_ptr)) return;
+    const unsigned lane = (unsigned)(first & 63ull);
+    for (unsigned long long p0 = first - lane; p0 < P; p0 += stride) {
+      const unsigned long long p = p0 + lane;
+      uint32_t i = 0, j = 0;
+      bool on = p < P;
+      if (on) {
+        const uint64_t e = pairs[p];
+        i = (uint32_t)(e >> 32), j = (uint32_t)(e & 0xffffffffull);
+        on = i != j && i < n32 && j < n32;
+      }
+      f(on, i, j);
+    }
+  }
+};
+
+// the edges of a bit matrix, walked as k_cl_hook_bits walks it: bits j > i only, the diagonal word masked, cut at N
+struct BuBits {
+  const uint64_t *bits;
+  int64_t W, N;
+  template <class F>
+  __device__ __forceinline__ void each(unsigned long long first, unsigned long long stride, const F &f) const {
+    const int64_t total = N * W;
+    const int64_t lane = (int64_t)(first & 63ull);
+    for (int64_t t0 = (int64_t)first - lane; t0 < total; t0 += (int64_t)stride) {
+      const int64_t t = t0 + lane;
+      int64_t i = 0, w = 0;
+      uint64_t word = 0ull;
+      if (t < total) {
+        i = t / W, w = t - i * W;
+        if (w >= (i >> 6)) word = bits[t];
+        if (w == (i >> 6)) word &= (i & 63) == 63 ? 0ull : ~0ull << ((i & 63) + 1);
+      }
+      while (__any(word != 0ull)) {  // wave-uniform
+        int64_t j = 0;
+        bool on = word != 0ull;
+        if (on) {
+          j = w * 64 + __ffsll((unsigned long long)word) - 1;
+          word &= word - 1;
+          if (j >= N) on = false, word = 0ull;  // (ascending: nothing behind it is a conformer)
+        }
+        f(on, (uint32_t)i, (uint32_t)j);
+      }
+    }
+  }
+};
+
+// the edge pass on one edge (on: this lane has one; the wavefront is converged).  live_e != nullptr: an edge with two
+// undecided ends is also written to the live list as (a << 32) | b, a before b in key order -- one add per wavefront
+__device__ __forceinline__ void bu_edge(bool on, uint32_t i, uint32_t j, const uint64_t *key, const int32_t *state,
+                                        int32_t *claim, int32_t *stamp, int32_t r, uint64_t *live_e,
+                                        unsigned long long *live_n, unsigned long long live_cap) {
+  uint32_t a = 0, b = 0;
+  bool both = false;
+  if (on) {
+    const bool first = key[i] < key[j];
+    a = first ? i : j, b = first ? j : i;
+    if (state[b] == kBuUndecided) {
+      const int32_t sa = state[a];
+      if (sa == kBuCentroid) claim[b] = 1;
+      both = sa == kBuUndecided;
+      if (both) stamp[b] = r;
+    }
+  }
+  if (live_e == nullptr) return;  // (uniform)
+  const uint64_t m = __ballot(both);
+  if (m == 0ull) return;  // wave-uniform
+  const int lane = (int)(__lane_id());
+  const int leader = __ffsll((unsigned long long)m) - 1;
+  unsigned long long base = 0ull;
+  if (lane == leader) base = atomicAdd(live_n, (unsigned long long)__popcll(m));
+  base = __shfl(base, leader);
+  const unsigned long long slot = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+  if (both && slot < live_cap) live_e[slot] = ((uint64_t)a << 32) | (uint64_t)b;
+}
+
+// the vertex pass on one vertex; true: it stays undecided
+__device__ __forceinline__ bool bu_vertex(uint32_t v, int32_t *state, const int32_t *claim, const int32_t *stamp, int32_t r) {
+  if (state[v] != kBuUndecided) return false;
+  if (claim[v] != 0)
+    state[v] = kBuMember;
+  else if (stamp[v] != r)
+    state[v] = kBuCentroid;
+  else
+    return true;
+  return false;
+}
+
+// key[], the cleared per-vertex words and the round words: und[0] = N, everything else 0
+__global__ void __launch_bounds__(kClThreads)
+k_bu_keys(const int32_t *__restrict__ deg, int64_t N, uint64_t *__restrict__ key, uint64_t *__restrict__ owner,
+          int32_t *__restrict__ state, int32_t *__restrict__ claim, int32_t *__restrict__ stamp,
+          unsigned long long *__restrict__ und, unsigned long long *__restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N) {
+    key[i] = ((uint64_t)(0x7fffffff - deg[i]) << 32) | (uint64_t)i;
+    owner[i] = ~0ull;
+    state[i] = kBuUndecided;
+    claim[i] = 0;
+    stamp[i] = 0;
+  }
+  if (blockIdx.x == 0) {
+    for (int k = threadIdx.x; k < kBuWords; k += kClThreads) und[k] = k == 0 ? (unsigned long long)N : 0ull;
+    if (threadIdx.x == 0) status[kBuStatusRounds] = 0ull, status[kBuStatusLeft] = 0ull;
+  }
+}
+
+// the edge pass of round r >= 1 (und[r - 1]: what the round before left).  live_e != nullptr: the round that writes the
+// live lists
+template <class Src>
+__global__ void __launch_bounds__(kClThreads)
+k_bu_edges(const Src src, const uint64_t *__restrict__ key, const int32_t *__restrict__ state, int32_t *claim, int32_t *stamp,
+           unsigned long long *und, int32_t r, uint64_t *live_e, unsigned long long live_cap) {
+  if (und[r - 1] == 0ull) return;
+  src.each((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, (unsigned long long)gridDim.x * blockDim.x,
+           [&](bool on, uint32_t i, uint32_t j) { bu_edge(on, i, j, key, state, claim, stamp, r, live_e, und + kBuLiveE, live_cap); });
+}
+
+// the vertex pass of round r.  What stays undecided is counted into und[r], one add per wavefront; live_v != nullptr:
+// and written there, at the slots the add returned (any order: the finish takes the list as a set)
+__global__ void __launch_bounds__(kClThreads)
+k_bu_vertices(int64_t N, int32_t *state, const int32_t *__restrict__ claim, const int32_t *__restrict__ stamp, int32_t r,
+              unsigned long long *und, int32_t *__restrict__ live_v, unsigned long long *__restrict__ status) {
+  if (und[r - 1] == 0ull) return;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool left = i < N && bu_vertex((uint32_t)i, state, claim, stamp, r);
+  const uint64_t m = __ballot(left);
+  if (m != 0ull) {  // wave-uniform
+    const int leader = __ffsll((unsigned long long)m) - 1;
+    unsigned long long base = 0ull;
+    if (lane == leader) base = atomicAdd(und + r, (unsigned long long)__popcll(m));
+    base = __shfl(base, leader);
+    if (left && live_v != nullptr) live_v[base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull))] = (int32_t)i;
+  }
+  if (i == 0) status[kBuStatusRounds] = (unsigned long long)r;
+}
+
+// The finish: ONE workgroup, rounds r0, r0 + 1, ... over the live vertices (und[r0 - 1] of them, left by round r0 - 1)
+// and the live edges, the two passes separated by __syncthreads().  Thread t owns the list entries t, t + 1024, ... and
+// keeps them compact in place, on its own: an edge stays only while both ends are undecided (nothing else can act
+// again), a vertex while it is undecided, so a round costs what is left, not what there was.  The entries are
+// (a << 32) | b with a before b already: no key is read here.  Every round decides at least the first undecided vertex
+// in key order, so as many rounds as there are live vertices are enough; not done after that is a bug in this file
+// and ends as the error word, never as a hang.  Returns at once when the live-edge list overflowed (k_bu_finish_graph).
+__global__ void __launch_bounds__(kBuFinishThreads)
+k_bu_finish(uint64_t *live_e, unsigned long long live_cap, int32_t *state, int32_t *claim, int32_t *stamp, int32_t *live_v,
+            const unsigned long long *und, int32_t r0, unsigned long long *status) {
+  const unsigned long long nv = und[r0 - 1], ne = und[kBuLiveE];
+  if (nv == 0ull || ne > live_cap) return;
+  const unsigned tid = threadIdx.x;
+  constexpr unsigned long long T = kBuFinishThreads;
+  // s_left[it % 3] != 0: round it left something undecided.  Three words in turn: the one of round it + 1 is cleared in
+  // round it ahead of the first barrier, when its readers (after the second barrier of round it - 2) are all through
+  __shared__ int s_left[3];
+  if (tid == 0) status[kBuStatusLeft] = nv, s_left[0] = 0;
+  unsigned long long ecnt = ne > tid ? (ne - tid + T - 1) / T : 0ull, vcnt = nv > tid ? (nv - tid + T - 1) / T : 0ull;
+  bool done = false;
+  int32_t r = r0;
+  for (unsigned long long it = 0; it < nv; ++it, ++r) {
+    if (tid == 0) s_left[(it + 1) % 3] = 0;
+    unsigned long long kept = 0ull;
+    for (unsigned long long k = 0; k < ecnt; k += 4) {  // four entries in flight; all four are read before one is written back
+      uint64_t e[4];
+      int32_t sa[4], sb[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) e[q] = k + q < ecnt ? live_e[tid + T * (k + q)] : ~0ull;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const bool on = e[q] != ~0ull;
+        sb[q] = on ? state[(uint32_t)(e[q] & 0xffffffffull)] : kBuMember;
+        sa[q] = on ? state[(uint32_t)(e[q] >> 32)] : kBuMember;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (sb[q] != kBuUndecided) continue;
+        const uint32_t b = (uint32_t)(e[q] & 0xffffffffull);
+        if (sa[q] == kBuCentroid) {
+          claim[b] = 1;
+        } else if (sa[q] == kBuUndecided) {
+          stamp[b] = r;
+          live_e[tid + T * kept++] = e[q];
+        }
+      }
+    }
+    ecnt = kept;
+    __syncthreads();
+    kept = 0ull;
+    for (unsigned long long k = 0; k < vcnt; ++k) {
+      const int32_t v = live_v[tid + T * k];
+      if (bu_vertex((uint32_t)v, state, claim, stamp, r)) live_v[tid + T * kept++] = v;
+    }
+    vcnt = kept;
+    if (kept != 0ull) s_left[it % 3] = 1;
+    __syncthreads();  // (also the barrier between this round's state and the next edge pass)
+    done = s_left[it % 3] == 0;
+    if (done) break;
+  }
+  if (tid == 0) {
+    if (done)
+      status[kBuStatusRounds] = (unsigned long long)r;
+    else
+      status[kClStatusErr] = 1ull;
+  }
+}
+
+// The finish when the live-edge list overflowed: the same rounds with the edge pass over the graph itself (the live
+// vertices always fit).  Slower -- every round walks every edge -- and the same result.
+template <class Src>
+__global__ void __launch_bounds__(kBuFinishThreads)
+k_bu_finish_graph(const Src src, unsigned long long live_cap, const uint64_t *key, int32_t *state, int32_t *claim,
+                  int32_t *stamp, int32_t *live_v, const unsigned long long *und, int32_t r0, unsigned long long *status) {
+  const unsigned long long nv = und[r0 - 1];
+  if (nv == 0ull || und[kBuLiveE] <= live_cap) return;
+  const unsigned tid = threadIdx.x;
+  constexpr unsigned long long T = kBuFinishThreads;
+  // s_left[it % 3] != 0: round it left something undecided.  Three words in turn: the one of round it + 1 is cleared in
+  // round it ahead of the first barrier, when its readers (after the second barrier of round it - 2) are all through
+  __shared__ int s_left[3];
+  if (tid == 0) status[kBuStatusLeft] = nv, s_left[0] = 0;
+  unsigned long long vcnt = nv > tid ? (nv - tid + T - 1) / T : 0ull;
+  bool done = false;
+  int32_t r = r0;
+  for (unsigned long long it = 0; it < nv; ++it, ++r) {
+    if (tid == 0) s_left[(it + 1) % 3] = 0;
+    src.each((unsigned long long)tid, T,
+             [&](bool on, uint32_t i, uint32_t j) { bu_edge(on, i, j, key, state, claim, stamp, r, nullptr, nullptr, 0ull); });
+    __syncthreads();
+    unsigned long long kept = 0ull;
+    for (unsigned long long k = 0; k < vcnt; ++k) {
+      const int32_t v = live_v[tid + T * k];
+      if (bu_vertex((uint32_t)v, state, claim, stamp, r)) live_v[tid + T * kept++] = v;
+    }
+    vcnt = kept;
+    if (kept != 0ull) s_left[it % 3] = 1;
+    __syncthreads();
+    done = s_left[it % 3] == 0;
+    if (done) break;
+  }
+  if (tid == 0) {
+    if (done)
+      status[kBuStatusRounds] = (unsigned long long)r;
+    else
+      status[kClStatusErr] = 1ull;
+  }
+}
+
+// Owners: the centroid of a member is the first centroid, in key order, among its neighbours.  A pass of its own over
+// every edge, after the last round: the centroid that claimed a member first need not be that one (an earlier centroid
+// can be decided in a later round).  owner[] starts as all ones.
+template <class Src>
+__global__ void __launch_bounds__(kClThreads)
+k_bu_owners(const Src src, const uint64_t *__restrict__ key, const int32_t *__restrict__ state, uint64_t *owner) {
+  src.each((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, (unsigned long long)gridDim.x * blockDim.x,
+           [&](bool on, uint32_t i, uint32_t j) {
+             if (!on) return;
+             const int32_t si = state[i], sj = state[j];
+             if (si == kBuCentroid && sj == kBuMember)
+               (void)__hip_atomic_fetch_min(owner + j, key[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+             else if (sj == kBuCentroid && si == kBuMember)
+               (void)__hip_atomic_fetch_min(owner + i, key[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+           });
+}
+
+// k_cl_flatten's outputs from state[] and owner[]: root[i] = the centroid's index, flags = the centroid ballot.  A vertex
+// that is neither a centroid nor owned (possible only behind the error word) is flagged as its own root, so that the
+// labelling stays inside its arrays, and raises the error word itself.
+__global__ void __launch_bounds__(kClThreads)
+k_bu_roots(const int32_t *__restrict__ state, const uint64_t *__restrict__ owner, int64_t N, int32_t *__restrict__ root,
+           uint64_t *__restrict__ flags, int64_t W, unsigned long long *__restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool is_root = false;
+  if (i < N) {
+    const uint64_t o = owner[i];
+    is_root = state[i] == kBuCentroid || o == ~0ull;
+    if (state[i] != kBuCentroid && o == ~0ull) status[kClStatusErr] = 1ull;
+    root[i] = is_root ? (int32_t)i : (int32_t)(o & 0xffffffffull);
+  }
+  const uint64_t m = __ballot(is_root);
+  if ((threadIdx.x & 63) == 0 && (i >> 6) < W) flags[i >> 6] = m;
+}
+
+// parallel rounds ahead of the finish (fc_tuning.h; FC_BUTINA_ROUNDS, read per call: the tests compare several values)
+int bu_rounds() {
+  long long r = kButinaRounds;
+  if (const char *v = getenv("FC_BUTINA_ROUNDS")) {
+    char *end = nullptr;
+    const long long f = strtoll(v, &end, 10);
+    if (end != v && *end == 0 && f >= 0) r = f;
+  }
+  return (int)std::min<long long>(r, kBuRoundsMax);
+}
+
+// everything behind the degrees, for either kind of edge source
+template <class Src>
+int bu_run(const ClWork &w, const Src &src, dim3 grid, int64_t N, size_t live_cap) {
+  const unsigned long long cap = (unsigned long long)live_cap;
+  hipLaunchKernelGGL(k_bu_keys, dim3(w.per_n), dim3(kClThreads), 0, w.st, w.deg, N, w.key, w.owner, w.state, w.claim, w.stamp,
+                     w.und, w.status);
+  FC_TRY(check_launch("k_bu_keys"));
+  const int R = bu_rounds();
+  for (int r = 1; r <= R + 1; ++r) {
+    const bool last = r == R + 1;
+    hipLaunchKernelGGL(k_bu_edges<Src>, grid, dim3(kClThreads), 0, w.st, src, w.key, w.state, w.claim, w.stamp, w.und, r,
+                       last ? w.live_e : nullptr, cap);
+    FC_TRY(check_launch("k_bu_edges"));
+    hipLaunchKernelGGL(k_bu_vertices, dim3(w.per_n), dim3(kClThreads), 0, w.st, N, w.state, w.claim, w.stamp, r, w.und,
+                       last ? w.live_v : nullptr, w.status);
+    FC_TRY(check_launch("k_bu_vertices"));
+  }
+  hipLaunchKernelGGL(k_bu_finish, dim3(1), dim3(kBuFinishThreads), 0, w.st, w.live_e, cap, w.state, w.claim, w.stamp, w.live_v,
+                     w.und, R + 2, w.status);
+  FC_TRY(check_launch("k_bu_finish"));
+  hipLaunchKernelGGL(k_bu_finish_graph<Src>, dim3(1), dim3(kBuFinishThreads), 0, w.st, src, cap, w.key, w.state, w.claim,
+                     w.stamp, w.live_v, w.und, R + 2, w.status);
+  FC_TRY(check_launch("k_bu_finish_graph"));
+  hipLaunchKernelGGL(k_bu_owners<Src>, grid, dim3(kClThreads), 0, w.st, src, w.key, w.state, w.owner);
+  FC_TRY(check_launch("k_bu_owners"));
+  hipLaunchKernelGGL(k_bu_roots, dim3(w.per_n), dim3(kClThreads), 0, w.st, w.state, w.owner, N, w.root, w.flags, w.W, w.status);
+  FC_TRY(check_launch("k_bu_roots"));
+  hipLaunchKernelGGL(k_cl_scan, dim3(1), dim3(1024), 0, w.st, w.flags, w.W, w.prefix, w.status);
+  FC_TRY(check_launch("k_cl_scan"));
+  hipLaunchKernelGGL(k_cl_label, dim3(w.per_n), dim3(kClThreads), 0, w.st, w.root, N, w.flags, w.prefix, w.labels, w.reps, w.sizes);
+  return check_launch("k_cl_label");
+}
+
+}  // namespace
+
+// entries of the live-edge list: no more than the graph can have, at most kButinaLiveEdges (fc_tuning.h;
+// FC_BUTINA_LIVE_CAP: test knob, forces the finish over the graph itself)
+size_t butina_live_cap(const ClusterGraph &g, int64_t N) {
+  const unsigned long long n = (unsigned long long)(N > 0 ? N : 1), all = n * (n - 1) / 2;
+  unsigned long long bound = g.pairs_dev == nullptr ? all : (g.n_pairs_dev != nullptr ? g.cand_cap : g.n_pairs_host);
+  bound = std::min<unsigned long long>(std::min(bound, all), (unsigned long long)kButinaLiveEdges);
+  if (const char *v = getenv("FC_BUTINA_LIVE_CAP")) {
+    char *end = nullptr;
+    const long long f = strtoll(v, &end, 10);
+    if (end != v && *end == 0 && f >= 1) bound = std::min<unsigned long long>(bound, (unsigned long long)f);
+  }
+  return (size_t)std::max<unsigned long long>(bound, 1ull);
+}
+
+// launch_clusters for the sphere-exclusion clusters
+int launch_butina(const ClusterGraph &g, int64_t N, DevBuf &work) {
+  ClWork w;
+  const size_t live_cap = butina_live_cap(g, N);
+  FC_TRY(cl_begin(g, N, kClButina, 1, work, &w, live_cap));
+  if (g.pairs_dev != nullptr) {
+    const unsigned long long *n_pairs_dev = g.n_pairs_dev != nullptr ? g.n_pairs_dev : w.status + kClStatusPairs;
+    const dim3 grid = cl_grid_pairs();
+    hipLaunchKernelGGL(k_db_degree_pairs, grid, dim3(kClThreads), 0, w.st, g.pairs_dev, n_pairs_dev, g.n_cand_dev, g.cand_cap,
+                       g.redo_dev, N, w.deg, w.status);
+    FC_TRY(check_launch("k_db_degree_pairs"));
+    return bu_run(w, BuPairs{g.pairs_dev, n_pairs_dev, g.n_cand_dev, g.cand_cap, g.redo_dev, (uint32_t)N}, grid, N, live_cap);
+  }
+  if (g.W < w.W) return set_error(FC_E_INVALID, "bit rows of %lld words, %lld needed", (long long)g.W, (long long)w.W);
+  hipLaunchKernelGGL(k_db_degree_bits, dim3((unsigned)w.W), dim3(kClThreads), 0, w.st, g.bits_dev, g.W, N, w.deg);
+  FC_TRY(check_launch("k_db_degree_bits"));
+  return bu_run(w, BuBits{g.bits_dev, g.W, N}, cl_grid_bits(N, g.W), N, live_cap);
 }
 
 __global__ void k_warm_clusters() {}

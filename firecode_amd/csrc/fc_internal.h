@@ -177,14 +177,25 @@ constexpr int kClStatusList = 1;   // 1: the pair list produced the result, 0: t
 constexpr int kClStatusK = 2;      // number of clusters
 constexpr int kClStatusPairs = 3;  // length of a list uploaded by the caller
 constexpr int64_t kClShortList = 1 << 16;  // pair lists below this are hooked in one launch (fc_clusters.hip)
+// words of the status block that only the sphere-exclusion form has
+constexpr int kBuStatusRounds = 4;  // rounds of the rule until nothing was undecided
+constexpr int kBuStatusLeft = 5;    // vertices that went to the finish
+// which labelling a block serves
+enum ClKind { kClComponents = 0, kClDensity = 1, kClButina = 2 };
 // one block: labels | reps | sizes [| core | degrees] | status (the part that travels to the host, result_bytes from
-// offset 0) | scratch [+ attach].  density: the density-based form, which adds the bracketed fields; they stay 0 without it
+// offset 0) | scratch [+ attach | the sphere-exclusion scratch].  kClDensity adds core, degrees and attach, kClButina
+// degrees (no core), four more status words and its own scratch behind everything else; the fields a kind does not have
+// stay 0, and the offsets of the other two kinds do not depend on it.  live_cap: entries of kClButina's live-edge list
 struct ClusterLayout {
   size_t labels, reps, sizes, status, result_bytes, parent, root, flags, prefix, total, core, degrees, attach;
+  size_t bu_key, bu_owner, bu_state, bu_claim, bu_stamp, bu_live_v, bu_words, bu_live_e;
 };
-inline ClusterLayout cluster_layout(int64_t N, bool density) {
+constexpr int kBuRoundsMax = 64;             // parallel rounds at most (FC_BUTINA_ROUNDS is cut to it)
+constexpr int kBuWords = kBuRoundsMax + 8;   // und[0 .. kBuRoundsMax + 1] and the live-edge count
+inline ClusterLayout cluster_layout(int64_t N, ClKind kind, size_t live_cap = 0) {
   const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t n = (size_t)(N > 0 ? N : 1), w = (n + 63) / 64;
+  const bool density = kind == kClDensity, butina = kind == kClButina;
   ClusterLayout L{};
   L.labels = 0;
   L.reps = up(n * sizeof(int32_t));
@@ -195,7 +206,11 @@ inline ClusterLayout cluster_layout(int64_t N, bool density) {
     L.degrees = L.core + up(n * sizeof(uint8_t));
     L.status = L.degrees + up(n * sizeof(int32_t));
   }
-  L.result_bytes = L.status + 4 * sizeof(uint64_t);
+  if (butina) {
+    L.degrees = L.status;
+    L.status = L.degrees + up(n * sizeof(int32_t));
+  }
+  L.result_bytes = L.status + (butina ? 8 : 4) * sizeof(uint64_t);
   L.parent = up(L.result_bytes);
   L.root = L.parent + up(n * sizeof(int32_t));
   L.flags = L.root + up(n * sizeof(int32_t));
@@ -205,13 +220,28 @@ inline ClusterLayout cluster_layout(int64_t N, bool density) {
     L.attach = L.total;
     L.total = L.attach + up(n * sizeof(uint32_t));
   }
+  if (butina) {
+    L.bu_key = L.total;
+    L.bu_owner = L.bu_key + up(n * sizeof(uint64_t));
+    L.bu_state = L.bu_owner + up(n * sizeof(uint64_t));
+    L.bu_claim = L.bu_state + up(n * sizeof(int32_t));
+    L.bu_stamp = L.bu_claim + up(n * sizeof(int32_t));
+    L.bu_live_v = L.bu_stamp + up(n * sizeof(int32_t));
+    L.bu_words = L.bu_live_v + up(n * sizeof(int32_t));
+    L.bu_live_e = L.bu_words + up(kBuWords * sizeof(uint64_t));
+    L.total = L.bu_live_e + up((live_cap > 0 ? live_cap : 1) * sizeof(uint64_t));
+  }
   return L;
 }
-// `work` holds cluster_layout(N, false).total bytes
+// `work` holds cluster_layout(N, kClComponents).total bytes
 int launch_clusters(const ClusterGraph &g, int64_t N, DevBuf &work);
 // the graph of launch_clusters under the core rule (degree + 1 >= min_samples); pair lists: each unordered pair once;
-// `work` holds cluster_layout(N, true).total bytes
+// `work` holds cluster_layout(N, kClDensity).total bytes
 int launch_dbscan(const ClusterGraph &g, int64_t N, int64_t min_samples, DevBuf &work);
+// the sphere-exclusion clusters of the same graph (include/fc_hip.h, "sphere-exclusion clusters"); pair lists: each
+// unordered pair once; `work` holds cluster_layout(N, kClButina, butina_live_cap(g, N)).total bytes
+size_t butina_live_cap(const ClusterGraph &g, int64_t N);
+int launch_butina(const ClusterGraph &g, int64_t N, DevBuf &work);
 int warm_clusters();
 // ---- fc_symm.hip -----------------------------------------------------------------------------------------
 constexpr int64_t kPermMax = FC_PERM_MAX;

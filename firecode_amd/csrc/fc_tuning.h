@@ -43,5 +43,12 @@ constexpr int64_t kDiverseLanes8MaxN = 10000;
 // strip count at run time; the outputs are the same bits for every value.
 constexpr int kKnnWorkgroupsPerCu = 4;
 constexpr int kKnnMaxStrips = 64;
+// fc_clusters.hip, sphere-exclusion clusters: rounds of the rule that are enqueued as grid-wide launches before the live
+// subgraph is written down (in one more round) and one workgroup finishes it.  FC_BUTINA_ROUNDS=<n> (0 .. 64) forces the
+// count at run time; outputs and stats[6] are the same for every value.  Why this count: DESIGN.md section 23.
+constexpr int kButinaRounds = 16;
+// ... and the entries of the live-edge list at most (8 bytes each).  A graph that leaves more is finished over the graph
+// itself.  FC_BUTINA_LIVE_CAP=<n>: test knob for that path.
+constexpr long long kButinaLiveEdges = 1ll << 22;
 }  // namespace fc
 #endif

@@ -204,6 +204,17 @@ class Ensemble:
                               debugfunction=self.logfunction if verbose else None, heavy_atoms_only=heavy_atoms_only,
                               prune_enantiomers=prune_enantiomers, symmetry=symmetry)
 
+    def butina_by_rmsd(self, max_rmsd=None, heavy_atoms_only=True, prune_enantiomers=False, verbose=True, symmetry=None):
+        """Centroids and populations (``firecode_amd.pruner.butina_by_rmsd``): sphere-exclusion clusters on the graph of
+        ``cluster_by_rmsd``, with its energies and window (``max_dE = 1.0`` when there is one energy per conformer).
+        Returns the ``RmsdButina``; the ensemble is not masked."""
+        from firecode_amd.pruner import butina_by_rmsd
+
+        use_en = len(self.energies) == len(self.coords)
+        return butina_by_rmsd(self.coords, self.atoms, max_rmsd, energies=self.energies if use_en else None,
+                              max_dE=1.0 if use_en else 0.0, debugfunction=self.logfunction if verbose else None,
+                              heavy_atoms_only=heavy_atoms_only, prune_enantiomers=prune_enantiomers, symmetry=symmetry)
+
     def similarity_pruning(self, moi=True, rmsd=True, rmsd_rot_corr=False, verbose=True, max_rmsd=None,
                            symmetric_torsions=None, graph=None, rotation_masks=None, prune_enantiomers=False,
                            symmetry=None):

@@ -439,7 +439,7 @@ def _labels_from_graph(name, graph, n, min_samples=None):
     """the C entry point ``name`` on a checked pair list or bit matrix; ``min_samples``: the density-based forms'"""
     import ctypes as C
 
-    dbscan = min_samples is not None
+    dbscan, butina = min_samples is not None, name.startswith("fc_butina_")
     labels = np.zeros(n, dtype=np.int32)
     reps, sizes = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
     k = C.c_int64(0)
@@ -448,8 +448,13 @@ def _labels_from_graph(name, graph, n, min_samples=None):
     if dbscan:
         core, degrees = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int32)
         args += [L.pb(core), L.ptr(degrees, C.c_int32)]
+    if butina:
+        degrees = np.zeros(n, dtype=np.int32)
+        args += [L.ptr(degrees, C.c_int32)]
     L.call(name, *args, C.byref(k))
     reps, sizes = reps[:k.value].copy(), sizes[:k.value].copy()
+    if butina:
+        return RmsdButina(labels, reps, sizes, degrees)
     return RmsdDbscan(labels, reps, sizes, core.astype(bool), degrees) if dbscan else RmsdClusters(labels, reps, sizes)
 
 
@@ -575,6 +580,73 @@ def dbscan_from_bits(bits, n, min_samples):
     n = _vertex_count(n)
     min_samples = L.check_min_samples(min_samples)
     return _labels_from_graph("fc_dbscan_from_bits", _bit_matrix(bits, n), n, min_samples)
+
+
+class RmsdButina(namedtuple("RmsdButina", ["labels", "centroids", "sizes", "degrees"])):
+    """What ``butina_by_rmsd`` returns; ``members(k)``: the indices of cluster ``k``, ascending."""
+    __slots__ = ()
+
+    def members(self, k):
+        if isinstance(k, (bool, np.bool_)) or int(k) != k or not 0 <= int(k) < len(self.centroids):
+            raise IndexError(f"cluster {k!r}: there are {len(self.centroids)}")
+        return np.flatnonzero(self.labels == int(k))
+
+
+def butina_by_rmsd(structures, atoms, max_rmsd=None, max_dev=None, energies=None, max_dE=0.0, debugfunction=None,
+                   heavy_atoms_only=True, prune_enantiomers=False, symmetry=None):
+    """Centroids and their members: the sphere-exclusion clustering of Butina (1999) on the similarity graph of
+    ``cluster_by_rmsd`` -- the same edges, the same options -- on the GPU (fc_rmsd_butina; the contract is written out
+    in include/fc_hip.h).  Conformers are ranked by their number of neighbours, the lower energy (the lower index where
+    ``energies`` is not usable) first on ties; the best-ranked unassigned conformer becomes a centroid and takes all of
+    its unassigned neighbours, until none is left.  Every member is a neighbour of its centroid -- within ``max_rmsd``
+    and ``max_dev`` of it -- which neither the components nor the density-based clusters promise.  Degrees are not
+    updated while clusters form (RDKit: ``reordering=False``).  Unlike RDKit's ``Butina.ClusterData`` the threshold is
+    the prune's strict ``<`` and a tie of degrees goes to the lowest, not the highest, index.
+
+    Returns ``RmsdButina(labels, centroids, sizes, degrees)`` in the caller's order: labels (N,) int32; centroids (K,)
+    int64 indices into ``structures``, clusters numbered by ascending centroid in processing order; sizes (K,) int64,
+    the centroid included; degrees (N,) int32.  ``.members(k)``: the indices of cluster ``k``."""
+    t0 = perf_counter()
+    enant = L.check_flag("prune_enantiomers", prune_enantiomers)
+    structures, table, (max_rmsd, max_dev, max_dE), heavy, order, en_sorted, X = _graph_inputs(
+        structures, atoms, max_rmsd, max_dev, energies, max_dE, heavy_atoms_only, enant, symmetry)
+    N = structures.shape[0]
+    if N == 0:
+        return RmsdButina(np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64),
+                          np.zeros(0, dtype=np.int32))
+    with L.DeviceEnsemble(X, atom_mask=heavy, center=True) as ens:
+        labels, reps, sizes, degrees, stats = ens.butina(max_rmsd, max_dev, energies=en_sorted, max_dE=max_dE,
+                                                         prune_enantiomers=enant, symmetry=table)
+    if order is not None:
+        labels, degrees = _unsort(labels, order), _unsort(degrees, order)
+        reps = order[reps].astype(np.int64)
+    if debugfunction is not None:
+        debugfunction(
+            f"DEBUG: butina_by_rmsd [gfx950{', mirror images included' if enant else ''}"
+            f"{'' if table is None else f', {len(table)} atom permutations'}] - {stats[0]} pairs screened, "
+            f"{stats[2]} similar: {len(sizes)} clusters, largest {int(sizes.max())}, {int((sizes == 1).sum())} singletons, "
+            f"{stats[6]} rounds, in {perf_counter() - t0:.3f} s")
+    return RmsdButina(labels, reps, sizes, degrees)
+
+
+def butina_from_pairs(pairs, n, assume_unique=False):
+    """The labelling of ``butina_by_rmsd`` on a caller's graph (fc_butina_from_pairs): ``pairs``, ``n`` and
+    ``assume_unique`` as ``dbscan_from_pairs`` takes them, with the same checks before any device use and the same
+    removal of duplicates.  Returns ``RmsdButina``; the smaller index comes first among vertices of one degree."""
+    n = _vertex_count(n)
+    assume_unique = L.check_flag("assume_unique", assume_unique)
+    pairs = _pair_words(pairs, n)
+    if not assume_unique:
+        hi, lo = pairs >> np.uint64(32), pairs & np.uint64(0xFFFFFFFF)
+        pairs = np.unique((np.minimum(hi, lo) << np.uint64(32)) | np.maximum(hi, lo))
+    return _labels_from_graph("fc_butina_from_pairs", np.ascontiguousarray(pairs, dtype=np.uint64), n)
+
+
+def butina_from_bits(bits, n):
+    """The labelling of ``butina_by_rmsd`` on a caller's (n, ceil(n/64)) uint64 bit matrix (fc_butina_from_bits): the
+    layout and the checks of ``clusters_from_bits``; only bits j > i are read."""
+    n = _vertex_count(n)
+    return _labels_from_graph("fc_butina_from_bits", _bit_matrix(bits, n), n)
 
 
 def rotation_mask(graph, torsion, n_atoms=None):

@@ -419,6 +419,56 @@ int fc_dbscan_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int6
 int fc_dbscan_from_bits(const uint64_t *bits, int64_t N, int64_t min_samples, int32_t *labels_out, int64_t *reps_out,
                         int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out, int64_t *n_clusters);
 
+/* ---- sphere-exclusion clusters: centroids and their members on the prune's graph (Butina 1999) ----
+ * The contract, once.  G = exactly the graph of fc_rmsd_clusters on the N conformers in processing order (fc_rmsd_butina_enant:
+ * of fc_rmsd_clusters_enant; fc_rmsd_butina_perm: of fc_rmsd_clusters_perm): the same thresholds, "<", max_dev, energy
+ * window and grey handling.  fc_prune_conventions and min_per_group play no part.
+ *
+ *   degree    d(i) = the number of neighbours of i in G, as fc_rmsd_dbscan counts them
+ *   priority  i comes before j when d(i) > d(j), or d(i) == d(j) and i < j
+ *   walk      the conformers are visited in priority order.  One that is unassigned when the walk reaches it becomes a
+ *             CENTROID and takes itself and every neighbour that is still unassigned.  Degrees are never recomputed:
+ *             Butina's fixed order (RDKit: reordering=False)
+ *
+ * The walk is these two statements, which are what the device computes:
+ *   - v is a centroid exactly when none of its neighbours that come before it is a centroid;
+ *   - the centroid of any other conformer u is the first centroid, in priority order, among u's neighbours.
+ * So every member is a neighbour of its centroid (within max_rmsd and max_dev of it), and no two centroids are neighbours.
+ *
+ *   labels_out  (N, int32)              the cluster of each conformer; clusters numbered 0 .. K-1 by ascending centroid index
+ *   reps_out    (N entries, K written)  the centroids
+ *   sizes_out   (N entries, K written)  members of each cluster, the centroid included
+ *   degrees_out (N, int32)              d(i)
+ *   *n_clusters = K
+ *
+ * The host pre-sorts by energy as for fc_rmsd_clusters, so among conformers of one degree the lower energy comes first.
+ * The result is a function of G and the processing order alone: never of launch order, grid size, FC_BUTINA_ROUNDS, or
+ * of which source (pair list or bit matrix) produced it.  stats (8 values, may be NULL): [0 .. 5] as fc_rmsd_clusters,
+ * [6] the synchronous rounds of the rule the device needed (the dependency depth of the walk on this graph; the same for
+ * every setting of the knob), [7] the conformers still undecided when the grid-wide rounds ended (FC_BUTINA_ROUNDS of them
+ * and the one that writes down what is left), which one workgroup then finished.  N = 0: K = 0.  Limit: N < 2^31 - 256.
+ * FC_E_INVALID before any device use: NULL ens / outputs, thresholds <= 0 (fc_rmsd_butina_perm: first the table's checks,
+ * as fc_rmsd_clusters_perm).  FC_E_INTERNAL: as fc_rmsd_clusters, and when the finish ran out of its round bound (one
+ * round per conformer it was given; every round decides at least one).
+ *
+ * fc_butina_from_pairs / fc_butina_from_bits: the same labelling of a caller's graph, in the formats and with the host-side
+ * checks of fc_dbscan_from_pairs / fc_dbscan_from_bits; as there, every unordered pair AT MOST ONCE in the list.
+ *
+ * Against RDKit's Butina.ClusterData, two differences in the definition: RDKit takes "<=" at the threshold and breaks
+ * degree ties by the HIGHEST index; here it is the prune's "<" and the lowest index (the lowest energy).  Parity with
+ * RDKit is not pinned by any test (it is not part of the build).  reordering=True (degrees updated
+ * after every cluster) is not offered. */
+int fc_rmsd_butina(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                   int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int32_t *degrees_out, int64_t *n_clusters,
+                   int64_t *stats);
+int fc_rmsd_butina_enant(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                         int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int32_t *degrees_out,
+                         int64_t *n_clusters, int64_t *stats);
+int fc_butina_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int32_t *labels_out, int64_t *reps_out,
+                         int64_t *sizes_out, int32_t *degrees_out, int64_t *n_clusters);
+int fc_butina_from_bits(const uint64_t *bits, int64_t N, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
+                        int32_t *degrees_out, int64_t *n_clusters);
+
 /* ---- symmetry-aware forms: atom permutations of equivalent atoms ----
  * The contract, once.  X = the prepared ensemble of the RMSD stage (atom selection applied, each conformer centred on the
  * centroid of its selected atoms).  perms = a (K, A_sel) row-major table of permutations of the selected atoms, in
@@ -465,6 +515,10 @@ int fc_rmsd_clusters_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int
 int fc_rmsd_dbscan_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
                         int64_t min_samples, const double *energies, double max_dE, int32_t *labels_out, int64_t *reps_out,
                         int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out, int64_t *n_clusters, int64_t *stats);
+/* the sphere-exclusion clusters (above) of the graph of fc_rmsd_clusters_perm */
+int fc_rmsd_butina_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
+                        const double *energies, double max_dE, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
+                        int32_t *degrees_out, int64_t *n_clusters, int64_t *stats);
 
 /* sharded form (conformer rows dealt block-cyclically to ranks):
  * fc_prune_rmsd_begin computes this rank's rows of the bit matrix;
