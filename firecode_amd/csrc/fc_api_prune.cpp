@@ -1,10 +1,10 @@
-// fc_api_prune.cpp -- the extern "C" surface (include/fc_hip.h) of the resident ensemble and of every prune that ends
-// in the ladder: argument checks, host<->HBM staging, kernel sequencing, the pipelines and their bench hooks.
+// fc_api_prune.cpp -- the extern "C" surface (include/fc_hip.h) of every prune that ends in a mask: the similarity bits
+// (plain, enantiomer- and symmetry-aware), the ladder in its device forms, the pipelines (staged, async, many, sharded)
+// and their bench and debug hooks: argument checks, host<->HBM staging, kernel sequencing.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
-#include <functional>
 #include <memory>
 
 #include "fc_internal.h"
@@ -20,194 +20,8 @@ __global__ void k_store_ladder_ks(LadderKs a, int64_t *__restrict__ out) {
   if ((int)threadIdx.x < a.n) out[threadIdx.x] = a.k[threadIdx.x];
 }
 
-static int make_selection(const uint8_t *atom_mask, int64_t A_all, std::vector<int32_t> &sel) {
-  sel.clear();
-  for (int64_t a = 0; a < A_all; ++a)
-    if (atom_mask == nullptr || atom_mask[a]) sel.push_back((int32_t)a);
-  if (sel.empty()) return set_error(FC_E_INVALID, "atom_mask selects no atom");
-  return FC_OK;
-}
-
-// prepared layout of N conformers taken from device-resident raw coordinates (all atoms, AoS):
-// conformer n is raw[conf_idx[n]] (conf_idx_dev == nullptr: raw[n])
-// defer_wait: return with the preparation kernel and the copy of the largest G still in flight -- the caller does host
-// work that does not need them (fc_prune_rmsd_host: the prune's reserves and item table) and then calls
-// ensemble_build_finish
-static int ensemble_build_finish(fc_ensemble *e) {
-  if (!e->g_max_pending) return FC_OK;
-  e->g_max_pending = false;
-  FC_TRY(sync());
-  std::memcpy(&e->g_max, ctx().pinned_word, sizeof(double));
-  auto *gmax_dev = reinterpret_cast<unsigned long long *>(e->counters.p) + (kCounters - 1);
-  FC_HIP_TRY(hipMemsetAsync(gmax_dev, 0, sizeof(unsigned long long), ctx().stream));
-  return FC_OK;
-}
-
-// The largest G of a SMALL ensemble from the caller's array, on the host: the preparation kernel's arithmetic in its order
-// (running sums over the selected atoms, the division, x*x + y*y + z*z per atom; nothing is fused on either side), so that
-// fc_prune_rmsd_host needs no wait between the preparation and the prune -- at the sizes of FIRECODE's own runs (hundreds of
-// conformers) the call is a chain of waits and launches, not of kernels (0.16 ms at 100 conformers).  Used a hair larger
-// than computed: the band rule and the split-half scale are both conservative in a LARGER value.
-static double host_largest_g(const double *coords, int64_t N, int64_t A_all, const std::vector<int32_t> &sel, int center) {
-  const int64_t A = (int64_t)sel.size();
-  double gmax = 0.0;
-  for (int64_t n = 0; n < N; ++n) {
-    const double *t = coords + n * A_all * 3;
-    double cx = 0.0, cy = 0.0, cz = 0.0;
-    if (center) {
-      for (int64_t a = 0; a < A; ++a) {
-        const double *r = t + (int64_t)sel[(size_t)a] * 3;
-        cx += r[0];
-        cy += r[1];
-        cz += r[2];
-      }
-      cx /= (double)A;
-      cy /= (double)A;
-      cz /= (double)A;
-    }
-    double g = 0.0;
-    for (int64_t a = 0; a < A; ++a) {
-      const double *r = t + (int64_t)sel[(size_t)a] * 3;
-      const double x = r[0] - cx, y = r[1] - cy, z = r[2] - cz;
-      g += x * x + y * y + z * z;
-    }
-    if (g == g && g > gmax) gmax = g;
-  }
-  return gmax;
-}
-// N * A * 3 up to which the host pass beats the wait: measured at 50 atoms -- 100 conformers 0.148 against 0.161 ms per call,
-// 300 conformers even, 1 000 conformers 0.247 against 0.228 (the pass is three dependent chains of additions per conformer)
-constexpr int64_t kHostGmaxDoubles = 36000;
-
-// Two halves: what does not need the coordinates on the device (selection, reserves, the selection's upload, the reset of the
-// largest-G word) and the preparation launch behind them -- ensemble_build issues the first half in FRONT of the upload, so
-// that nothing but the launch itself stands between the last piece's DMA and the kernel (the trace of one
-// prune_by_rmsd(host arrays) call showed 39 us there).
-static int ensemble_build_prepare(int64_t N, int64_t A_all, const uint8_t *atom_mask, fc_ensemble *e, DevBuf &dsel) {
-  std::vector<int32_t> &sel = e->sel_host;
-  FC_TRY(make_selection(atom_mask, A_all, sel));
-  e->N = N;
-  e->A = (int64_t)sel.size();
-  {  // (Context::hint_*: the last prune of an ensemble of this shape, scaled to this one's number of pairs)
-    const Context &c = ctx();
-    if (c.hint_A == e->A && c.hint_N >= 2 && N >= c.hint_N / 2 && N <= 2 * c.hint_N) {
-      const double scale = ((double)N * (double)N) / ((double)c.hint_N * (double)c.hint_N);
-      e->last_candidates = (int64_t)((double)c.hint_candidates * scale);
-      e->last_similar = (int64_t)((double)c.hint_similar * scale);
-    }
-  }
-  e->Npad = ceil_div(std::max<int64_t>(N, 1), 64) * 64;
-  e->W = e->Npad / 64;
-  FC_TRY(e->Xs.reserve((size_t)((e->A + 3) / 4 * 4) * 3 * e->Npad * sizeof(double)));
-  FC_TRY(e->G.reserve((size_t)e->Npad * sizeof(double)));
-  FC_TRY(e->Xa.reserve((size_t)std::max<int64_t>(N, 1) * e->A * 3 * sizeof(double)));
-  FC_TRY(e->counters.reserve(kCounters * sizeof(uint64_t)));
-  FC_TRY(upload(dsel, sel.data(), sel.size()));
-  return launch_prep_begin(e);
-}
-
-static int ensemble_build_launch(const double *raw_dev, int64_t N, int64_t A_all, int center, const int32_t *conf_idx_dev,
-                                 fc_ensemble *e, DevBuf &dsel, bool defer_wait, bool host_gmax = false) {
-  FC_TRY(launch_prep_body(raw_dev, N, A_all, dsel.as<int32_t>(), e->A, center, e, conf_idx_dev));
-  if (host_gmax) return FC_OK;  // (the caller computes the largest G from its array: fc_prune_rmsd_host on small ensembles)
-  // the largest G (left by the prep kernel in the last counter word) comes back behind the same wait
-  unsigned long long gmax_bits = 0;
-  auto *gmax_dev = reinterpret_cast<unsigned long long *>(e->counters.p) + (kCounters - 1);
-  if (defer_wait) {
-    Context &c = ctx();
-    if (!c.pinned_word && hipHostMalloc(&c.pinned_word, 64, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      c.pinned_word = nullptr;
-    }
-    if (c.pinned_word) {
-      FC_HIP_TRY(hipMemcpyAsync(c.pinned_word, gmax_dev, sizeof gmax_bits, hipMemcpyDeviceToHost, c.stream));
-      e->g_max_pending = true;
-      return FC_OK;  // (dsel returns to the pool: its next user is ordered behind the kernel on this stream)
-    }
-  }
-  FC_TRY(d2h(&gmax_bits, gmax_dev, sizeof gmax_bits));
-  FC_TRY(sync());  // (also keeps `sel` / dsel alive until the kernel has read them)
-  std::memcpy(&e->g_max, &gmax_bits, sizeof(double));
-  FC_HIP_TRY(hipMemsetAsync(gmax_dev, 0, sizeof(unsigned long long), ctx().stream));
-  return FC_OK;
-}
-
-static int ensemble_build_dev(const double *raw_dev, int64_t N, int64_t A_all, const uint8_t *atom_mask,
-                              int center, const int32_t *conf_idx_dev, fc_ensemble *e, bool defer_wait = false) {
-  DevBuf dsel;
-  FC_TRY(ensemble_build_prepare(N, A_all, atom_mask, e, dsel));
-  return ensemble_build_launch(raw_dev, N, A_all, center, conf_idx_dev, e, dsel, defer_wait);
-}
-
-// Host arrays in (the drop-in call prune_by_rmsd(structures, ...)): the coordinates go through the pinned pieces like every
-// large upload from pageable memory (h2d_staged; fc_common.h says why the caller's pages are not handed to the runtime,
-// nor registered by the library for the duration of the copy).
-// What that costs and what was tried against it (round 4; tools/attic/pin_probe.py, tools/hostin_breakdown.py; 12 MB):
-// DMA from pinned memory 0.22 ms (54 GB/s), from the caller's pageable pages THE SAME 0.22 ms (the driver maps them; that
-// mapping is what later stalls the queues when the caller frees the array), memmove into pinned memory 0.24 ms on one
-// core -- piece by piece (3 x 4 MB, copy of piece k + 1 beside the DMA of piece k) 0.44 ms per ensemble with the
-// preparation kernel.  Built and not kept: ~2 MB pieces of whole 64-conformer tiles, each followed by its own preparation
-// launch -- on one stream every copy -> kernel -> copy hand-over between the copy engine and the compute queue costs
-// ~25 us (0.67 ms); with the copies on a stream of their own every extra piece costs ~10 us and every event ~7 us
-// (0.53 ms); the copy of each 4 MB piece split between this thread and a helper thread (0.41 ms: a thread per call
-// for 0.03 ms).
-static int ensemble_build(const double *coords, int64_t N, int64_t A_all, const uint8_t *atom_mask,
-                          int center, fc_ensemble *e, bool defer_wait = false, bool host_gmax = false) {
-  DevBuf dsel, raw;
-  FC_TRY(ensemble_build_prepare(N, A_all, atom_mask, e, dsel));
-  FC_TRY(upload(raw, coords, (size_t)N * A_all * 3));
-  return ensemble_build_launch(raw.as<double>(), N, A_all, center, nullptr, e, dsel, defer_wait, host_gmax);
-}
-
-// (re)shape the bit-matrix workspace for a given sharding
-static int ensemble_shard(fc_ensemble *e, int64_t rank, int64_t world, int64_t row_block) {
-  FC_REQUIRE(e->epoch == 0 || e->epoch == ctx().epoch,
-             "this ensemble was created before fc_shutdown / a device switch: create it again");
-  FC_REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank/world %lld/%lld", (long long)rank,
-             (long long)world);
-  FC_REQUIRE(row_block >= 32 && row_block % 32 == 0 && row_block <= 4096,
-             "row_block must be a multiple of 32 in [32, 4096]");
-  e->rank = rank;
-  e->world = world;
-  e->row_block = row_block;
-  const int64_t n_gblocks = ceil_div(e->N, row_block);
-  const int64_t n_lblocks = local_block_count(n_gblocks, rank, world);
-  e->rows_local = n_lblocks * row_block;
-  if ((uint64_t)e->rows_local * (uint64_t)e->W >= (1ull << 32))
-    return set_error(FC_E_LIMIT, "bit matrix of %lld x %lld words exceeds the 32-bit word index",
-                     (long long)e->rows_local, (long long)e->W);
-  FC_TRY(e->bits.reserve(std::max<size_t>((size_t)e->rows_local * e->W * sizeof(uint64_t), 8)));
-  FC_TRY(e->cand.reserve(std::max<size_t>((size_t)e->rows_local * e->W * sizeof(uint32_t), 8)));
-  // candidate-pair queue: 256 entries per conformer, 1M..64M entries
-  e->pairq_cap = std::min<int64_t>(std::max<int64_t>(256 * e->N, 1 << 20), 1 << 26);
-  if (const char *v = getenv("FC_PAIRQ_CAP")) {  // test knob: force the word-queue fallback
-    const long long c = std::strtoll(v, nullptr, 10);
-    if (c >= 1 && c <= (1ll << 26)) e->pairq_cap = c;
-  }
-  FC_TRY(e->pairq.reserve((size_t)e->pairq_cap * sizeof(uint64_t)));
-  FC_TRY(e->simq.reserve((size_t)e->pairq_cap * sizeof(uint64_t)));
-  {  // buckets of the long-queue refine: (row buckets of 1 024) x (column tiles of 64), numbered supertile by supertile
-     // (8 column tiles of one row bucket; fc_kabsch.hip); sized here, before any pipeline forks
-    const int64_t n_rb = ceil_div(e->N, (int64_t)kBucketRows), n_sc = ceil_div(e->Npad >> kBucketColShift, (int64_t)8);
-    const int64_t n_st = n_rb * n_sc, nb = n_st * 8;
-    e->bk_buckets = nb <= ((int64_t)1 << 22) ? nb : 0;  // one workgroup scans the counts; work items are bucket | piece << 24
-    if (e->bk_buckets > 0) {
-      FC_TRY(e->bk.reserve((size_t)(512 + 2 * nb + 1) * sizeof(int)));
-      FC_TRY(e->bk_off.reserve((size_t)((nb + 1) + (n_st + 1) + 8 * ((n_st + 7) / 8 + 1)) * sizeof(int)));  // offsets | supertile starts | per-XCD prefixes
-      FC_TRY(e->bk_list.reserve((size_t)(nb + e->pairq_cap / 256 + 1) * sizeof(int)));  // pieces of <= 512 pairs (256 in tuning builds)
-      FC_TRY(e->sortq.reserve((size_t)e->pairq_cap * sizeof(uint64_t)));
-    }
-  }
-  FC_TRY(e->maskA.reserve((size_t)e->Npad));
-  FC_TRY(e->maskB.reserve((size_t)e->Npad));
-  FC_TRY(e->mbits.reserve((size_t)e->W * sizeof(uint64_t)));
-  e->bits_valid = false;
-  return FC_OK;
-}
-
-
 // rows of the bit matrix per workgroup (tuning knob FC_ROW_BLOCK, multiple of 128)
-static int64_t default_row_block() {
+int64_t default_row_block() {
   const char *v = getenv("FC_ROW_BLOCK");
   if (v) {
     const long r = std::strtol(v, nullptr, 10);
@@ -217,8 +31,8 @@ static int64_t default_row_block() {
 }
 
 // similarity bits of this rank's rows: screen + exact refine; counters[1..3]
-static int simbits_local(fc_ensemble *e, double max_rmsd, double max_dev, const double *energies,
-                         double max_dE, bool zero_counters, bool lean = false) {
+int simbits_local(fc_ensemble *e, double max_rmsd, double max_dev, const double *energies,
+                  double max_dE, bool zero_counters, bool lean) {
   e->lean = lean;
   const double *en_dev = nullptr;
   if (energies != nullptr) {
@@ -430,7 +244,7 @@ static int ladder_single(fc_ensemble *e, int64_t min_per_group, const LadderJob 
 // result of a deferred pair ladder (after the caller's synchronisation); false: the kernel
 // declined (queue overflow / list too long) and the prune has to be redone synchronously
 // what a finished prune says about the length of this ensemble's candidate queue -> every workspace over its coordinates
-static void note_candidates(fc_ensemble *e, unsigned long long refined, unsigned long long similar) {
+void note_candidates(fc_ensemble *e, unsigned long long refined, unsigned long long similar) {
   // (every workspace of the chain, whichever lane the prune ran on: the choice of the refine's and the ladder's form must not
   // depend on which lane finished last)
   int guard = 0;
@@ -451,40 +265,11 @@ static bool ladder_collect(fc_ensemble *e, int64_t slot, uint8_t *mask_out, int6
   return true;
 }
 
-// second prune workspace over the coordinates of `ens` (created once, destroyed with it)
-static int ensemble_twin(fc_ensemble *ens, fc_ensemble **out) {
-  if (!ens->twin) {
-    std::unique_ptr<fc_ensemble> t(new (std::nothrow) fc_ensemble);
-    if (!t) return set_error(FC_E_NOMEM, "host allocation failed");
-    t->epoch = ens->epoch;
-    t->N = ens->N, t->A = ens->A, t->Npad = ens->Npad, t->W = ens->W;
-    t->Xs.alias(ens->Xs), t->Xa.alias(ens->Xa), t->G.alias(ens->G);
-    if (ens->xsf_valid) t->Xsf.alias(ens->Xsf), t->sub.alias(ens->sub), t->xsf_valid = true;
-    if (ens->xt_valid) t->Xt.alias(ens->Xt), t->xt_valid = true;
-    if (ens->xh_valid) t->Xh.alias(ens->Xh), t->xh_valid = true, t->xh_scale = ens->xh_scale;
-    t->g_max = ens->g_max;
-    t->head = ens->head ? ens->head : ens;
-    t->last_candidates = ens->last_candidates, t->last_similar = ens->last_similar;
-    FC_TRY(t->counters.reserve(kCounters * sizeof(uint64_t)));
-    ens->twin = t.release();
-  }
-  *out = ens->twin;
-  return FC_OK;
-}
-
-// pairs (i, j > i) whose row i lies in a row block dealt to `rank`
-static int64_t owned_pairs(int64_t N, int64_t row_block, int64_t rank, int64_t world) {
-  int64_t n = 0;
-  const int64_t nb = ceil_div(N, row_block);
-  for (int64_t lb = 0, b; (b = global_block(lb, rank, world)) < nb; ++lb)
-    for (int64_t i = b * row_block; i < std::min(N, (b + 1) * row_block); ++i) n += N - 1 - i;
-  return n;
-}
 static int64_t owned_pairs(const fc_ensemble *ens) { return owned_pairs(ens->N, ens->row_block, ens->rank, ens->world); }
 
 // stats[0..5] of a prune: pairs looked at, candidates / similar / grey pairs from the counters, and two slots whose
 // meaning belongs to the entry point (include/fc_hip.h)
-static void fill_stats(int64_t *stats, int64_t pairs, const unsigned long long *cnt, int64_t s4, int64_t s5) {
+void fill_stats(int64_t *stats, int64_t pairs, const unsigned long long *cnt, int64_t s4, int64_t s5) {
   stats[0] = pairs, stats[1] = (int64_t)cnt[1], stats[2] = (int64_t)cnt[2], stats[3] = (int64_t)cnt[3];
   stats[4] = s4, stats[5] = s5;
 }
@@ -547,33 +332,36 @@ static int64_t bench_event_stride() {
   return stride_ev;
 }
 
-// at least n timing events in Context::ev_pool
-static int timing_events(int64_t n) {
-  std::vector<hipEvent_t> &ev = ctx().ev_pool;
-  while ((int64_t)ev.size() < n) {
-    hipEvent_t e = nullptr;
-    FC_HIP_TRY(hipEventCreate(&e));
-    ev.push_back(e);
+// bits, similar-pair queue and counters of the whole ensemble under similar_sym; `dperm` lives until the caller's wait
+int symm_local(fc_ensemble *e, const std::vector<uint16_t> &table, int64_t K, DevBuf &dperm, double max_rmsd, double max_dev,
+               const double *energies, double max_dE) {
+  FC_TRY(ensemble_shard(e, 0, 1, default_row_block()));
+  e->lean = false;
+  const double *en_dev = nullptr;
+  if (energies != nullptr) {
+    FC_TRY(upload(e->energies, energies, (size_t)e->N));
+    en_dev = e->energies.as<double>();
   }
+  FC_TRY(upload(dperm, table.data(), table.size()));
+  FC_HIP_TRY(hipMemsetAsync(e->counters.p, 0, kCounters * sizeof(uint64_t), ctx().stream));
+  FC_TRY(launch_symm_simbits(e, dperm.as<uint16_t>(), K, max_rmsd, max_dev, en_dev, max_dE));
+  e->bits_valid = true;
   return FC_OK;
 }
 
-// milliseconds between two recorded events (out may be null: nothing is asked)
-static int elapsed_ms(hipEvent_t a, hipEvent_t b, double *out) {
-  float ms = 0.f;
-  if (out) FC_HIP_TRY(hipEventElapsedTime(&ms, a, b));
-  if (out) *out = ms;
-  return FC_OK;
-}
-// mean over the event pairs (ev[per * r], ev[per * r + 1]) of the prunes r = 0, step, 2 step, ... < n
-static int mean_elapsed_ms(const std::vector<hipEvent_t> &ev, int64_t n, int64_t per, int64_t step, double *out) {
-  double sum = 0.0, ms = 0.0;
-  int64_t n_timed = 0;
-  for (int64_t r = 0; r < n; r += step, ++n_timed) {
-    FC_TRY(elapsed_ms(ev[per * r], ev[per * r + 1], &ms));
-    sum += ms;
-  }
-  *out = sum / (double)std::max<int64_t>(n_timed, 1);
+static int prune_rmsd_perm_run(fc_ensemble *ens, const std::vector<uint16_t> &table, int64_t K, DevBuf &dperm,
+                               double max_rmsd, double max_dev, const double *energies, double max_dE,
+                               int64_t min_per_group, uint8_t *mask_out, int64_t *stats) {
+  FC_TRY(symm_local(ens, table, K, dperm, max_rmsd, max_dev, energies, max_dE));
+  // the pair ladder over the queue; it declines a queue that overflowed or is too long for it, and the bit-matrix levels
+  // take over from the matrix the same launch wrote
+  unsigned long long cnt[8];
+  int64_t levels = 0, survivors = 0;
+  LadderJob job;
+  job.pairs_dev = ens->simq.as<uint64_t>(), job.bits_dev = ens->bits.as<uint64_t>(), job.counters_zeroed = true;
+  job.mask_out = mask_out, job.levels = &levels, job.survivors = &survivors, job.counters_out = cnt;
+  FC_TRY(ladder_single(ens, min_per_group, job));
+  if (stats) fill_stats(stats, ens->N * (ens->N - 1) / 2, cnt, levels, survivors);
   return FC_OK;
 }
 
@@ -582,467 +370,6 @@ static int mean_elapsed_ms(const std::vector<hipEvent_t> &ev, int64_t n, int64_t
 using namespace fc;
 
 extern "C" {
-
-// ---- ensemble ------------------------------------------------------------------
-int fc_ensemble_create(const double *coords, int64_t N, int64_t A, const uint8_t *atom_mask,
-                       int center, fc_ensemble **out) {
-  FC_API_LOCK;
-  FC_REQUIRE(out != nullptr, "out is NULL");
-  *out = nullptr;
-  FC_REQUIRE(coords != nullptr || N == 0, "coords is NULL");
-  FC_REQUIRE(N >= 0 && A >= 1, "bad shape N=%lld A=%lld", (long long)N, (long long)A);
-  FC_REQUIRE(A <= 32767, "A=%lld exceeds 32767 atoms", (long long)A);
-  FC_TRY(ensure_init());
-  std::unique_ptr<fc_ensemble> e(new (std::nothrow) fc_ensemble);
-  if (!e) return set_error(FC_E_NOMEM, "host allocation failed");
-  e->epoch = ctx().epoch;
-  FC_TRY(ensemble_build(coords, N, A, atom_mask, center, e.get()));
-  *out = e.release();
-  return FC_OK;
-}
-
-int fc_ensemble_destroy(fc_ensemble *ens) {
-  FC_API_LOCK;
-  delete ens;
-  return FC_OK;
-}
-
-int fc_ensemble_shape(const fc_ensemble *ens, int64_t *N, int64_t *A_selected) {
-  FC_API_LOCK;
-  FC_REQUIRE(ens != nullptr, "ens is NULL");
-  if (N) *N = ens->N;
-  if (A_selected) *A_selected = ens->A;
-  return FC_OK;
-}
-
-// ---- a4 ------------------------------------------------------------------------
-static int ensemble_rmsd_pairs(fc_ensemble *ens, const int64_t *pair_i, const int64_t *pair_j, int64_t P, double *rmsd_out,
-                               double *maxdev_out, bool inverted) {
-  FC_API_LOCK;
-  FC_REQUIRE(ens != nullptr, "ens is NULL");
-  FC_REQUIRE(ens->epoch == ctx().epoch, "this ensemble was created before fc_shutdown / a device switch: create it again");
-  FC_REQUIRE(P >= 0, "P < 0");
-  if (P == 0) return FC_OK;
-  FC_REQUIRE(pair_i && pair_j && rmsd_out && maxdev_out, "NULL pointer argument");
-  for (int64_t k = 0; k < P; ++k)
-    FC_REQUIRE(pair_i[k] >= 0 && pair_i[k] < ens->N && pair_j[k] >= 0 && pair_j[k] < ens->N,
-               "pair %lld = (%lld, %lld) out of range [0, %lld)", (long long)k,
-               (long long)pair_i[k], (long long)pair_j[k], (long long)ens->N);
-  FC_TRY(ensure_init());
-  DevBuf di, dj, dr, dm;
-  FC_TRY(upload(di, pair_i, (size_t)P));
-  FC_TRY(upload(dj, pair_j, (size_t)P));
-  FC_TRY(dr.reserve((size_t)P * sizeof(double)));
-  FC_TRY(dm.reserve((size_t)P * sizeof(double)));
-  FC_TRY(launch_pairs_exact(ens, di.as<int64_t>(), dj.as<int64_t>(), P, dr.as<double>(),
-                            dm.as<double>(), nullptr, inverted));
-  FC_TRY(d2h(rmsd_out, dr.p, (size_t)P * sizeof(double)));
-  FC_TRY(d2h(maxdev_out, dm.p, (size_t)P * sizeof(double)));
-  return sync();
-}
-int fc_ensemble_rmsd_pairs(fc_ensemble *ens, const int64_t *pair_i, const int64_t *pair_j,
-                           int64_t P, double *rmsd_out, double *maxdev_out) {
-  return ensemble_rmsd_pairs(ens, pair_i, pair_j, P, rmsd_out, maxdev_out, false);
-}
-// the values of (X_i, -X_j): the partner inverted through the origin (include/fc_hip.h, "enantiomer-aware forms")
-int fc_ensemble_rmsd_pairs_inv(fc_ensemble *ens, const int64_t *pair_i, const int64_t *pair_j, int64_t P, double *rmsd_out,
-                               double *maxdev_out) {
-  return ensemble_rmsd_pairs(ens, pair_i, pair_j, P, rmsd_out, maxdev_out, true);
-}
-
-static int kabsch_rmsd_pairs(const double *coords, int64_t N, int64_t A, const uint8_t *atom_mask, const int64_t *pair_i,
-                             const int64_t *pair_j, int64_t P, int center, double *rmsd_out, double *maxdev_out,
-                             bool inverted) {
-  FC_API_LOCK;
-  fc_ensemble *e = nullptr;
-  FC_TRY(fc_ensemble_create(coords, N, A, atom_mask, center, &e));
-  const int rc = ensemble_rmsd_pairs(e, pair_i, pair_j, P, rmsd_out, maxdev_out, inverted);
-  fc_ensemble_destroy(e);
-  return rc;
-}
-int fc_kabsch_rmsd_pairs(const double *coords, int64_t N, int64_t A, const uint8_t *atom_mask,
-                         const int64_t *pair_i, const int64_t *pair_j, int64_t P, int center,
-                         double *rmsd_out, double *maxdev_out) {
-  return kabsch_rmsd_pairs(coords, N, A, atom_mask, pair_i, pair_j, P, center, rmsd_out, maxdev_out, false);
-}
-int fc_kabsch_rmsd_pairs_inv(const double *coords, int64_t N, int64_t A, const uint8_t *atom_mask, const int64_t *pair_i,
-                             const int64_t *pair_j, int64_t P, int center, double *rmsd_out, double *maxdev_out) {
-  return kabsch_rmsd_pairs(coords, N, A, atom_mask, pair_i, pair_j, P, center, rmsd_out, maxdev_out, true);
-}
-
-// all pairs, both outputs: covariance tiles on the fp64 matrix pipe, rotation + explicit rotated
-// difference in the epilogue (k_simbits_screen_mfma<.., 2>); structures beyond the LDS column tile
-// (A > 104) take the one-wave-per-row kernel.  Outputs may both be NULL (timing only).
-static bool rmsd_and_max_tiled(const fc_ensemble *ens) {
-  // (a 64-column tile up to 104 atoms, 32 columns up to 208, 16 up to 416: launch_rmsd_values picks)
-  const size_t lds_m = ((size_t)(((ens->A + 3) / 4 + 1) / 2) * 384 + 16 + 128) * sizeof(double) + 1024;
-  return lds_m <= kLdsLimit && (uint64_t)((ens->A + 3) / 4 * 4) * 3 * (uint64_t)ens->Npad < (1ull << 32);
-}
-
-static int rmsd_and_max_all(fc_ensemble *ens, double *rmsd_out, double *maxdev_out, double *ms_kernel) {
-  FC_TRY(ensure_init());
-  const int64_t N = ens->N;
-  if (N == 0) return FC_OK;
-  Context &c = ctx();
-  DevBuf dr, dm;
-  const size_t bytes = (size_t)N * N * sizeof(double);
-  FC_TRY(dr.reserve(bytes));
-  FC_TRY(dm.reserve(bytes));
-  const bool tiled = rmsd_and_max_tiled(ens);
-  unsigned long long cnt[16] = {0};
-  if (tiled) {
-    // the tiled kernel writes every (i, j >= i), exact zeros on the diagonal; the lower triangle is
-    // mirrored on the device below: nothing to clear (2 x 800 MB of memset per call at 10^4 conformers)
-    FC_TRY(ensemble_shard(ens, 0, 1, 256));  // sizes the pair queue of the fix-up
-    FC_HIP_TRY(hipMemsetAsync(ens->counters.p, 0, 16 * sizeof(uint64_t), c.stream));
-  } else {
-    FC_HIP_TRY(hipMemsetAsync(dr.p, 0, bytes, c.stream));
-    FC_HIP_TRY(hipMemsetAsync(dm.p, 0, bytes, c.stream));
-  }
-  FC_HIP_TRY(hipEventRecord(c.ev0, c.stream));
-  if (tiled) FC_TRY(launch_rmsd_values(ens, 0.0, dr.as<double>(), dm.as<double>()));
-  else FC_TRY(launch_matrix_exact(ens, dr.as<double>(), dm.as<double>()));
-  FC_HIP_TRY(hipEventRecord(c.ev1, c.stream));
-  if (tiled) FC_TRY(d2h(cnt, ens->counters.p, sizeof cnt));
-  FC_TRY(sync());
-  FC_TRY(elapsed_ms(c.ev0, c.ev1, ms_kernel));
-  if (tiled && cnt[6] > (unsigned long long)ens->pairq_cap) {
-    // more pairs for the fix-up than its queue holds.  Near-duplicates first (the eigenvalue form of the rmsd declines pairs
-    // closer than ~1e-3 A): the same kernel with the running sum
-    FC_HIP_TRY(hipMemsetAsync(ens->counters.p, 0, 16 * sizeof(uint64_t), c.stream));
-    FC_TRY(launch_rmsd_values(ens, 0.0, dr.as<double>(), dm.as<double>(), 0, 1, /*explicit_sum=*/true));
-    FC_TRY(d2h(cnt, ens->counters.p, sizeof cnt));
-    FC_TRY(sync());
-  }
-  if (tiled && cnt[6] > (unsigned long long)ens->pairq_cap) {
-    // more degenerate pairs than the fix-up queue holds (planar or collinear structures: every pair): the plain kernel
-    // redoes the matrix
-    FC_HIP_TRY(hipMemsetAsync(dr.p, 0, bytes, c.stream));
-    FC_HIP_TRY(hipMemsetAsync(dm.p, 0, bytes, c.stream));
-    FC_TRY(launch_matrix_exact(ens, dr.as<double>(), dm.as<double>()));
-  }
-  // both kernels write the upper triangle and the diagonal: the lower one is mirrored on the device, then the matrices
-  // travel (the host's element loop took ~0.1 s per call at 10^4 conformers)
-  if (rmsd_out) FC_TRY(launch_mirror_upper(dr.as<double>(), N));
-  if (maxdev_out) FC_TRY(launch_mirror_upper(dm.as<double>(), N));
-  if (rmsd_out) FC_TRY(d2h(rmsd_out, dr.p, bytes));
-  if (maxdev_out) FC_TRY(d2h(maxdev_out, dm.p, bytes));
-  return sync();
-}
-
-// bench hook: `reps` complete all-pairs alignment passes over the resident ensemble, enqueued back to
-// back on the library's stream (outputs: two dense (N, N) matrices that stay in HBM), one host wait.
-// ms_kernel_mean: HIP events around the dominant kernel (k_simbits_screen_mfma<., 2>) of every launch;
-// ms_total: first launch to the end of the last fix-up kernel.  stats[0] = pairs per pass,
-// stats[1] = pairs the last pass queued for the Jacobi fix-up, stats[2] = 1 when the tiled kernel ran.
-// sample_*: P elements (i, j) of the LAST pass's two output matrices, read back for the caller's checker
-static int bench_rmsd_and_max_all(fc_ensemble *ens, int64_t reps, double *ms_kernel_mean, double *ms_total,
-                                  int64_t *stats, const int64_t *sample_i = nullptr, const int64_t *sample_j = nullptr,
-                                  int64_t P = 0, double *sample_rmsd = nullptr, double *sample_maxdev = nullptr) {
-  FC_TRY(ensure_init());
-  const int64_t N = ens->N;
-  FC_REQUIRE(N >= 2, "needs at least two conformers");
-  Context &c = ctx();
-  DevBuf dr, dm;
-  const size_t bytes = (size_t)N * N * sizeof(double);
-  FC_TRY(dr.reserve(bytes));
-  FC_TRY(dm.reserve(bytes));
-  const bool tiled = rmsd_and_max_tiled(ens);
-  // under a communicator (or the loopback hook) a rank computes the rows dealt to it: the units shard with
-  // no exchange; every rank keeps its rows of the two matrices
-  const int64_t rank = comm_rank(), world = comm_world();
-  FC_REQUIRE(tiled || world == 1, "structures beyond the tiled kernel are not sharded");
-  if (tiled) FC_TRY(ensemble_shard(ens, 0, 1, 256));
-  FC_TRY(timing_events(2 * reps + 2));
-  std::vector<hipEvent_t> &ev = c.ev_pool;
-  FC_HIP_TRY(hipEventRecord(ev[2 * reps], c.stream));
-  for (int64_t r = 0; r < reps; ++r) {
-    if (tiled) {
-      FC_HIP_TRY(hipMemsetAsync(ens->counters.p, 0, 16 * sizeof(uint64_t), c.stream));
-      FC_HIP_TRY(hipEventRecord(ev[2 * r], c.stream));
-      c.mark_after_screen = ev[2 * r + 1];  // recorded right behind the tiled kernel, in front of the fix-up
-      const int rc = launch_rmsd_values(ens, 0.0, dr.as<double>(), dm.as<double>(), rank, world);
-      c.mark_after_screen = nullptr;
-      FC_TRY(rc);
-    } else {
-      FC_HIP_TRY(hipEventRecord(ev[2 * r], c.stream));
-      FC_TRY(launch_matrix_exact(ens, dr.as<double>(), dm.as<double>()));
-      FC_HIP_TRY(hipEventRecord(ev[2 * r + 1], c.stream));
-    }
-  }
-  FC_HIP_TRY(hipEventRecord(ev[2 * reps + 1], c.stream));
-  unsigned long long cnt[16] = {0};
-  if (tiled) FC_TRY(d2h(cnt, ens->counters.p, sizeof cnt));
-  FC_TRY(sync());
-  double mean = 0.0;
-  FC_TRY(mean_elapsed_ms(ev, reps, 2, 1, &mean));
-  if (ms_kernel_mean) *ms_kernel_mean = mean;
-  FC_TRY(elapsed_ms(ev[2 * reps], ev[2 * reps + 1], ms_total));
-  if (stats) {
-    stats[0] = owned_pairs(N, 128, rank, world);  // pairs this rank computed: rows of its blocks of 128, columns right of the diagonal
-    stats[1] = (int64_t)cnt[6];
-    stats[2] = tiled ? 1 : 0;
-  }
-  if (tiled && cnt[6] > (unsigned long long)ens->pairq_cap)
-    return set_error(FC_E_LIMIT, "%llu degenerate pairs exceed the fix-up queue (%lld)", cnt[6], (long long)ens->pairq_cap);
-  if (P > 0) {  // behind the timed passes and their events: what the last pass left in the two matrices
-    DevBuf di, dj, sr, sm;
-    FC_TRY(upload(di, sample_i, (size_t)P));
-    FC_TRY(upload(dj, sample_j, (size_t)P));
-    FC_TRY(sr.reserve((size_t)P * sizeof(double)));
-    FC_TRY(sm.reserve((size_t)P * sizeof(double)));
-    FC_TRY(launch_gather_matrix_pairs(dr.as<double>(), dm.as<double>(), N, di.as<int64_t>(), dj.as<int64_t>(), P,
-                                      sr.as<double>(), sm.as<double>()));
-    FC_TRY(d2h(sample_rmsd, sr.p, (size_t)P * sizeof(double)));
-    FC_TRY(d2h(sample_maxdev, sm.p, (size_t)P * sizeof(double)));
-    FC_TRY(sync());
-  }
-  return FC_OK;
-}
-
-// ---- RMSD-diverse selection (greedy max-min; the contract: include/fc_hip.h, fc_diverse.hip) ----------------------
-// prepare_sym (may be empty): the symmetry-aware form -- called behind the checks and ensure_init to put the table on the
-// device and fill the DiverseSym the steps then take
-static int select_diverse_checked(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
-                                  double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected,
-                                  double *ms_device, const std::function<int(DiverseSym &)> &prepare_sym = nullptr) {
-  FC_REQUIRE(ens != nullptr, "ens is NULL");
-  FC_REQUIRE(indices_out != nullptr && n_selected != nullptr, "indices_out / n_selected is NULL");
-  FC_REQUIRE(n_max >= 1, "n_max=%lld < 1", (long long)n_max);
-  FC_REQUIRE(!(stop_rmsd != stop_rmsd), "stop_rmsd is NaN");
-  FC_REQUIRE(ens->epoch == ctx().epoch, "this ensemble was created before fc_shutdown / a device switch: create it again");
-  *n_selected = 0;
-  if (ens->N == 0) return FC_OK;
-  FC_REQUIRE(start >= 0 && start < ens->N, "start=%lld outside [0, %lld)", (long long)start, (long long)ens->N);
-  FC_REQUIRE(ens->N <= (int64_t)INT32_MAX - 256, "N=%lld: the selection indexes conformers with 32 bits", (long long)ens->N);
-  FC_TRY(ensure_init());
-  DiverseSym sym;
-  if (prepare_sym) FC_TRY(prepare_sym(sym));
-  return select_diverse(ens, n_max, start, stop_rmsd, indices_out, radii_out, labels_out, dist_out, n_selected, ms_device,
-                        prepare_sym ? &sym : nullptr);
-}
-
-int fc_ensemble_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
-                               double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected) {
-  FC_API_LOCK;
-  return select_diverse_checked(ens, n_max, start, stop_rmsd, indices_out, radii_out, labels_out, dist_out, n_selected,
-                                nullptr);
-}
-
-int fc_bench_select_diverse(fc_ensemble *ens, int64_t n_max, int64_t start, double stop_rmsd, int64_t reps,
-                            double *ms_device_mean, double *ms_host_mean, int64_t *indices_out, int64_t *n_selected,
-                            int64_t *lanes_out) {
-  FC_API_LOCK;
-  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
-  double dev = 0.0, host = 0.0;
-  for (int64_t r = 0; r < reps; ++r) {
-    double ms = 0.0;
-    const auto t0 = std::chrono::steady_clock::now();
-    FC_TRY(select_diverse_checked(ens, n_max, start, stop_rmsd, indices_out, nullptr, nullptr, nullptr, n_selected, &ms));
-    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    dev += ms;
-  }
-  *ms_device_mean = dev / (double)reps;
-  *ms_host_mean = host / (double)reps;
-  if (lanes_out) *lanes_out = diverse_lanes(ens->N);
-  return FC_OK;
-}
-
-// ---- k nearest neighbours under the RMSD (the contract: include/fc_hip.h; the kernels: fc_knn.hip) ------------------
-// a checked table for the forms under d_sym (fc_ensemble_knn_perm, fc_ensemble_knn_cross_perm, further down)
-struct KnnPerm {
-  std::vector<uint16_t> table;  // (K, A_sel), as perm_table_check leaves it
-  int K = 1;
-  bool mirror = false;
-  int64_t *stats = nullptr;  // (may be NULL) the two counters of KnnSym::stats_dev after the call
-};
-
-// knn() behind the checks and ensure_init; perm (may be NULL): under d_sym -- the table goes up first and lives, like the
-// counters, until knn()'s last wait
-static int knn_run(fc_ensemble *q, fc_ensemble *r, bool cross, int64_t k, double max_rmsd, int32_t *indices_out,
-                   double *dist_out, double *ms_device, int64_t *strips_out, const KnnPerm *perm) {
-  if (!perm) return knn(q, r, cross, k, max_rmsd, indices_out, dist_out, ms_device, strips_out);
-  DevBuf dperm, dstats;
-  const auto run = [&]() -> int {
-    KnnSym sym;
-    FC_TRY(upload(dperm, perm->table.data(), perm->table.size()));
-    sym.perms_dev = dperm.as<uint16_t>(), sym.K = perm->K, sym.mirror = perm->mirror;
-    if (perm->stats) {
-      FC_TRY(dstats.reserve(2 * sizeof(unsigned long long)));
-      FC_HIP_TRY(hipMemsetAsync(dstats.p, 0, 2 * sizeof(unsigned long long), ctx().stream));
-      sym.stats_dev = reinterpret_cast<unsigned long long *>(dstats.p);
-    }
-    FC_TRY(knn(q, r, cross, k, max_rmsd, indices_out, dist_out, ms_device, strips_out, &sym));
-    if (perm->stats) {
-      unsigned long long cnt[2] = {0, 0};
-      FC_TRY(d2h(cnt, dstats.p, sizeof cnt));
-      FC_TRY(sync());
-      perm->stats[0] = (int64_t)cnt[0], perm->stats[1] = (int64_t)cnt[1];
-    }
-    return FC_OK;
-  };
-  const int rc = run();
-  if (rc != FC_OK && ctx().ready) (void)hipStreamSynchronize(cur_stream());  // nothing of the buffers may be in flight when they go
-  return rc;
-}
-
-static int knn_checked(fc_ensemble *ens, int64_t k, int32_t *indices_out, double *dist_out, double *ms_device,
-                       int64_t *strips_out, const KnnPerm *perm = nullptr) {
-  FC_REQUIRE(ens != nullptr, "ens is NULL");
-  FC_REQUIRE(indices_out != nullptr && dist_out != nullptr, "indices_out / dist_out is NULL");
-  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
-  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
-  FC_REQUIRE(ens->epoch == ctx().epoch, "this ensemble was created before fc_shutdown / a device switch: create it again");
-  if (strips_out) *strips_out = 0;
-  if (ms_device) *ms_device = 0.0;
-  if (ens->N == 0) return FC_OK;
-  FC_REQUIRE(ens->N <= (int64_t)INT32_MAX - 256, "N=%lld: the lists index conformers with 32 bits", (long long)ens->N);
-  FC_TRY(ensure_init());
-  return knn_run(ens, ens, false, k, INFINITY, indices_out, dist_out, ms_device, strips_out, perm);
-}
-
-int fc_ensemble_knn(fc_ensemble *ens, int64_t k, int32_t *indices_out, double *dist_out) {
-  FC_API_LOCK;
-  return knn_checked(ens, k, indices_out, dist_out, nullptr, nullptr);
-}
-
-int fc_bench_knn(fc_ensemble *ens, int64_t k, int64_t reps, double *ms_device_mean, double *ms_host_mean,
-                 int64_t *strips_out) {
-  FC_API_LOCK;
-  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
-  FC_REQUIRE(ens != nullptr, "ens is NULL");
-  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
-  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
-  std::vector<int32_t> idx((size_t)ens->N * (size_t)k + 1);
-  std::vector<double> dist((size_t)ens->N * (size_t)k + 1);
-  double dev = 0.0, host = 0.0;
-  for (int64_t r = 0; r < reps; ++r) {
-    double ms = 0.0;
-    const auto t0 = std::chrono::steady_clock::now();
-    FC_TRY(knn_checked(ens, k, idx.data(), dist.data(), &ms, strips_out));
-    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    dev += ms;
-  }
-  *ms_device_mean = dev / (double)reps;
-  *ms_host_mean = host / (double)reps;
-  return FC_OK;
-}
-
-// the rows of `queries` against the columns of `refs` (the contract: include/fc_hip.h, fc_ensemble_knn_cross); the
-// scalar arguments are judged first, so that their refusals do not depend on the handles
-static int knn_cross_checked(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int32_t *indices_out,
-                             double *dist_out, double *ms_device, int64_t *strips_out, const KnnPerm *perm = nullptr) {
-  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
-  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
-  FC_REQUIRE(max_rmsd > 0.0, "max_rmsd=%g must be positive (+inf: no cap)", max_rmsd);  // (a NaN fails it)
-  FC_REQUIRE(queries != nullptr && refs != nullptr, "queries / refs is NULL");
-  FC_REQUIRE(indices_out != nullptr && dist_out != nullptr, "indices_out / dist_out is NULL");
-  FC_REQUIRE(queries->epoch == ctx().epoch && refs->epoch == ctx().epoch,
-             "an ensemble was created before fc_shutdown / a device switch: create it again");
-  FC_REQUIRE(queries->A == refs->A, "queries select %lld atoms, refs %lld: one atom selection for both", (long long)queries->A,
-             (long long)refs->A);
-  if (refs->N > (int64_t)INT32_MAX - 256 || queries->N > (int64_t)INT32_MAX - 256)
-    return set_error(FC_E_LIMIT, "Nq=%lld, Nr=%lld: the lists index conformers with 32 bits", (long long)queries->N,
-                     (long long)refs->N);
-  if (strips_out) *strips_out = 0;
-  if (ms_device) *ms_device = 0.0;
-  if (queries->N == 0) return FC_OK;
-  if (refs->N == 0) {  // no reference: every slot is empty, and no device is needed to say so
-    std::fill(indices_out, indices_out + queries->N * k, (int32_t)-1);
-    std::fill(dist_out, dist_out + queries->N * k, (double)INFINITY);
-    return FC_OK;
-  }
-  FC_TRY(ensure_init());
-  return knn_run(queries, refs, true, k, max_rmsd, indices_out, dist_out, ms_device, strips_out, perm);
-}
-
-int fc_ensemble_knn_cross(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int32_t *indices_out,
-                          double *dist_out) {
-  FC_API_LOCK;
-  return knn_cross_checked(queries, refs, k, max_rmsd, indices_out, dist_out, nullptr, nullptr);
-}
-
-int fc_bench_knn_cross(fc_ensemble *queries, fc_ensemble *refs, int64_t k, double max_rmsd, int64_t reps,
-                       double *ms_device_mean, double *ms_host_mean, int64_t *strips_out) {
-  FC_API_LOCK;
-  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
-  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
-  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
-  FC_REQUIRE(queries != nullptr && refs != nullptr, "queries / refs is NULL");
-  std::vector<int32_t> idx((size_t)queries->N * (size_t)k + 1);
-  std::vector<double> dist((size_t)queries->N * (size_t)k + 1);
-  double dev = 0.0, host = 0.0;
-  for (int64_t r = 0; r < reps; ++r) {
-    double ms = 0.0;
-    const auto t0 = std::chrono::steady_clock::now();
-    FC_TRY(knn_cross_checked(queries, refs, k, max_rmsd, idx.data(), dist.data(), &ms, strips_out));
-    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    dev += ms;
-  }
-  *ms_device_mean = dev / (double)reps;
-  *ms_host_mean = host / (double)reps;
-  return FC_OK;
-}
-
-int fc_ensemble_rmsd_matrix(fc_ensemble *ens, double *rmsd_out, double *maxdev_out) {
-  FC_API_LOCK;
-  FC_REQUIRE(ens && rmsd_out && maxdev_out, "NULL pointer argument");
-  return rmsd_and_max_all(ens, rmsd_out, maxdev_out, nullptr);
-}
-
-int fc_ensemble_rmsd_and_max_all(fc_ensemble *ens, double *rmsd_out, double *maxdev_out, double *ms_kernel) {
-  FC_API_LOCK;
-  FC_REQUIRE(ens != nullptr, "ens is NULL");
-  return rmsd_and_max_all(ens, rmsd_out, maxdev_out, ms_kernel);
-}
-
-int fc_bench_rmsd_and_max_all(fc_ensemble *ens, int64_t reps, double *ms_kernel_mean, double *ms_total,
-                              int64_t *stats) {
-  FC_API_LOCK;
-  FC_REQUIRE(ens != nullptr && reps >= 1 && reps <= 4096, "bad arguments");
-  return bench_rmsd_and_max_all(ens, reps, ms_kernel_mean, ms_total, stats);
-}
-
-int fc_bench_rmsd_and_max_all_sampled(fc_ensemble *ens, int64_t reps, const int64_t *pair_i, const int64_t *pair_j,
-                                      int64_t P, double *rmsd_out, double *maxdev_out, double *ms_kernel_mean,
-                                      double *ms_total, int64_t *stats) {
-  FC_API_LOCK;
-  FC_REQUIRE(ens != nullptr && reps >= 1 && reps <= 4096, "bad arguments");
-  FC_REQUIRE(P >= 0 && (P == 0 || (pair_i && pair_j && rmsd_out && maxdev_out)), "NULL sample arrays");
-  for (int64_t p = 0; p < P; ++p)
-    FC_REQUIRE(pair_i[p] >= 0 && pair_i[p] < ens->N && pair_j[p] >= 0 && pair_j[p] < ens->N,
-               "sample pair %lld out of range", (long long)p);
-  return bench_rmsd_and_max_all(ens, reps, ms_kernel_mean, ms_total, stats, pair_i, pair_j, P, rmsd_out, maxdev_out);
-}
-
-int fc_ensemble_rmsd_values(fc_ensemble *ens, double *rmsd_out, double *ms_kernel) {
-  FC_API_LOCK;
-  FC_REQUIRE(ens != nullptr, "ens is NULL");
-  FC_TRY(ensure_init());
-  const int64_t N = ens->N;
-  if (N == 0) return FC_OK;
-  FC_TRY(ensemble_shard(ens, 0, 1, 256));  // sizes the pair queue
-  Context &c = ctx();
-  DevBuf dr;
-  const size_t bytes = (size_t)N * N * sizeof(double);
-  FC_TRY(dr.reserve(bytes));
-  FC_HIP_TRY(hipMemsetAsync(dr.p, 0, bytes, c.stream));
-  FC_HIP_TRY(hipMemsetAsync(ens->counters.p, 0, 16 * sizeof(uint64_t), c.stream));
-  FC_HIP_TRY(hipEventRecord(c.ev0, c.stream));
-  FC_TRY(launch_rmsd_values(ens, 0.02, dr.as<double>(), nullptr));
-  FC_HIP_TRY(hipEventRecord(c.ev1, c.stream));
-  unsigned long long cnt[16];
-  FC_TRY(d2h(cnt, ens->counters.p, sizeof cnt));
-  if (rmsd_out) {  // (the lower triangle mirrored on the device, then one copy)
-    FC_TRY(launch_mirror_upper(dr.as<double>(), N));
-    FC_TRY(d2h(rmsd_out, dr.p, bytes));
-  }
-  FC_TRY(sync());
-  if (cnt[6] > (unsigned long long)ens->pairq_cap)
-    return set_error(FC_E_LIMIT, "%llu pairs closer than 0.02 A or without a unique optimal rotation exceed the fix-up queue (%lld): "
-                     "use fc_ensemble_rmsd_matrix", cnt[6], (long long)ens->pairq_cap);
-  return elapsed_ms(c.ev0, c.ev1, ms_kernel);
-}
 
 // ---- a5 ------------------------------------------------------------------------
 int fc_rmsd_simbits(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies,
@@ -1100,19 +427,7 @@ int fc_prune_rmsd(fc_ensemble *ens, double max_rmsd, double max_dev, const doubl
   return FC_OK;
 }
 
-// ---- enantiomer-aware forms (include/fc_hip.h): the same entry points with fc_ensemble::enant set for the call ----
-// The flag selects the ENANT instantiations of the screen and refine kernels (launch_simbits_screen / _refine); it is
-// cleared when the call returns, whatever it returns, so no other entry point ever sees it.
-namespace {
-struct EnantScope {
-  fc_ensemble *e;
-  explicit EnantScope(fc_ensemble *ens) : e(ens) { e->enant = true; }
-  ~EnantScope() { e->enant = false; }
-  EnantScope(const EnantScope &) = delete;
-  EnantScope &operator=(const EnantScope &) = delete;
-};
-}  // namespace
-
+// ---- enantiomer-aware forms (include/fc_hip.h): the same entry points under an EnantScope ----------------------------
 int fc_rmsd_simbits_enant(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
                           int64_t row_begin, int64_t row_end, uint64_t *bits_out, int64_t *n_grey) {
   FC_API_LOCK;
@@ -1158,10 +473,7 @@ int fc_prune_rmsd_host(const double *coords, int64_t N, int64_t A, const uint8_t
   if (rc == FC_OK) rc = ensemble_shard(&e, 0, 1, default_row_block());
   if (rc == FC_OK) rc = prebuild_screen_items(&e);
   const int rc_fin = ensemble_build_finish(&e);  // (always: nothing of `e` may be in flight when it goes out of scope)
-  if (rc != FC_OK || rc_fin != FC_OK) {
-    (void)hipStreamSynchronize(cur_stream());
-    return rc != FC_OK ? rc : rc_fin;
-  }
+  if (rc != FC_OK || rc_fin != FC_OK) return drained(rc != FC_OK ? rc : rc_fin);
   return fc_prune_rmsd(&e, max_rmsd, max_dev, energies, max_dE, min_per_group, mask_out, stats);
 }
 
@@ -1210,329 +522,7 @@ int fc_debug_ladder_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N
   return ladder_single(&e, min_per_group, job);
 }
 
-// ---- similarity clusters and density-based clusters (the contract: include/fc_hip.h; the kernels: fc_clusters.hip) ----
-// Two axes, each said once: WHICH labelling runs on the graph (Labelling) and WHO makes the graph (a graph source, below).
-namespace {
-// the components of the graph, its density-based clusters with min_samples bound, or its sphere-exclusion clusters
-struct Labelling {
-  bool density;
-  int64_t min_samples;
-  const char *what;  // (in the error text)
-  bool butina = false;
-  ClKind kind() const { return density ? kClDensity : butina ? kClButina : kClComponents; }
-  ClusterLayout layout(const ClusterGraph &g, int64_t N) const {
-    return cluster_layout(N, kind(), butina ? butina_live_cap(g, N) : 0);
-  }
-  int launch(const ClusterGraph &g, int64_t N, DevBuf &work) const {
-    if (butina) return launch_butina(g, N, work);
-    return density ? launch_dbscan(g, N, min_samples, work) : launch_clusters(g, N, work);
-  }
-  int n_stats() const { return density || butina ? 8 : 6; }
-};
-Labelling components() { return {false, 1, "cluster labelling"}; }
-Labelling density_based(int64_t min_samples) { return {true, min_samples, "density-based clusters"}; }
-Labelling sphere_exclusion() { return {false, 1, "sphere-exclusion clusters", true}; }
-
-// the caller's arrays; core: the density-based form's; degrees: its and the sphere-exclusion form's
-struct LabelOut {
-  int32_t *labels;
-  int64_t *reps, *sizes;
-  uint8_t *core;
-  int32_t *degrees;
-  int64_t *n_clusters;
-  bool complete(const Labelling &lab) const {
-    return labels && reps && sizes && (!lab.density || core) && (!(lab.density || lab.butina) || degrees);
-  }
-};
-
-// what one labelling left in the pinned staging area: the result region of the workspace, then `extra` counter words
-struct ClusterResult {
-  const char *host = nullptr;
-  ClusterLayout L{};
-  const unsigned long long *status() const { return reinterpret_cast<const unsigned long long *>(host + L.status); }
-  const unsigned long long *extra() const { return reinterpret_cast<const unsigned long long *>(host + L.parent); }
-};
-
-// labels the graph and brings the result to the host: enqueue, ONE copy chain into pinned memory, one wait.
-// counters_dev (may be null): 16 counter words of the prune that travel behind the result.
-int label_run(const Labelling &lab, const ClusterGraph &g, int64_t N, DevBuf &work, const void *counters_dev,
-              ClusterResult *out) {
-  const ClusterLayout L = lab.layout(g, N);
-  FC_TRY(work.reserve(L.total));
-  FC_TRY(pinned_reserve(L.parent + 16 * sizeof(uint64_t)));
-  FC_TRY(lab.launch(g, N, work));
-  char *host = static_cast<char *>(ctx().pinned);
-  FC_TRY(d2h(host, work.p, L.result_bytes));
-  if (counters_dev) FC_TRY(d2h(host + L.parent, counters_dev, 16 * sizeof(uint64_t)));
-  FC_TRY(sync());
-  out->host = host, out->L = L;
-  if (out->status()[kClStatusErr] != 0ull)
-    return set_error(FC_E_INTERNAL, "%s: %s on the device", lab.what,
-                     lab.butina ? "the rounds ended with conformers undecided" : "a union exceeded its retry bound");
-  return FC_OK;
-}
-
-// -> the caller's arrays; tail (may be NULL): the density-based form's [0] core points, [1] noise points; the
-// sphere-exclusion form's [0] rounds, [1] conformers that went to the finish
-void label_unpack(const ClusterResult &r, int64_t N, const LabelOut &o, int64_t *tail) {
-  const int64_t K = (int64_t)r.status()[kClStatusK];
-  std::memcpy(o.labels, r.host + r.L.labels, (size_t)N * sizeof(int32_t));
-  std::memcpy(o.reps, r.host + r.L.reps, (size_t)K * sizeof(int64_t));
-  std::memcpy(o.sizes, r.host + r.L.sizes, (size_t)K * sizeof(int64_t));
-  if (r.L.core != 0) {  // (the density-based layout)
-    std::memcpy(o.core, r.host + r.L.core, (size_t)N * sizeof(uint8_t));
-    std::memcpy(o.degrees, r.host + r.L.degrees, (size_t)N * sizeof(int32_t));
-  } else if (r.L.degrees != 0) {  // (the sphere-exclusion layout)
-    std::memcpy(o.degrees, r.host + r.L.degrees, (size_t)N * sizeof(int32_t));
-  }
-  *o.n_clusters = K;
-  if (tail == nullptr) return;
-  if (r.L.core == 0) {
-    tail[0] = (int64_t)r.status()[kBuStatusRounds], tail[1] = (int64_t)r.status()[kBuStatusLeft];
-    return;
-  }
-  tail[0] = tail[1] = 0;
-  for (int64_t i = 0; i < N; ++i) tail[0] += o.core[i] != 0, tail[1] += o.labels[i] < 0;
-}
-
-// The protocol of every resident entry point: list, status, matrix.  A graph source `make(lean)` fills the ensemble's
-// pair queue and counters (lean) and, asked again with !lean, its bit matrix.  The labelling runs from the list first; the
-// hook / degree kernel itself declines a list that is incomplete (the candidate queue overflowed: counters[6] >
-// pairq_cap, read on the device), the host sees that in the status word that comes back with the results, and only then
-// asks for the matrix and labels again.  Source::screened: the graph is the prune's own (ScreenSource) -- the similar-pair
-// count last seen for these coordinates picks the hook's form as it picks the ladder's (-1: nothing seen yet), and this
-// call's counts are noted for the next one.  May return with work in flight (the caller drains on error).
-extern "C++" {  // (a template inside this file's extern "C")
-template <class Source>
-int label_resident(fc_ensemble *ens, const Source &make, const Labelling &lab, DevBuf &work, const LabelOut &o,
-                   int64_t *stats) {
-  const int64_t N = ens->N;
-  FC_TRY(make(/*lean=*/true));
-  auto *cnt = reinterpret_cast<unsigned long long *>(ens->counters.p);
-  ClusterGraph g;
-  g.pairs_dev = ens->simq.as<uint64_t>(), g.n_pairs_dev = cnt + 2;
-  g.n_cand_dev = cnt + 6, g.cand_cap = (unsigned long long)ens->pairq_cap, g.redo_dev = cnt + 12;
-  g.known_short = Source::screened && ens->last_similar >= 0 && ens->last_similar < kClShortList;
-  ClusterResult res;
-  FC_TRY(label_run(lab, g, N, work, cnt, &res));
-  int64_t from_bits = 0;
-  if (res.status()[kClStatusList] == 0ull) {
-    FC_TRY(make(/*lean=*/false));
-    ClusterGraph gb;
-    gb.bits_dev = ens->bits.as<uint64_t>(), gb.W = ens->W;
-    FC_TRY(label_run(lab, gb, N, work, cnt, &res));
-    from_bits = 1;
-  }
-  const unsigned long long *c = res.extra();
-  if (Source::screened) note_candidates(ens, c[6], c[2]);
-  label_unpack(res, N, o, stats && lab.n_stats() == 8 ? stats + 6 : nullptr);
-  if (stats) fill_stats(stats, N * (N - 1) / 2, c, from_bits, *o.n_clusters);
-  return FC_OK;
-}
-}  // extern "C++"
-
-// the plain graph, or the enantiomer-aware one under EnantScope: lean first, as fc_prune_rmsd -- only the pair lists; the
-// screen and the refine run again for the bit matrix
-struct ScreenSource {
-  static constexpr bool screened = true;
-  fc_ensemble *ens;
-  double max_rmsd, max_dev;
-  const double *energies;
-  double max_dE;
-  int operator()(bool lean) const {
-    if (lean) FC_TRY(ensemble_shard(ens, 0, 1, default_row_block()));
-    return simbits_local(ens, max_rmsd, max_dev, energies, max_dE, true, lean);
-  }
-};
-
-// fc_rmsd_clusters and fc_rmsd_dbscan behind the API lock
-int rmsd_label(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
-               const Labelling &lab, const LabelOut &o, int64_t *stats) {
-  FC_REQUIRE(ens && o.n_clusters, "NULL pointer argument");
-  FC_REQUIRE(max_rmsd > 0.0 && max_dev > 0.0, "thresholds must be positive");
-  if (lab.density) FC_REQUIRE(lab.min_samples >= 1, "min_samples=%lld must be >= 1", (long long)lab.min_samples);
-  *o.n_clusters = 0;
-  if (stats) std::memset(stats, 0, lab.n_stats() * sizeof(int64_t));
-  FC_TRY(ensure_init());
-  if (ens->N == 0) return FC_OK;
-  FC_REQUIRE(o.complete(lab), "NULL pointer argument");
-  FC_REQUIRE(ens->N <= (int64_t)INT32_MAX - 256, "N=%lld: clusters index conformers with 32 bits", (long long)ens->N);
-  DevBuf work;
-  const int rc = label_resident(ens, ScreenSource{ens, max_rmsd, max_dev, energies, max_dE}, lab, work, o, stats);
-  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());  // nothing of `work` may be in flight when it goes out of scope
-  return rc;
-}
-}  // namespace
-
-int fc_rmsd_clusters(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
-                     int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int64_t *n_clusters, int64_t *stats) {
-  FC_API_LOCK;
-  return rmsd_label(ens, max_rmsd, max_dev, energies, max_dE, components(),
-                    {labels_out, reps_out, sizes_out, nullptr, nullptr, n_clusters}, stats);
-}
-
-int fc_rmsd_clusters_enant(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
-                           int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int64_t *n_clusters,
-                           int64_t *stats) {
-  FC_API_LOCK;
-  FC_REQUIRE(ens && n_clusters, "NULL pointer argument");
-  EnantScope scope(ens);
-  return fc_rmsd_clusters(ens, max_rmsd, max_dev, energies, max_dE, labels_out, reps_out, sizes_out, n_clusters, stats);
-}
-
 // ---- symmetry-aware forms (include/fc_hip.h; the kernels: fc_symm.hip) -----------------------------------------------
-namespace {
-// every check the contract lists for the table, on the host; -> the table as the kernels take it (16-bit indices)
-int perm_table_check(const int32_t *perms, int64_t K, int64_t A_sel, std::vector<uint16_t> &table) {
-  FC_REQUIRE(perms != nullptr, "perms is NULL");
-  FC_REQUIRE(K >= 1, "K=%lld: the table holds at least the identity", (long long)K);
-  if (K > kPermMax)
-    return set_error(FC_E_LIMIT, "K=%lld permutations exceed FC_PERM_MAX=%lld", (long long)K, (long long)kPermMax);
-  FC_REQUIRE(A_sel >= 1 && A_sel <= 32767, "A_sel=%lld outside [1, 32767]", (long long)A_sel);
-  const size_t A = (size_t)A_sel;
-  std::vector<uint8_t> seen(A);
-  for (int64_t k = 0; k < K; ++k) {
-    std::fill(seen.begin(), seen.end(), (uint8_t)0);
-    for (size_t a = 0; a < A; ++a) {
-      const int32_t v = perms[(size_t)k * A + a];
-      FC_REQUIRE(v >= 0 && v < A_sel && !seen[(size_t)v], "row %lld of perms is not a permutation of 0..%lld", (long long)k,
-                 (long long)A_sel - 1);
-      seen[(size_t)v] = 1;
-    }
-  }
-  for (size_t a = 0; a < A; ++a) FC_REQUIRE(perms[a] == (int32_t)a, "row 0 of perms is not the identity");
-  std::vector<int32_t> inv(A);
-  for (int64_t k = 0; k < K; ++k) {
-    const int32_t *row = perms + (size_t)k * A;
-    for (size_t a = 0; a < A; ++a) inv[(size_t)row[a]] = (int32_t)a;
-    bool found = false;
-    for (int64_t l = 0; l < K && !found; ++l) found = std::equal(inv.begin(), inv.end(), perms + (size_t)l * A);
-    FC_REQUIRE(found, "perms is not closed under inverse: the inverse of row %lld is not in the table", (long long)k);
-  }
-  table.resize((size_t)K * A);
-  for (size_t t = 0; t < table.size(); ++t) table[t] = (uint16_t)perms[t];
-  return FC_OK;
-}
-
-// what the table and the ensemble have to satisfy together, still before any device use
-int perm_ensemble_check(const fc_ensemble *ens, int64_t K, int64_t A_sel, bool bit_matrix) {
-  FC_REQUIRE(ens != nullptr, "ens is NULL");
-  FC_REQUIRE(ens->epoch == ctx().epoch, "this ensemble was created before fc_shutdown / a device switch: create it again");
-  FC_REQUIRE(A_sel == ens->A, "A_sel=%lld, the ensemble has %lld selected atoms", (long long)A_sel, (long long)ens->A);
-  if (!bit_matrix) return FC_OK;
-  const size_t lds = symm_lds_bytes(A_sel, K);
-  if (lds > kLdsLimit)
-    return set_error(FC_E_LIMIT, "A_sel=%lld selected atoms with K=%lld permutations need %zu bytes of LDS per tile (limit %zu)",
-                     (long long)A_sel, (long long)K, lds, kLdsLimit);
-  const int64_t rb = default_row_block();
-  if ((uint64_t)(ceil_div(ens->N, rb) * rb) * (uint64_t)ens->W >= (1ull << 32))
-    return set_error(FC_E_LIMIT, "N=%lld: the bit matrix exceeds the 32-bit word index", (long long)ens->N);
-  return FC_OK;
-}
-
-// bits, similar-pair queue and counters of the whole ensemble under similar_sym; `dperm` lives until the caller's wait
-int symm_local(fc_ensemble *e, const std::vector<uint16_t> &table, int64_t K, DevBuf &dperm, double max_rmsd, double max_dev,
-               const double *energies, double max_dE) {
-  FC_TRY(ensemble_shard(e, 0, 1, default_row_block()));
-  e->lean = false;
-  const double *en_dev = nullptr;
-  if (energies != nullptr) {
-    FC_TRY(upload(e->energies, energies, (size_t)e->N));
-    en_dev = e->energies.as<double>();
-  }
-  FC_TRY(upload(dperm, table.data(), table.size()));
-  FC_HIP_TRY(hipMemsetAsync(e->counters.p, 0, kCounters * sizeof(uint64_t), ctx().stream));
-  FC_TRY(launch_symm_simbits(e, dperm.as<uint16_t>(), K, max_rmsd, max_dev, en_dev, max_dE));
-  e->bits_valid = true;
-  return FC_OK;
-}
-
-int prune_rmsd_perm_run(fc_ensemble *ens, const std::vector<uint16_t> &table, int64_t K, DevBuf &dperm, double max_rmsd,
-                        double max_dev, const double *energies, double max_dE, int64_t min_per_group, uint8_t *mask_out,
-                        int64_t *stats) {
-  FC_TRY(symm_local(ens, table, K, dperm, max_rmsd, max_dev, energies, max_dE));
-  // the pair ladder over the queue; it declines a queue that overflowed or is too long for it, and the bit-matrix levels
-  // take over from the matrix the same launch wrote
-  unsigned long long cnt[8];
-  int64_t levels = 0, survivors = 0;
-  LadderJob job;
-  job.pairs_dev = ens->simq.as<uint64_t>(), job.bits_dev = ens->bits.as<uint64_t>(), job.counters_zeroed = true;
-  job.mask_out = mask_out, job.levels = &levels, job.survivors = &survivors, job.counters_out = cnt;
-  FC_TRY(ladder_single(ens, min_per_group, job));
-  if (stats) fill_stats(stats, ens->N * (ens->N - 1) / 2, cnt, levels, survivors);
-  return FC_OK;
-}
-
-// the symmetry-aware graph: one launch writes the queue AND the matrix, so a declined list costs nothing more
-struct SymmSource {
-  static constexpr bool screened = false;
-  fc_ensemble *ens;
-  const std::vector<uint16_t> &table;
-  int64_t K;
-  DevBuf &dperm;
-  double max_rmsd, max_dev;
-  const double *energies;
-  double max_dE;
-  int operator()(bool lean) const {
-    return lean ? symm_local(ens, table, K, dperm, max_rmsd, max_dev, energies, max_dE) : FC_OK;
-  }
-};
-
-// fc_rmsd_clusters_perm and fc_rmsd_dbscan_perm behind the API lock
-int rmsd_label_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
-                    const double *energies, double max_dE, const Labelling &lab, const LabelOut &o, int64_t *stats) {
-  std::vector<uint16_t> table;
-  FC_TRY(perm_table_check(perms, K, A_sel, table));
-  FC_TRY(perm_ensemble_check(ens, K, A_sel, true));
-  FC_REQUIRE(o.n_clusters != nullptr, "NULL pointer argument");
-  FC_REQUIRE(max_rmsd > 0.0 && max_dev > 0.0, "thresholds must be positive");
-  if (lab.density) FC_REQUIRE(lab.min_samples >= 1, "min_samples=%lld must be >= 1", (long long)lab.min_samples);
-  *o.n_clusters = 0;
-  if (stats) std::memset(stats, 0, lab.n_stats() * sizeof(int64_t));
-  if (ens->N > (int64_t)INT32_MAX - 256)
-    return set_error(FC_E_LIMIT, "N=%lld: clusters index conformers with 32 bits", (long long)ens->N);
-  FC_TRY(ensure_init());
-  if (ens->N == 0) return FC_OK;
-  FC_REQUIRE(o.complete(lab), "NULL pointer argument");
-  DevBuf dperm, work;
-  const int rc = label_resident(ens, SymmSource{ens, table, K, dperm, max_rmsd, max_dev, energies, max_dE}, lab, work, o, stats);
-  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());
-  return rc;
-}
-}  // namespace
-
-int fc_ensemble_rmsd_pairs_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, const int64_t *pair_i,
-                                const int64_t *pair_j, int64_t P, double *rmsd_out, double *maxdev_out) {
-  FC_API_LOCK;
-  std::vector<uint16_t> table;
-  FC_TRY(perm_table_check(perms, K, A_sel, table));
-  FC_TRY(perm_ensemble_check(ens, K, A_sel, false));
-  FC_REQUIRE(P >= 0, "P < 0");
-  if (P == 0) return FC_OK;
-  FC_REQUIRE(pair_i && pair_j && rmsd_out && maxdev_out, "NULL pointer argument");
-  for (int64_t k = 0; k < P; ++k)
-    FC_REQUIRE(pair_i[k] >= 0 && pair_i[k] < ens->N && pair_j[k] >= 0 && pair_j[k] < ens->N,
-               "pair %lld = (%lld, %lld) out of range [0, %lld)", (long long)k, (long long)pair_i[k], (long long)pair_j[k],
-               (long long)ens->N);
-  FC_TRY(ensure_init());
-  DevBuf di, dj, dr, dm, dperm;
-  const auto run = [&]() -> int {
-    FC_TRY(upload(di, pair_i, (size_t)P));
-    FC_TRY(upload(dj, pair_j, (size_t)P));
-    FC_TRY(upload(dperm, table.data(), table.size()));
-    FC_TRY(dr.reserve((size_t)P * K * sizeof(double)));
-    FC_TRY(dm.reserve((size_t)P * K * sizeof(double)));
-    FC_TRY(launch_symm_pairs(ens, dperm.as<uint16_t>(), K, di.as<int64_t>(), dj.as<int64_t>(), P, dr.as<double>(),
-                             dm.as<double>()));
-    FC_TRY(d2h(rmsd_out, dr.p, (size_t)P * K * sizeof(double)));
-    FC_TRY(d2h(maxdev_out, dm.p, (size_t)P * K * sizeof(double)));
-    return sync();
-  };
-  const int rc = run();
-  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());  // nothing of the buffers may be in flight when they go
-  return rc;
-}
-
 int fc_rmsd_simbits_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
                          const double *energies, double max_dE, int64_t row_begin, int64_t row_end, uint64_t *bits_out,
                          int64_t *n_grey) {
@@ -1556,11 +546,7 @@ int fc_rmsd_simbits_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int6
     FC_TRY(d2h(cnt, ens->counters.p, sizeof cnt));
     return sync();
   };
-  const int rc = run();
-  if (rc != FC_OK) {
-    (void)hipStreamSynchronize(cur_stream());
-    return rc;
-  }
+  FC_TRY(drained(run()));
   for (int64_t i = row_begin; i < row_end; ++i)
     for (int64_t w = 0; w < W; ++w) bits_out[(i - row_begin) * W + w] = all[(size_t)i * W + w];
   if (n_grey) *n_grey = (int64_t)cnt[3];
@@ -1579,347 +565,7 @@ int fc_prune_rmsd_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_
   FC_TRY(ensure_init());
   if (ens->N == 0) return FC_OK;
   DevBuf dperm;
-  const int rc = prune_rmsd_perm_run(ens, table, K, dperm, max_rmsd, max_dev, energies, max_dE, min_per_group, mask_out, stats);
-  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());
-  return rc;
-}
-
-int fc_rmsd_clusters_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd,
-                          double max_dev, const double *energies, double max_dE, int32_t *labels_out, int64_t *reps_out,
-                          int64_t *sizes_out, int64_t *n_clusters, int64_t *stats) {
-  FC_API_LOCK;
-  return rmsd_label_perm(ens, perms, K, A_sel, max_rmsd, max_dev, energies, max_dE, components(),
-                         {labels_out, reps_out, sizes_out, nullptr, nullptr, n_clusters}, stats);
-}
-
-// ---- the diverse selection under d_sym (include/fc_hip.h; the kernel: k_diverse_step_sym, fc_diverse.hip) ---------------
-// stats (may be NULL): the two counters of DiverseSym::stats_dev after the selection
-static int select_diverse_perm_checked(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
-                                       int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out, double *radii_out,
-                                       int32_t *labels_out, double *dist_out, int64_t *n_selected, double *ms_device,
-                                       int64_t *stats) {
-  std::vector<uint16_t> table;
-  FC_TRY(perm_table_check(perms, K, A_sel, table));
-  const size_t lds = diverse_sym_lds_bytes(A_sel, K);
-  if (lds > kLdsLimit)
-    return set_error(FC_E_LIMIT, "A_sel=%lld selected atoms with K=%lld permutations need %zu bytes of LDS (limit %zu)",
-                     (long long)A_sel, (long long)K, lds, kLdsLimit);
-  FC_REQUIRE(mirror == 0 || mirror == 1, "mirror=%d: 0 or 1", mirror);
-  FC_TRY(perm_ensemble_check(ens, K, A_sel, false));
-  if (stats) stats[0] = stats[1] = 0;
-  if (K == 1 && !mirror)  // d_sym = d: the default's kernels, bit for bit
-    return select_diverse_checked(ens, n_max, start, stop_rmsd, indices_out, radii_out, labels_out, dist_out, n_selected,
-                                  ms_device);
-  DevBuf dperm, dstats;
-  // (behind the sibling's checks and ensure_init; the buffers live until select_diverse's last wait)
-  const auto run = [&](DiverseSym &sym) -> int {
-    FC_TRY(upload(dperm, table.data(), table.size()));
-    sym.perms_dev = dperm.as<uint16_t>(), sym.K = (int)K, sym.mirror = mirror != 0;
-    if (!stats) return FC_OK;
-    FC_TRY(dstats.reserve(2 * sizeof(unsigned long long)));
-    FC_HIP_TRY(hipMemsetAsync(dstats.p, 0, 2 * sizeof(unsigned long long), ctx().stream));
-    sym.stats_dev = reinterpret_cast<unsigned long long *>(dstats.p);
-    return FC_OK;
-  };
-  int rc = select_diverse_checked(ens, n_max, start, stop_rmsd, indices_out, radii_out, labels_out, dist_out, n_selected,
-                                  ms_device, run);
-  if (rc == FC_OK && stats && ens->N > 0) {
-    unsigned long long cnt[2] = {0, 0};
-    rc = d2h(cnt, dstats.p, sizeof cnt);
-    if (rc == FC_OK) rc = sync();
-    stats[0] = (int64_t)cnt[0], stats[1] = (int64_t)cnt[1];
-  }
-  if (rc != FC_OK) (void)hipStreamSynchronize(cur_stream());  // nothing of the buffers may be in flight when they go
-  return rc;
-}
-
-int fc_ensemble_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
-                                    int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
-                                    double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected) {
-  FC_API_LOCK;
-  return select_diverse_perm_checked(ens, perms, K, A_sel, mirror, n_max, start, stop_rmsd, indices_out, radii_out,
-                                     labels_out, dist_out, n_selected, nullptr, nullptr);
-}
-
-int fc_bench_select_diverse_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
-                                 int64_t n_max, int64_t start, double stop_rmsd, int64_t reps, double *ms_device_mean,
-                                 double *ms_host_mean, int64_t *indices_out, int64_t *n_selected, int64_t *stats) {
-  FC_API_LOCK;
-  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
-  double dev = 0.0, host = 0.0;
-  for (int64_t r = 0; r < reps; ++r) {
-    double ms = 0.0;
-    const auto t0 = std::chrono::steady_clock::now();
-    FC_TRY(select_diverse_perm_checked(ens, perms, K, A_sel, mirror, n_max, start, stop_rmsd, indices_out, nullptr, nullptr,
-                                       nullptr, n_selected, &ms, nullptr));
-    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    dev += ms;
-  }
-  *ms_device_mean = dev / (double)reps;
-  *ms_host_mean = host / (double)reps;
-  if (stats)  // counted in a selection of its own: the timed ones run without the counters
-    FC_TRY(select_diverse_perm_checked(ens, perms, K, A_sel, mirror, n_max, start, stop_rmsd, indices_out, nullptr, nullptr,
-                                       nullptr, n_selected, nullptr, stats));
-  return FC_OK;
-}
-
-// ---- nearest neighbours under d_sym (include/fc_hip.h; the kernel: k_knn_tile_sym, fc_knn.hip) --------------------------
-namespace {
-// what both forms refuse first, in the order of select_diverse_perm_checked: the table, its LDS, the flag
-int knn_perm_table(const int32_t *perms, int64_t K, int64_t A_sel, int mirror, std::vector<uint16_t> &table) {
-  FC_TRY(perm_table_check(perms, K, A_sel, table));
-  const size_t lds = knn_sym_lds_bytes(A_sel, K);
-  if (lds > kLdsLimit)
-    return set_error(FC_E_LIMIT, "A_sel=%lld selected atoms with K=%lld permutations need %zu bytes of LDS (limit %zu)",
-                     (long long)A_sel, (long long)K, lds, kLdsLimit);
-  FC_REQUIRE(mirror == 0 || mirror == 1, "mirror=%d: 0 or 1", mirror);
-  return FC_OK;
-}
-
-int knn_perm_checked(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, int64_t k,
-                     int32_t *indices_out, double *dist_out, double *ms_device, int64_t *strips_out, int64_t *stats) {
-  KnnPerm perm;
-  FC_TRY(knn_perm_table(perms, K, A_sel, mirror, perm.table));
-  FC_TRY(perm_ensemble_check(ens, K, A_sel, false));
-  if (stats) stats[0] = stats[1] = 0;
-  if (K == 1 && !mirror)  // d_sym = d: the default's kernels, bit for bit
-    return knn_checked(ens, k, indices_out, dist_out, ms_device, strips_out);
-  perm.K = (int)K, perm.mirror = mirror != 0, perm.stats = stats;
-  return knn_checked(ens, k, indices_out, dist_out, ms_device, strips_out, &perm);
-}
-
-int knn_cross_perm_checked(fc_ensemble *queries, fc_ensemble *refs, const int32_t *perms, int64_t K, int64_t A_sel,
-                           int mirror, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out,
-                           double *ms_device, int64_t *strips_out, int64_t *stats) {
-  KnnPerm perm;
-  FC_TRY(knn_perm_table(perms, K, A_sel, mirror, perm.table));
-  FC_REQUIRE(queries != nullptr && refs != nullptr, "queries / refs is NULL");
-  FC_TRY(perm_ensemble_check(queries, K, A_sel, false));
-  FC_TRY(perm_ensemble_check(refs, K, A_sel, false));
-  if (stats) stats[0] = stats[1] = 0;
-  if (K == 1 && !mirror)
-    return knn_cross_checked(queries, refs, k, max_rmsd, indices_out, dist_out, ms_device, strips_out);
-  perm.K = (int)K, perm.mirror = mirror != 0, perm.stats = stats;
-  return knn_cross_checked(queries, refs, k, max_rmsd, indices_out, dist_out, ms_device, strips_out, &perm);
-}
-}  // namespace
-
-int fc_ensemble_knn_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, int64_t k,
-                         int32_t *indices_out, double *dist_out) {
-  FC_API_LOCK;
-  return knn_perm_checked(ens, perms, K, A_sel, mirror, k, indices_out, dist_out, nullptr, nullptr, nullptr);
-}
-
-int fc_ensemble_knn_cross_perm(fc_ensemble *queries, fc_ensemble *refs, const int32_t *perms, int64_t K, int64_t A_sel,
-                               int mirror, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out) {
-  FC_API_LOCK;
-  return knn_cross_perm_checked(queries, refs, perms, K, A_sel, mirror, k, max_rmsd, indices_out, dist_out, nullptr, nullptr,
-                                nullptr);
-}
-
-int fc_bench_knn_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, int64_t k, int64_t reps,
-                      double *ms_device_mean, double *ms_host_mean, int64_t *strips_out, int64_t *stats) {
-  FC_API_LOCK;
-  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
-  std::vector<uint16_t> table;
-  FC_TRY(knn_perm_table(perms, K, A_sel, mirror, table));
-  FC_TRY(perm_ensemble_check(ens, K, A_sel, false));
-  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
-  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
-  std::vector<int32_t> idx((size_t)ens->N * (size_t)k + 1);
-  std::vector<double> dist((size_t)ens->N * (size_t)k + 1);
-  double dev = 0.0, host = 0.0;
-  for (int64_t r = 0; r < reps; ++r) {
-    double ms = 0.0;
-    const auto t0 = std::chrono::steady_clock::now();
-    FC_TRY(knn_perm_checked(ens, perms, K, A_sel, mirror, k, idx.data(), dist.data(), &ms, strips_out, nullptr));
-    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    dev += ms;
-  }
-  *ms_device_mean = dev / (double)reps;
-  *ms_host_mean = host / (double)reps;
-  if (stats)  // counted in a call of its own: the timed ones run without the counters
-    FC_TRY(knn_perm_checked(ens, perms, K, A_sel, mirror, k, idx.data(), dist.data(), nullptr, nullptr, stats));
-  return FC_OK;
-}
-
-int fc_bench_knn_cross_perm(fc_ensemble *queries, fc_ensemble *refs, const int32_t *perms, int64_t K, int64_t A_sel,
-                            int mirror, int64_t k, double max_rmsd, int64_t reps, double *ms_device_mean,
-                            double *ms_host_mean, int64_t *strips_out, int64_t *stats) {
-  FC_API_LOCK;
-  FC_REQUIRE(reps >= 1 && reps <= 4096 && ms_device_mean && ms_host_mean, "bad arguments");
-  std::vector<uint16_t> table;
-  FC_TRY(knn_perm_table(perms, K, A_sel, mirror, table));
-  FC_REQUIRE(queries != nullptr && refs != nullptr, "queries / refs is NULL");
-  FC_TRY(perm_ensemble_check(queries, K, A_sel, false));
-  FC_REQUIRE(k >= 1, "k=%lld < 1", (long long)k);
-  if (k > FC_KNN_MAX) return set_error(FC_E_LIMIT, "k=%lld neighbours: at most FC_KNN_MAX = %d", (long long)k, FC_KNN_MAX);
-  std::vector<int32_t> idx((size_t)queries->N * (size_t)k + 1);
-  std::vector<double> dist((size_t)queries->N * (size_t)k + 1);
-  double dev = 0.0, host = 0.0;
-  for (int64_t r = 0; r < reps; ++r) {
-    double ms = 0.0;
-    const auto t0 = std::chrono::steady_clock::now();
-    FC_TRY(knn_cross_perm_checked(queries, refs, perms, K, A_sel, mirror, k, max_rmsd, idx.data(), dist.data(), &ms, strips_out,
-                                  nullptr));
-    host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    dev += ms;
-  }
-  *ms_device_mean = dev / (double)reps;
-  *ms_host_mean = host / (double)reps;
-  if (stats)
-    FC_TRY(knn_cross_perm_checked(queries, refs, perms, K, A_sel, mirror, k, max_rmsd, idx.data(), dist.data(), nullptr, nullptr,
-                                  stats));
-  return FC_OK;
-}
-
-// ---- a caller's graph (fc_clusters_from_* / fc_dbscan_from_*) ------------------------------------------------------------
-namespace {
-// one upload, the same labelling (the checks are label_from_pairs' / label_from_bits')
-int label_uploaded(const uint64_t *pairs, int64_t n_pairs, const uint64_t *bits, int64_t N, const Labelling &lab,
-                   const LabelOut &o) {
-  FC_TRY(ensure_init());
-  DevBuf graph, work;
-  ClusterGraph g;
-  ClusterResult res;
-  int rc = FC_OK;
-  if (bits != nullptr) {
-    const int64_t W = ceil_div(N, 64);
-    rc = upload(graph, bits, (size_t)N * (size_t)W);
-    g.bits_dev = graph.as<uint64_t>(), g.W = W;
-  } else {
-    rc = upload(graph, pairs, (size_t)n_pairs);  // (n_pairs == 0: an 8-byte block that is never read)
-    g.pairs_dev = graph.as<uint64_t>(), g.n_pairs_host = (unsigned long long)n_pairs;
-    g.known_short = n_pairs < kClShortList;
-  }
-  if (rc == FC_OK) rc = label_run(lab, g, N, work, nullptr, &res);
-  if (rc != FC_OK) {
-    (void)hipStreamSynchronize(cur_stream());  // nothing of `graph` / `work` may be in flight when they go out of scope
-    return rc;
-  }
-  label_unpack(res, N, o, nullptr);
-  return FC_OK;
-}
-
-int label_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, const Labelling &lab, const LabelOut &o) {
-  FC_REQUIRE(o.n_clusters != nullptr, "n_clusters is NULL");
-  FC_REQUIRE(N >= 0 && n_pairs >= 0, "bad arguments N=%lld n_pairs=%lld", (long long)N, (long long)n_pairs);
-  if (lab.density) FC_REQUIRE(lab.min_samples >= 1, "min_samples=%lld must be >= 1", (long long)lab.min_samples);
-  FC_REQUIRE(N <= (int64_t)INT32_MAX - 256, "N=%lld: clusters index conformers with 32 bits", (long long)N);
-  FC_REQUIRE(pairs != nullptr || n_pairs == 0, "pairs is NULL");
-  for (int64_t p = 0; p < n_pairs; ++p) {
-    const uint64_t i = pairs[p] >> 32, j = pairs[p] & 0xffffffffull;
-    FC_REQUIRE(i != j && i < (uint64_t)N && j < (uint64_t)N, "pair %lld = (%llu, %llu): i == j or an index outside [0, %lld)",
-               (long long)p, (unsigned long long)i, (unsigned long long)j, (long long)N);
-  }
-  *o.n_clusters = 0;
-  if (N == 0) return FC_OK;
-  FC_REQUIRE(o.complete(lab), "NULL pointer argument");
-  return label_uploaded(pairs, n_pairs, nullptr, N, lab, o);
-}
-
-int label_from_bits(const uint64_t *bits, int64_t N, const Labelling &lab, const LabelOut &o) {
-  FC_REQUIRE(o.n_clusters != nullptr, "n_clusters is NULL");
-  FC_REQUIRE(N >= 0, "N=%lld < 0", (long long)N);
-  if (lab.density) FC_REQUIRE(lab.min_samples >= 1, "min_samples=%lld must be >= 1", (long long)lab.min_samples);
-  FC_REQUIRE(N <= (int64_t)INT32_MAX - 256, "N=%lld: clusters index conformers with 32 bits", (long long)N);
-  *o.n_clusters = 0;
-  if (N == 0) return FC_OK;
-  FC_REQUIRE(bits != nullptr && o.complete(lab), "NULL pointer argument");
-  return label_uploaded(nullptr, 0, bits, N, lab, o);
-}
-}  // namespace
-
-int fc_clusters_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int32_t *labels_out, int64_t *reps_out,
-                           int64_t *sizes_out, int64_t *n_clusters) {
-  FC_API_LOCK;
-  return label_from_pairs(pairs, n_pairs, N, components(), {labels_out, reps_out, sizes_out, nullptr, nullptr, n_clusters});
-}
-
-int fc_clusters_from_bits(const uint64_t *bits, int64_t N, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
-                          int64_t *n_clusters) {
-  FC_API_LOCK;
-  return label_from_bits(bits, N, components(), {labels_out, reps_out, sizes_out, nullptr, nullptr, n_clusters});
-}
-
-// ---- density-based clusters (the contract: include/fc_hip.h; the kernels: fc_clusters.hip, k_db_*) ---------------------
-int fc_rmsd_dbscan(fc_ensemble *ens, double max_rmsd, double max_dev, int64_t min_samples, const double *energies,
-                   double max_dE, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, uint8_t *core_out,
-                   int32_t *degrees_out, int64_t *n_clusters, int64_t *stats) {
-  FC_API_LOCK;
-  return rmsd_label(ens, max_rmsd, max_dev, energies, max_dE, density_based(min_samples),
-                    {labels_out, reps_out, sizes_out, core_out, degrees_out, n_clusters}, stats);
-}
-
-int fc_rmsd_dbscan_enant(fc_ensemble *ens, double max_rmsd, double max_dev, int64_t min_samples, const double *energies,
-                         double max_dE, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, uint8_t *core_out,
-                         int32_t *degrees_out, int64_t *n_clusters, int64_t *stats) {
-  FC_API_LOCK;
-  FC_REQUIRE(ens && n_clusters, "NULL pointer argument");
-  EnantScope scope(ens);
-  return fc_rmsd_dbscan(ens, max_rmsd, max_dev, min_samples, energies, max_dE, labels_out, reps_out, sizes_out, core_out,
-                        degrees_out, n_clusters, stats);
-}
-
-int fc_rmsd_dbscan_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
-                        int64_t min_samples, const double *energies, double max_dE, int32_t *labels_out, int64_t *reps_out,
-                        int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out, int64_t *n_clusters, int64_t *stats) {
-  FC_API_LOCK;
-  return rmsd_label_perm(ens, perms, K, A_sel, max_rmsd, max_dev, energies, max_dE, density_based(min_samples),
-                         {labels_out, reps_out, sizes_out, core_out, degrees_out, n_clusters}, stats);
-}
-
-int fc_dbscan_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int64_t min_samples, int32_t *labels_out,
-                         int64_t *reps_out, int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out,
-                         int64_t *n_clusters) {
-  FC_API_LOCK;
-  return label_from_pairs(pairs, n_pairs, N, density_based(min_samples),
-                          {labels_out, reps_out, sizes_out, core_out, degrees_out, n_clusters});
-}
-
-int fc_dbscan_from_bits(const uint64_t *bits, int64_t N, int64_t min_samples, int32_t *labels_out, int64_t *reps_out,
-                        int64_t *sizes_out, uint8_t *core_out, int32_t *degrees_out, int64_t *n_clusters) {
-  FC_API_LOCK;
-  return label_from_bits(bits, N, density_based(min_samples), {labels_out, reps_out, sizes_out, core_out, degrees_out, n_clusters});
-}
-
-// ---- sphere-exclusion clusters (the contract: include/fc_hip.h; the kernels: fc_clusters.hip, k_bu_*) ------------------
-int fc_rmsd_butina(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
-                   int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int32_t *degrees_out, int64_t *n_clusters,
-                   int64_t *stats) {
-  FC_API_LOCK;
-  return rmsd_label(ens, max_rmsd, max_dev, energies, max_dE, sphere_exclusion(),
-                    {labels_out, reps_out, sizes_out, nullptr, degrees_out, n_clusters}, stats);
-}
-
-int fc_rmsd_butina_enant(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies, double max_dE,
-                         int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out, int32_t *degrees_out,
-                         int64_t *n_clusters, int64_t *stats) {
-  FC_API_LOCK;
-  FC_REQUIRE(ens && n_clusters, "NULL pointer argument");
-  EnantScope scope(ens);
-  return fc_rmsd_butina(ens, max_rmsd, max_dev, energies, max_dE, labels_out, reps_out, sizes_out, degrees_out, n_clusters,
-                        stats);
-}
-
-int fc_rmsd_butina_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, double max_rmsd, double max_dev,
-                        const double *energies, double max_dE, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
-                        int32_t *degrees_out, int64_t *n_clusters, int64_t *stats) {
-  FC_API_LOCK;
-  return rmsd_label_perm(ens, perms, K, A_sel, max_rmsd, max_dev, energies, max_dE, sphere_exclusion(),
-                         {labels_out, reps_out, sizes_out, nullptr, degrees_out, n_clusters}, stats);
-}
-
-int fc_butina_from_pairs(const uint64_t *pairs, int64_t n_pairs, int64_t N, int32_t *labels_out, int64_t *reps_out,
-                         int64_t *sizes_out, int32_t *degrees_out, int64_t *n_clusters) {
-  FC_API_LOCK;
-  return label_from_pairs(pairs, n_pairs, N, sphere_exclusion(), {labels_out, reps_out, sizes_out, nullptr, degrees_out, n_clusters});
-}
-
-int fc_butina_from_bits(const uint64_t *bits, int64_t N, int32_t *labels_out, int64_t *reps_out, int64_t *sizes_out,
-                        int32_t *degrees_out, int64_t *n_clusters) {
-  FC_API_LOCK;
-  return label_from_bits(bits, N, sphere_exclusion(), {labels_out, reps_out, sizes_out, nullptr, degrees_out, n_clusters});
+  return drained(prune_rmsd_perm_run(ens, table, K, dperm, max_rmsd, max_dev, energies, max_dE, min_per_group, mask_out, stats));
 }
 
 int fc_prune_rmsd_begin(fc_ensemble *ens, double max_rmsd, double max_dev, const double *energies,
@@ -2019,13 +665,6 @@ int fc_prune_rmsd_begin_async(fc_ensemble *ens, double max_rmsd, double max_dev,
   FC_TRY(ensemble_shard(ens, rank, world, row_block));
   if (ens->N == 0) return FC_OK;
   return simbits_local(ens, max_rmsd, max_dev, nullptr, 0.0, true, /*lean=*/true);  // consumer: the exported pair list
-}
-
-int fc_ensemble_twin(fc_ensemble *ens, fc_ensemble **twin_out) {
-  FC_API_LOCK;
-  FC_REQUIRE(ens && twin_out, "NULL pointer argument");
-  FC_TRY(ensure_init());
-  return ensemble_twin(ens, twin_out);
 }
 
 // counters reset on the current stream (behind the last user of this workspace), the screen on

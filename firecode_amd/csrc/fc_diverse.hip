@@ -381,7 +381,7 @@ static const void *step_sym_kernel() {
 }
 
 template <int LANES, bool MIRROR>
-static int launch_step_sym(const fc_ensemble *e, const DiverseSym &sym, int k, int start, double stop, int n_steps, DevBuf &D,
+static int launch_step_sym(const fc_ensemble *e, const SymTable &sym, int k, int start, double stop, int n_steps, DevBuf &D,
                            DevBuf &L, DevBuf &rep, DevBuf &pv, DevBuf &pi, int nb, DevBuf &idx, DevBuf &rad, DevBuf &state) {
   const size_t lds = diverse_sym_lds_bytes(e->A, sym.K) - kDiverseSymStaticLds;
   hipLaunchKernelGGL((k_diverse_step_sym<LANES, MIRROR>), dim3((unsigned)nb), dim3(kDivThreads), lds, ctx().stream,
@@ -398,7 +398,7 @@ static int launch_step_sym(const fc_ensemble *e, const DiverseSym &sym, int k, i
 // representative and the table fit the LDS).
 int select_diverse(fc_ensemble *e, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
                    double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected, double *ms_device,
-                   const DiverseSym *sym) {
+                   const SymTable *sym) {
   constexpr int kDiverseBatch = 64;
   const int64_t N = e->N;
   const int n_steps = (int)std::min<int64_t>(n_max, N);

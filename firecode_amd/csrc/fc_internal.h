@@ -144,19 +144,22 @@ int launch_tri_embed(const double *const coords_dev[3], const int64_t *const rea
                      const int32_t *aidx_dev, int S, double thresh, int max_clashes, double rmsd_thr, double *dirs_dev,
                      double *Rt_dev, uint8_t *pass_dev, uint8_t *accept_dev);
 int warm_embed3();
-// ---- fc_diverse.hip --------------------------------------------------------------------------------------
-int diverse_lanes(int64_t N);
-// the symmetry- and mirror-aware step (k_diverse_step_sym): the table on the device as 16-bit indices, K rows of e->A
-struct DiverseSym {
+// ---- fc_diverse.hip and fc_knn.hip: the table of a launch under d_sym -----------------------------------------
+// on the device as 16-bit indices, K rows of the ensembles' A selected atoms (k_diverse_step_sym, k_knn_tile_sym)
+struct SymTable {
   const uint16_t *perms_dev = nullptr;
   int K = 1;
   bool mirror = false;
-  unsigned long long *stats_dev = nullptr;  // two counters, or nullptr: (k, h) whose eigenvalue was formed / that went on to the explicit pass
+  // two counters, or nullptr: the (k, h) of a step / the (pair, p, h) of a tile whose eigenvalue was formed, and those
+  // of them that went on to the explicit pass
+  unsigned long long *stats_dev = nullptr;
 };
+// ---- fc_diverse.hip --------------------------------------------------------------------------------------
+int diverse_lanes(int64_t N);
 size_t diverse_sym_lds_bytes(int64_t A, int64_t K);  // representative + table + the kernel's static LDS
 int select_diverse(fc_ensemble *e, int64_t n_max, int64_t start, double stop_rmsd, int64_t *indices_out,
                    double *radii_out, int32_t *labels_out, double *dist_out, int64_t *n_selected, double *ms_device,
-                   const DiverseSym *sym = nullptr);
+                   const SymTable *sym = nullptr);
 int warm_diverse();
 // ---- fc_clusters.hip -------------------------------------------------------------------------------------
 // the graph whose components are labelled: a device pair list OR a bit matrix
@@ -253,16 +256,9 @@ int launch_symm_pairs(const fc_ensemble *e, const uint16_t *perms_dev, int64_t K
 int warm_symm();
 // ---- fc_knn.hip ------------------------------------------------------------------------------------------
 int knn_strips(int64_t Nq, int64_t Nr);  // column strips of the launch of Nq rows against Nr columns (FC_KNN_STRIPS forces it)
-// the tile kernel under d_sym (k_knn_tile_sym): the table on the device, K rows of the ensembles' A selected atoms
-struct KnnSym {
-  const uint16_t *perms_dev = nullptr;
-  int K = 1;
-  bool mirror = false;
-  unsigned long long *stats_dev = nullptr;  // two counters, or nullptr: (pair, p, h) whose eigenvalue was formed / that made the explicit pass
-};
 size_t knn_sym_lds_bytes(int64_t A, int64_t K);  // the workgroup's 16 row conformers + the table
 int knn(fc_ensemble *q, fc_ensemble *r, bool cross, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out,
-        double *ms_device, int64_t *strips_out, const KnnSym *sym = nullptr);
+        double *ms_device, int64_t *strips_out, const SymTable *sym = nullptr);
 int warm_knn();
 // ---- fc_tfd_ladder.hip -----------------------------------------------------------------------------------
 int tfd_ladder_device(const int64_t *fm_dev, const int64_t *fm_host, int64_t N, uint8_t *mask_out);
@@ -288,6 +284,31 @@ void comm_teardown();
 int xyz_write(const char *path, const char *const *atoms, int64_t A, const double *coords, int64_t N, const char *label,
               int mode);
 int xyz_read(const char *path, int64_t *N_io, int64_t *A_io, char *atoms_out, double *coords_out);
+// ---- fc_api_ensemble.cpp ---------------------------------------------------------------------------------
+constexpr int64_t kHostGmaxDoubles = 36000;  // N * A * 3 up to which host_largest_g beats the wait for the device's
+double host_largest_g(const double *coords, int64_t N, int64_t A_all, const std::vector<int32_t> &sel, int center);
+int ensemble_build(const double *coords, int64_t N, int64_t A_all, const uint8_t *atom_mask, int center, fc_ensemble *e,
+                   bool defer_wait = false, bool host_gmax = false);
+int ensemble_build_dev(const double *raw_dev, int64_t N, int64_t A_all, const uint8_t *atom_mask, int center,
+                       const int32_t *conf_idx_dev, fc_ensemble *e, bool defer_wait = false);
+int ensemble_build_finish(fc_ensemble *e);
+int ensemble_shard(fc_ensemble *e, int64_t rank, int64_t world, int64_t row_block);
+int ensemble_twin(fc_ensemble *ens, fc_ensemble **out);
+int64_t owned_pairs(int64_t N, int64_t row_block, int64_t rank, int64_t world);
+int timing_events(int64_t n);
+int elapsed_ms(hipEvent_t a, hipEvent_t b, double *out);
+int mean_elapsed_ms(const std::vector<hipEvent_t> &ev, int64_t n, int64_t per, int64_t step, double *out);
+int perm_table_check(const int32_t *perms, int64_t K, int64_t A_sel, std::vector<uint16_t> &table);
+int perm_lds_check(size_t lds, int64_t A_sel, int64_t K, const char *per = "");
+int perm_ensemble_check(const fc_ensemble *ens, int64_t K, int64_t A_sel, bool bit_matrix);
+// ---- fc_api_prune.cpp ------------------------------------------------------------------------------------
+int64_t default_row_block();
+int simbits_local(fc_ensemble *e, double max_rmsd, double max_dev, const double *energies, double max_dE,
+                  bool zero_counters, bool lean = false);
+int symm_local(fc_ensemble *e, const std::vector<uint16_t> &table, int64_t K, DevBuf &dperm, double max_rmsd,
+               double max_dev, const double *energies, double max_dE);
+void note_candidates(fc_ensemble *e, unsigned long long refined, unsigned long long similar);
+void fill_stats(int64_t *stats, int64_t pairs, const unsigned long long *cnt, int64_t s4, int64_t s5);
 
 // ---- shared by the fc_api_*.cpp files ----------------------------------------------------------------------------
 // host array -> device buffer (grown to fit)
@@ -296,5 +317,23 @@ inline int upload(DevBuf &b, const T *host, size_t count) {
   FC_TRY(b.reserve(count * sizeof(T)));
   return h2d(b.p, host, count * sizeof(T));
 }
+
+// On an error nothing of a DevBuf may be in flight when it goes out of scope: `return drained(rc);` in front of it waits
+// for the stream first (rc passes through; FC_OK costs nothing).
+inline int drained(int rc) {
+  if (rc != FC_OK && ctx().ready) (void)hipStreamSynchronize(cur_stream());
+  return rc;
+}
+
+// The enantiomer-aware forms (include/fc_hip.h) are the plain entry points with fc_ensemble::enant set for the call: the
+// flag selects the ENANT instantiations of the screen and refine kernels (launch_simbits_screen / _refine); it is cleared
+// when the call returns, whatever it returns, so no other entry point ever sees it.
+struct EnantScope {
+  fc_ensemble *e;
+  explicit EnantScope(fc_ensemble *ens) : e(ens) { e->enant = true; }
+  ~EnantScope() { e->enant = false; }
+  EnantScope(const EnantScope &) = delete;
+  EnantScope &operator=(const EnantScope &) = delete;
+};
 
 }  // namespace fc

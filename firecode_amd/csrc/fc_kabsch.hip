@@ -3569,7 +3569,7 @@ int launch_scatter_pairs(const uint64_t *pairs_dev, int64_t n_pairs, int64_t N, 
 }
 
 // ---------------------------------------------------------------------------
-// host-side launchers (called from fc_api_prune.cpp and fc_api_geom.cpp; declared in fc_internal.h)
+// host-side launchers (called from the fc_api_*.cpp files; declared in fc_internal.h)
 // ---------------------------------------------------------------------------
 // the largest G lands in the last counter word (zeroed here); ensemble_build reads it behind its own wait
 int launch_prep_begin(fc_ensemble *e) {

@@ -483,7 +483,7 @@ static int launch_knn_tile(const KnnLaunch &a, double *part_d, int32_t *part_j) 
 }
 
 template <bool CROSS, bool MIRROR>
-static int launch_knn_tile_sym(const KnnLaunch &a, const KnnSym &sym, double *part_d, int32_t *part_j) {
+static int launch_knn_tile_sym(const KnnLaunch &a, const SymTable &sym, double *part_d, int32_t *part_j) {
   const size_t lds = knn_sym_lds_bytes(a.q->A, sym.K);
   FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_knn_tile_sym<CROSS, MIRROR>), lds, "k_knn_tile_sym"));
   const unsigned gx = (unsigned)std::min<int64_t>(a.n_tiles, (int64_t)1 << 20);
@@ -497,7 +497,7 @@ static int launch_knn_tile_sym(const KnnLaunch &a, const KnnSym &sym, double *pa
 
 static int knn_enqueue(const fc_ensemble *q, const fc_ensemble *r, bool cross, int k, double cap, int S, int32_t *indices_out,
                        double *dist_out, double *ms_device, DevBuf &pd, DevBuf &pj, DevBuf &oi, DevBuf &od,
-                       const KnnSym *sym) {
+                       const SymTable *sym) {
   const int64_t Nq = q->N;
   const KnnLaunch a{q, r, k, knn_filter(), (int)ceil_div(Nq, kKnnTileRows), (int)ceil_div(r->N, 64), S, cap};
   const size_t entries = (size_t)Nq * (size_t)k;
@@ -539,7 +539,7 @@ static int knn_enqueue(const fc_ensemble *q, const fc_ensemble *r, bool cross, i
 // merge; strips_out (may be NULL): the strip count used.  sym (may be NULL): the tiles are k_knn_tile_sym's
 // (fc_ensemble_knn_perm / fc_ensemble_knn_cross_perm, which have checked that the rows and the table fit the LDS).
 int knn(fc_ensemble *q, fc_ensemble *r, bool cross, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out,
-        double *ms_device, int64_t *strips_out, const KnnSym *sym) {
+        double *ms_device, int64_t *strips_out, const SymTable *sym) {
   const int S = knn_strips(q->N, r->N);
   if (strips_out) *strips_out = S;
   if (sym && knn_sym_lds_bytes(q->A, sym->K) > kLdsLimit)

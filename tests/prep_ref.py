@@ -29,7 +29,7 @@ LDS_DEFAULT = 64 * 1024
 LDS_LIMIT = 160 * 1024
 LDS_HEADROOM = 2048
 # the complete alignments of all pairs (rmsd_and_max_all): column tiles of 64 conformers up to 104 selected atoms, of 32
-# up to 208, of 16 up to 416 (fc_api_prune.cpp: rmsd_and_max_tiled); from 417 selected atoms on k_matrix_exact
+# up to 208, of 16 up to 416 (fc_api_ensemble.cpp: rmsd_and_max_tiled); from 417 selected atoms on k_matrix_exact
 TILED_MAX_ATOMS = 416
 # the values alone (rmsd_values) keep the 64-column tile: (A4 * 3 * 64 + 64 + 128) * 8 + 488 bytes of LDS, A4 = A rounded
 # up to 4, fit LDS_LIMIT up to 104 selected atoms; beyond, the call reports FC_E_LIMIT

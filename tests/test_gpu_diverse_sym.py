@@ -246,3 +246,25 @@ def test_drivers_pass_both_keywords_through(fc):
     assert out.shape == (n_out, A, 3) and np.array_equal(out, pruned[sel.indices])
     sel_plain = fc.pruner.select_diverse(pruned, catoms, n=n_out, start=0)
     assert not np.array_equal(sel.indices, sel_plain.indices)  # (the chain's mirror images and reversals do matter)
+
+
+def test_bench_hook_under_d_sym(fc):
+    """fc_bench_select_diverse_perm: the picks of the product call with the same arguments, and the two counters of a
+    selection of its own -- every (conformer, permutation, handedness) of a step forms at most one eigenvalue, and only
+    some of those go on to the explicit pass; with K = 1 and no mirror images it is the plain hook, and counts nothing"""
+    N, A, n_max = 64, 12, 8
+    X = syn.continuous_ensemble(N, A, seed=12)
+    swap = np.arange(A)
+    swap[[0, 1]] = 1, 0
+    table = np.stack([np.arange(A), swap])
+    with fc.DeviceEnsemble(X, atom_mask=np.ones(A, bool), center=True) as ens:
+        want = ens.select_diverse(n_max, symmetry=table, prune_enantiomers=True)[0]
+        dev, host, idx, (formed, explicit) = ens.bench_select_diverse(n_max, reps=2, symmetry=table, prune_enantiomers=True)
+        print(f"device {dev:.3f} ms, host {host:.3f} ms, formed {formed}, explicit {explicit}")
+        assert len(want) == n_max and np.array_equal(idx, want)
+        assert 0 < explicit <= formed <= n_max * N * 2 * 2
+        assert dev > 0.0 and host > 0.0
+        plain = ens.bench_select_diverse(n_max, reps=2)
+        ident = ens.bench_select_diverse(n_max, reps=2, symmetry=np.arange(A)[None])
+        assert np.array_equal(ident[2], plain[2]) and np.array_equal(plain[2], ens.select_diverse(n_max)[0])
+        assert ident[3] == (0, 0)
