@@ -200,6 +200,9 @@ _SIGNATURES = {
     "fc_bench_knn_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, _i64, _i64, _p_f64, _p_f64, _p_i64, _p_i64],
     "fc_bench_knn_cross_perm": [_ens, _ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, _i64, C.c_double, _i64, _p_f64, _p_f64,
                                 _p_i64, _p_i64],
+    "fc_ensemble_subset": [_ens, _p_i64, _i64, C.POINTER(_ens)],
+    "fc_ensemble_medoids": [_ens, C.POINTER(C.c_int32), _i64, _p_i64, _p_i64, _p_f64, _p_f64, _p_u64, _p_f64, _p_f64],
+    "fc_ensemble_kmedoids": [_ens, _p_i64, _i64, _i64, _p_i64, C.POINTER(C.c_int32), _p_f64, _p_u64, _p_i64],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("fc_last_error",)
@@ -480,6 +483,50 @@ def check_max_rmsd_cap(value):
     return float(value)
 
 
+def check_count(name, value, low=1, high=None):
+    """An integer argument of the medoid calls (``n``, ``n_groups``, ``max_iter``): a real integer in [low, high], checked
+    before any device use -- ``True`` or ``2.5`` would otherwise be truncated into another count."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or int(value) < low:
+        raise FirecodeHipInputError(FC_E_INVALID, f"{name} must be an integer >= {low}, got {value!r}")
+    if int(value) >= 2 ** 63 or (high is not None and int(value) > high):
+        raise FirecodeHipInputError(FC_E_INVALID, f"{name}={value!r} exceeds {2 ** 63 - 1 if high is None else high}")
+    return int(value)
+
+
+def check_indices(name, value, n_conformers, distinct=False, count=None):
+    """Conformer indices (``indices``, ``init``): a 1-D integer array inside [0, N), ``count`` long and without repeats
+    where asked, checked before any device use -> a contiguous int64 array"""
+    idx = np.asarray(value)
+    if idx.ndim != 1 or (idx.size and (idx.dtype == np.bool_ or not np.issubdtype(idx.dtype, np.integer))):
+        raise FirecodeHipInputError(FC_E_INVALID, f"{name} must be a 1-D array of integers, got {idx.dtype} {idx.shape}")
+    idx = i64(idx)
+    if count is not None and idx.shape[0] != count:
+        raise FirecodeHipInputError(FC_E_INVALID, f"{name} holds {idx.shape[0]} indices, expected {count}")
+    if idx.size and (idx.min() < 0 or idx.max() >= n_conformers):
+        raise FirecodeHipInputError(FC_E_INVALID, f"{name} has an entry outside [0, {n_conformers})")
+    if distinct and np.unique(idx).shape[0] != idx.shape[0]:
+        raise FirecodeHipInputError(FC_E_INVALID, f"{name} names a conformer more than once")
+    return idx
+
+
+def check_group_labels(labels, n_conformers, n_groups=None):
+    """``labels`` / ``n_groups`` of the medoids: one integer per conformer (negative: in no group) below ``n_groups``
+    (default: the largest label + 1, at least 1), checked before any device use -> (a contiguous int32 array or None,
+    n_groups)"""
+    if labels is None:
+        return None, 1 if n_groups is None else check_count("n_groups", n_groups, high=2 ** 31 - 1)
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or lab.shape[0] != n_conformers:
+        raise FirecodeHipInputError(FC_E_INVALID, f"labels must hold one entry per conformer ({n_conformers}), got {lab.shape}")
+    if lab.size and (lab.dtype == np.bool_ or not np.issubdtype(lab.dtype, np.integer)):
+        raise FirecodeHipInputError(FC_E_INVALID, f"labels must be integers, got {lab.dtype}")
+    top = int(lab.max()) if lab.size else -1
+    n_groups = max(top + 1, 1) if n_groups is None else check_count("n_groups", n_groups, high=2 ** 31 - 1)
+    if top >= n_groups:
+        raise FirecodeHipInputError(FC_E_INVALID, f"labels holds {top}, which is not below n_groups={n_groups}")
+    return np.ascontiguousarray(np.maximum(lab.astype(np.int64), -1), dtype=np.int32), n_groups
+
+
 class DeviceEnsemble:
     """HBM-resident prepared ensemble (fc_ensemble)."""
 
@@ -701,6 +748,52 @@ class DeviceEnsemble:
         call("fc_bench_knn_cross", self.handle, self._other(other), check_knn_k(k, limit=False), check_max_rmsd_cap(max_rmsd),
              int(reps), C.byref(dev), C.byref(host), C.byref(strips))
         return dev.value, host.value, strips.value
+
+    def subset(self, indices):
+        """The conformers ``indices`` (in that order, repeats allowed) as a new ``DeviceEnsemble`` with this one's atom
+        selection (fc_ensemble_subset): the prepared coordinates are copied on the device, not prepared again, so every
+        distance within the subset has the bits it has here."""
+        idx = check_indices("indices", indices, self.N)
+        sub = DeviceEnsemble.__new__(DeviceEnsemble)
+        sub.N, sub.A_all, sub._atom_mask = int(idx.shape[0]), self.A_all, getattr(self, "_atom_mask", None)
+        sub.W = (max(sub.N, 1) + 63) // 64
+        sub._h = _ens()
+        call("fc_ensemble_subset", self.handle, pi(idx), sub.N, C.byref(sub._h))
+        return sub
+
+    def medoids(self, labels=None, n_groups=None, want_ms=False):
+        """The medoid of every group of conformers under this ensemble's RMSD (fc_ensemble_medoids; the contract is in
+        include/fc_hip.h): ``labels`` (N,) integers, negative = in no group (``None``: one group of all conformers),
+        ``n_groups`` (default: the largest label + 1) -> ``(medoids (n_groups,) int64, sizes (n_groups,) int64,
+        mean_distance (n_groups,), radius (n_groups,), sums_q32 (N,) uint64 in units of 2^-32 A, eccentricity (N,))``;
+        an empty group has medoid -1 and NaN mean and radius.  ``want_ms=True`` appends the kernel's milliseconds."""
+        lab, n_groups = check_group_labels(labels, self.N, n_groups)
+        med, sizes = np.empty(n_groups, dtype=np.int64), np.empty(n_groups, dtype=np.int64)
+        mean, radius = np.empty(n_groups), np.empty(n_groups)
+        sums, ecc = np.zeros(self.N, dtype=np.uint64), np.zeros(self.N)
+        ms = C.c_double(0)
+        call("fc_ensemble_medoids", self.handle, ptr(lab, C.c_int32), n_groups, pi(med), pi(sizes), pf(mean), pf(radius),
+             pw(sums), pf(ecc), C.byref(ms))
+        out = (med, sizes, mean, radius, sums, ecc)
+        return out + (ms.value,) if want_ms else out
+
+    def kmedoids(self, n, init=None, max_iter=50):
+        """``n`` representatives that minimise the summed RMSD of every conformer to its representative, by alternating
+        "assign to the nearest" and "move to the group's medoid" (fc_ensemble_kmedoids; the contract is in
+        include/fc_hip.h).  ``init``: ``n`` distinct conformers to start from (default: the picks of
+        ``select_diverse(n, start=0)``) -> ``(medoids (n,) int64, labels (N,) int32 = position in ``medoids``,
+        distances (N,), cost_q32 (int, units of 2^-32 A), n_iter)``."""
+        n = check_count("n", n)
+        max_iter = check_count("max_iter", max_iter, low=0)
+        if self.N and n > self.N:
+            raise FirecodeHipInputError(FC_E_INVALID, f"n={n} representatives of N={self.N} conformers")
+        start = None if init is None else check_indices("init", init, self.N, distinct=True, count=n)
+        med = np.empty(n, dtype=np.int64)
+        lab, dist = np.empty(self.N, dtype=np.int32), np.empty(self.N)
+        cost, n_iter = C.c_uint64(0), C.c_int64(0)
+        call("fc_ensemble_kmedoids", self.handle, pi(start), n, max_iter, pi(med), ptr(lab, C.c_int32), pf(dist),
+             C.byref(cost), C.byref(n_iter))
+        return (med if self.N else med[:0]), lab, dist, int(cost.value), int(n_iter.value)
 
     def rmsd_matrix(self):
         r = np.zeros((self.N, self.N))

@@ -260,6 +260,11 @@ size_t knn_sym_lds_bytes(int64_t A, int64_t K);  // the workgroup's 16 row confo
 int knn(fc_ensemble *q, fc_ensemble *r, bool cross, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out,
         double *ms_device, int64_t *strips_out, const SymTable *sym = nullptr);
 int warm_knn();
+// ---- fc_medoid.hip ---------------------------------------------------------------------------------------
+int medoid_strips(int64_t N);  // strips a row tile's chunk range is cut into (FC_MEDOID_STRIPS forces it)
+int launch_group_sums(const fc_ensemble *e, const int32_t *seg_end_dev, unsigned long long *out_dev, bool timed);  // S | E
+int ensemble_gather(const fc_ensemble *src, const int32_t *idx_dev, int64_t n, fc_ensemble *out, bool exact_gmax);
+int warm_medoid();
 // ---- fc_tfd_ladder.hip -----------------------------------------------------------------------------------
 int tfd_ladder_device(const int64_t *fm_dev, const int64_t *fm_host, int64_t N, uint8_t *mask_out);
 int pyset_order_pairs_device(const int64_t *pairs_host, int64_t n, int64_t *order_out);

@@ -1,0 +1,281 @@
+// fc_medoid.hip -- per-conformer sums of the ensemble's Kabsch RMSD over the conformers of the same group, the quantity
+// a cluster's medoid and the k-medoids update are read from, over a resident ensemble and without an N x N matrix, for
+// gfx950 (wave64, float64).
+//
+// The contract (include/fc_hip.h, fc_ensemble_medoids) -- d(i, j), i < j, is the d of
+// fc_ensemble_knn: covariance, kabsch_rotation_qcp with the kabsch_rotation fallback, the explicit rotated difference
+// with conformer i as the row (p) and j as the column (q), never the eigenvalue form; q(d) = (uint64) rint(d 2^32):
+//
+//   S[i] = sum of q(d(i, j)) over j != i of i's group,      E[i] = max of d(i, j) over the same j
+//
+// d is evaluated ONCE per unordered pair and handed to both partners, so S is exactly symmetric in a pair; the sums are
+// 64-bit integers, so they do not depend on the order, the launch shape or the arrival of the atomics.
+//
+// k_group_sums is k_knn_tile's tile (fc_knn.hip) without the filter and the lists: 256 threads, four wavefronts x 4 rows
+// from Xa (staged in LDS up to kMedLdsAtoms atoms, read from global memory beyond), 64 columns per chunk, one lane per
+// column, the column's coordinates coalesced from Xs.  It walks a LABEL-SORTED copy of the ensemble (the host's stable
+// order by label, one k_ensemble_gather): the group of a row is then the contiguous range of positions that ends at
+// seg_end[row], and the pairs of a row that count are the columns row < j < seg_end[row] -- the upper triangle of its
+// group's block.  A wavefront's four rows may belong to several small groups: it walks the union of their ranges
+// (seg_end is nondecreasing) and masks per row.  Every pair that counts goes through the explicit pass; a (row, chunk)
+// in which no lane counts is skipped by a ballot.
+// q(d) goes to the row's sum, kept in registers over the strip's chunks, reduced over the wavefront and flushed by one
+// atomicAdd per row and strip; and to the column's sum, the lane's four rows added up first: one 64-bit integer
+// atomicAdd per lane and chunk, to consecutive addresses.  E goes the same way by atomicMax on the bit pattern of the
+// non-negative double (non-negative doubles order like their bits).  About 4 bytes of atomics per alignment.
+// The triangle is balanced over (row tile, column strip) items, heaviest tiles first for a single group: a tile's own
+// chunk range -- not the ensemble's -- is cut into S strips, the grid is one workgroup per item up to 2^20 (grid-stride
+// beyond), and the hardware hands the items out as workgroups retire.  FC_MEDOID_STRIPS=<n> forces S (speed and tests
+// only: the same bits for every value).  No spin-waits, no grid barrier, no float atomics.
+//
+// k_ensemble_gather copies Xs, Xa and G of chosen conformers into a new ensemble; it computes nothing, so the
+// coordinates and G keep their bits: the sorted copy above, the medoid sub-ensemble of the k-medoids assignment and
+// fc_ensemble_subset.
+#include "fc_internal.h"
+#include "fc_kabsch_math.h"
+
+#include <cmath>
+#include <cstdlib>
+
+namespace fc {
+
+constexpr int kMedThreads = 256;
+constexpr int kMedR = 4;                                     // rows per wavefront
+constexpr int kMedTileRows = (kMedThreads / 64) * kMedR;     // rows per workgroup
+constexpr int64_t kMedLdsAtoms = 256;                        // 16 rows x A x 24 B = 96 KiB of LDS (k_knn_tile's stage)
+constexpr int kMedMaxStrips = 64;
+constexpr int kMedItemsPerCu = 32;  // items aimed at per CU: the largest item is then a few percent of a CU's share
+
+template <bool STAGE>
+__global__ void __launch_bounds__(kMedThreads)
+k_group_sums(const double *__restrict__ Xs, const double *__restrict__ Xa, const double *__restrict__ G, int N, int64_t Npad,
+             int A, const int32_t *__restrict__ seg_end, int n_tiles, int S, unsigned long long *__restrict__ sums,
+             unsigned long long *__restrict__ ecc) {
+  extern __shared__ double s_rows[];  // [kMedTileRows][A][3] when STAGE
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int A3 = 3 * A;
+  const double dA = (double)A;
+  const int64_t n_items = (int64_t)n_tiles * S;
+
+  for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+    const int tile = (int)(item / S), s = (int)(item % S);
+    const int row0 = tile * kMedTileRows;
+    // the tile's chunks of 64 columns: the columns behind its first row up to the end of its last row's group
+    const int tb = (row0 + 1) >> 6, te = (seg_end[min(row0 + kMedTileRows - 1, N - 1)] + 63) >> 6;
+    const int nt = max(te - tb, 0);
+    const int c0 = tb + (int)((int64_t)s * nt / S), c1 = tb + (int)((int64_t)(s + 1) * nt / S);
+    if (c0 >= c1) continue;  // (the same for the whole workgroup)
+    if (STAGE) {
+      __syncthreads();  // (the previous item's readers)
+      for (int r = w; r < kMedTileRows; r += kMedThreads / 64) {
+        const double *__restrict__ src = Xa + (int64_t)min(row0 + r, N - 1) * A3;
+        for (int t = lane; t < A3; t += 64) s_rows[r * A3 + t] = src[t];
+      }
+      __syncthreads();
+    }
+    const int wrow = row0 + w * kMedR;
+    if (wrow >= N) continue;  // (wave-uniform; no barrier follows in this item)
+    int row[kMedR], se[kMedR];
+    const double *__restrict__ P[kMedR];
+    double Gi[kMedR], re[kMedR];
+    unsigned long long rs[kMedR];
+#pragma unroll
+    for (int r = 0; r < kMedR; ++r) {
+      row[r] = wrow + r;
+      const int rl = min(row[r], N - 1);
+      P[r] = STAGE ? s_rows + (w * kMedR + r) * A3 : Xa + (int64_t)rl * A3;
+      Gi[r] = G[rl];
+      se[r] = row[r] < N ? seg_end[rl] : 0;  // (a row past the end counts nowhere)
+      rs[r] = 0ull;
+      re[r] = 0.0;
+    }
+    // the wavefront's own part of the strip: behind its first row, up to the end of its last row's group
+    const int wc0 = max(c0, (wrow + 1) >> 6), wc1 = min(c1, (seg_end[min(wrow + kMedR - 1, N - 1)] + 63) >> 6);
+    for (int c = wc0; c < wc1; ++c) {
+      const int j = c * 64 + lane;
+      const int jl = min(j, N - 1);
+      const double *__restrict__ q0 = Xs + jl;
+      const int64_t step = 3 * Npad;
+      // ---- 1. covariances with the 4 rows (k_knn_tile's loop)
+      double B[kMedR][9];
+#pragma unroll
+      for (int r = 0; r < kMedR; ++r)
+#pragma unroll
+        for (int e = 0; e < 9; ++e) B[r][e] = 0.0;
+      {
+        const double *__restrict__ qa = q0;
+#pragma unroll 2
+        for (int a = 0; a < A; ++a, qa += step) {
+          const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
+#pragma unroll
+          for (int r = 0; r < kMedR; ++r) {
+            const double px = P[r][a * 3], py = P[r][a * 3 + 1], pz = P[r][a * 3 + 2];
+            B[r][0] = fma(px, qx, B[r][0]); B[r][1] = fma(px, qy, B[r][1]); B[r][2] = fma(px, qz, B[r][2]);
+            B[r][3] = fma(py, qx, B[r][3]); B[r][4] = fma(py, qy, B[r][4]); B[r][5] = fma(py, qz, B[r][5]);
+            B[r][6] = fma(pz, qx, B[r][6]); B[r][7] = fma(pz, qy, B[r][7]); B[r][8] = fma(pz, qz, B[r][8]);
+          }
+        }
+      }
+      // ---- 2. per row: the rotation and the explicit rotated difference where a lane's pair counts
+      const double Gj = G[jl];
+      unsigned long long cs = 0ull;  // this column's share of the 4 rows
+      double ce = 0.0;
+#pragma unroll
+      for (int r = 0; r < kMedR; ++r) {
+        const bool ok = row[r] < j && j < se[r];  // the upper triangle of the row's group (se <= N)
+        if (__ballot(ok) == 0) continue;          // (wave-uniform)
+        const double GG = Gi[r] + Gj;
+        double R[9];
+        if (!kabsch_rotation_qcp(B[r], GG, R)) (void)kabsch_rotation(B[r], R);
+        double ssq = 0.0;
+        const double *__restrict__ qa = q0;
+#pragma unroll 2
+        for (int a = 0; a < A; ++a, qa += step) {
+          const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
+          const double px = P[r][a * 3], py = P[r][a * 3 + 1], pz = P[r][a * 3 + 2];
+          const double dx = px - (R[0] * qx + R[1] * qy + R[2] * qz);
+          const double dy = py - (R[3] * qx + R[4] * qy + R[5] * qz);
+          const double dz = pz - (R[6] * qx + R[7] * qy + R[8] * qz);
+          ssq += dx * dx + dy * dy + dz * dz;
+        }
+        const double d = sqrt(ssq / dA);
+        if (ok) {
+          const unsigned long long qd = (unsigned long long)rint(d * 4294967296.0);
+          rs[r] += qd;
+          cs += qd;
+          re[r] = fmax(re[r], d);
+          ce = fmax(ce, d);
+        }
+      }
+      if (cs != 0ull) atomicAdd(&sums[j], cs);  // (cs != 0 only where a pair counted: j < N)
+      if (ce > 0.0) atomicMax(&ecc[j], (unsigned long long)__double_as_longlong(ce));
+    }
+    // ---- 3. the rows' sums over the strip: one atomic per row
+#pragma unroll
+    for (int r = 0; r < kMedR; ++r) {
+      unsigned long long v = rs[r];
+      double m = re[r];
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        v += __shfl_xor(v, o);
+        m = fmax(m, __shfl_xor(m, o));
+      }
+      if (lane == 0 && row[r] < N) {
+        if (v != 0ull) atomicAdd(&sums[row[r]], v);
+        if (m > 0.0) atomicMax(&ecc[row[r]], (unsigned long long)__double_as_longlong(m));
+      }
+    }
+  }
+}
+
+// strips a tile's chunk range is cut into (FC_MEDOID_STRIPS=<n> forces it): enough items to hand out evenly
+int medoid_strips(int64_t N) {
+  const int64_t n_chunks = std::max<int64_t>(1, ceil_div(N, 64));
+  int64_t S = 0;
+  if (const char *v = getenv("FC_MEDOID_STRIPS")) {
+    char *end = nullptr;
+    const long long f = strtoll(v, &end, 10);
+    if (end != v && *end == 0 && f >= 1) S = std::min<long long>(f, kMedMaxStrips);
+  }
+  if (S == 0) {
+    const int64_t tiles = std::max<int64_t>(1, ceil_div(N, kMedTileRows));
+    S = std::min<int64_t>(kMedMaxStrips, ceil_div((int64_t)kMedItemsPerCu * std::max(1, ctx().n_cu), tiles));
+  }
+  return (int)std::max<int64_t>(1, std::min(S, n_chunks));
+}
+
+template <bool STAGE>
+static int launch_group_sums_as(const fc_ensemble *e, const int32_t *seg_end_dev, int n_tiles, int S, unsigned long long *sums_dev,
+                                unsigned long long *ecc_dev) {
+  const size_t lds = STAGE ? (size_t)kMedTileRows * e->A * 3 * sizeof(double) : 0;
+  FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_group_sums<STAGE>), lds, "k_group_sums"));
+  const unsigned gx = (unsigned)std::min<int64_t>((int64_t)n_tiles * S, (int64_t)1 << 20);
+  hipLaunchKernelGGL((k_group_sums<STAGE>), dim3(gx), dim3(kMedThreads), lds, ctx().stream, e->Xs.as<double>(),
+                     e->Xa.as<double>(), e->G.as<double>(), (int)e->N, e->Npad, (int)e->A, seg_end_dev, n_tiles, S, sums_dev,
+                     ecc_dev);
+  return check_launch("k_group_sums");
+}
+
+// S (out_dev[0 .. N)) and E (out_dev[N .. 2 N), the doubles' bit patterns), zeroed here, of the label-sorted ensemble e,
+// 1 <= N < 2^31 - 256: seg_end_dev[i] = the end of the group of position i.  Enqueued only; timed: the context's events
+// ev0 / ev1 are recorded around the zeroing and the kernel, for the caller to read behind its wait.
+int launch_group_sums(const fc_ensemble *e, const int32_t *seg_end_dev, unsigned long long *out_dev, bool timed) {
+  Context &c = ctx();
+  const int S = medoid_strips(e->N);
+  const int n_tiles = (int)ceil_div(e->N, kMedTileRows);
+  if (timed) FC_HIP_TRY(hipEventRecord(c.ev0, c.stream));
+  FC_HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)e->N * 2 * sizeof(unsigned long long), c.stream));
+  FC_TRY((e->A <= kMedLdsAtoms ? launch_group_sums_as<true> : launch_group_sums_as<false>)(e, seg_end_dev, n_tiles, S, out_dev,
+                                                                                         out_dev + e->N));
+  if (timed) FC_HIP_TRY(hipEventRecord(c.ev1, c.stream));
+  return FC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// k_ensemble_gather: conformer m of the new ensemble is conformer idx[m] of the old one -- Xs (zero beyond n and beyond
+// the selected atoms, as k_prep leaves it), Xa and G, copied; gmax_bits (may be NULL): the largest G of the copy
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_ensemble_gather(const double *__restrict__ Xs_in, const double *__restrict__ Xa_in, const double *__restrict__ G_in,
+                  int64_t Npad_in, const int32_t *__restrict__ idx, int64_t n, int64_t Npad_out, int64_t A,
+                  double *__restrict__ Xs_out, double *__restrict__ Xa_out, double *__restrict__ G_out,
+                  unsigned long long *__restrict__ gmax_bits) {
+  const int64_t A3 = 3 * A;
+  const int64_t n_xs = ((A + 3) & ~(int64_t)3) * 3 * Npad_out, n_xa = n * A3;
+  const int64_t total = n_xs > n_xa ? n_xs : n_xa;  // (n_xs >= Npad_out)
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    if (e < n_xs) {
+      const int64_t r = e / Npad_out, m = e - r * Npad_out;
+      Xs_out[e] = (r < A3 && m < n) ? Xs_in[r * Npad_in + idx[m]] : 0.0;
+    }
+    if (e < n_xa) {
+      const int64_t m = e / A3, t = e - m * A3;
+      Xa_out[e] = Xa_in[(int64_t)idx[m] * A3 + t];
+    }
+    if (e < Npad_out) {
+      const double g = e < n ? G_in[idx[e]] : 0.0;
+      G_out[e] = g;
+      if (gmax_bits != nullptr && g == g) atomicMax(gmax_bits, (unsigned long long)__double_as_longlong(g));
+    }
+  }
+}
+
+// `out` (a fresh fc_ensemble) becomes the ensemble of the conformers idx_dev[0 .. n) of src, 0 <= idx < src->N, n >= 0.
+// exact_gmax: the largest G of the copy is found and waited for (fc_ensemble_subset); otherwise src's stands in -- never
+// smaller, which is the side every user of g_max is conservative on -- and nothing is waited for.
+int ensemble_gather(const fc_ensemble *src, const int32_t *idx_dev, int64_t n, fc_ensemble *out, bool exact_gmax) {
+  out->epoch = src->epoch;
+  out->N = n, out->A = src->A;
+  out->Npad = ceil_div(std::max<int64_t>(n, 1), 64) * 64;
+  out->W = out->Npad / 64;
+  out->sel_host = src->sel_host;
+  FC_TRY(out->Xs.reserve((size_t)((out->A + 3) / 4 * 4) * 3 * out->Npad * sizeof(double)));
+  FC_TRY(out->G.reserve((size_t)out->Npad * sizeof(double)));
+  FC_TRY(out->Xa.reserve((size_t)std::max<int64_t>(n, 1) * out->A * 3 * sizeof(double)));
+  FC_TRY(out->counters.reserve(kCounters * sizeof(uint64_t)));
+  FC_HIP_TRY(hipMemsetAsync(out->counters.p, 0, kCounters * sizeof(uint64_t), ctx().stream));
+  auto *gmax_dev = reinterpret_cast<unsigned long long *>(out->counters.p) + (kCounters - 1);
+  const int64_t total = std::max(((out->A + 3) / 4 * 4) * 3 * out->Npad, n * out->A * 3);
+  const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(total, 256), (int64_t)1 << 16);
+  hipLaunchKernelGGL(k_ensemble_gather, dim3(grid), dim3(256), 0, ctx().stream, src->Xs.as<double>(), src->Xa.as<double>(),
+                     src->G.as<double>(), src->Npad, idx_dev, n, out->Npad, out->A, out->Xs.as<double>(), out->Xa.as<double>(),
+                     out->G.as<double>(), exact_gmax ? gmax_dev : nullptr);
+  FC_TRY(check_launch("k_ensemble_gather"));
+  out->g_max = src->g_max;
+  if (exact_gmax) {
+    unsigned long long bits = 0;
+    FC_TRY(d2h(&bits, gmax_dev, sizeof bits));
+    FC_TRY(sync());
+    std::memcpy(&out->g_max, &bits, sizeof(double));
+    FC_HIP_TRY(hipMemsetAsync(gmax_dev, 0, sizeof(unsigned long long), ctx().stream));
+  }
+  return FC_OK;
+}
+
+__global__ void k_warm_medoid() {}
+int warm_medoid() {
+  hipLaunchKernelGGL(k_warm_medoid, dim3(1), dim3(64), 0, ctx().stream);
+  return check_launch("k_warm_medoid");
+}
+
+}  // namespace fc

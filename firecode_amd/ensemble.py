@@ -137,6 +137,38 @@ class Ensemble:
                 f"{perf_counter() - t0:.3f} s)")
         return sel
 
+    def medoids(self, labels=None, heavy_atoms_only=True):
+        """The structure that stands for each group: the member with the smallest summed heavy-atom RMSD to the other
+        members (``firecode_amd.pruner.medoids_by_rmsd``).  ``labels``: the ``labels`` of ``cluster_by_rmsd``,
+        ``dbscan_by_rmsd`` or ``butina_by_rmsd`` (negative: in no group); ``None``: the whole ensemble is one group.
+        Returns the ``RmsdMedoids``; the ensemble is not masked."""
+        from firecode_amd.pruner import medoids_by_rmsd
+
+        return medoids_by_rmsd(self.coords, self.atoms, labels=labels, heavy_atoms_only=heavy_atoms_only)
+
+    def kmedoids_selection(self, n, heavy_atoms_only=True, max_iter=50, verbose=True):
+        """Keep the ``n`` most representative structures: k-medoids under the heavy-atom RMSD
+        (``firecode_amd.pruner.kmedoids_by_rmsd``), started from the ``n`` most diverse ones.  Where
+        ``diversity_selection`` keeps the extremes, this keeps the centres: the ``n`` structures with the smallest mean
+        distance of every structure to its representative.  The kept structures stay in the order of the
+        representatives and ``energies`` follow them.  Returns the ``RmsdKMedoids`` of the ensemble as it was."""
+        from firecode_amd._lib import check_count
+        from firecode_amd.pruner import kmedoids_by_rmsd
+
+        n = check_count("n", n)
+        n0, t0 = len(self.coords), perf_counter()
+        use_en = len(self.energies) == n0 and n0 > 0
+        sel = kmedoids_by_rmsd(self.coords, self.atoms, min(n, n0) if n0 else n, max_iter=max_iter,  # (n > N: all of them)
+                               heavy_atoms_only=heavy_atoms_only)
+        self.coords = self.coords[sel.medoids]
+        if use_en:
+            self.apply_mask(("energies",), sel.medoids)
+        if verbose and self.logfunction is not None:
+            mean = sel.cost / n0 if n0 else 0.0
+            self.logfunction(f"Kept {len(sel.medoids)} of {n0} candidates as RMSD medoids (mean distance to the representative "
+                             f"{mean:.3f} A, {sel.n_iter} assignments, {perf_counter() - t0:.3f} s)")
+        return sel
+
     def nearest_neighbours(self, k, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
         """The ``k`` nearest neighbours of every structure under the heavy-atom RMSD of the other RMSD stages
         (``firecode_amd.pruner.knn_by_rmsd``).  Returns the ``RmsdNeighbours``, whose ``k_distances(min_samples - 1)`` is

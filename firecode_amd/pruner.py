@@ -395,6 +395,71 @@ def ensemble_coverage(structures, references, atoms, max_rmsd, heavy_atoms_only=
     return EnsembleCoverage.from_neighbours(nb, max_rmsd)
 
 
+RmsdMedoids = namedtuple("RmsdMedoids", ["medoids", "sizes", "mean_distance", "radius", "sums", "eccentricity"])
+RmsdKMedoids = namedtuple("RmsdKMedoids", ["medoids", "labels", "distances", "cost", "n_iter"])
+
+Q32 = 2.0 ** -32  # the unit of the integer sums of the medoid calls (include/fc_hip.h: q(d) = rint(d * 2^32))
+
+
+def _medoid_inputs(structures, atoms, heavy_atoms_only):
+    structures, atoms = _structures_and_atoms(structures, atoms)
+    heavy = (atoms != "H") if heavy_atoms_only else np.ones(len(atoms), dtype=bool)
+    if not heavy.any():
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, "the atom selection is empty (no heavy atom)")
+    return structures, heavy
+
+
+def medoids_by_rmsd(structures, atoms, labels=None, heavy_atoms_only=True):
+    """Which conformer stands for each group: the medoid, the member with the smallest summed heavy-atom Kabsch RMSD
+    (the RMSD of ``prune_by_rmsd``: centred, ``rmsd_and_max(...)[0]``) to the other members of its group, the lowest
+    index on ties -- on the GPU, without an N x N matrix (fc_ensemble_medoids; the contract is written out in
+    include/fc_hip.h).  ``labels``: one integer per conformer, a negative one = in no group -- the ``labels`` of
+    ``RmsdClusters``, ``RmsdDbscan`` (-1 is noise) and ``RmsdButina`` as they come; ``None``: the whole ensemble is one
+    group.
+
+    Returns ``RmsdMedoids(medoids, sizes, mean_distance, radius, sums, eccentricity)``: per group (largest label + 1 of
+    them) the medoid's index, the member count, the medoid's mean distance to the other members (0 for a singleton) and
+    its largest (the group's radius around it); per conformer the summed distance to the other members of its group
+    in A (float64; exact multiples of 2^-32: the sums are made in integers and are the same bits on every run) and
+    the largest such distance.  An empty group id has medoid -1, size 0 and NaN mean and radius."""
+    structures, heavy = _medoid_inputs(structures, atoms, heavy_atoms_only)
+    N = structures.shape[0]
+    lab, n_groups = L.check_group_labels(labels, N)
+    if N == 0:
+        nan = np.full(n_groups, np.nan)
+        return RmsdMedoids(np.full(n_groups, -1, dtype=np.int64), np.zeros(n_groups, dtype=np.int64), nan, nan.copy(),
+                           np.zeros(0), np.zeros(0))
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
+        med, sizes, mean, radius, sums, ecc = ens.medoids(lab, n_groups)
+    return RmsdMedoids(med, sizes, mean, radius, sums.astype(np.float64) * Q32, ecc)
+
+
+def kmedoids_by_rmsd(structures, atoms, n, init=None, max_iter=50, heavy_atoms_only=True):
+    """``n`` representative conformers: k-medoids under the heavy-atom Kabsch RMSD of ``prune_by_rmsd`` -- the ``n``
+    conformers that (locally) minimise the mean distance of every conformer to its representative -- on the GPU
+    (fc_ensemble_kmedoids; the contract is written out in include/fc_hip.h): starting from ``init`` (``n`` distinct
+    indices; default: the ``n`` picks of ``select_diverse(..., n=n, start=0)``, the extremes of the ensemble), assign
+    every conformer to its nearest representative and move each representative to the medoid of its group, until the
+    cost stops falling or ``max_iter`` moves have been made.  ``select_diverse`` answers "the n most different",
+    this "the n most typical".
+
+    Returns ``RmsdKMedoids(medoids, labels, distances, cost, n_iter)``: medoids (n,) int64; labels (N,) int32, the
+    position in ``medoids`` of each conformer's representative; distances (N,) to it (0 for a representative); cost in
+    A, the sum of the distances rounded to 2^-32 A each (the same bits on every run); n_iter, the assignments made."""
+    structures, heavy = _medoid_inputs(structures, atoms, heavy_atoms_only)
+    N = structures.shape[0]
+    n = L.check_count("n", n)
+    max_iter = L.check_count("max_iter", max_iter, low=0)
+    if N == 0:
+        return RmsdKMedoids(np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0), 0.0, 0)
+    if n > N:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"n={n} representatives of N={N} conformers")
+    start = None if init is None else L.check_indices("init", init, N, distinct=True, count=n)
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
+        med, lab, dist, cost, n_iter = ens.kmedoids(n, init=start, max_iter=max_iter)
+    return RmsdKMedoids(med, lab, dist, cost * Q32, n_iter)
+
+
 RmsdClusters = namedtuple("RmsdClusters", ["labels", "representatives", "sizes"])
 
 

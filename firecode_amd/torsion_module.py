@@ -187,12 +187,26 @@ def most_diverse_conformers(n, structures, seed=None, method="random", atoms=Non
     (``firecode_amd.pruner.select_diverse(..., n=n, start=0)``), in selection order -- also with at most n structures,
     where that is all of them; ``atoms`` (one symbol per atom) makes it the heavy-atom RMSD, ``None`` aligns all atoms.
     ``symmetry=`` / ``prune_enantiomers=True``: as in ``select_diverse`` (a graph needs ``atoms``); an input error with
-    ``method="random"``."""
-    if method not in ("random", "rmsd"):
-        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"method={method!r}: 'random' or 'rmsd'")
+    ``method="random"``.
+
+    ``method="kmedoids"``: the n most REPRESENTATIVE structures instead -- k-medoids under the same RMSD, started from the
+    ``method="rmsd"`` picks (``firecode_amd.pruner.kmedoids_by_rmsd``), in the order of the representatives; all of
+    them when there are at most n.  It has no symmetry- or mirror-aware form: the two keywords are an input error."""
+    if method not in ("random", "rmsd", "kmedoids"):
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"method={method!r}: 'random', 'rmsd' or 'kmedoids'")
     enant = _diversity_keywords("method", method, symmetry, prune_enantiomers)
+    if method == "kmedoids" and (symmetry is not None or enant):
+        raise L.FirecodeHipInputError(
+            L.FC_E_INVALID, "symmetry= / prune_enantiomers= belong to method='rmsd': k-medoids has no such form")
     if len(structures) == 0 or (len(structures) <= n and method == "random"):
         return list(np.array(structures))
+    if method == "kmedoids":
+        from firecode_amd.pruner import kmedoids_by_rmsd
+
+        X = L.f64(np.array(structures))
+        sym = np.array(["C"] * X.shape[1]) if atoms is None else np.asarray(atoms)
+        sel = kmedoids_by_rmsd(X, sym, min(L.check_count("n", n), len(X)), heavy_atoms_only=atoms is not None)
+        return list(X[sel.medoids])
     if method == "rmsd":
         from firecode_amd.pruner import select_diverse
 

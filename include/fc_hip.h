@@ -269,6 +269,63 @@ int fc_ensemble_knn_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int6
                          int32_t *indices_out, double *dist_out);
 int fc_ensemble_knn_cross_perm(fc_ensemble *queries, fc_ensemble *refs, const int32_t *perms, int64_t K, int64_t A_sel,
                                int mirror, int64_t k, double max_rmsd, int32_t *indices_out, double *dist_out);
+/* ---- medoids and k-medoids under the RMSD: which conformer stands for a group ----
+ * The distance.  d(i, j) for i < j is the d of fc_ensemble_knn, computed as k_knn_tile computes the value it writes out:
+ * the covariance, the rotation from the Newton eigenvalue and the adjugate (the Jacobi sweeps where the eigenvalue is not
+ * clearly simple), the explicit rotated difference with conformer i as the row (p) and j as the column (q); never the
+ * eigenvalue form.  d is evaluated ONCE per unordered pair and used for both partners.
+ *   q(d) = (uint64) rint(d * 2^32)          the distance in units of 2^-32 A
+ * Per-conformer sums and the k-medoids cost are sums of q values in 64-bit integers: they do not depend on the order, the
+ * launch shape (FC_MEDOID_STRIPS=<n>) or the arrival of atomics -- the same bits every time -- and the two members of a
+ * two-member group tie exactly.
+ *
+ * fc_ensemble_medoids.  labels: (N) int32, a negative label = in no group, labels[i] < n_groups; NULL = one group (0) of
+ * all conformers (the other n_groups - 1 groups are empty).  The labels of fc_rmsd_clusters, fc_rmsd_dbscan (-1 = noise)
+ * and fc_rmsd_butina are taken as they come.
+ *   S[i] = sum of q(d(i, j)) over j != i with labels[j] == labels[i] >= 0
+ *   E[i] = max of d(i, j) over the same j (a double; a max is exact); both 0 for a singleton and an unlabelled conformer
+ *   for each group c < n_groups:  medoid[c] = the member with the smallest S, the lowest index on ties;
+ *     size[c] = the member count;  mean[c] = S[medoid] 2^-32 / (size - 1), 0 for a singleton;  radius[c] = E[medoid];
+ *     an empty group: medoid -1, size 0, mean and radius NaN.
+ * Outputs: medoids_out, sizes_out, mean_out, radius_out (n_groups each, required); sums_q32_out (N, the S) and ecc_out
+ * (N, the E), each or NULL; ms_kernel (or NULL): HIP-event time of the sums kernel with the zeroing of its outputs (0 when
+ * no group has two members: then no device is used).
+ *
+ * fc_ensemble_kmedoids.  n representatives by the alternating form (Park & Jun 2009); init: n distinct conformers, or NULL:
+ * the picks of fc_ensemble_select_diverse(n_max = n, start = 0).
+ *   M_0 = init
+ *   for t = 0, 1, ...:
+ *     assign: (lab_t[j], dist_t[j]) = the nearest member of M_t to j, ties to the earlier position in M_t -- the k = 1
+ *             list of fc_ensemble_knn_cross(ens, fc_ensemble_subset(ens, M_t)), bit for bit; a medoid gets its own
+ *             position and distance 0, set by index
+ *     cost_t = sum over j of q(dist_t[j])
+ *     if t > 0 and cost_t >= cost_{t-1}: return iteration t-1's (M, lab, dist, cost)
+ *     if t == max_iter:                  return iteration t's
+ *     M_{t+1}[c] = the medoid of {j : lab_t[j] == c}   (the rule of fc_ensemble_medoids)
+ *     if M_{t+1} == M_t:                 return iteration t's
+ * The integer costs fall strictly until the loop ends, so it ends (the assignment and the sums round d differently in the
+ * last bits: row and column change places); the cost returned is the smallest seen.  Outputs, all required: medoids_out
+ * (n), labels_out (N) int32 = position in medoids_out, dist_out (N), *cost_q32_out, *n_iter_out = assignments made.
+ *
+ * fc_ensemble_subset.  *out = a new ensemble (fc_ensemble_destroy) of the conformers indices[0 .. n), in that order,
+ * repeats allowed, n >= 0: the prepared coordinates and G are COPIED, not recomputed -- every distance within the subset
+ * has the bits it has in `ens`.  The atom selection is that of `ens`.
+ *
+ * Refused with FC_E_INVALID before any device use, the message naming the argument: a NULL ens or required output;
+ * n_groups < 1; labels[i] >= n_groups; n < 1 (subset: n < 0) or n > N; max_iter < 0; init or indices outside [0, N), or
+ * repeated within init; an ensemble of an earlier context epoch.  The scalar arguments (n_groups, n, max_iter) are judged
+ * first, then the pointers, then what needs N.  N = 0 is an empty success (medoids: every group empty;
+ * k-medoids: cost 0, 0 iterations, nothing else written).  FC_E_LIMIT: N >= 2^31 - 256; and, once the ensemble's largest
+ * G is known, a group too large for the 64-bit sum: (largest size) (ceil(sqrt(4 g_max / A)) + 1) 2^32 >= 2^63 (k-medoids
+ * judges N, which no group exceeds) -- tens of millions of members at molecular coordinates.
+ * Not offered: symmetry- and mirror-aware forms, a multi-GPU form, between-group sums (silhouettes), PAM's swap phase. */
+int fc_ensemble_subset(fc_ensemble *ens, const int64_t *indices, int64_t n, fc_ensemble **out);
+int fc_ensemble_medoids(fc_ensemble *ens, const int32_t *labels, int64_t n_groups, int64_t *medoids_out, int64_t *sizes_out,
+                        double *mean_out, double *radius_out, uint64_t *sums_q32_out /* N or NULL */,
+                        double *ecc_out /* N or NULL */, double *ms_kernel /* or NULL */);
+int fc_ensemble_kmedoids(fc_ensemble *ens, const int64_t *init /* n or NULL */, int64_t n, int64_t max_iter,
+                         int64_t *medoids_out, int32_t *labels_out, double *dist_out, uint64_t *cost_q32_out,
+                         int64_t *n_iter_out);
 /* a9: get_alignment_matrix(p, q) -- prism_pruner.rmsd; call site
  * hypermolecule_class.py:77.  M (3,3) row-major, applied as (M @ q.T).T */
 int fc_alignment_matrices(const double *p, const double *q, int64_t n_pairs, int64_t A,
