@@ -1,6 +1,6 @@
 """Degenerate geometries for the nearest-neighbour and diverse-selection kernels (k_knn_tile, k_knn_tile_sym,
-k_diverse_step and its symmetry form), with closed-form distances where the geometry has one.  Test infrastructure: the
-product never imports it.
+k_diverse_step and its symmetry form) and for the prunes, the refine and the medoids (test_gpu_degenerate_prunes.py), with
+closed-form distances where the geometry has one.  Test infrastructure: the product never imports it.
 
 Every generator is seeded and gives every conformer a random proper rotation and a translation; the chains are also
 reversed in atom order for a random half.  The kinds and what makes them hard:
@@ -15,6 +15,11 @@ reversed in atom order for a random half.  The kinds and what makes them hard:
   mirrored_tops C3-symmetric chiral structures, longest along the axis, and their mirror images: a structure against its
                 own image has B = diag(c1, c2, -c2), a DOUBLE largest root c1 on a covariance of full rank; without the
                 mirror flag the image is far, with it at 0 (the oracle's rows are the reference)
+
+  scaled        one centred base structure b times a_i = 1 +- d_i / rms(b), the last conformer b itself ("the reference"):
+                a_i a_j b^T b is symmetric positive semidefinite, the best rotation is the identity whatever the rank of b;
+                rmsd(i, j) = |a_i - a_j| rms(b), maxdev(i, j) = |a_i - a_j| max_a |b_a|.  With d a hair on either side of
+                a cap, every (conformer, reference) pair sits at a known distance from a threshold of the prune
 
 tests/test_degenerate_ref.py checks the closed forms against the oracle's rows."""
 
@@ -148,3 +153,70 @@ def mirrored_tops(N, A, seed=5, sigma=0.15):
     image_of[:N - n0] = np.arange(n0, N)
     image_of[n0:] = np.arange(N - n0)
     return place(np.concatenate([X, Y]), rng), image_of
+
+
+# ---- one structure at many scales: pairs at a known distance from a threshold ---------------------------------------------
+SCALED_BASES = ("full", "planar", "line", "full224")
+KNIFE_DELTA = (1e-8, 3e-5)  # A: how far inside / outside the cap the knife-edge families put their pairs
+
+
+def scaled_base(name, seed=7):
+    """(A, 3), centred: ``full`` 23 atoms of full rank (an odd count: a padded row), ``planar`` 12 atoms with z = 0,
+    ``line`` 40 atoms 1.4 A apart on the x axis, ``full224`` 224 atoms of full rank (the 32-column screen tiles)"""
+    if name in ("full", "full224"):
+        b = syn.continuous_ensemble(1, 23 if name == "full" else 224, seed)[0]
+    elif name == "planar":
+        b = np.zeros((12, 3))
+        b[:, :2] = np.random.default_rng(seed).normal(scale=2.0, size=(12, 2)) * np.array([1.6, 1.0])
+    elif name == "line":
+        b = np.zeros((40, 3))
+        b[:, 0] = 1.4 * np.arange(40)
+    else:
+        raise KeyError(name)
+    return np.ascontiguousarray(b - b.mean(axis=0, keepdims=True))
+
+
+def base_rms(base):
+    return float(np.sqrt((np.asarray(base, dtype=np.float64) ** 2).sum(axis=1).mean()))
+
+
+def base_reach(base):
+    """max_a |b_a|: the atom farthest from the centroid"""
+    return float(np.sqrt((np.asarray(base, dtype=np.float64) ** 2).sum(axis=1).max()))
+
+
+def knife_offsets(cap, n):
+    """(n,) distances from the reference: the first half at cap - delta, the second at cap + delta, delta log-spaced over
+    KNIFE_DELTA"""
+    delta = np.logspace(np.log10(KNIFE_DELTA[0]), np.log10(KNIFE_DELTA[1]), n // 2)
+    return np.concatenate([cap - delta, cap + delta[:n - n // 2]])
+
+
+def scaled_family(base, d, seed):
+    """-> (X (n + 1, A, 3), a (n + 1,)): conformer i = a_i b under a random proper rotation and a translation,
+    a_i = 1 +- d_i / rms(b) with the sign drawn per conformer; the last conformer, a = 1, is the reference"""
+    rng = np.random.default_rng(seed)
+    b, d = np.asarray(base, dtype=np.float64), np.asarray(d, dtype=np.float64)
+    a = np.append(1.0 + rng.choice([-1.0, 1.0], size=len(d)) * d / base_rms(b), 1.0)
+    return place(a[:, None, None] * b[None], rng), a
+
+
+def scaled_rmsd(base, a):
+    """(n, n): |a_i - a_j| rms(b)"""
+    a = np.asarray(a, dtype=np.float64)
+    return np.abs(a[:, None] - a[None, :]) * base_rms(base)
+
+
+def scaled_maxdev(base, a):
+    """(n, n): |a_i - a_j| max_a |b_a|"""
+    a = np.asarray(a, dtype=np.float64)
+    return np.abs(a[:, None] - a[None, :]) * base_reach(base)
+
+
+def knife_thresholds(base, cap, edge):
+    """(max_rmsd, max_dev) that put the (conformer, reference) pairs of ``knife_offsets(cap, .)`` at the edge of the RMSD
+    test (``edge="rmsd"``: the max deviation, about 1.5 RMSD on these bases, is clear) or of the max-deviation test
+    (``edge="dev"``: the RMSD is clear, and pairs of opposite sign, 2 cap apart, are out on the RMSD)"""
+    if edge == "rmsd":
+        return cap, 4.0 * cap
+    return 1.5 * cap, base_reach(base) / base_rms(base) * cap

@@ -1,6 +1,6 @@
 """tests/degenerate_ref.py against the oracle (no GPU): the closed-form distances of the one-atom, two-atom and collinear
-kinds equal the oracle's Kabsch rows to 1e-12, the planar and mirrored kinds have the geometry they promise, and every
-generator is seeded."""
+kinds and of the scaled family equal the oracle's Kabsch rows to 1e-12, the planar and mirrored kinds have the geometry
+they promise, and every generator is seeded."""
 
 import numpy as np
 import pytest
@@ -8,9 +8,12 @@ import pytest
 import degenerate_ref as dg
 import diverse_ref as dr
 import diverse_sym_ref as ds
+import enant_ref as er
 import knn_cross_ref as xr
 import knn_ref
+import knn_sym_ref as ks
 import symm_ref as sr
+from oracle import cpu_ref as o
 
 CLOSED = 1e-12
 CHAIN = {"spacing": 1.4, "jitter": 0.02, "stretch": 0.05}
@@ -96,10 +99,53 @@ def test_mirrored_tops_have_a_double_root_against_their_image():
         assert others.min() < plain[i, j]  # without the flag the image is not the nearest neighbour
 
 
+GAP = 1e-9
+
+
+@pytest.mark.parametrize("cap", [0.05, 0.25])
+@pytest.mark.parametrize("name", dg.SCALED_BASES)
+def test_scaled_family_closed_forms(name, cap):
+    """128 conformers a hair inside and outside ``cap`` of the reference: the closed-form RMSD and max-deviation matrices
+    against the oracle's; every pair more than GAP from both thresholds under both threshold settings, and the oracle's
+    own bits -- plain, with the mirror flag, under the reversal table -- are the closed form's; under the reversal table
+    with the mirror flag the distance is the plain one"""
+    b = dg.scaled_base(name)
+    A = len(b)
+    assert np.abs(b.mean(axis=0)).max() < 1e-13 and A == {"full": 23, "planar": 12, "line": 40, "full224": 224}[name]
+    assert np.linalg.matrix_rank(b, tol=1e-9) == {"full": 3, "planar": 2, "line": 1, "full224": 3}[name]
+    assert 1.0 < dg.base_reach(b) / dg.base_rms(b) < 4.0  # (max_dev = 4 cap is clear at the RMSD edge)
+    X, a = dg.scaled_family(b, dg.knife_offsets(cap, 128), seed=A)
+    assert X.shape == (129, A, 3) and a[-1] == 1.0 and 40 < (a[:-1] > 1.0).sum() < 88
+    R, M = dg.scaled_rmsd(b, a), dg.scaled_maxdev(b, a)
+    assert np.abs(R[:-1, -1] - dg.knife_offsets(cap, 128)).max() < 1e-14
+    atoms = np.array(["C"] * A)
+    _, R0, M0 = o.rmsd_similarity_matrix(X, atoms, cap)
+    print(f"{name} cap={cap}: max|R - oracle|={np.abs(R - R0).max():.3g} max|M - oracle|={np.abs(M - M0).max():.3g}")
+    assert np.abs(R - R0).max() < CLOSED and np.abs(M - M0).max() < CLOSED
+    iu = np.triu_indices(129, 1)
+    for edge in ("rmsd", "dev"):
+        thr, dev = dg.knife_thresholds(b, cap, edge)
+        gap = min(np.abs(R[iu] - thr).min(), np.abs(M[iu] - dev)[R[iu] < thr].min())
+        S = (R < thr) & (M < dev) & ~np.eye(129, dtype=bool)
+        edge_pairs = S[:-1, -1]
+        print(f"  {edge} edge: thr={thr:.6g} dev={dev:.6g} gap={gap:.3g}, {int(edge_pairs.sum())} of 128 inside")
+        assert gap > GAP and np.array_equal(edge_pairs, np.arange(128) < 64)
+        assert np.array_equal(o.rmsd_similarity_matrix(X, atoms, thr, dev)[0], S)
+        mats = er.similarity(X, atoms, thr, dev)
+        assert mats.min_gap > GAP and np.array_equal(mats.S, S)
+        if A <= 40:
+            sym = sr.similarity(X, atoms, sr.path_table(A), thr, dev)
+            assert sym.min_gap > GAP and np.array_equal(sym.S, S)
+    if A <= 40:
+        rows = np.arange(0, 129, 8)
+        assert np.abs(ks.distance_rows(X[rows], X, sr.path_table(A), mirror=True) - R[rows]).max() < CLOSED
+
+
 def test_generators_are_seeded():
     for make in (lambda s: dg.one_atom(5, seed=s), lambda s: dg.two_atoms(5, dg.two_atoms_lengths(5), seed=s),
                  lambda s: dg.collinear(5, 13, CHAIN, seed=s)[0], lambda s: dg.planar(5, 12, seed=s),
-                 lambda s: dg.mirrored_tops(5, 12, seed=s)[0]):
+                 lambda s: dg.mirrored_tops(5, 12, seed=s)[0],
+                 lambda s: dg.scaled_family(dg.scaled_base("full"), dg.knife_offsets(0.25, 5), seed=s)[0]):
         assert np.array_equal(make(3), make(3)) and not np.array_equal(make(3), make(4))
 
 
