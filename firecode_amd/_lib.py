@@ -203,6 +203,8 @@ _SIGNATURES = {
     "fc_ensemble_subset": [_ens, _p_i64, _i64, C.POINTER(_ens)],
     "fc_ensemble_medoids": [_ens, C.POINTER(C.c_int32), _i64, _p_i64, _p_i64, _p_f64, _p_f64, _p_u64, _p_f64, _p_f64],
     "fc_ensemble_kmedoids": [_ens, _p_i64, _i64, _i64, _p_i64, C.POINTER(C.c_int32), _p_f64, _p_u64, _p_i64],
+    "fc_ensemble_silhouette": [_ens, C.POINTER(C.c_int32), _i64, _p_f64, _p_f64, _p_f64, C.POINTER(C.c_int32), _p_f64, _p_i64,
+                               _p_f64, _p_f64],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("fc_last_error",)
@@ -794,6 +796,23 @@ class DeviceEnsemble:
         call("fc_ensemble_kmedoids", self.handle, pi(start), n, max_iter, pi(med), ptr(lab, C.c_int32), pf(dist),
              C.byref(cost), C.byref(n_iter))
         return (med if self.N else med[:0]), lab, dist, int(cost.value), int(n_iter.value)
+
+    def silhouette(self, labels=None, n_groups=None, want_ms=False):
+        """The silhouette of every labelled conformer under this ensemble's RMSD (fc_ensemble_silhouette; the contract is
+        in include/fc_hip.h): ``labels`` and ``n_groups`` as for ``medoids`` -> ``(s (N,), a (N,) = the mean distance to
+        the other members of the conformer's own group, b (N,) = the smallest mean distance to another group, nearest
+        (N,) int32 = that group, cluster_mean (n_groups,), sizes (n_groups,) int64, score)``.  A conformer in no group
+        has NaN ``s``, ``a``, ``b`` and ``nearest`` -1; with fewer than two non-empty groups ``b``, ``s`` and ``score``
+        are NaN.  ``want_ms=True`` appends the kernels' milliseconds."""
+        lab, n_groups = check_group_labels(labels, self.N, n_groups)
+        s, a, b = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        nearest = np.empty(self.N, dtype=np.int32)
+        mean, sizes = np.empty(n_groups), np.empty(n_groups, dtype=np.int64)
+        score, ms = C.c_double(0), C.c_double(0)
+        call("fc_ensemble_silhouette", self.handle, ptr(lab, C.c_int32), n_groups, pf(s), pf(a), pf(b), ptr(nearest, C.c_int32),
+             pf(mean), pi(sizes), C.byref(score), C.byref(ms))
+        out = (s, a, b, nearest, mean, sizes, score.value)
+        return out + (ms.value,) if want_ms else out
 
     def rmsd_matrix(self):
         r = np.zeros((self.N, self.N))

@@ -1,7 +1,8 @@
 // fc_api_medoids.cpp -- the extern "C" surface (include/fc_hip.h) of "which conformer stands for this group": the medoids
 // of given groups under the ensemble's RMSD, the k-medoids selection (the alternating form: assign, move to the medoid)
-// and the subset of a resident ensemble that both are built on.  The kernels: fc_medoid.hip; the assignment step is the
-// cross k-NN with k = 1 (fc_knn.hip), the default start the diverse selection (fc_diverse.hip).
+// and the subset of a resident ensemble that both are built on; and of "how good is this grouping": the silhouettes.
+// The kernels: fc_medoid.hip, fc_silhouette.hip; the assignment step is the cross k-NN with k = 1 (fc_knn.hip), the
+// default start the diverse selection (fc_diverse.hip).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -146,6 +147,112 @@ static int medoids_checked(fc_ensemble *ens, const int32_t *labels, int64_t n_gr
   medoids_of(g, S, E, medoids_out, sizes_out, mean_out, radius_out);
   if (sums_q32_out) std::copy(S.begin(), S.end(), sums_q32_out);
   if (ecc_out) std::copy(E.begin(), E.end(), ecc_out);
+  return FC_OK;
+}
+
+// a, b and nearest of the silhouette's contract for the labelled conformers, by conformer; the unlabelled ones and --
+// b, nearest -- everything the device was not needed for keep what the caller put there.  M >= 2 labelled conformers.
+static int silhouette_device(fc_ensemble *ens, const Grouping &g, const int32_t *labels, double *a_out, double *b_out,
+                             int32_t *nearest_out, double *ms_kernel) {
+  const int64_t N = ens->N, M = (int64_t)g.order.size();
+  std::vector<int32_t> seg((size_t)M * 2);  // seg_begin | seg_end
+  for (size_t c = 0; c + 1 < g.offs.size(); ++c)
+    for (int64_t p = g.offs[c]; p < g.offs[c + 1]; ++p)
+      seg[(size_t)p] = (int32_t)g.offs[c], seg[(size_t)(M + p)] = (int32_t)g.offs[c + 1];
+  bool identity = M == N;
+  for (int64_t p = 0; identity && p < M; ++p) identity = g.order[(size_t)p] == p;
+  fc_ensemble sorted;  // the label-sorted copy (not made when the ensemble is in that order already)
+  DevBuf d_order, d_seg, d_work;
+  const int S = silhouette_strips(M);
+  const size_t n_res = silhouette_result_bytes(M);
+  std::vector<uint64_t> res((n_res + 7) / 8);  // a | b | nearest
+  const auto run = [&]() {
+    FC_TRY(upload(d_seg, seg.data(), (size_t)M * 2));
+    const fc_ensemble *e = ens;
+    if (!identity) {
+      FC_TRY(upload(d_order, g.order.data(), (size_t)M));
+      FC_TRY(ensemble_gather(ens, d_order.as<int32_t>(), M, &sorted, false));
+      e = &sorted;
+    }
+    FC_TRY(d_work.reserve(silhouette_work_bytes(M, S)));
+    FC_TRY(launch_silhouette(e, d_seg.as<int32_t>(), d_seg.as<int32_t>() + M, S, d_work.as<uint8_t>(), ms_kernel != nullptr));
+    FC_TRY(d2h(res.data(), d_work.p, n_res));
+    FC_TRY(sync());
+    if (ms_kernel) {
+      float ms = 0.0f;
+      FC_HIP_TRY(hipEventElapsedTime(&ms, ctx().ev0, ctx().ev1));
+      *ms_kernel = ms;
+    }
+    return FC_OK;
+  };
+  FC_TRY(drained(run()));
+  const double *a = reinterpret_cast<const double *>(res.data()), *b = a + M;
+  const int32_t *near = reinterpret_cast<const int32_t *>(b + M);
+  for (int64_t p = 0; p < M; ++p) {
+    const size_t i = (size_t)g.order[(size_t)p];
+    a_out[i] = a[p];
+    b_out[i] = b[p];
+    // a group is named by its first position in the sorted copy: back to its label
+    nearest_out[i] = near[p] < 0 ? -1 : labels == nullptr ? 0 : labels[(size_t)g.order[(size_t)near[p]]];
+  }
+  return FC_OK;
+}
+
+static int silhouette_checked(fc_ensemble *ens, const int32_t *labels, int64_t n_groups, double *s_out, double *a_out,
+                              double *b_out, int32_t *nearest_out, double *cluster_mean_out, int64_t *sizes_out, double *score_out,
+                              double *ms_kernel) {
+  // (the scalar arguments are judged first, so that their refusals do not depend on the handle)
+  FC_REQUIRE(n_groups >= 1, "n_groups=%lld < 1", (long long)n_groups);
+  FC_REQUIRE(n_groups <= (int64_t)INT32_MAX, "n_groups=%lld: labels are 32-bit", (long long)n_groups);
+  FC_REQUIRE(ens != nullptr, "ens is NULL");
+  FC_REQUIRE(s_out != nullptr && a_out != nullptr && b_out != nullptr && nearest_out != nullptr && cluster_mean_out != nullptr &&
+                 sizes_out != nullptr && score_out != nullptr,
+             "s_out / a_out / b_out / nearest_out / cluster_mean_out / sizes_out / score_out is NULL");
+  FC_TRY(labels_check(labels, ens->N, n_groups));
+  FC_REQUIRE(ens->epoch == ctx().epoch, "this ensemble was created before fc_shutdown / a device switch: create it again");
+  if (ms_kernel) *ms_kernel = 0.0;
+  const int64_t N = ens->N;
+  if (N > (int64_t)INT32_MAX - 256)
+    return set_error(FC_E_LIMIT, "N=%lld: the sums index conformers with 32 bits", (long long)N);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  Grouping g;
+  group_by_label(labels, N, n_groups, g);
+  const int64_t M = (int64_t)g.order.size();
+  int64_t n_nonempty = 0;
+  for (int64_t c = 0; c < n_groups; ++c) n_nonempty += g.offs[(size_t)c + 1] > g.offs[(size_t)c];
+  for (int64_t i = 0; i < N; ++i) {
+    const bool in = labels == nullptr || labels[i] >= 0;
+    s_out[i] = b_out[i] = nan;
+    a_out[i] = in ? 0.0 : nan;  // (a single labelled conformer: a singleton)
+    nearest_out[i] = -1;
+  }
+  if (M >= 2) {  // a pair: the device
+    FC_TRY(ensure_init());
+    FC_TRY(sum_limit_check(ens, M));  // (a prefix runs over a whole row)
+    FC_TRY(silhouette_device(ens, g, labels, a_out, b_out, nearest_out, ms_kernel));
+  }
+  std::vector<double> sum((size_t)n_groups, 0.0);
+  double total = 0.0;
+  for (int64_t i = 0; i < N; ++i) {  // (ascending conformer index: the order of the sums of the contract)
+    const int64_t c = labels == nullptr ? 0 : labels[i];
+    if (c < 0) continue;
+    double s;
+    if (n_nonempty < 2) {
+      s = b_out[i] = nan, nearest_out[i] = -1;
+    } else {
+      const double a = a_out[i], b = b_out[i], top = a > b ? a : b;
+      s = g.offs[(size_t)c + 1] - g.offs[(size_t)c] == 1 || top == 0.0 ? 0.0 : (b - a) / top;
+    }
+    s_out[i] = s;
+    sum[(size_t)c] += s;
+    total += s;
+  }
+  for (int64_t c = 0; c < n_groups; ++c) {
+    const int64_t size = g.offs[(size_t)c + 1] - g.offs[(size_t)c];
+    sizes_out[c] = size;
+    cluster_mean_out[c] = size == 0 ? nan : sum[(size_t)c] / (double)size;
+  }
+  *score_out = M == 0 ? nan : total / (double)M;
   return FC_OK;
 }
 
@@ -303,6 +410,14 @@ int fc_ensemble_kmedoids(fc_ensemble *ens, const int64_t *init, int64_t n, int64
                          int32_t *labels_out, double *dist_out, uint64_t *cost_q32_out, int64_t *n_iter_out) {
   FC_API_LOCK;
   return kmedoids_checked(ens, init, n, max_iter, medoids_out, labels_out, dist_out, cost_q32_out, n_iter_out);
+}
+
+int fc_ensemble_silhouette(fc_ensemble *ens, const int32_t *labels, int64_t n_groups, double *s_out, double *a_out, double *b_out,
+                           int32_t *nearest_out, double *cluster_mean_out, int64_t *sizes_out, double *score_out,
+                           double *ms_kernel) {
+  FC_API_LOCK;
+  return silhouette_checked(ens, labels, n_groups, s_out, a_out, b_out, nearest_out, cluster_mean_out, sizes_out, score_out,
+                            ms_kernel);
 }
 
 }  // extern "C"

@@ -168,11 +168,12 @@ k_group_sums(const double *__restrict__ Xs, const double *__restrict__ Xa, const
   }
 }
 
-// strips a tile's chunk range is cut into (FC_MEDOID_STRIPS=<n> forces it): enough items to hand out evenly
-int medoid_strips(int64_t N) {
+// strips a tile's chunk range is cut into (the environment variable `knob`=<n> forces it): enough items to hand out
+// evenly; shared by the tiles of this shape (k_group_sums, k_silhouette_tile)
+int strips_by_knob(const char *knob, int64_t N) {
   const int64_t n_chunks = std::max<int64_t>(1, ceil_div(N, 64));
   int64_t S = 0;
-  if (const char *v = getenv("FC_MEDOID_STRIPS")) {
+  if (const char *v = getenv(knob)) {
     char *end = nullptr;
     const long long f = strtoll(v, &end, 10);
     if (end != v && *end == 0 && f >= 1) S = std::min<long long>(f, kMedMaxStrips);
@@ -183,6 +184,8 @@ int medoid_strips(int64_t N) {
   }
   return (int)std::max<int64_t>(1, std::min(S, n_chunks));
 }
+
+int medoid_strips(int64_t N) { return strips_by_knob("FC_MEDOID_STRIPS", N); }
 
 template <bool STAGE>
 static int launch_group_sums_as(const fc_ensemble *e, const int32_t *seg_end_dev, int n_tiles, int S, unsigned long long *sums_dev,

@@ -146,6 +146,15 @@ class Ensemble:
 
         return medoids_by_rmsd(self.coords, self.atoms, labels=labels, heavy_atoms_only=heavy_atoms_only)
 
+    def silhouette(self, labels, heavy_atoms_only=True):
+        """How good is a grouping of the structures: the silhouette of every labelled structure under the heavy-atom
+        RMSD, per group and overall (``firecode_amd.pruner.silhouette_by_rmsd``).  ``labels``: the ``labels`` of
+        ``cluster_by_rmsd``, ``dbscan_by_rmsd``, ``butina_by_rmsd`` or ``kmedoids_by_rmsd`` (negative: in no group).
+        Returns the ``RmsdSilhouette``; the ensemble is not masked."""
+        from firecode_amd.pruner import silhouette_by_rmsd
+
+        return silhouette_by_rmsd(self.coords, self.atoms, labels, heavy_atoms_only=heavy_atoms_only)
+
     def kmedoids_selection(self, n, heavy_atoms_only=True, max_iter=50, verbose=True):
         """Keep the ``n`` most representative structures: k-medoids under the heavy-atom RMSD
         (``firecode_amd.pruner.kmedoids_by_rmsd``), started from the ``n`` most diverse ones.  Where

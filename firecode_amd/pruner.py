@@ -714,6 +714,69 @@ def butina_from_bits(bits, n):
     return _labels_from_graph("fc_butina_from_bits", _bit_matrix(bits, n), n)
 
 
+RmsdSilhouette = namedtuple("RmsdSilhouette", ["values", "intra", "nearest_mean", "nearest", "cluster_means", "sizes", "score"])
+SilhouetteScanRecord = namedtuple("SilhouetteScanRecord", ["max_rmsd", "n_clusters", "n_noise", "score"])
+
+
+def silhouette_by_rmsd(structures, atoms, labels, heavy_atoms_only=True):
+    """How good is a labelling: the silhouette of every labelled conformer under the heavy-atom Kabsch RMSD of
+    ``prune_by_rmsd`` (centred, ``rmsd_and_max(...)[0]``), on the GPU, without an N x N matrix
+    (fc_ensemble_silhouette; the contract is written out in include/fc_hip.h).  ``labels``: one integer per conformer, a
+    negative one = in no group -- the ``labels`` of ``RmsdClusters``, ``RmsdDbscan`` (-1 is noise), ``RmsdButina`` and
+    ``RmsdKMedoids`` as they come; ``None``: the whole ensemble is one group.
+
+    Returns ``RmsdSilhouette(values, intra, nearest_mean, nearest, cluster_means, sizes, score)``: per conformer the
+    silhouette ``s = (b - a) / max(a, b)`` in [-1, 1] (0 for the only member of a group), ``a`` = the mean distance to
+    the other members of its own group, ``b`` = the smallest mean distance to the members of another group and
+    ``nearest`` (int32) = that group, the lowest label on ties -- a conformer with ``s`` near 0 sits between its own
+    group and ``nearest``; per group (largest label + 1 of them) the mean of ``s`` and the member count; ``score``,
+    the mean of ``s`` over the labelled conformers.  A conformer in no group has NaN values and ``nearest`` -1, an empty
+    group id a NaN mean; with fewer than two non-empty groups ``values``, ``nearest_mean`` and ``score`` are NaN."""
+    structures, heavy = _medoid_inputs(structures, atoms, heavy_atoms_only)
+    N = structures.shape[0]
+    lab, n_groups = L.check_group_labels(labels, N)
+    if N == 0:
+        return RmsdSilhouette(np.zeros(0), np.zeros(0), np.zeros(0), np.zeros(0, dtype=np.int32), np.full(n_groups, np.nan),
+                              np.zeros(n_groups, dtype=np.int64), float("nan"))
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
+        return RmsdSilhouette(*ens.silhouette(lab, n_groups))
+
+
+def silhouette_scan(structures, atoms, thresholds, method="butina", max_dev=None, min_samples=5, heavy_atoms_only=True):
+    """Which ``max_rmsd`` should I cluster at: for every threshold of ``thresholds`` the clusters of ``method`` --
+    ``"butina"`` (``butina_by_rmsd``), ``"components"`` (``cluster_by_rmsd``) or ``"dbscan"`` (``dbscan_by_rmsd`` with
+    ``min_samples``) -- and their silhouette score, with the ensemble uploaded ONCE: the clusterer and the silhouette
+    of every step run on the same resident ensemble.  ``max_dev``: as in the clusterers (default: twice the step's
+    ``max_rmsd``).
+
+    Returns one ``SilhouetteScanRecord(max_rmsd, n_clusters, n_noise, score)`` per threshold, in their order:
+    ``n_noise`` counts the conformers in no cluster (DBSCAN's noise; 0 otherwise), ``score`` is that of
+    ``silhouette_by_rmsd`` under the step's labels (NaN with fewer than two clusters)."""
+    if method not in ("butina", "components", "dbscan"):
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"method={method!r}: 'butina', 'components' or 'dbscan'")
+    structures, heavy = _medoid_inputs(structures, atoms, heavy_atoms_only)
+    min_samples = L.check_min_samples(min_samples)
+    ts = np.asarray(thresholds, dtype=np.float64)
+    if ts.ndim != 1:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"thresholds must be a 1-D sequence of max_rmsd values, got {ts.shape}")
+    steps = [_thresholds(L.check_max_rmsd_cap(t), max_dev, 0.0) for t in ts]
+    if structures.shape[0] == 0:
+        return [SilhouetteScanRecord(float(t), 0, 0, float("nan")) for t in ts]
+    records = []
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
+        for t, (max_rmsd, dev, _) in zip(ts, steps):
+            if method == "butina":
+                out = ens.butina(max_rmsd, dev)
+            elif method == "components":
+                out = ens.clusters(max_rmsd, dev)
+            else:
+                out = ens.dbscan(max_rmsd, dev, min_samples)
+            labels, sizes = out[0], out[2]  # (every clusterer: labels, representatives, sizes, ...)
+            score = ens.silhouette(labels, max(len(sizes), 1))[6]
+            records.append(SilhouetteScanRecord(float(t), len(sizes), int((labels < 0).sum()), score))
+    return records
+
+
 def rotation_mask(graph, torsion, n_atoms=None):
     """``_get_rotation_mask`` (firecode/torsion_module.py:354-382): the atoms that rotate
     with i4 -- reachable from i4 once the i2-i3 edge is removed -- with i3 excluded."""

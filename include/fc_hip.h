@@ -318,7 +318,36 @@ int fc_ensemble_knn_cross_perm(fc_ensemble *queries, fc_ensemble *refs, const in
  * k-medoids: cost 0, 0 iterations, nothing else written).  FC_E_LIMIT: N >= 2^31 - 256; and, once the ensemble's largest
  * G is known, a group too large for the 64-bit sum: (largest size) (ceil(sqrt(4 g_max / A)) + 1) 2^32 >= 2^63 (k-medoids
  * judges N, which no group exceeds) -- tens of millions of members at molecular coordinates.
- * Not offered: symmetry- and mirror-aware forms, a multi-GPU form, between-group sums (silhouettes), PAM's swap phase. */
+ * Not offered: symmetry- and mirror-aware forms, a multi-GPU form, PAM's swap phase (between-group sums: the
+ * silhouettes below).
+ *
+ * fc_ensemble_silhouette.  How good is a labelling: labels and n_groups as for fc_ensemble_medoids.
+ * A conformer with a negative label is in no group: it is neither a row nor a column, and gets a = b = s = NaN and
+ * nearest = -1.  For the labelled conformers d(i, j) is the d of fc_ensemble_knn as above (i the row, j the column),
+ * evaluated for EVERY ORDERED pair i != j -- the full square, not once per unordered pair -- and, with size_g the member
+ * count of group g:
+ *   T[i, g] = sum of q(d(i, j)) over the members j != i of g       64-bit integers: the same bits for every launch shape
+ *                                                                  (FC_SILHOUETTE_STRIPS=<n>) and on every run
+ *   a[i]    = (double) T[i, own] 2^-32 / (size_own - 1), 0 for a singleton
+ *   m[i, g] = (double) T[i, g] 2^-32 / size_g                      for every non-empty g != own
+ *   b[i]    = min over g of m[i, g];  nearest[i] = the g that attains it, the lowest label on ties
+ *   s[i]    = (b - a) / max(a, b);  0 for a singleton;  0 when max(a, b) == 0
+ * Fewer than two non-empty groups: b = s = NaN and nearest = -1 for everyone (a singleton included), a is still given,
+ * and the device is used only for a (not at all with fewer than two labelled conformers).
+ *   for each group c < n_groups:  size[c];  cluster_mean[c] = the mean of s over its members, summed in ascending
+ *     conformer index, NaN for an empty group;  score = the mean of s over all labelled conformers, summed in the same
+ *     order, NaN when there is none.  s, cluster_mean and score are formed on the host from a, b and the labels.
+ * a comes from this call's own full-square values, the S of fc_ensemble_medoids from one evaluation per unordered pair:
+ * a (size - 1) 2^32 and S may differ by the last unit of q per distance.
+ * Outputs, all required but ms_kernel: s_out, a_out, b_out (N doubles each), nearest_out (N int32), cluster_mean_out
+ * (n_groups), sizes_out (n_groups int64), *score_out; ms_kernel (or NULL): HIP-event time of the kernel pair (0 when no
+ * device is used).  Refusals and limits as for fc_ensemble_medoids, in the same order (N = 0: every group empty, score
+ * NaN); the 64-bit check is made on the number of LABELLED conformers -- a prefix runs over a whole row.
+ * Not offered: symmetry- and mirror-aware forms, a multi-GPU form, the "simplified" silhouette against medoids, other
+ * indices (Davies-Bouldin, Calinski-Harabasz). */
+int fc_ensemble_silhouette(fc_ensemble *ens, const int32_t *labels /* N or NULL = one group */, int64_t n_groups,
+                           double *s_out, double *a_out, double *b_out, int32_t *nearest_out, double *cluster_mean_out,
+                           int64_t *sizes_out, double *score_out, double *ms_kernel /* or NULL */);
 int fc_ensemble_subset(fc_ensemble *ens, const int64_t *indices, int64_t n, fc_ensemble **out);
 int fc_ensemble_medoids(fc_ensemble *ens, const int32_t *labels, int64_t n_groups, int64_t *medoids_out, int64_t *sizes_out,
                         double *mean_out, double *radius_out, uint64_t *sums_q32_out /* N or NULL */,
