@@ -35,7 +35,13 @@
 // same kernel reads them from global memory (k_diverse_step<.., false>): no size limit of its own besides N < 2^31.
 //
 // k_diverse_step_sym (further down) is the same step under the smallest rmsd over a table of atom permutations and,
-// optionally, both handednesses (fc_ensemble_select_diverse_perm); the host loop is shared.
+// optionally, both handednesses (fc_ensemble_select_diverse_perm); the host loop is shared, and so
+// are parts 1 and 3 and the D / L update (div_pick_rep, div_update, div_write_partial, above the kernels).  The two atom
+// loops of part 2 stay written out in each kernel: as shared __forceinline__ functions they compiled to the same
+// instruction counts and registers but measured 0.4 % (8 lanes) to 10 % (1 lane, 10^5 conformers, 8 permutations) slower
+// per step (tools/bench_diverse.py, tools/bench_diverse_sym.py; docs/rmsd_tile_measurements.md: the parent's spread
+// there is 0.2 ... 0.4 %).  One or eight lanes per conformer against one
+// representative: not fc_rmsd_tile.h's row tile.
 #include "fc_internal.h"
 #include "fc_kabsch_math.h"
 
@@ -83,7 +89,65 @@ __device__ __forceinline__ double div_group8_sum(double v) {
   return v;
 }
 
-// state[0]: 1 once the radius stop was met; state[1]: number of representatives selected
+// Part 1 of a step: the representative s of this step, from the partials the previous step left.  false: the selection
+// has ended and the whole workgroup returns.  state[0]: 1 once the radius stop was met; state[1]: number of
+// representatives selected
+__device__ __forceinline__ bool div_pick_rep(int k, int start, double stop_rmsd, int n_steps, const double *part_v,
+                                             const int32_t *part_i, int nb, int64_t *idx_out, double *rad_out, int64_t *state,
+                                             double *s_v, int *s_i, int *s_stop, int &s) {
+  const int tid = threadIdx.x;
+  s = start;
+  if (k > 0) {
+    // the radius stop was met at an earlier step.  ONE read per workgroup, shared by all its waves: workgroup 0 of the
+    // launch that meets the stop writes the word while other workgroups of that launch start, and waves that each read
+    // it could disagree -- those that returned would leave their slots of the block reduction below unwritten
+    if (tid == 0) *s_stop = *(volatile int64_t *)state != 0;
+    __syncthreads();
+    if (*s_stop) return false;
+    const double *__restrict__ pv = part_v + (size_t)((k - 1) & 1) * nb;
+    const int32_t *__restrict__ pi = part_i + (size_t)((k - 1) & 1) * nb;
+    double m = -1.0;
+    int mi = INT_MAX;
+    for (int b = tid; b < nb; b += kDivThreads)
+      if (div_better(pv[b], pi[b], m, mi)) m = pv[b], mi = pi[b];
+    div_block_argmax(m, mi, s_v, s_i);
+    if (mi == INT_MAX || (stop_rmsd >= 0.0 && m <= stop_rmsd)) {  // (no conformer left: the host never asks for that)
+      if (blockIdx.x == 0 && tid == 0) state[0] = 1, state[1] = k;
+      return false;
+    }
+    if (blockIdx.x == 0 && tid == 0) idx_out[k] = mi, rad_out[k] = m;
+    s = mi;
+  } else if (blockIdx.x == 0 && tid == 0) {
+    idx_out[0] = start, rad_out[0] = INFINITY;
+    state[0] = 0, state[1] = n_steps;
+  }
+  return true;
+}
+
+// D, L and is_rep of conformer j, at distance t from this step's representative, and the lane's candidate for the next
+// step's max: the updated D[j] (strict: ties keep the earlier representative).  One lane per conformer calls it.
+__device__ __forceinline__ void div_update(int k, int j, double t, double *D, int32_t *L, uint8_t *is_rep, double &cand,
+                                           int &cand_i) {
+  double d = t;
+  if (k == 0) {
+    D[j] = t, L[j] = 0, is_rep[j] = 0;
+  } else {
+    d = D[j];
+    if (t < d) D[j] = t, L[j] = k, d = t;
+  }
+  cand = d, cand_i = j;
+}
+
+// Part 3 of a step: this workgroup's partial for the next step
+__device__ __forceinline__ void div_write_partial(int k, double cand, int cand_i, double *part_v, int32_t *part_i, int nb,
+                                                  double *s_v, int *s_i) {
+  div_block_argmax(cand, cand_i, s_v, s_i);
+  if (threadIdx.x == 0) {
+    part_v[(size_t)(k & 1) * nb + blockIdx.x] = cand;
+    part_i[(size_t)(k & 1) * nb + blockIdx.x] = cand_i;
+  }
+}
+
 template <int LANES, bool STAGE>
 __global__ void __launch_bounds__(kDivThreads)
 k_diverse_step(const double *__restrict__ Xs, const double *__restrict__ Xa, const double *__restrict__ G, int N, int64_t Npad, int A, int k,
@@ -98,31 +162,8 @@ k_diverse_step(const double *__restrict__ Xs, const double *__restrict__ Xa, con
   const int tid = threadIdx.x;
 
   // ---- 1. the representative of this step
-  int s = start;
-  if (k > 0) {
-    // the radius stop was met at an earlier step.  ONE read per workgroup, shared by all its waves: workgroup 0 of the
-    // launch that meets the stop writes the word while other workgroups of that launch start, and waves that each read
-    // it could disagree -- those that returned would leave their slots of the block reduction below unwritten
-    if (tid == 0) s_stop = *(volatile int64_t *)state != 0;
-    __syncthreads();
-    if (s_stop) return;
-    const double *__restrict__ pv = part_v + (size_t)((k - 1) & 1) * nb;
-    const int32_t *__restrict__ pi = part_i + (size_t)((k - 1) & 1) * nb;
-    double m = -1.0;
-    int mi = INT_MAX;
-    for (int b = tid; b < nb; b += kDivThreads)
-      if (div_better(pv[b], pi[b], m, mi)) m = pv[b], mi = pi[b];
-    div_block_argmax(m, mi, s_v, s_i);
-    if (mi == INT_MAX || (stop_rmsd >= 0.0 && m <= stop_rmsd)) {  // (no conformer left: the host never asks for that)
-      if (blockIdx.x == 0 && tid == 0) state[0] = 1, state[1] = k;
-      return;
-    }
-    if (blockIdx.x == 0 && tid == 0) idx_out[k] = mi, rad_out[k] = m;
-    s = mi;
-  } else if (blockIdx.x == 0 && tid == 0) {
-    idx_out[0] = start, rad_out[0] = INFINITY;
-    state[0] = 0, state[1] = n_steps;
-  }
+  int s;
+  if (!div_pick_rep(k, start, stop_rmsd, n_steps, part_v, part_i, nb, idx_out, rad_out, state, s_v, s_i, &s_stop, s)) return;
 
   // ---- 2. align s against every conformer of this workgroup
   const double *__restrict__ P;
@@ -172,25 +213,12 @@ k_diverse_step(const double *__restrict__ Xs, const double *__restrict__ Xa, con
       }
       if (LANES > 1) ssq = div_group8_sum(ssq);
       const double t = sqrt(ssq / (double)A);
-      if (sub == 0) {
-        double d = t;
-        if (k == 0) {
-          D[j] = t, L[j] = 0, is_rep[j] = 0;
-        } else {
-          d = D[j];
-          if (t < d) D[j] = t, L[j] = k, d = t;
-        }
-        cand = d, cand_i = j;
-      }
+      if (sub == 0) div_update(k, j, t, D, L, is_rep, cand, cand_i);
     }
   }
 
   // ---- 3. this workgroup's partial for the next step
-  div_block_argmax(cand, cand_i, s_v, s_i);
-  if (tid == 0) {
-    part_v[(size_t)(k & 1) * nb + blockIdx.x] = cand;
-    part_i[(size_t)(k & 1) * nb + blockIdx.x] = cand_i;
-  }
+  div_write_partial(k, cand, cand_i, part_v, part_i, nb, s_v, s_i);
 }
 
 // ---------------------------------------------------------------------------
@@ -235,29 +263,9 @@ k_diverse_step_sym(const double *__restrict__ Xs, const double *__restrict__ Xa,
   static_assert(sizeof s_v + sizeof s_i + sizeof s_stop <= kDiverseSymStaticLds, "diverse_sym_lds_bytes counts less");
   const int tid = threadIdx.x;
 
-  // ---- 1. the representative of this step (as k_diverse_step, which says why the stop word is read once)
-  int s = start;
-  if (k > 0) {
-    if (tid == 0) s_stop = *(volatile int64_t *)state != 0;
-    __syncthreads();
-    if (s_stop) return;
-    const double *__restrict__ pv = part_v + (size_t)((k - 1) & 1) * nb;
-    const int32_t *__restrict__ pi = part_i + (size_t)((k - 1) & 1) * nb;
-    double m = -1.0;
-    int mi = INT_MAX;
-    for (int b = tid; b < nb; b += kDivThreads)
-      if (div_better(pv[b], pi[b], m, mi)) m = pv[b], mi = pi[b];
-    div_block_argmax(m, mi, s_v, s_i);
-    if (mi == INT_MAX || (stop_rmsd >= 0.0 && m <= stop_rmsd)) {
-      if (blockIdx.x == 0 && tid == 0) state[0] = 1, state[1] = k;
-      return;
-    }
-    if (blockIdx.x == 0 && tid == 0) idx_out[k] = mi, rad_out[k] = m;
-    s = mi;
-  } else if (blockIdx.x == 0 && tid == 0) {
-    idx_out[0] = start, rad_out[0] = INFINITY;
-    state[0] = 0, state[1] = n_steps;
-  }
+  // ---- 1. the representative of this step
+  int s;
+  if (!div_pick_rep(k, start, stop_rmsd, n_steps, part_v, part_i, nb, idx_out, rad_out, state, s_v, s_i, &s_stop, s)) return;
 
   // ---- 2. align s, under every row of the table and either handedness, against every conformer of this workgroup
   uint16_t *pt = reinterpret_cast<uint16_t *>(s_sym + 3 * A);
@@ -325,18 +333,8 @@ k_diverse_step_sym(const double *__restrict__ Xs, const double *__restrict__ Xa,
         }
       }
       const double t = sqrt(best / (double)A);
-      if (sub == 0) {
-        double d = t;
-        if (k == 0) {
-          D[j] = t, L[j] = 0, is_rep[j] = 0;
-        } else {
-          d = D[j];
-          if (t < d) D[j] = t, L[j] = k, d = t;
-        }
-        cand = d, cand_i = j;
-      } else {
-        n_formed = n_explicit = 0;  // (counted once per conformer)
-      }
+      if (sub == 0) div_update(k, j, t, D, L, is_rep, cand, cand_i);
+      else n_formed = n_explicit = 0;  // (counted once per conformer)
     }
   }
   if (stats != nullptr) {  // (uniform: a bench hook's counters)
@@ -349,11 +347,7 @@ k_diverse_step_sym(const double *__restrict__ Xs, const double *__restrict__ Xa,
   }
 
   // ---- 3. this workgroup's partial for the next step
-  div_block_argmax(cand, cand_i, s_v, s_i);
-  if (tid == 0) {
-    part_v[(size_t)(k & 1) * nb + blockIdx.x] = cand;
-    part_i[(size_t)(k & 1) * nb + blockIdx.x] = cand_i;
-  }
+  div_write_partial(k, cand, cand_i, part_v, part_i, nb, s_v, s_i);
 }
 
 int diverse_lanes(int64_t N) {  // lanes per conformer of the step kernel at N conformers (fc_bench_select_diverse reports it)

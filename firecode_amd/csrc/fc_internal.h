@@ -261,13 +261,12 @@ int knn(fc_ensemble *q, fc_ensemble *r, bool cross, int64_t k, double max_rmsd, 
         double *ms_device, int64_t *strips_out, const SymTable *sym = nullptr);
 int warm_knn();
 // ---- fc_medoid.hip ---------------------------------------------------------------------------------------
-int strips_by_knob(const char *knob, int64_t N);  // strips a row tile's chunk range is cut into (the variable `knob` forces it)
-int medoid_strips(int64_t N);                     // ... under FC_MEDOID_STRIPS
+int medoid_strips(int64_t N);  // strips a row tile's chunk range is cut into (FC_MEDOID_STRIPS forces it)
 int launch_group_sums(const fc_ensemble *e, const int32_t *seg_end_dev, unsigned long long *out_dev, bool timed);  // S | E
 int ensemble_gather(const fc_ensemble *src, const int32_t *idx_dev, int64_t n, fc_ensemble *out, bool exact_gmax);
 int warm_medoid();
 // ---- fc_silhouette.hip -----------------------------------------------------------------------------------
-int silhouette_strips(int64_t M);  // ... under FC_SILHOUETTE_STRIPS
+int silhouette_strips(int64_t M);  // the same rule (FC_SILHOUETTE_STRIPS forces it)
 size_t silhouette_result_bytes(int64_t M);  // a (M doubles) | b (M doubles) | nearest (M int32) at the front of the work block
 size_t silhouette_work_bytes(int64_t M, int S);
 int launch_silhouette(const fc_ensemble *e, const int32_t *seg_begin_dev, const int32_t *seg_end_dev, int S, uint8_t *work_dev,

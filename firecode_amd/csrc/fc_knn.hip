@@ -7,12 +7,9 @@
 //   for every conformer i: the k conformers j != i with the smallest d(i, j), in ascending order of (d(i, j), j) --
 //   equal distances: the lower index first, inside the list and at its cut; slots beyond N - 1: index -1, distance +inf.
 //
-// k_knn_tile -- grid: row tiles x column strips.  A workgroup (4 wavefronts) takes kKnnTileRows = 16 rows, stages their
-// selected atoms (the centred conformer-major copy Xa, 24 B per atom) in LDS up to kKnnLdsAtoms atoms and reads them
-// from global memory beyond; each WAVEFRONT owns kKnnR = 4 of the rows and walks the strip's columns 64 at a time, one
-// lane per column conformer, the column's coordinates read from the conformer-minor Xs (coalesced over conformers):
-//   1. the covariances of the column with the 4 rows in one atom loop -- one load of the column's atom serves 4 rows,
-//      the row atoms are wave-uniform (LDS broadcasts);
+// k_knn_tile -- grid: row tiles x column strips.  The tile is fc_rmsd_tile.h's: a workgroup takes 16 rows, each WAVEFRONT
+// owns 4 of them and walks the strip's columns 64 at a time, one lane per column conformer:
+//   1. the covariances of the column with the 4 rows in one atom loop (tile_covariance);
 //   2. per row, the filter: the Newton eigenvalue of the covariance gives A msd = (Gi + Gj) - 2 lambda, never above the
 //      explicit sum by more than rounding WHERE THE ITERATION HAS SETTLED ON ITS LARGEST ROOT, A SIMPLE ONE
 //      (kabsch_lambda_is_settled certifies that); on a (nearly) double root -- atoms on a line, two atoms, a symmetric
@@ -21,10 +18,8 @@
 //      row's current k-th distance -- by more than the margin for EVERY column of the chunk, none of them can enter
 //      the row's list and the rest of the row is skipped (wave-uniform).  The eigenvalue decides nothing else: FC_KNN_FILTER=0 takes every pair through step 3 and gives
 //      the same bits;
-//   3. otherwise the rotation -- kabsch_rotation_qcp (Newton eigenvalue + adjugate eigenvector), the Jacobi sweeps of
-//      kabsch_rotation where the eigenvalue is not clearly simple, as k_diverse_step -- and the explicit rotated
-//      difference in a second atom loop, pair_exact_aos's sums: the value that is written out is never the eigenvalue
-//      form, which cancels for near neighbours;
+//   3. otherwise the rotation and the explicit rotated difference in a second atom loop (tile_rmsd): the value that is
+//      written out is never the eigenvalue form, which cancels for near neighbours;
 //   4. lanes whose (d, j) comes before the row's current k-th entry are found by a ballot and inserted one at a time
 //      into the row's running list.
 // The running list of a row is a sorted top-64 held ONE SLOT PER LANE in the registers of the wavefront that owns the
@@ -66,19 +61,12 @@
 // above tau as well and is not inserted (nor under the cap) -- and tau only shrinks, so the pair is in no final list.
 // (3) A pair that belongs in the final list has d_sym <= every tau its row ever had in any strip, so (p*, h*) is
 // visited and the exact bits are offered.  Visiting MORE (other lanes of the ballot, the filter off) changes no minimum.
-#include "fc_internal.h"
-#include "fc_kabsch_math.h"
+#include "fc_rmsd_tile.h"
 
 #include <climits>
-#include <cmath>
-#include <cstdlib>
 
 namespace fc {
 
-constexpr int kKnnThreads = 256;
-constexpr int kKnnR = 4;                                     // rows per wavefront
-constexpr int kKnnTileRows = (kKnnThreads / 64) * kKnnR;     // rows per workgroup
-constexpr int64_t kKnnLdsAtoms = 256;                        // 16 rows x A x 24 B = 96 KiB of LDS
 static_assert(FC_KNN_MAX == 64, "a row's list is one slot per lane of a wavefront");
 // The filter's margin on A * msd, beside A * kScreenMargin: the eigenvalue form (Gp + Gq) - 2 lambda and the explicit sum
 // differ by the rounding of G, of the covariance and of Newton's last step, a few (2 A + 10) u (Gp + Gq) -- 7e-12 of
@@ -127,7 +115,7 @@ struct KnnCross<true> {
 
 // CROSS = false: one ensemble, the self-pair left out by index.  CROSS = true: no pair left out, the cap.
 template <bool STAGE, bool CROSS>
-__global__ void __launch_bounds__(kKnnThreads)
+__global__ void __launch_bounds__(kTileThreads)
 k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const double *__restrict__ Gq, int Nq, int64_t Npad, int A,
            int k, int filter, int n_tiles, int n_chunks, double *__restrict__ part_d, int32_t *__restrict__ part_j,
            const KnnCross<CROSS> x) {
@@ -136,7 +124,7 @@ k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const d
   double cap;
   if constexpr (CROSS) Gr = x.Gr, Nr = x.Nr, cap = x.cap;
   else Gr = Gq, Nr = Nq, cap = INFINITY;
-  extern __shared__ double s_rows[];  // [kKnnTileRows][A][3] when STAGE
+  extern __shared__ double s_rows[];  // [kTileRows][A][3] when STAGE
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int S = gridDim.y, s = blockIdx.y;
   // the strip's chunks of 64 columns
@@ -145,27 +133,17 @@ k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const d
   const double dA = (double)A;
 
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const int row0 = tile * kKnnTileRows;
-    if (STAGE) {
-      __syncthreads();  // (the previous tile's readers)
-      for (int r = w; r < kKnnTileRows; r += kKnnThreads / 64) {
-        const double *__restrict__ src = Xa + (int64_t)min(row0 + r, Nq - 1) * A3;
-        for (int t = lane; t < A3; t += 64) s_rows[r * A3 + t] = src[t];
-      }
-      __syncthreads();
-    }
-    const int wrow = row0 + w * kKnnR;
+    const int row0 = tile * kTileRows;
+    if (STAGE) tile_stage_rows(s_rows, Xa, row0, Nq, A3);
+    const int wrow = row0 + w * kTileR;
     if (wrow < Nq) {  // (wave-uniform)
-      int row[kKnnR];
-      const double *__restrict__ P[kKnnR];
-      double Gi[kKnnR], ld[kKnnR], td[kKnnR];
-      int lj[kKnnR], tj[kKnnR];
+      int row[kTileR];
+      const double *__restrict__ P[kTileR];
+      double Gi[kTileR], ld[kTileR], td[kTileR];
+      int lj[kTileR], tj[kTileR];
+      tile_rows<STAGE>(s_rows, Xa, Gq, row0, wrow, Nq, A3, row, P, Gi);
 #pragma unroll
-      for (int r = 0; r < kKnnR; ++r) {
-        row[r] = wrow + r;
-        const int rl = min(row[r], Nq - 1);
-        P[r] = STAGE ? s_rows + (w * kKnnR + r) * A3 : Xa + (int64_t)rl * A3;
-        Gi[r] = Gq[rl];
+      for (int r = 0; r < kTileR; ++r) {
         ld[r] = td[r] = INFINITY;
         lj[r] = tj[r] = INT_MAX;
       }
@@ -173,31 +151,13 @@ k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const d
         const int j = c * 64 + lane;
         const int jl = min(j, Nr - 1);
         const double *__restrict__ q0 = Xs + jl;
-        const int64_t step = 3 * Npad;
         // ---- 1. covariances with the 4 rows
-        double B[kKnnR][9];
-#pragma unroll
-        for (int r = 0; r < kKnnR; ++r)
-#pragma unroll
-          for (int e = 0; e < 9; ++e) B[r][e] = 0.0;
-        {
-          const double *__restrict__ qa = q0;
-#pragma unroll 2
-          for (int a = 0; a < A; ++a, qa += step) {
-            const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
-#pragma unroll
-            for (int r = 0; r < kKnnR; ++r) {
-              const double px = P[r][a * 3], py = P[r][a * 3 + 1], pz = P[r][a * 3 + 2];
-              B[r][0] = fma(px, qx, B[r][0]); B[r][1] = fma(px, qy, B[r][1]); B[r][2] = fma(px, qz, B[r][2]);
-              B[r][3] = fma(py, qx, B[r][3]); B[r][4] = fma(py, qy, B[r][4]); B[r][5] = fma(py, qz, B[r][5]);
-              B[r][6] = fma(pz, qx, B[r][6]); B[r][7] = fma(pz, qy, B[r][7]); B[r][8] = fma(pz, qz, B[r][8]);
-            }
-          }
-        }
+        double B[kTileR][9];
+        tile_covariance(P, q0, Npad, A, TileNoPerm{}, B);
         // ---- 2. per row: the filter, and where a lane passes it the rotation, the explicit rotated difference and the list
         const double Gj = Gr[jl];
 #pragma unroll
-        for (int r = 0; r < kKnnR; ++r) {
+        for (int r = 0; r < kTileR; ++r) {
           const bool ok = j < Nr && (CROSS || j != row[r]) && row[r] < Nq;  // one ensemble: the self-pair is left out by index
           const double GG = Gi[r] + Gj;
           bool may = ok;
@@ -207,26 +167,13 @@ k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const d
             may = ok && !(msdA > dA * tau * tau + (dA * kScreenMargin + kKnnFilterRel * GG));
           }
           if (__ballot(may) == 0) continue;  // (wave-uniform) no column of this chunk can enter the row's list
-          double R[9];
-          if (!kabsch_rotation_qcp(B[r], GG, R)) (void)kabsch_rotation(B[r], R);
-          double ssq = 0.0;
-          const double *__restrict__ qa = q0;
-#pragma unroll 2
-          for (int a = 0; a < A; ++a, qa += step) {
-            const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
-            const double px = P[r][a * 3], py = P[r][a * 3 + 1], pz = P[r][a * 3 + 2];
-            const double dx = px - (R[0] * qx + R[1] * qy + R[2] * qz);
-            const double dy = py - (R[3] * qx + R[4] * qy + R[5] * qz);
-            const double dz = pz - (R[6] * qx + R[7] * qy + R[8] * qz);
-            ssq += dx * dx + dy * dy + dz * dz;
-          }
-          const double d = sqrt(ssq / dA);
+          const double d = tile_rmsd(P[r], q0, Npad, A, B[r], GG, dA);
           // (the cap is tested on the value itself, beside the list: slot k - 1, which knn_offer re-reads, never holds it)
           knn_offer(ld[r], lj[r], td[r], tj[r], d, j, CROSS ? ok && d < cap : ok, k, lane);
         }
       }
 #pragma unroll
-      for (int r = 0; r < kKnnR; ++r)
+      for (int r = 0; r < kTileR; ++r)
         if (row[r] < Nq && lane < k) {
           const int64_t at = ((int64_t)row[r] * S + s) * k + lane;
           part_d[at] = ld[r];
@@ -236,11 +183,11 @@ k_knn_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const d
   }
 }
 
-__global__ void __launch_bounds__(kKnnThreads)
+__global__ void __launch_bounds__(kTileThreads)
 k_knn_merge(const double *__restrict__ part_d, const int32_t *__restrict__ part_j, int N, int S, int k,
             int32_t *__restrict__ idx_out, double *__restrict__ dist_out) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  constexpr int kWaves = kKnnThreads / 64;
+  constexpr int kWaves = kTileThreads / 64;
   for (int64_t row = (int64_t)blockIdx.x * kWaves + w; row < N; row += (int64_t)gridDim.x * kWaves) {  // (wave-uniform)
     double ld = INFINITY, td = INFINITY;
     int lj = INT_MAX, tj = INT_MAX;
@@ -268,7 +215,8 @@ k_knn_merge(const double *__restrict__ part_d, const int32_t *__restrict__ part_
 //
 //   d_sym(i, j) = min over p < K, h in H of rmsd(Q[i], h * R[j][perms[p]]),   H = {+1} or, MIRROR, {+1, -1}
 //
-// k_knn_tile with its chunk walking the table, as k_diverse_step_sym does for its step.  The workgroup's 16 row
+// k_knn_tile with its chunk walking the table, as k_diverse_step_sym does for its step: fc_rmsd_tile.h's functions with a
+// row of the table and, for the explicit pass, the sign passed in.  The workgroup's 16 row
 // conformers AND the table (16-bit indices) sit in LDS -- this form is staged only -- and the permutation is applied to
 // the row side: sum_a p_a q_pi(a)^T = sum_b p_pi^-1(b) q_b^T and the table is closed under inverse, so the minimum over
 // "rows of the table applied to the row conformer" is the minimum the contract names, a permutation costs one LDS
@@ -286,7 +234,7 @@ k_knn_merge(const double *__restrict__ part_d, const int32_t *__restrict__ part_
 // (the lanes of a wavefront that made the pass: a pair rides along when another lane of its chunk needs it).
 // ---------------------------------------------------------------------------
 size_t knn_sym_lds_bytes(int64_t A, int64_t K) {
-  return (size_t)kKnnTileRows * (size_t)A * 3 * sizeof(double) + (((size_t)K * (size_t)A * sizeof(uint16_t) + 7) & ~(size_t)7);
+  return tile_rows_lds_bytes(A) + (((size_t)K * (size_t)A * sizeof(uint16_t) + 7) & ~(size_t)7);
 }
 
 #ifdef FC_KNN_SYM_ROWS  // (a tuning build: fc_tuning.h)
@@ -298,10 +246,10 @@ constexpr int kKnnSymR = FC_KNN_SYM_ROWS;
 // instead of 4.  The outputs do not depend on it.
 constexpr int kKnnSymR = 2;
 #endif
-static_assert(kKnnR % kKnnSymR == 0, "a wavefront's rows in whole groups");
+static_assert(kTileR % kKnnSymR == 0, "a wavefront's rows in whole groups");
 
 template <bool CROSS, bool MIRROR>
-__global__ void __launch_bounds__(kKnnThreads)
+__global__ void __launch_bounds__(kTileThreads)
 k_knn_tile_sym(const double *__restrict__ Xs, const double *__restrict__ Xa, const double *__restrict__ Gq, int Nq, int64_t Npad,
                int A, const uint16_t *__restrict__ perms, int K, int k, int filter, int n_tiles, int n_chunks,
                double *__restrict__ part_d, int32_t *__restrict__ part_j, unsigned long long *__restrict__ stats,
@@ -311,36 +259,29 @@ k_knn_tile_sym(const double *__restrict__ Xs, const double *__restrict__ Xa, con
   double cap;
   if constexpr (CROSS) Gr = x.Gr, Nr = x.Nr, cap = x.cap;
   else Gr = Gq, Nr = Nq, cap = INFINITY;
-  extern __shared__ double s_rows[];  // [kKnnTileRows][A][3], then the table [K][A] as uint16_t
+  extern __shared__ double s_rows[];  // [kTileRows][A][3], then the table [K][A] as uint16_t
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int S = gridDim.y, s = blockIdx.y;
   const int c0 = (int)((int64_t)s * n_chunks / S), c1 = (int)((int64_t)(s + 1) * n_chunks / S);
   const int A3 = 3 * A;
   const double dA = (double)A;
   const double margin = dA * kScreenMargin;
-  uint16_t *pt = reinterpret_cast<uint16_t *>(s_rows + kKnnTileRows * A3);
-  for (int t = tid; t < K * A; t += kKnnThreads) pt[t] = perms[t];  // (the first tile's barrier covers it)
+  uint16_t *pt = reinterpret_cast<uint16_t *>(s_rows + kTileRows * A3);
+  for (int t = tid; t < K * A; t += kTileThreads) pt[t] = perms[t];  // (the first tile's barrier covers it)
   unsigned long long n_formed = 0, n_explicit = 0;  // (wave-uniform: ballots)
 
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const int row0 = tile * kKnnTileRows;
-    __syncthreads();  // (the previous tile's readers)
-    for (int r = w; r < kKnnTileRows; r += kKnnThreads / 64) {
-      const double *__restrict__ src = Xa + (int64_t)min(row0 + r, Nq - 1) * A3;
-      for (int t = lane; t < A3; t += 64) s_rows[r * A3 + t] = src[t];
-    }
-    __syncthreads();
-    // the wavefront's kKnnR rows, kKnnSymR at a time (each group walks the strip: the outputs do not depend on the split)
-    for (int wrow = row0 + w * kKnnR; wrow < min(row0 + (w + 1) * kKnnR, Nq); wrow += kKnnSymR) {  // (wave-uniform)
+    const int row0 = tile * kTileRows;
+    tile_stage_rows(s_rows, Xa, row0, Nq, A3);
+    // the wavefront's kTileR rows, kKnnSymR at a time (each group walks the strip: the outputs do not depend on the split)
+    for (int wrow = row0 + w * kTileR; wrow < min(row0 + (w + 1) * kTileR, Nq); wrow += kKnnSymR) {  // (wave-uniform)
       int row[kKnnSymR];
       const double *__restrict__ P[kKnnSymR];
       double Gi[kKnnSymR], ld[kKnnSymR], td[kKnnSymR];
       int lj[kKnnSymR], tj[kKnnSymR];
+      tile_rows<true>(s_rows, Xa, Gq, row0, wrow, Nq, A3, row, P, Gi);
 #pragma unroll
       for (int r = 0; r < kKnnSymR; ++r) {
-        row[r] = wrow + r;
-        P[r] = s_rows + (wrow - row0 + r) * A3;
-        Gi[r] = Gq[min(row[r], Nq - 1)];
         ld[r] = td[r] = INFINITY;
         lj[r] = tj[r] = INT_MAX;
       }
@@ -348,7 +289,6 @@ k_knn_tile_sym(const double *__restrict__ Xs, const double *__restrict__ Xa, con
         const int j = c * 64 + lane;
         const int jl = min(j, Nr - 1);
         const double *__restrict__ q0 = Xs + jl;
-        const int64_t step = 3 * Npad;
         const double Gj = Gr[jl];
         double best[kKnnSymR];  // the pair's smallest explicit sum of squares so far
 #pragma unroll
@@ -358,25 +298,7 @@ k_knn_tile_sym(const double *__restrict__ Xs, const double *__restrict__ Xa, con
           const uint16_t *__restrict__ pr = pt + p * A;
           // ---- 1. covariances of the column with the rows under row p of the table
           double B[kKnnSymR][9];
-#pragma unroll
-          for (int r = 0; r < kKnnSymR; ++r)
-#pragma unroll
-            for (int e = 0; e < 9; ++e) B[r][e] = 0.0;
-          {
-            const double *__restrict__ qa = q0;
-#pragma unroll 2
-            for (int a = 0; a < A; ++a, qa += step) {
-              const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
-              const int b = (int)pr[a] * 3;
-#pragma unroll
-              for (int r = 0; r < kKnnSymR; ++r) {
-                const double px = P[r][b], py = P[r][b + 1], pz = P[r][b + 2];
-                B[r][0] = fma(px, qx, B[r][0]); B[r][1] = fma(px, qy, B[r][1]); B[r][2] = fma(px, qz, B[r][2]);
-                B[r][3] = fma(py, qx, B[r][3]); B[r][4] = fma(py, qy, B[r][4]); B[r][5] = fma(py, qz, B[r][5]);
-                B[r][6] = fma(pz, qx, B[r][6]); B[r][7] = fma(pz, qy, B[r][7]); B[r][8] = fma(pz, qz, B[r][8]);
-              }
-            }
-          }
+          tile_covariance(P, q0, Npad, A, pr, B);
           // ---- 2. per row and handedness: the filter, and where a lane passes it the rotation and the explicit pass
 #pragma unroll
           for (int r = 0; r < kKnnSymR; ++r) {
@@ -395,23 +317,7 @@ k_knn_tile_sym(const double *__restrict__ Xs, const double *__restrict__ Xa, con
               }
               if (__ballot(may) == 0) continue;  // (wave-uniform) this (p, h) is ruled out for every column of the chunk
               n_explicit += (unsigned long long)__popcll(__ballot(ok));
-              const double sg = h ? -1.0 : 1.0;
-              double Bh[9], R[9];
-#pragma unroll
-              for (int e = 0; e < 9; ++e) Bh[e] = sg * B[r][e];
-              if (!kabsch_rotation_qcp(Bh, GG, R)) (void)kabsch_rotation(Bh, R);
-              double ssq = 0.0;
-              const double *__restrict__ qa = q0;
-#pragma unroll 2
-              for (int a = 0; a < A; ++a, qa += step) {
-                const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
-                const int b = (int)pr[a] * 3;
-                const double px = P[r][b], py = P[r][b + 1], pz = P[r][b + 2];
-                const double dx = px - sg * (R[0] * qx + R[1] * qy + R[2] * qz);
-                const double dy = py - sg * (R[3] * qx + R[4] * qy + R[5] * qz);
-                const double dz = pz - sg * (R[6] * qx + R[7] * qy + R[8] * qz);
-                ssq += dx * dx + dy * dy + dz * dz;
-              }
+              const double ssq = tile_explicit_ssq<true>(P[r], q0, Npad, A, pr, B[r], GG, h ? -1.0 : 1.0);
               if (!(ssq >= best[r])) best[r] = ssq;
             }
           }
@@ -439,22 +345,8 @@ k_knn_tile_sym(const double *__restrict__ Xs, const double *__restrict__ Xa, con
   }
 }
 
-// column strips of a launch of Nq rows against Nr columns: enough workgroups to fill the chip where the row tiles alone do
-// not; FC_KNN_STRIPS=<n> forces it (speed only: the outputs are the same bits for every value)
-int knn_strips(int64_t Nq, int64_t Nr) {
-  const int64_t n_chunks = std::max<int64_t>(1, ceil_div(Nr, 64));
-  int64_t S = 0;
-  if (const char *v = getenv("FC_KNN_STRIPS")) {
-    char *end = nullptr;
-    const long long f = strtoll(v, &end, 10);
-    if (end != v && *end == 0 && f >= 1) S = std::min<long long>(f, kKnnMaxStrips);
-  }
-  if (S == 0) {
-    const int64_t tiles = std::max<int64_t>(1, ceil_div(Nq, kKnnTileRows));
-    S = std::min<int64_t>(kKnnMaxStrips, ceil_div((int64_t)kKnnWorkgroupsPerCu * std::max(1, ctx().n_cu), tiles));
-  }
-  return (int)std::max<int64_t>(1, std::min(S, n_chunks));
-}
+// column strips of a launch of Nq rows against Nr columns (speed only: the outputs are the same bits for every value)
+int knn_strips(int64_t Nq, int64_t Nr) { return tile_strips("FC_KNN_STRIPS", kKnnWorkgroupsPerCu, kKnnMaxStrips, Nq, Nr); }
 
 // FC_KNN_FILTER=0: the explicit pass for every pair (speed only: the outputs are the same bits either way)
 static int knn_filter() {
@@ -471,12 +363,12 @@ struct KnnLaunch {
 
 template <bool STAGE, bool CROSS>
 static int launch_knn_tile(const KnnLaunch &a, double *part_d, int32_t *part_j) {
-  const size_t lds = STAGE ? (size_t)kKnnTileRows * a.q->A * 3 * sizeof(double) : 0;
+  const size_t lds = STAGE ? tile_rows_lds_bytes(a.q->A) : 0;
   FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_knn_tile<STAGE, CROSS>), lds, "k_knn_tile"));
   const unsigned gx = (unsigned)std::min<int64_t>(a.n_tiles, (int64_t)1 << 20);
   KnnCross<CROSS> x;
   if constexpr (CROSS) x = KnnCross<true>{a.r->G.as<double>(), (int)a.r->N, a.cap};
-  hipLaunchKernelGGL((k_knn_tile<STAGE, CROSS>), dim3(gx, (unsigned)a.S), dim3(kKnnThreads), lds, ctx().stream,
+  hipLaunchKernelGGL((k_knn_tile<STAGE, CROSS>), dim3(gx, (unsigned)a.S), dim3(kTileThreads), lds, ctx().stream,
                      a.r->Xs.as<double>(), a.q->Xa.as<double>(), a.q->G.as<double>(), (int)a.q->N, a.r->Npad, (int)a.q->A, a.k,
                      a.filter, a.n_tiles, a.n_chunks, part_d, part_j, x);
   return check_launch("k_knn_tile");
@@ -489,7 +381,7 @@ static int launch_knn_tile_sym(const KnnLaunch &a, const SymTable &sym, double *
   const unsigned gx = (unsigned)std::min<int64_t>(a.n_tiles, (int64_t)1 << 20);
   KnnCross<CROSS> x;
   if constexpr (CROSS) x = KnnCross<true>{a.r->G.as<double>(), (int)a.r->N, a.cap};
-  hipLaunchKernelGGL((k_knn_tile_sym<CROSS, MIRROR>), dim3(gx, (unsigned)a.S), dim3(kKnnThreads), lds, ctx().stream,
+  hipLaunchKernelGGL((k_knn_tile_sym<CROSS, MIRROR>), dim3(gx, (unsigned)a.S), dim3(kTileThreads), lds, ctx().stream,
                      a.r->Xs.as<double>(), a.q->Xa.as<double>(), a.q->G.as<double>(), (int)a.q->N, a.r->Npad, (int)a.q->A,
                      sym.perms_dev, sym.K, a.k, a.filter, a.n_tiles, a.n_chunks, part_d, part_j, sym.stats_dev, x);
   return check_launch("k_knn_tile_sym");
@@ -499,7 +391,7 @@ static int knn_enqueue(const fc_ensemble *q, const fc_ensemble *r, bool cross, i
                        double *dist_out, double *ms_device, DevBuf &pd, DevBuf &pj, DevBuf &oi, DevBuf &od,
                        const SymTable *sym) {
   const int64_t Nq = q->N;
-  const KnnLaunch a{q, r, k, knn_filter(), (int)ceil_div(Nq, kKnnTileRows), (int)ceil_div(r->N, 64), S, cap};
+  const KnnLaunch a{q, r, k, knn_filter(), (int)ceil_div(Nq, kTileRows), (int)ceil_div(r->N, 64), S, cap};
   const size_t entries = (size_t)Nq * (size_t)k;
   FC_TRY(pd.reserve(entries * (size_t)S * sizeof(double)));
   FC_TRY(pj.reserve(entries * (size_t)S * sizeof(int32_t)));
@@ -507,7 +399,7 @@ static int knn_enqueue(const fc_ensemble *q, const fc_ensemble *r, bool cross, i
   FC_TRY(od.reserve(entries * sizeof(double)));
   Context &c = ctx();
   if (ms_device) FC_HIP_TRY(hipEventRecord(c.ev0, c.stream));
-  const bool stage = q->A <= kKnnLdsAtoms;
+  const bool stage = q->A <= kTileLdsAtoms;
   const auto tile = cross ? (stage ? launch_knn_tile<true, true> : launch_knn_tile<false, true>)
                          : (stage ? launch_knn_tile<true, false> : launch_knn_tile<false, false>);
   if (sym) {
@@ -517,8 +409,8 @@ static int knn_enqueue(const fc_ensemble *q, const fc_ensemble *r, bool cross, i
   } else {
     FC_TRY(tile(a, pd.as<double>(), pj.as<int32_t>()));
   }
-  const unsigned gm = (unsigned)std::min<int64_t>(ceil_div(Nq, kKnnThreads / 64), (int64_t)1 << 20);
-  hipLaunchKernelGGL(k_knn_merge, dim3(gm), dim3(kKnnThreads), 0, c.stream, pd.as<double>(), pj.as<int32_t>(), (int)Nq, S, k,
+  const unsigned gm = (unsigned)std::min<int64_t>(ceil_div(Nq, kTileThreads / 64), (int64_t)1 << 20);
+  hipLaunchKernelGGL(k_knn_merge, dim3(gm), dim3(kTileThreads), 0, c.stream, pd.as<double>(), pj.as<int32_t>(), (int)Nq, S, k,
                      oi.as<int32_t>(), od.as<double>());
   FC_TRY(check_launch("k_knn_merge"));
   if (ms_device) FC_HIP_TRY(hipEventRecord(c.ev1, c.stream));

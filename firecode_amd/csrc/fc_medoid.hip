@@ -11,9 +11,8 @@
 // d is evaluated ONCE per unordered pair and handed to both partners, so S is exactly symmetric in a pair; the sums are
 // 64-bit integers, so they do not depend on the order, the launch shape or the arrival of the atomics.
 //
-// k_group_sums is k_knn_tile's tile (fc_knn.hip) without the filter and the lists: 256 threads, four wavefronts x 4 rows
-// from Xa (staged in LDS up to kMedLdsAtoms atoms, read from global memory beyond), 64 columns per chunk, one lane per
-// column, the column's coordinates coalesced from Xs.  It walks a LABEL-SORTED copy of the ensemble (the host's stable
+// k_group_sums walks fc_rmsd_tile.h's tile, as k_knn_tile (fc_knn.hip) does, without the filter and the lists.  It
+// walks a LABEL-SORTED copy of the ensemble (the host's stable
 // order by label, one k_ensemble_gather): the group of a row is then the contiguous range of positions that ends at
 // seg_end[row], and the pairs of a row that count are the columns row < j < seg_end[row] -- the upper triangle of its
 // group's block.  A wavefront's four rows may belong to several small groups: it walks the union of their ranges
@@ -31,27 +30,16 @@
 // k_ensemble_gather copies Xs, Xa and G of chosen conformers into a new ensemble; it computes nothing, so the
 // coordinates and G keep their bits: the sorted copy above, the medoid sub-ensemble of the k-medoids assignment and
 // fc_ensemble_subset.
-#include "fc_internal.h"
-#include "fc_kabsch_math.h"
-
-#include <cmath>
-#include <cstdlib>
+#include "fc_rmsd_tile.h"
 
 namespace fc {
 
-constexpr int kMedThreads = 256;
-constexpr int kMedR = 4;                                     // rows per wavefront
-constexpr int kMedTileRows = (kMedThreads / 64) * kMedR;     // rows per workgroup
-constexpr int64_t kMedLdsAtoms = 256;                        // 16 rows x A x 24 B = 96 KiB of LDS (k_knn_tile's stage)
-constexpr int kMedMaxStrips = 64;
-constexpr int kMedItemsPerCu = 32;  // items aimed at per CU: the largest item is then a few percent of a CU's share
-
 template <bool STAGE>
-__global__ void __launch_bounds__(kMedThreads)
+__global__ void __launch_bounds__(kTileThreads)
 k_group_sums(const double *__restrict__ Xs, const double *__restrict__ Xa, const double *__restrict__ G, int N, int64_t Npad,
              int A, const int32_t *__restrict__ seg_end, int n_tiles, int S, unsigned long long *__restrict__ sums,
              unsigned long long *__restrict__ ecc) {
-  extern __shared__ double s_rows[];  // [kMedTileRows][A][3] when STAGE
+  extern __shared__ double s_rows[];  // [kTileRows][A][3] when STAGE
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int A3 = 3 * A;
   const double dA = (double)A;
@@ -59,72 +47,48 @@ k_group_sums(const double *__restrict__ Xs, const double *__restrict__ Xa, const
 
   for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
     const int tile = (int)(item / S), s = (int)(item % S);
-    const int row0 = tile * kMedTileRows;
+    const int row0 = tile * kTileRows;
     // the tile's chunks of 64 columns: the columns behind its first row up to the end of its last row's group
-    const int tb = (row0 + 1) >> 6, te = (seg_end[min(row0 + kMedTileRows - 1, N - 1)] + 63) >> 6;
+    const int tb = (row0 + 1) >> 6, te = (seg_end[min(row0 + kTileRows - 1, N - 1)] + 63) >> 6;
     const int nt = max(te - tb, 0);
     const int c0 = tb + (int)((int64_t)s * nt / S), c1 = tb + (int)((int64_t)(s + 1) * nt / S);
     if (c0 >= c1) continue;  // (the same for the whole workgroup)
-    if (STAGE) {
-      __syncthreads();  // (the previous item's readers)
-      for (int r = w; r < kMedTileRows; r += kMedThreads / 64) {
-        const double *__restrict__ src = Xa + (int64_t)min(row0 + r, N - 1) * A3;
-        for (int t = lane; t < A3; t += 64) s_rows[r * A3 + t] = src[t];
-      }
-      __syncthreads();
-    }
-    const int wrow = row0 + w * kMedR;
+    if (STAGE) tile_stage_rows(s_rows, Xa, row0, N, A3);
+    const int wrow = row0 + w * kTileR;
     if (wrow >= N) continue;  // (wave-uniform; no barrier follows in this item)
-    int row[kMedR], se[kMedR];
-    const double *__restrict__ P[kMedR];
-    double Gi[kMedR], re[kMedR];
-    unsigned long long rs[kMedR];
+    int row[kTileR], se[kTileR];
+    const double *__restrict__ P[kTileR];
+    double Gi[kTileR], re[kTileR];
+    unsigned long long rs[kTileR];
+    tile_rows<STAGE>(s_rows, Xa, G, row0, wrow, N, A3, row, P, Gi);
 #pragma unroll
-    for (int r = 0; r < kMedR; ++r) {
-      row[r] = wrow + r;
-      const int rl = min(row[r], N - 1);
-      P[r] = STAGE ? s_rows + (w * kMedR + r) * A3 : Xa + (int64_t)rl * A3;
-      Gi[r] = G[rl];
-      se[r] = row[r] < N ? seg_end[rl] : 0;  // (a row past the end counts nowhere)
+    for (int r = 0; r < kTileR; ++r) {
+      const int e = seg_end[min(row[r], N - 1)];
+      se[r] = row[r] < N ? e : 0;  // (a row past the end counts nowhere)
       rs[r] = 0ull;
       re[r] = 0.0;
     }
     // the wavefront's own part of the strip: behind its first row, up to the end of its last row's group
-    const int wc0 = max(c0, (wrow + 1) >> 6), wc1 = min(c1, (seg_end[min(wrow + kMedR - 1, N - 1)] + 63) >> 6);
+    const int wc0 = max(c0, (wrow + 1) >> 6), wc1 = min(c1, (seg_end[min(wrow + kTileR - 1, N - 1)] + 63) >> 6);
     for (int c = wc0; c < wc1; ++c) {
       const int j = c * 64 + lane;
       const int jl = min(j, N - 1);
       const double *__restrict__ q0 = Xs + jl;
-      const int64_t step = 3 * Npad;
-      // ---- 1. covariances with the 4 rows (k_knn_tile's loop)
-      double B[kMedR][9];
-#pragma unroll
-      for (int r = 0; r < kMedR; ++r)
-#pragma unroll
-        for (int e = 0; e < 9; ++e) B[r][e] = 0.0;
-      {
-        const double *__restrict__ qa = q0;
-#pragma unroll 2
-        for (int a = 0; a < A; ++a, qa += step) {
-          const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
-#pragma unroll
-          for (int r = 0; r < kMedR; ++r) {
-            const double px = P[r][a * 3], py = P[r][a * 3 + 1], pz = P[r][a * 3 + 2];
-            B[r][0] = fma(px, qx, B[r][0]); B[r][1] = fma(px, qy, B[r][1]); B[r][2] = fma(px, qz, B[r][2]);
-            B[r][3] = fma(py, qx, B[r][3]); B[r][4] = fma(py, qy, B[r][4]); B[r][5] = fma(py, qz, B[r][5]);
-            B[r][6] = fma(pz, qx, B[r][6]); B[r][7] = fma(pz, qy, B[r][7]); B[r][8] = fma(pz, qz, B[r][8]);
-          }
-        }
-      }
+      // ---- 1. covariances with the 4 rows
+      double B[kTileR][9];
+      tile_covariance(P, q0, Npad, A, TileNoPerm{}, B);
       // ---- 2. per row: the rotation and the explicit rotated difference where a lane's pair counts
       const double Gj = G[jl];
       unsigned long long cs = 0ull;  // this column's share of the 4 rows
       double ce = 0.0;
 #pragma unroll
-      for (int r = 0; r < kMedR; ++r) {
+      for (int r = 0; r < kTileR; ++r) {
         const bool ok = row[r] < j && j < se[r];  // the upper triangle of the row's group (se <= N)
         if (__ballot(ok) == 0) continue;          // (wave-uniform)
+        // tile_rmsd's body, written out: as a call it compiles to the same instruction counts, but this kernel then
+        // measured 4 ... 12 % slower (tools/bench_medoids.py; docs/rmsd_tile_measurements.md) -- k_knn_tile does not
         const double GG = Gi[r] + Gj;
+        const int64_t step = 3 * Npad;
         double R[9];
         if (!kabsch_rotation_qcp(B[r], GG, R)) (void)kabsch_rotation(B[r], R);
         double ssq = 0.0;
@@ -152,7 +116,7 @@ k_group_sums(const double *__restrict__ Xs, const double *__restrict__ Xa, const
     }
     // ---- 3. the rows' sums over the strip: one atomic per row
 #pragma unroll
-    for (int r = 0; r < kMedR; ++r) {
+    for (int r = 0; r < kTileR; ++r) {
       unsigned long long v = rs[r];
       double m = re[r];
 #pragma unroll
@@ -168,32 +132,16 @@ k_group_sums(const double *__restrict__ Xs, const double *__restrict__ Xa, const
   }
 }
 
-// strips a tile's chunk range is cut into (the environment variable `knob`=<n> forces it): enough items to hand out
-// evenly; shared by the tiles of this shape (k_group_sums, k_silhouette_tile)
-int strips_by_knob(const char *knob, int64_t N) {
-  const int64_t n_chunks = std::max<int64_t>(1, ceil_div(N, 64));
-  int64_t S = 0;
-  if (const char *v = getenv(knob)) {
-    char *end = nullptr;
-    const long long f = strtoll(v, &end, 10);
-    if (end != v && *end == 0 && f >= 1) S = std::min<long long>(f, kMedMaxStrips);
-  }
-  if (S == 0) {
-    const int64_t tiles = std::max<int64_t>(1, ceil_div(N, kMedTileRows));
-    S = std::min<int64_t>(kMedMaxStrips, ceil_div((int64_t)kMedItemsPerCu * std::max(1, ctx().n_cu), tiles));
-  }
-  return (int)std::max<int64_t>(1, std::min(S, n_chunks));
-}
-
-int medoid_strips(int64_t N) { return strips_by_knob("FC_MEDOID_STRIPS", N); }
+// strips a tile's chunk range is cut into: enough items to hand out evenly
+int medoid_strips(int64_t N) { return tile_strips("FC_MEDOID_STRIPS", kTileItemsPerCu, kTileItemMaxStrips, N, N); }
 
 template <bool STAGE>
 static int launch_group_sums_as(const fc_ensemble *e, const int32_t *seg_end_dev, int n_tiles, int S, unsigned long long *sums_dev,
                                 unsigned long long *ecc_dev) {
-  const size_t lds = STAGE ? (size_t)kMedTileRows * e->A * 3 * sizeof(double) : 0;
+  const size_t lds = STAGE ? tile_rows_lds_bytes(e->A) : 0;
   FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_group_sums<STAGE>), lds, "k_group_sums"));
   const unsigned gx = (unsigned)std::min<int64_t>((int64_t)n_tiles * S, (int64_t)1 << 20);
-  hipLaunchKernelGGL((k_group_sums<STAGE>), dim3(gx), dim3(kMedThreads), lds, ctx().stream, e->Xs.as<double>(),
+  hipLaunchKernelGGL((k_group_sums<STAGE>), dim3(gx), dim3(kTileThreads), lds, ctx().stream, e->Xs.as<double>(),
                      e->Xa.as<double>(), e->G.as<double>(), (int)e->N, e->Npad, (int)e->A, seg_end_dev, n_tiles, S, sums_dev,
                      ecc_dev);
   return check_launch("k_group_sums");
@@ -205,10 +153,10 @@ static int launch_group_sums_as(const fc_ensemble *e, const int32_t *seg_end_dev
 int launch_group_sums(const fc_ensemble *e, const int32_t *seg_end_dev, unsigned long long *out_dev, bool timed) {
   Context &c = ctx();
   const int S = medoid_strips(e->N);
-  const int n_tiles = (int)ceil_div(e->N, kMedTileRows);
+  const int n_tiles = (int)ceil_div(e->N, kTileRows);
   if (timed) FC_HIP_TRY(hipEventRecord(c.ev0, c.stream));
   FC_HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)e->N * 2 * sizeof(unsigned long long), c.stream));
-  FC_TRY((e->A <= kMedLdsAtoms ? launch_group_sums_as<true> : launch_group_sums_as<false>)(e, seg_end_dev, n_tiles, S, out_dev,
+  FC_TRY((e->A <= kTileLdsAtoms ? launch_group_sums_as<true> : launch_group_sums_as<false>)(e, seg_end_dev, n_tiles, S, out_dev,
                                                                                          out_dev + e->N));
   if (timed) FC_HIP_TRY(hipEventRecord(c.ev1, c.stream));
   return FC_OK;

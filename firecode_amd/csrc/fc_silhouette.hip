@@ -12,9 +12,8 @@
 //   b[i] = min over the other non-empty groups g of m[i, g] = (double) T[i, g] 2^-32 / size_g, nearest[i] = that g,
 //          the lowest on ties
 //
-// k_silhouette_tile is k_group_sums' tile (fc_medoid.hip), which is k_knn_tile's (fc_knn.hip): 256 threads, four
-// wavefronts x 4 rows from Xa (staged in LDS up to kSilLdsAtoms atoms, read from global memory beyond), 64 columns per
-// chunk, one lane per column, the column's coordinates coalesced from Xs -- over the LABEL-SORTED copy of the labelled
+// k_silhouette_tile walks fc_rmsd_tile.h's tile, as k_group_sums (fc_medoid.hip) and k_knn_tile (fc_knn.hip) do -- over
+// the LABEL-SORTED copy of the labelled
 // conformers (the host's stable order by label, one k_ensemble_gather), and over the FULL SQUARE: every row owns its
 // results, nothing is handed to a column, no atomics.
 // In the sorted copy a group is the contiguous column range [seg_begin[j], seg_end[j]) around any of its columns j, and
@@ -39,18 +38,11 @@
 // k_silhouette_join -- one thread per row -- walks the row's strips in order, adds the partial sums of a cut group from
 // the tail records up to its head record, forms its m, takes the minimum against the strips' own bests and writes a, b
 // and nearest.  No spin-waits, no grid barrier, no float atomics.
-#include "fc_internal.h"
-#include "fc_kabsch_math.h"
+#include "fc_rmsd_tile.h"
 
 #include <climits>
-#include <cmath>
 
 namespace fc {
-
-constexpr int kSilThreads = 256;
-constexpr int kSilR = 4;                                     // rows per wavefront
-constexpr int kSilTileRows = (kSilThreads / 64) * kSilR;     // rows per workgroup
-constexpr int64_t kSilLdsAtoms = 256;                        // 16 rows x A x 24 B = 96 KiB of LDS (k_knn_tile's stage)
 
 // the mean of a complete integer sum over n distances, in A: the one expression both kernels use
 __host__ __device__ __forceinline__ double sil_mean(unsigned long long T, int n) {
@@ -78,11 +70,11 @@ struct SilRecords {
 };
 
 template <bool STAGE>
-__global__ void __launch_bounds__(kSilThreads)
+__global__ void __launch_bounds__(kTileThreads)
 k_silhouette_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, const double *__restrict__ G, int M, int64_t Npad,
                   int A, const int32_t *__restrict__ seg_begin, const int32_t *__restrict__ seg_end, int n_tiles, int n_chunks,
                   int S, const SilRecords out) {
-  extern __shared__ double s_rows[];  // [kSilTileRows][A][3] when STAGE
+  extern __shared__ double s_rows[];  // [kTileRows][A][3] when STAGE
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int A3 = 3 * A;
   const double dA = (double)A;
@@ -90,31 +82,21 @@ k_silhouette_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, 
 
   for (int64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
     const int tile = (int)(item / S), s = (int)(item % S);
-    const int row0 = tile * kSilTileRows;
+    const int row0 = tile * kTileRows;
     // the strip's chunks of 64 columns (S <= n_chunks: never empty)
     const int c0 = (int)((int64_t)s * n_chunks / S), c1 = (int)((int64_t)(s + 1) * n_chunks / S);
     const int col0 = c0 * 64;
-    if (STAGE) {
-      __syncthreads();  // (the previous item's readers)
-      for (int r = w; r < kSilTileRows; r += kSilThreads / 64) {
-        const double *__restrict__ src = Xa + (int64_t)min(row0 + r, M - 1) * A3;
-        for (int t = lane; t < A3; t += 64) s_rows[r * A3 + t] = src[t];
-      }
-      __syncthreads();
-    }
-    const int wrow = row0 + w * kSilR;
+    if (STAGE) tile_stage_rows(s_rows, Xa, row0, M, A3);
+    const int wrow = row0 + w * kTileR;
     if (wrow >= M) continue;  // (wave-uniform; no barrier follows in this item)
-    int row[kSilR], rsb[kSilR], bg[kSilR];
-    const double *__restrict__ P[kSilR];
-    double Gi[kSilR], bm[kSilR];
-    unsigned long long carry[kSilR];
+    int row[kTileR], rsb[kTileR], bg[kTileR];
+    const double *__restrict__ P[kTileR];
+    double Gi[kTileR], bm[kTileR];
+    unsigned long long carry[kTileR];
+    tile_rows<STAGE>(s_rows, Xa, G, row0, wrow, M, A3, row, P, Gi);
 #pragma unroll
-    for (int r = 0; r < kSilR; ++r) {
-      row[r] = wrow + r;
-      const int rl = min(row[r], M - 1);
-      P[r] = STAGE ? s_rows + (w * kSilR + r) * A3 : Xa + (int64_t)rl * A3;
-      Gi[r] = G[rl];
-      rsb[r] = seg_begin[rl];
+    for (int r = 0; r < kTileR; ++r) {
+      rsb[r] = seg_begin[min(row[r], M - 1)];
       carry[r] = 0ull;
       bm[r] = INFINITY;
       bg[r] = INT_MAX;
@@ -125,27 +107,9 @@ k_silhouette_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, 
       const int j = cbase + lane;
       const int jl = min(j, M - 1);
       const double *__restrict__ q0 = Xs + jl;
-      const int64_t step = 3 * Npad;
-      // ---- 1. covariances with the 4 rows (k_knn_tile's loop)
-      double B[kSilR][9];
-#pragma unroll
-      for (int r = 0; r < kSilR; ++r)
-#pragma unroll
-        for (int e = 0; e < 9; ++e) B[r][e] = 0.0;
-      {
-        const double *__restrict__ qa = q0;
-#pragma unroll 2
-        for (int a = 0; a < A; ++a, qa += step) {
-          const double qx = qa[0], qy = qa[Npad], qz = qa[2 * Npad];
-#pragma unroll
-          for (int r = 0; r < kSilR; ++r) {
-            const double px = P[r][a * 3], py = P[r][a * 3 + 1], pz = P[r][a * 3 + 2];
-            B[r][0] = fma(px, qx, B[r][0]); B[r][1] = fma(px, qy, B[r][1]); B[r][2] = fma(px, qz, B[r][2]);
-            B[r][3] = fma(py, qx, B[r][3]); B[r][4] = fma(py, qy, B[r][4]); B[r][5] = fma(py, qz, B[r][5]);
-            B[r][6] = fma(pz, qx, B[r][6]); B[r][7] = fma(pz, qy, B[r][7]); B[r][8] = fma(pz, qz, B[r][8]);
-          }
-        }
-      }
+      // ---- 1. covariances with the 4 rows
+      double B[kTileR][9];
+      tile_covariance(P, q0, Npad, A, TileNoPerm{}, B);
       // ---- 2. the column's group: where it begins, whether this column closes it, whether it goes on behind the chunk
       const double Gj = G[jl];
       const int sb = seg_begin[jl], se = seg_end[jl];  // (sb <= jl < se <= M)
@@ -157,9 +121,12 @@ k_silhouette_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, 
       open_g = goes_on ? sb63 : -1;
       // ---- 3. per row: the rotation, the explicit rotated difference, the scan and the groups that close here
 #pragma unroll
-      for (int r = 0; r < kSilR; ++r) {
+      for (int r = 0; r < kTileR; ++r) {
         if (row[r] >= M) continue;  // (wave-uniform)
+        // tile_rmsd's body, written out: as a call it takes this kernel from 242 / 250 to 248 / 256 VGPRs, the last count
+        // at which two wavefronts fit a SIMD (the same instructions and the same speed, but no room for the next change)
         const double GG = Gi[r] + Gj;
+        const int64_t step = 3 * Npad;
         double R[9];
         if (!kabsch_rotation_qcp(B[r], GG, R)) (void)kabsch_rotation(B[r], R);
         double ssq = 0.0;
@@ -200,7 +167,7 @@ k_silhouette_tile(const double *__restrict__ Xs, const double *__restrict__ Xa, 
     }
     // ---- 4. the strip's best per row, and what is open at its end
 #pragma unroll
-    for (int r = 0; r < kSilR; ++r) {
+    for (int r = 0; r < kTileR; ++r) {
       if (row[r] >= M) continue;  // (wave-uniform)
       double m = bm[r];
       int g = bg[r];
@@ -261,7 +228,7 @@ k_silhouette_join(const int32_t *__restrict__ seg_begin, const int32_t *__restri
   }
 }
 
-int silhouette_strips(int64_t M) { return strips_by_knob("FC_SILHOUETTE_STRIPS", M); }
+int silhouette_strips(int64_t M) { return tile_strips("FC_SILHOUETTE_STRIPS", kTileItemsPerCu, kTileItemMaxStrips, M, M); }
 
 // bytes of the work block of launch_silhouette for M sorted conformers: the outputs first -- a (M doubles) | b (M
 // doubles) | nearest (M int32), the part that travels to the host: silhouette_result_bytes -- then the records of S strips
@@ -275,10 +242,10 @@ size_t silhouette_work_bytes(int64_t M, int S) {
 template <bool STAGE>
 static int launch_silhouette_tile_as(const fc_ensemble *e, const int32_t *seg_begin_dev, const int32_t *seg_end_dev, int n_tiles,
                                      int n_chunks, int S, const SilRecords &rec) {
-  const size_t lds = STAGE ? (size_t)kSilTileRows * e->A * 3 * sizeof(double) : 0;
+  const size_t lds = STAGE ? tile_rows_lds_bytes(e->A) : 0;
   FC_TRY(allow_dynamic_lds(reinterpret_cast<const void *>(k_silhouette_tile<STAGE>), lds, "k_silhouette_tile"));
   const unsigned gx = (unsigned)std::min<int64_t>((int64_t)n_tiles * S, (int64_t)1 << 20);
-  hipLaunchKernelGGL((k_silhouette_tile<STAGE>), dim3(gx), dim3(kSilThreads), lds, ctx().stream, e->Xs.as<double>(),
+  hipLaunchKernelGGL((k_silhouette_tile<STAGE>), dim3(gx), dim3(kTileThreads), lds, ctx().stream, e->Xs.as<double>(),
                      e->Xa.as<double>(), e->G.as<double>(), (int)e->N, e->Npad, (int)e->A, seg_begin_dev, seg_end_dev, n_tiles,
                      n_chunks, S, rec);
   return check_launch("k_silhouette_tile");
@@ -309,10 +276,10 @@ int launch_silhouette(const fc_ensemble *e, const int32_t *seg_begin_dev, const 
   rec.head_g = reinterpret_cast<int32_t *>(take(ms * 4));
   rec.tail_g = reinterpret_cast<int32_t *>(take(ms * 4));
   rec.own_sum = reinterpret_cast<unsigned long long *>(take((size_t)M * 8));
-  const int n_tiles = (int)ceil_div(M, kSilTileRows), n_chunks = (int)ceil_div(M, 64);
+  const int n_tiles = (int)ceil_div(M, kTileRows), n_chunks = (int)ceil_div(M, 64);
   if (timed) FC_HIP_TRY(hipEventRecord(c.ev0, c.stream));
   FC_HIP_TRY(hipMemsetAsync(rec.head_g, 0xFF, ms * 4, c.stream));  // -1: no head record
-  FC_TRY((e->A <= kSilLdsAtoms ? launch_silhouette_tile_as<true> : launch_silhouette_tile_as<false>)(e, seg_begin_dev, seg_end_dev,
+  FC_TRY((e->A <= kTileLdsAtoms ? launch_silhouette_tile_as<true> : launch_silhouette_tile_as<false>)(e, seg_begin_dev, seg_end_dev,
                                                                                                    n_tiles, n_chunks, S, rec));
   const unsigned gj = (unsigned)std::min<int64_t>(ceil_div(M, 256), (int64_t)1 << 16);
   hipLaunchKernelGGL(k_silhouette_join, dim3(gj), dim3(256), 0, c.stream, seg_begin_dev, seg_end_dev, (int)M, S, rec, a_dev, b_dev,
