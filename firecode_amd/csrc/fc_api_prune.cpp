@@ -93,7 +93,10 @@ static size_t slot_bytes(int64_t n_slots, int64_t W) { return (size_t)n_slots * 
 struct LadderJob {
   const uint64_t *bits_dev = nullptr;   // bit matrix for the level-by-level form (dense similarity / no pair list)
   const uint64_t *pairs_dev = nullptr;  // device list of the exactly-similar pairs (see ladder_single)
-  bool pairs_are_final = false;         // the list's length is counters[2] alone (uploaded or gathered by the caller)
+  bool pairs_are_final = false;         // the list is complete as it stands (uploaded or gathered by the caller): no candidate count to check
+  // where the list's length stands on the device (nullptr: counters[2]).  A caller's own list brings a word of its own:
+  // counters[2] stays the length of the ensemble's simq, which fc_prune_similar_pairs and the export read afterwards
+  const unsigned long long *n_pairs_dev = nullptr;
   bool counters_zeroed = false;         // counters[8 ..) are already zero on the stream
   // which device form of the ladder runs: -1 the prune's own choice (below); 0 the bit-matrix levels, 1 the one-workgroup
   // pair ladder, 2 the launch-per-level pair ladder -- exactly that one or FC_E_LIMIT (fc_debug_ladder_from_pairs)
@@ -132,6 +135,7 @@ static int ladder_single(fc_ensemble *e, int64_t min_per_group, const LadderJob 
   if (defer_slot < 0) FC_TRY(pinned_reserve((size_t)(W + 16) * sizeof(uint64_t)));
   uint64_t *mb = e->ladder.as<uint64_t>();
   auto *cnt = reinterpret_cast<unsigned long long *>(e->counters.p);
+  const unsigned long long *const n_pairs_dev = job.n_pairs_dev ? job.n_pairs_dev : cnt + 2;
   // ladder values that can ever run (n_active <= N) -- decided here, the rest on the device
   std::vector<int64_t> ks;
   for (int64_t k : kLadder)
@@ -202,12 +206,12 @@ static int ladder_single(fc_ensemble *e, int64_t min_per_group, const LadderJob 
     // is the only level, which the prunes never send there)
     uint64_t *const result_dev = mb + (size_t)std::max(n_lv, 2) * W;
     if (many)
-      FC_TRY(launch_ladder_pairs_many(pairs_dev, e->levelmask.as<uint64_t>(), cnt + 2, job.pairs_are_final ? nullptr : cnt + 6,
+      FC_TRY(launch_ladder_pairs_many(pairs_dev, e->levelmask.as<uint64_t>(), n_pairs_dev, job.pairs_are_final ? nullptr : cnt + 6,
                                       (unsigned long long)e->pairq_cap, ladder_cap, N, W, min_per_group,
                                       ks_dev ? ks_dev : e->ladder_k.as<int64_t>(), ks.data(), n_lv, mb, result_dev, cnt,
                                       job.many_grid ? job.many_grid : ladder_many_grid()));
     else
-      FC_TRY(launch_ladder_pairs(pairs_dev, e->levelmask.as<uint64_t>(), cnt + 2,
+      FC_TRY(launch_ladder_pairs(pairs_dev, e->levelmask.as<uint64_t>(), n_pairs_dev,
                                  job.pairs_are_final ? nullptr : cnt + 6,
                                  (unsigned long long)e->pairq_cap, ladder_cap, N, W, min_per_group,
                                  ks_dev ? ks_dev : e->ladder_k.as<int64_t>(), n_lv, result_dev, cnt));
@@ -634,15 +638,16 @@ int fc_prune_from_pairs(fc_ensemble *ens, const uint64_t *pairs, int64_t n_pairs
   const int64_t N = ens->N, W = ens->W;
   if (N == 0) return FC_OK;
   FC_TRY(ens->counters.reserve(kCounters * sizeof(uint64_t)));
-  auto *cnt = reinterpret_cast<unsigned long long *>(ens->counters.p);
-  DevBuf dp;
+  DevBuf dp, dn;
   FC_TRY(upload(dp, pairs, (size_t)n_pairs));
+  // the length of the caller's list travels in a word of its own: counters[2] is the length of this ensemble's simq (the
+  // list fc_prune_similar_pairs and fc_prune_export_pairs_dev hand out), which a prune from another list must not change
   const unsigned long long np = (unsigned long long)n_pairs;
-  FC_TRY(h2d(cnt + 2, &np, sizeof np));  // k_ladder_pairs reads the list length from counters[2]
+  FC_TRY(upload(dn, &np, 1));
   LadderJob job;
   job.mask_out = mask_out;
   if (np <= kPairLadderCap && fits_pair_ladder(W)) {  // sparse: one launch over the pair list; no bit matrix needed
-    job.pairs_dev = dp.as<uint64_t>(), job.pairs_are_final = true;
+    job.pairs_dev = dp.as<uint64_t>(), job.pairs_are_final = true, job.n_pairs_dev = dn.as<unsigned long long>();
     return ladder_single(ens, min_per_group, job);
   }
   // dense: rebuild the whole bit matrix (rows padded like ladder_single expects) and run the levels

@@ -623,7 +623,9 @@ int fc_prune_level(fc_ensemble *ens, int64_t k, const uint8_t *mask_in, uint8_t 
  * similar pairs as (i << 32) | j in processing order indices (n_out = count;
  * FC_E_LIMIT when the candidate queue overflowed -- use fc_prune_level then).
  * The ranks all-gather the lists ONCE and every rank replays the whole ladder
- * locally with fc_prune_from_pairs (pairs from all ranks, any order). */
+ * locally with fc_prune_from_pairs (pairs from all ranks, any order).
+ * fc_prune_from_pairs leaves the rank's own list and its length alone:
+ * fc_prune_similar_pairs returns the same list before and after it. */
 int fc_prune_similar_pairs(fc_ensemble *ens, uint64_t *pairs_out, int64_t capacity, int64_t *n_out);
 int fc_prune_from_pairs(fc_ensemble *ens, const uint64_t *pairs, int64_t n_pairs,
                         int64_t min_per_group, uint8_t *mask_out);
