@@ -205,6 +205,12 @@ _SIGNATURES = {
     "fc_ensemble_kmedoids": [_ens, _p_i64, _i64, _i64, _p_i64, C.POINTER(C.c_int32), _p_f64, _p_u64, _p_i64],
     "fc_ensemble_silhouette": [_ens, C.POINTER(C.c_int32), _i64, _p_f64, _p_f64, _p_f64, C.POINTER(C.c_int32), _p_f64, _p_i64,
                                _p_f64, _p_f64],
+    "fc_ensemble_medoids_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, C.POINTER(C.c_int32), _i64, _p_i64, _p_i64,
+                                 _p_f64, _p_f64, _p_u64, _p_f64, _p_f64, _p_i64],
+    "fc_ensemble_kmedoids_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, _p_i64, _i64, _i64, _p_i64,
+                                  C.POINTER(C.c_int32), _p_f64, _p_u64, _p_i64],
+    "fc_ensemble_silhouette_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, C.POINTER(C.c_int32), _i64, _p_f64, _p_f64,
+                                    _p_f64, C.POINTER(C.c_int32), _p_f64, _p_i64, _p_f64, _p_f64, _p_i64],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("fc_last_error",)
@@ -813,6 +819,79 @@ class DeviceEnsemble:
              pf(mean), pi(sizes), C.byref(score), C.byref(ms))
         out = (s, a, b, nearest, mean, sizes, score.value)
         return out + (ms.value,) if want_ms else out
+
+    def _sums_perm_args(self, symmetry, prune_enantiomers):
+        """``symmetry=`` (a (K, A_all) table) and the mirror flag of ``medoids_sym`` / ``kmedoids_sym`` /
+        ``silhouette_sym`` -> None when neither is set, else the arguments of the ``_perm`` entry points behind the
+        handle; every check made before the handle is used"""
+        from firecode_amd import symmetry as S
+
+        enant = check_flag("prune_enantiomers", prune_enantiomers)
+        if symmetry is None and not enant:
+            return None
+        # (a twin workspace refuses here; the identity table stands for "mirror images only")
+        keep, args = self._perm_args(np.arange(self.A_all, dtype=np.int64)[None] if symmetry is None else symmetry)
+        S.medoid_lds_check(args[1], args[2])
+        return keep, args + (int(enant),)
+
+    def medoids_sym(self, labels=None, n_groups=None, symmetry=None, prune_enantiomers=False, want_ms=False):
+        """``medoids`` under the symmetry-corrected distance (fc_ensemble_medoids_perm; the contract is in
+        include/fc_hip.h): ``symmetry=`` a (K, A_all) table of atom permutations and / or ``prune_enantiomers=True`` make
+        the distance the smallest RMSD over the permutations and, with the flag, over both handednesses -- the distance
+        of ``knn(symmetry=, prune_enantiomers=)``, bit for bit.  The outputs of ``medoids``; ``want_ms=True`` appends the
+        kernel's milliseconds and ``(formed, explicit)``, the (pair, permutation, handedness) combinations whose
+        eigenvalue was formed and those taken through the explicit pass.  With neither keyword: ``medoids`` itself."""
+        perm = self._sums_perm_args(symmetry, prune_enantiomers)
+        if perm is None:
+            out = self.medoids(labels, n_groups, want_ms=want_ms)
+            return out + ((0, 0),) if want_ms else out
+        lab, n_groups = check_group_labels(labels, self.N, n_groups)
+        med, sizes = np.empty(n_groups, dtype=np.int64), np.empty(n_groups, dtype=np.int64)
+        mean, radius = np.empty(n_groups), np.empty(n_groups)
+        sums, ecc = np.zeros(self.N, dtype=np.uint64), np.zeros(self.N)
+        ms, stats = C.c_double(0), np.zeros(2, dtype=np.int64)
+        call("fc_ensemble_medoids_perm", self.handle, *perm[1], ptr(lab, C.c_int32), n_groups, pi(med), pi(sizes), pf(mean),
+             pf(radius), pw(sums), pf(ecc), C.byref(ms), pi(stats) if want_ms else None)
+        out = (med, sizes, mean, radius, sums, ecc)
+        return out + (ms.value, (int(stats[0]), int(stats[1]))) if want_ms else out
+
+    def kmedoids_sym(self, n, init=None, max_iter=50, symmetry=None, prune_enantiomers=False):
+        """``kmedoids`` under the symmetry-corrected distance of ``medoids_sym`` (fc_ensemble_kmedoids_perm): the default
+        start is ``select_diverse(n, start=0, symmetry=, prune_enantiomers=)``, the assignment the nearest
+        representative under that distance, the move the medoid of ``medoids_sym``.  The outputs of ``kmedoids``.  With
+        neither keyword: ``kmedoids`` itself."""
+        perm = self._sums_perm_args(symmetry, prune_enantiomers)
+        if perm is None:
+            return self.kmedoids(n, init=init, max_iter=max_iter)
+        n = check_count("n", n)
+        max_iter = check_count("max_iter", max_iter, low=0)
+        if self.N and n > self.N:
+            raise FirecodeHipInputError(FC_E_INVALID, f"n={n} representatives of N={self.N} conformers")
+        start = None if init is None else check_indices("init", init, self.N, distinct=True, count=n)
+        med = np.empty(n, dtype=np.int64)
+        lab, dist = np.empty(self.N, dtype=np.int32), np.empty(self.N)
+        cost, n_iter = C.c_uint64(0), C.c_int64(0)
+        call("fc_ensemble_kmedoids_perm", self.handle, *perm[1], pi(start), n, max_iter, pi(med), ptr(lab, C.c_int32), pf(dist),
+             C.byref(cost), C.byref(n_iter))
+        return (med if self.N else med[:0]), lab, dist, int(cost.value), int(n_iter.value)
+
+    def silhouette_sym(self, labels=None, n_groups=None, symmetry=None, prune_enantiomers=False, want_ms=False):
+        """``silhouette`` under the symmetry-corrected distance of ``medoids_sym`` (fc_ensemble_silhouette_perm).  The
+        outputs of ``silhouette``; ``want_ms=True`` appends the kernels' milliseconds and ``(formed, explicit)`` as
+        ``medoids_sym``.  With neither keyword: ``silhouette`` itself."""
+        perm = self._sums_perm_args(symmetry, prune_enantiomers)
+        if perm is None:
+            out = self.silhouette(labels, n_groups, want_ms=want_ms)
+            return out + ((0, 0),) if want_ms else out
+        lab, n_groups = check_group_labels(labels, self.N, n_groups)
+        s, a, b = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        nearest = np.empty(self.N, dtype=np.int32)
+        mean, sizes = np.empty(n_groups), np.empty(n_groups, dtype=np.int64)
+        score, ms, stats = C.c_double(0), C.c_double(0), np.zeros(2, dtype=np.int64)
+        call("fc_ensemble_silhouette_perm", self.handle, *perm[1], ptr(lab, C.c_int32), n_groups, pf(s), pf(a), pf(b),
+             ptr(nearest, C.c_int32), pf(mean), pi(sizes), C.byref(score), C.byref(ms), pi(stats) if want_ms else None)
+        out = (s, a, b, nearest, mean, sizes, score.value)
+        return out + (ms.value, (int(stats[0]), int(stats[1]))) if want_ms else out
 
     def rmsd_matrix(self):
         r = np.zeros((self.N, self.N))

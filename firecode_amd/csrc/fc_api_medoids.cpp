@@ -53,8 +53,10 @@ static int sum_limit_check(fc_ensemble *ens, int64_t largest) {
   return FC_OK;
 }
 
-// S and E of the contract, by conformer (N each; 0 for singletons and unlabelled conformers).  ms_kernel may be NULL.
-static int group_sums(fc_ensemble *ens, const Grouping &g, std::vector<uint64_t> &S, std::vector<double> &E, double *ms_kernel) {
+// S and E of the contract, by conformer (N each; 0 for singletons and unlabelled conformers).  ms_kernel may be NULL;
+// sym (may be NULL): under d_sym.
+static int group_sums(fc_ensemble *ens, const Grouping &g, std::vector<uint64_t> &S, std::vector<double> &E, double *ms_kernel,
+                      const SymTable *sym = nullptr) {
   const int64_t N = ens->N, M = (int64_t)g.order.size();
   S.assign((size_t)N, 0);
   E.assign((size_t)N, 0.0);
@@ -77,7 +79,7 @@ static int group_sums(fc_ensemble *ens, const Grouping &g, std::vector<uint64_t>
       e = &sorted;
     }
     FC_TRY(d_out.reserve((size_t)M * 2 * sizeof(uint64_t)));
-    FC_TRY(launch_group_sums(e, d_end.as<int32_t>(), d_out.as<unsigned long long>(), ms_kernel != nullptr));  // S | E
+    FC_TRY(launch_group_sums(e, d_end.as<int32_t>(), d_out.as<unsigned long long>(), ms_kernel != nullptr, sym));  // S | E
     FC_TRY(d2h(out.data(), d_out.p, (size_t)M * 2 * sizeof(uint64_t)));
     FC_TRY(sync());
     if (ms_kernel) {
@@ -121,8 +123,10 @@ static int labels_check(const int32_t *labels, int64_t N, int64_t n_groups) {
   return FC_OK;
 }
 
+// sym_args (may be NULL): under d_sym, already checked -- the table goes up only where the device is used
 static int medoids_checked(fc_ensemble *ens, const int32_t *labels, int64_t n_groups, int64_t *medoids_out, int64_t *sizes_out,
-                           double *mean_out, double *radius_out, uint64_t *sums_q32_out, double *ecc_out, double *ms_kernel) {
+                           double *mean_out, double *radius_out, uint64_t *sums_q32_out, double *ecc_out, double *ms_kernel,
+                           const SymArgs *sym_args = nullptr) {
   // (the scalar arguments are judged first, so that their refusals do not depend on the handle)
   FC_REQUIRE(n_groups >= 1, "n_groups=%lld < 1", (long long)n_groups);
   FC_REQUIRE(n_groups <= (int64_t)INT32_MAX, "n_groups=%lld: labels are 32-bit", (long long)n_groups);
@@ -139,11 +143,14 @@ static int medoids_checked(fc_ensemble *ens, const int32_t *labels, int64_t n_gr
   group_by_label(labels, N, n_groups, g);
   std::vector<uint64_t> S;
   std::vector<double> E;
+  const auto sums = [&](const SymTable *sym) { return group_sums(ens, g, S, E, ms_kernel, sym); };
   if (g.largest >= 2) {
     FC_TRY(ensure_init());
     FC_TRY(sum_limit_check(ens, g.largest));
+    FC_TRY(with_sym_table(sym_args, sums));
+  } else {
+    FC_TRY(sums(nullptr));  // (no pair: no device)
   }
-  FC_TRY(group_sums(ens, g, S, E, ms_kernel));
   medoids_of(g, S, E, medoids_out, sizes_out, mean_out, radius_out);
   if (sums_q32_out) std::copy(S.begin(), S.end(), sums_q32_out);
   if (ecc_out) std::copy(E.begin(), E.end(), ecc_out);
@@ -152,8 +159,9 @@ static int medoids_checked(fc_ensemble *ens, const int32_t *labels, int64_t n_gr
 
 // a, b and nearest of the silhouette's contract for the labelled conformers, by conformer; the unlabelled ones and --
 // b, nearest -- everything the device was not needed for keep what the caller put there.  M >= 2 labelled conformers.
+// sym (may be NULL): under d_sym.
 static int silhouette_device(fc_ensemble *ens, const Grouping &g, const int32_t *labels, double *a_out, double *b_out,
-                             int32_t *nearest_out, double *ms_kernel) {
+                             int32_t *nearest_out, double *ms_kernel, const SymTable *sym = nullptr) {
   const int64_t N = ens->N, M = (int64_t)g.order.size();
   std::vector<int32_t> seg((size_t)M * 2);  // seg_begin | seg_end
   for (size_t c = 0; c + 1 < g.offs.size(); ++c)
@@ -175,7 +183,8 @@ static int silhouette_device(fc_ensemble *ens, const Grouping &g, const int32_t 
       e = &sorted;
     }
     FC_TRY(d_work.reserve(silhouette_work_bytes(M, S)));
-    FC_TRY(launch_silhouette(e, d_seg.as<int32_t>(), d_seg.as<int32_t>() + M, S, d_work.as<uint8_t>(), ms_kernel != nullptr));
+    FC_TRY(launch_silhouette(e, d_seg.as<int32_t>(), d_seg.as<int32_t>() + M, S, d_work.as<uint8_t>(), ms_kernel != nullptr,
+                             sym));
     FC_TRY(d2h(res.data(), d_work.p, n_res));
     FC_TRY(sync());
     if (ms_kernel) {
@@ -200,7 +209,7 @@ static int silhouette_device(fc_ensemble *ens, const Grouping &g, const int32_t 
 
 static int silhouette_checked(fc_ensemble *ens, const int32_t *labels, int64_t n_groups, double *s_out, double *a_out,
                               double *b_out, int32_t *nearest_out, double *cluster_mean_out, int64_t *sizes_out, double *score_out,
-                              double *ms_kernel) {
+                              double *ms_kernel, const SymArgs *sym_args = nullptr) {
   // (the scalar arguments are judged first, so that their refusals do not depend on the handle)
   FC_REQUIRE(n_groups >= 1, "n_groups=%lld < 1", (long long)n_groups);
   FC_REQUIRE(n_groups <= (int64_t)INT32_MAX, "n_groups=%lld: labels are 32-bit", (long long)n_groups);
@@ -229,7 +238,9 @@ static int silhouette_checked(fc_ensemble *ens, const int32_t *labels, int64_t n
   if (M >= 2) {  // a pair: the device
     FC_TRY(ensure_init());
     FC_TRY(sum_limit_check(ens, M));  // (a prefix runs over a whole row)
-    FC_TRY(silhouette_device(ens, g, labels, a_out, b_out, nearest_out, ms_kernel));
+    FC_TRY(with_sym_table(sym_args, [&](const SymTable *sym) {
+      return silhouette_device(ens, g, labels, a_out, b_out, nearest_out, ms_kernel, sym);
+    }));
   }
   std::vector<double> sum((size_t)n_groups, 0.0);
   double total = 0.0;
@@ -308,9 +319,9 @@ struct KmState {
   uint64_t cost = 0;
 };
 
-// the assignment step: the k = 1 list of fc_ensemble_knn_cross(ens, subset(ens, M)); a medoid gets its own position and
-// distance 0, set by index
-static int km_assign(fc_ensemble *ens, KmState &s) {
+// the assignment step: the k = 1 list of fc_ensemble_knn_cross(ens, subset(ens, M)) -- sym (may be NULL): of
+// fc_ensemble_knn_cross_perm; a medoid gets its own position and distance 0, set by index
+static int km_assign(fc_ensemble *ens, KmState &s, const SymTable *sym) {
   const int64_t N = ens->N, n = (int64_t)s.M.size();
   std::vector<int32_t> idx((size_t)n);
   for (int64_t c = 0; c < n; ++c) idx[(size_t)c] = (int32_t)s.M[(size_t)c];
@@ -321,7 +332,7 @@ static int km_assign(fc_ensemble *ens, KmState &s) {
   const auto run = [&]() {
     FC_TRY(upload(d_idx, idx.data(), (size_t)n));
     FC_TRY(ensemble_gather(ens, d_idx.as<int32_t>(), n, &reps, false));
-    return knn(ens, &reps, true, 1, INFINITY, s.lab.data(), s.dist.data(), nullptr, nullptr);  // (ends with a wait)
+    return knn(ens, &reps, true, 1, INFINITY, s.lab.data(), s.dist.data(), nullptr, nullptr, sym);  // (ends with a wait)
   };
   FC_TRY(drained(run()));
   for (int64_t c = 0; c < n; ++c) s.lab[(size_t)s.M[(size_t)c]] = (int32_t)c, s.dist[(size_t)s.M[(size_t)c]] = 0.0;
@@ -330,8 +341,55 @@ static int km_assign(fc_ensemble *ens, KmState &s) {
   return FC_OK;
 }
 
+// the loop of the contract behind the checks; sym (may be NULL): under d_sym -- the start, the assignment and the move
+static int kmedoids_run(fc_ensemble *ens, const int64_t *init, int64_t n, int64_t max_iter, int64_t *medoids_out,
+                        int32_t *labels_out, double *dist_out, uint64_t *cost_q32_out, int64_t *n_iter_out, const SymTable *sym) {
+  const int64_t N = ens->N;
+  KmState cur, prev;
+  cur.M.resize((size_t)n);
+  if (init != nullptr) {
+    std::copy(init, init + n, cur.M.begin());
+  } else {
+    int64_t picked = 0;
+    FC_TRY(select_diverse(ens, n, 0, -1.0, cur.M.data(), nullptr, nullptr, nullptr, &picked, nullptr, sym));
+    if (picked != n) return set_error(FC_E_INTERNAL, "the diverse selection returned %lld of %lld picks", (long long)picked, (long long)n);
+  }
+  int64_t n_iter = 0;
+  const KmState *result = nullptr;
+  for (int64_t t = 0;; ++t) {
+    FC_TRY(km_assign(ens, cur, sym));
+    ++n_iter;
+    if (t > 0 && cur.cost >= prev.cost) {
+      result = &prev;
+      break;
+    }
+    result = &cur;
+    if (t == max_iter) break;
+    Grouping g;
+    group_by_label(cur.lab.data(), N, n, g);
+    std::vector<uint64_t> S;
+    std::vector<double> E;
+    FC_TRY(group_sums(ens, g, S, E, nullptr, sym));
+    std::vector<int64_t> next((size_t)n);
+    medoids_of(g, S, E, next.data(), nullptr, nullptr, nullptr);
+    if (next == cur.M) break;
+    prev = std::move(cur);
+    cur = KmState();
+    cur.M = std::move(next);
+    result = nullptr;
+  }
+  std::copy(result->M.begin(), result->M.end(), medoids_out);
+  std::copy(result->lab.begin(), result->lab.end(), labels_out);
+  std::copy(result->dist.begin(), result->dist.end(), dist_out);
+  *cost_q32_out = result->cost;
+  *n_iter_out = n_iter;
+  return FC_OK;
+}
+
+// sym_args (may be NULL): under d_sym, already checked -- one upload of the table serves the whole call
 static int kmedoids_checked(fc_ensemble *ens, const int64_t *init, int64_t n, int64_t max_iter, int64_t *medoids_out,
-                            int32_t *labels_out, double *dist_out, uint64_t *cost_q32_out, int64_t *n_iter_out) {
+                            int32_t *labels_out, double *dist_out, uint64_t *cost_q32_out, int64_t *n_iter_out,
+                            const SymArgs *sym_args = nullptr) {
   // (the scalar arguments are judged first, so that their refusals do not depend on the handle)
   FC_REQUIRE(n >= 1, "n=%lld < 1", (long long)n);
   FC_REQUIRE(max_iter >= 0, "max_iter=%lld < 0", (long long)max_iter);
@@ -348,45 +406,50 @@ static int kmedoids_checked(fc_ensemble *ens, const int64_t *init, int64_t n, in
     return set_error(FC_E_LIMIT, "N=%lld: the selection indexes conformers with 32 bits", (long long)N);
   FC_TRY(ensure_init());
   FC_TRY(sum_limit_check(ens, N));  // (no group is larger than the ensemble)
-  KmState cur, prev;
-  cur.M.resize((size_t)n);
-  if (init != nullptr) {
-    std::copy(init, init + n, cur.M.begin());
-  } else {
-    int64_t picked = 0;
-    FC_TRY(select_diverse(ens, n, 0, -1.0, cur.M.data(), nullptr, nullptr, nullptr, &picked, nullptr));
-    if (picked != n) return set_error(FC_E_INTERNAL, "the diverse selection returned %lld of %lld picks", (long long)picked, (long long)n);
-  }
-  int64_t n_iter = 0;
-  const KmState *result = nullptr;
-  for (int64_t t = 0;; ++t) {
-    FC_TRY(km_assign(ens, cur));
-    ++n_iter;
-    if (t > 0 && cur.cost >= prev.cost) {
-      result = &prev;
-      break;
-    }
-    result = &cur;
-    if (t == max_iter) break;
-    Grouping g;
-    group_by_label(cur.lab.data(), N, n, g);
-    std::vector<uint64_t> S;
-    std::vector<double> E;
-    FC_TRY(group_sums(ens, g, S, E, nullptr));
-    std::vector<int64_t> next((size_t)n);
-    medoids_of(g, S, E, next.data(), nullptr, nullptr, nullptr);
-    if (next == cur.M) break;
-    prev = std::move(cur);
-    cur = KmState();
-    cur.M = std::move(next);
-    result = nullptr;
-  }
-  std::copy(result->M.begin(), result->M.end(), medoids_out);
-  std::copy(result->lab.begin(), result->lab.end(), labels_out);
-  std::copy(result->dist.begin(), result->dist.end(), dist_out);
-  *cost_q32_out = result->cost;
-  *n_iter_out = n_iter;
+  return with_sym_table(sym_args, [&](const SymTable *sym) {
+    return kmedoids_run(ens, init, n, max_iter, medoids_out, labels_out, dist_out, cost_q32_out, n_iter_out, sym);
+  });
+}
+
+// ---- the three under d_sym (include/fc_hip.h): the table's checks where fc_ensemble_knn_perm has
+// them, then the plain twin's in its own order.  K = 1 without the flag: d_sym = d, the default's kernels, bit for bit.
+static int sums_sym_args(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, int64_t *stats, SymArgs &a) {
+  FC_TRY(sym_args_check(perms, K, A_sel, mirror, knn_sym_lds_bytes, a));
+  FC_TRY(perm_ensemble_check(ens, K, A_sel, false));
+  if (stats) stats[0] = stats[1] = 0;
+  a.stats = stats;
   return FC_OK;
+}
+
+static int medoids_perm_checked(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, const int32_t *labels,
+                                int64_t n_groups, int64_t *medoids_out, int64_t *sizes_out, double *mean_out, double *radius_out,
+                                uint64_t *sums_q32_out, double *ecc_out, double *ms_kernel, int64_t *stats) {
+  SymArgs a;
+  FC_TRY(sums_sym_args(ens, perms, K, A_sel, mirror, stats, a));
+  const bool plain = K == 1 && !mirror;
+  return medoids_checked(ens, labels, n_groups, medoids_out, sizes_out, mean_out, radius_out, sums_q32_out, ecc_out, ms_kernel,
+                         plain ? nullptr : &a);
+}
+
+static int kmedoids_perm_checked(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, const int64_t *init,
+                                 int64_t n, int64_t max_iter, int64_t *medoids_out, int32_t *labels_out, double *dist_out,
+                                 uint64_t *cost_q32_out, int64_t *n_iter_out) {
+  SymArgs a;
+  FC_TRY(sums_sym_args(ens, perms, K, A_sel, mirror, nullptr, a));
+  // (the start under d_sym, k_diverse_step_sym, keeps one conformer and the table in LDS: within the tiles' need)
+  const bool plain = K == 1 && !mirror;
+  return kmedoids_checked(ens, init, n, max_iter, medoids_out, labels_out, dist_out, cost_q32_out, n_iter_out, plain ? nullptr : &a);
+}
+
+static int silhouette_perm_checked(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
+                                   const int32_t *labels, int64_t n_groups, double *s_out, double *a_out, double *b_out,
+                                   int32_t *nearest_out, double *cluster_mean_out, int64_t *sizes_out, double *score_out,
+                                   double *ms_kernel, int64_t *stats) {
+  SymArgs a;
+  FC_TRY(sums_sym_args(ens, perms, K, A_sel, mirror, stats, a));
+  const bool plain = K == 1 && !mirror;
+  return silhouette_checked(ens, labels, n_groups, s_out, a_out, b_out, nearest_out, cluster_mean_out, sizes_out, score_out,
+                            ms_kernel, plain ? nullptr : &a);
 }
 
 }  // namespace fc
@@ -418,6 +481,31 @@ int fc_ensemble_silhouette(fc_ensemble *ens, const int32_t *labels, int64_t n_gr
   FC_API_LOCK;
   return silhouette_checked(ens, labels, n_groups, s_out, a_out, b_out, nearest_out, cluster_mean_out, sizes_out, score_out,
                             ms_kernel);
+}
+
+int fc_ensemble_medoids_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, const int32_t *labels,
+                             int64_t n_groups, int64_t *medoids_out, int64_t *sizes_out, double *mean_out, double *radius_out,
+                             uint64_t *sums_q32_out, double *ecc_out, double *ms_kernel, int64_t *stats) {
+  FC_API_LOCK;
+  return medoids_perm_checked(ens, perms, K, A_sel, mirror, labels, n_groups, medoids_out, sizes_out, mean_out, radius_out,
+                              sums_q32_out, ecc_out, ms_kernel, stats);
+}
+
+int fc_ensemble_kmedoids_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror, const int64_t *init,
+                              int64_t n, int64_t max_iter, int64_t *medoids_out, int32_t *labels_out, double *dist_out,
+                              uint64_t *cost_q32_out, int64_t *n_iter_out) {
+  FC_API_LOCK;
+  return kmedoids_perm_checked(ens, perms, K, A_sel, mirror, init, n, max_iter, medoids_out, labels_out, dist_out, cost_q32_out,
+                               n_iter_out);
+}
+
+int fc_ensemble_silhouette_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
+                                const int32_t *labels, int64_t n_groups, double *s_out, double *a_out, double *b_out,
+                                int32_t *nearest_out, double *cluster_mean_out, int64_t *sizes_out, double *score_out,
+                                double *ms_kernel, int64_t *stats) {
+  FC_API_LOCK;
+  return silhouette_perm_checked(ens, perms, K, A_sel, mirror, labels, n_groups, s_out, a_out, b_out, nearest_out,
+                                 cluster_mean_out, sizes_out, score_out, ms_kernel, stats);
 }
 
 }  // extern "C"

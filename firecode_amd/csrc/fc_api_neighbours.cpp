@@ -9,57 +9,7 @@
 
 namespace fc {
 
-// a checked table for the forms under d_sym, as the entry point was given it
-struct SymArgs {
-  std::vector<uint16_t> table;  // (K, A_sel), as perm_table_check leaves it
-  int K = 1;
-  bool mirror = false;
-  int64_t *stats = nullptr;  // (may be NULL) the two counters of SymTable::stats_dev after the call
-};
-
-// what every form under d_sym refuses first: the table, the LDS its kernel needs for it, the flag
-static int sym_args_check(const int32_t *perms, int64_t K, int64_t A_sel, int mirror, size_t (*lds_bytes)(int64_t, int64_t),
-                          SymArgs &a) {
-  FC_TRY(perm_table_check(perms, K, A_sel, a.table));
-  FC_TRY(perm_lds_check(lds_bytes(A_sel, K), A_sel, K));
-  FC_REQUIRE(mirror == 0 || mirror == 1, "mirror=%d: 0 or 1", mirror);
-  a.K = (int)K, a.mirror = mirror != 0;
-  return FC_OK;
-}
-
-// the table on the device and, when they are asked for, the two counters behind it
-struct SymUpload {
-  DevBuf perm, stats;
-  int put(const SymArgs &a, SymTable &sym) {
-    FC_TRY(upload(perm, a.table.data(), a.table.size()));
-    sym.perms_dev = perm.as<uint16_t>(), sym.K = a.K, sym.mirror = a.mirror;
-    if (!a.stats) return FC_OK;
-    FC_TRY(stats.reserve(2 * sizeof(unsigned long long)));
-    FC_HIP_TRY(hipMemsetAsync(stats.p, 0, 2 * sizeof(unsigned long long), ctx().stream));
-    sym.stats_dev = reinterpret_cast<unsigned long long *>(stats.p);
-    return FC_OK;
-  }
-  int read(int64_t out[2]) {
-    unsigned long long cnt[2] = {0, 0};
-    FC_TRY(d2h(cnt, stats.p, sizeof cnt));
-    FC_TRY(sync());
-    out[0] = (int64_t)cnt[0], out[1] = (int64_t)cnt[1];
-    return FC_OK;
-  }
-};
-
-// call(sym) behind the checks and ensure_init; a (may be NULL): under d_sym -- the table goes up first and lives, like the
-// counters, until the call's last wait
-template <class Call>
-static int with_sym_table(const SymArgs *a, const Call &call) {
-  if (!a) return call(nullptr);
-  SymUpload up;
-  SymTable sym;
-  int rc = up.put(*a, sym);
-  if (rc == FC_OK) rc = call(&sym);
-  if (rc == FC_OK && a->stats) rc = up.read(a->stats);
-  return drained(rc);
-}
+// (SymArgs, sym_args_check and with_sym_table -- the checked table of the forms under d_sym -- are in fc_internal.h)
 
 // `reps` calls of call(&ms_device) -> the means of the device time they report and of the host time around them
 template <class Call>

@@ -262,7 +262,10 @@ int knn(fc_ensemble *q, fc_ensemble *r, bool cross, int64_t k, double max_rmsd, 
 int warm_knn();
 // ---- fc_medoid.hip ---------------------------------------------------------------------------------------
 int medoid_strips(int64_t N);  // strips a row tile's chunk range is cut into (FC_MEDOID_STRIPS forces it)
-int launch_group_sums(const fc_ensemble *e, const int32_t *seg_end_dev, unsigned long long *out_dev, bool timed);  // S | E
+// S | E; sym (may be NULL): under d_sym (k_group_sums_sym), the rows and the table within the LDS (knn_sym_lds_bytes)
+int launch_group_sums(const fc_ensemble *e, const int32_t *seg_end_dev, unsigned long long *out_dev, bool timed,
+                      const SymTable *sym = nullptr);
+int sums_sym_filter();  // FC_MEDOID_SYM_FILTER=0: every (p, h) explicit in k_group_sums_sym and k_silhouette_tile_sym
 int ensemble_gather(const fc_ensemble *src, const int32_t *idx_dev, int64_t n, fc_ensemble *out, bool exact_gmax);
 int warm_medoid();
 // ---- fc_silhouette.hip -----------------------------------------------------------------------------------
@@ -270,7 +273,7 @@ int silhouette_strips(int64_t M);  // the same rule (FC_SILHOUETTE_STRIPS forces
 size_t silhouette_result_bytes(int64_t M);  // a (M doubles) | b (M doubles) | nearest (M int32) at the front of the work block
 size_t silhouette_work_bytes(int64_t M, int S);
 int launch_silhouette(const fc_ensemble *e, const int32_t *seg_begin_dev, const int32_t *seg_end_dev, int S, uint8_t *work_dev,
-                      bool timed);
+                      bool timed, const SymTable *sym = nullptr);  // sym (may be NULL): under d_sym (k_silhouette_tile_sym)
 int warm_silhouette();
 // ---- fc_tfd_ladder.hip -----------------------------------------------------------------------------------
 int tfd_ladder_device(const int64_t *fm_dev, const int64_t *fm_host, int64_t N, uint8_t *mask_out);
@@ -335,6 +338,59 @@ inline int upload(DevBuf &b, const T *host, size_t count) {
 inline int drained(int rc) {
   if (rc != FC_OK && ctx().ready) (void)hipStreamSynchronize(cur_stream());
   return rc;
+}
+
+// ---- the forms under d_sym (fc_api_neighbours.cpp, fc_api_medoids.cpp) -------------------------------------------
+// a checked table, as the entry point was given it
+struct SymArgs {
+  std::vector<uint16_t> table;  // (K, A_sel), as perm_table_check leaves it
+  int K = 1;
+  bool mirror = false;
+  int64_t *stats = nullptr;  // (may be NULL) the two counters of SymTable::stats_dev after the call
+};
+
+// what every form under d_sym refuses first: the table, the LDS its kernel needs for it, the flag
+inline int sym_args_check(const int32_t *perms, int64_t K, int64_t A_sel, int mirror, size_t (*lds_bytes)(int64_t, int64_t),
+                          SymArgs &a) {
+  FC_TRY(perm_table_check(perms, K, A_sel, a.table));
+  FC_TRY(perm_lds_check(lds_bytes(A_sel, K), A_sel, K));
+  FC_REQUIRE(mirror == 0 || mirror == 1, "mirror=%d: 0 or 1", mirror);
+  a.K = (int)K, a.mirror = mirror != 0;
+  return FC_OK;
+}
+
+// the table on the device and, when they are asked for, the two counters behind it
+struct SymUpload {
+  DevBuf perm, stats;
+  int put(const SymArgs &a, SymTable &sym) {
+    FC_TRY(upload(perm, a.table.data(), a.table.size()));
+    sym.perms_dev = perm.as<uint16_t>(), sym.K = a.K, sym.mirror = a.mirror;
+    if (!a.stats) return FC_OK;
+    FC_TRY(stats.reserve(2 * sizeof(unsigned long long)));
+    FC_HIP_TRY(hipMemsetAsync(stats.p, 0, 2 * sizeof(unsigned long long), ctx().stream));
+    sym.stats_dev = reinterpret_cast<unsigned long long *>(stats.p);
+    return FC_OK;
+  }
+  int read(int64_t out[2]) {
+    unsigned long long cnt[2] = {0, 0};
+    FC_TRY(d2h(cnt, stats.p, sizeof cnt));
+    FC_TRY(sync());
+    out[0] = (int64_t)cnt[0], out[1] = (int64_t)cnt[1];
+    return FC_OK;
+  }
+};
+
+// call(sym) behind the checks and ensure_init; a (may be NULL): under d_sym -- the table goes up first and lives, like the
+// counters, until the call's last wait
+template <class Call>
+inline int with_sym_table(const SymArgs *a, const Call &call) {
+  if (!a) return call(nullptr);
+  SymUpload up;
+  SymTable sym;
+  int rc = up.put(*a, sym);
+  if (rc == FC_OK) rc = call(&sym);
+  if (rc == FC_OK && a->stats) rc = up.read(a->stats);
+  return drained(rc);
 }
 
 // The enantiomer-aware forms (include/fc_hip.h) are the plain entry points with fc_ensemble::enant set for the call: the

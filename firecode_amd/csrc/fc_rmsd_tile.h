@@ -1,6 +1,7 @@
 // fc_rmsd_tile.h -- the row tile "for every row conformer, over all column conformers, under the Kabsch RMSD" that
-// k_knn_tile / k_knn_tile_sym (fc_knn.hip), k_group_sums (fc_medoid.hip) and k_silhouette_tile (fc_silhouette.hip)
-// walk, said once (DESIGN.md sections 18, 21, 25 and 26), for gfx950 (wave64, float64).
+// k_knn_tile / k_knn_tile_sym (fc_knn.hip), k_group_sums / k_group_sums_sym (fc_medoid.hip) and k_silhouette_tile /
+// k_silhouette_tile_sym (fc_silhouette.hip) walk, said once (DESIGN.md sections 18, 21, 25, 26 and 28), for gfx950
+// (wave64, float64).
 //
 // A workgroup of kTileThreads = 256 threads takes kTileRows = 16 row conformers from the centred conformer-major copy Xa
 // (24 B per atom), staged in LDS up to kTileLdsAtoms atoms and read from global memory beyond; each WAVEFRONT owns

@@ -178,6 +178,46 @@ class Ensemble:
                              f"{mean:.3f} A, {sel.n_iter} assignments, {perf_counter() - t0:.3f} s)")
         return sel
 
+    def medoids_sym(self, labels=None, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
+        """``medoids`` under the symmetry-corrected distance (``firecode_amd.pruner.medoids_by_rmsd_sym``): ``symmetry=`` /
+        ``prune_enantiomers=True`` as in ``nearest_neighbours`` -- flipped or mirrored copies of a member are at distance
+        0 from it.  Returns the ``RmsdMedoids``; the ensemble is not masked."""
+        from firecode_amd.pruner import medoids_by_rmsd_sym
+
+        return medoids_by_rmsd_sym(self.coords, self.atoms, labels=labels, heavy_atoms_only=heavy_atoms_only, symmetry=symmetry,
+                                   prune_enantiomers=prune_enantiomers)
+
+    def silhouette_sym(self, labels, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
+        """``silhouette`` under the symmetry-corrected distance (``firecode_amd.pruner.silhouette_by_rmsd_sym``): the one
+        to judge the ``labels`` of a clusterer that was given ``symmetry=`` or ``prune_enantiomers=True`` by.  Returns
+        the ``RmsdSilhouette``; the ensemble is not masked."""
+        from firecode_amd.pruner import silhouette_by_rmsd_sym
+
+        return silhouette_by_rmsd_sym(self.coords, self.atoms, labels, heavy_atoms_only=heavy_atoms_only, symmetry=symmetry,
+                                      prune_enantiomers=prune_enantiomers)
+
+    def kmedoids_selection_sym(self, n, heavy_atoms_only=True, max_iter=50, verbose=True, symmetry=None,
+                               prune_enantiomers=False):
+        """``kmedoids_selection`` under the symmetry-corrected distance (``firecode_amd.pruner.kmedoids_by_rmsd_sym``):
+        relabelled copies and mirror images count as the same structure.  Returns the ``RmsdKMedoids`` of the ensemble
+        as it was."""
+        from firecode_amd._lib import check_count
+        from firecode_amd.pruner import kmedoids_by_rmsd_sym
+
+        n = check_count("n", n)
+        n0, t0 = len(self.coords), perf_counter()
+        use_en = len(self.energies) == n0 and n0 > 0
+        sel = kmedoids_by_rmsd_sym(self.coords, self.atoms, min(n, n0) if n0 else n, max_iter=max_iter,  # (n > N: all of them)
+                                   heavy_atoms_only=heavy_atoms_only, symmetry=symmetry, prune_enantiomers=prune_enantiomers)
+        self.coords = self.coords[sel.medoids]
+        if use_en:
+            self.apply_mask(("energies",), sel.medoids)
+        if verbose and self.logfunction is not None:
+            mean = sel.cost / n0 if n0 else 0.0
+            self.logfunction(f"Kept {len(sel.medoids)} of {n0} candidates as symmetry-aware RMSD medoids (mean distance to the "
+                             f"representative {mean:.3f} A, {sel.n_iter} assignments, {perf_counter() - t0:.3f} s)")
+        return sel
+
     def nearest_neighbours(self, k, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
         """The ``k`` nearest neighbours of every structure under the heavy-atom RMSD of the other RMSD stages
         (``firecode_amd.pruner.knn_by_rmsd``).  Returns the ``RmsdNeighbours``, whose ``k_distances(min_samples - 1)`` is

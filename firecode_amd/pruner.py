@@ -460,6 +460,64 @@ def kmedoids_by_rmsd(structures, atoms, n, init=None, max_iter=50, heavy_atoms_o
     return RmsdKMedoids(med, lab, dist, cost * Q32, n_iter)
 
 
+def _sums_symmetry(symmetry, prune_enantiomers, atoms, heavy, heavy_atoms_only):
+    """``symmetry=`` (a bond graph or a table) and ``prune_enantiomers=`` of the ``*_sym`` medoid and silhouette drivers
+    -> (the checked table over all atoms or None, the flag), resolved as ``_knn_symmetry`` does; every check, the LDS
+    limit included, made before any device use"""
+    from firecode_amd import symmetry as S
+
+    enant = L.check_flag("prune_enantiomers", prune_enantiomers)
+    table = S.resolve(symmetry, atoms, heavy_atoms_only)
+    if table is not None or enant:
+        t = S.selected_table(np.arange(len(atoms), dtype=np.int64)[None] if table is None else table, heavy)
+        S.medoid_lds_check(t.shape[0], t.shape[1])
+    return table, enant
+
+
+def medoids_by_rmsd_sym(structures, atoms, labels=None, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
+    """``medoids_by_rmsd`` under the symmetry-corrected distance the clusterers group by (fc_ensemble_medoids_perm; the
+    contract is written out in include/fc_hip.h).  ``symmetry=`` (a bond graph or a (K, A) table over all atoms, as in
+    ``prune_by_rmsd``) and ``prune_enantiomers=True`` -- the two combine, as in ``knn_by_rmsd`` -- make the distance the
+    smallest RMSD over the atom permutations and, with the flag, over both handednesses: a phenyl flip or a mirror
+    image of a member is at distance 0 from it and no longer decides which member is the medoid.  With neither
+    keyword this is ``medoids_by_rmsd``.  A name of its own because ``medoids_by_rmsd`` refuses the two keywords.
+    Returns ``RmsdMedoids``."""
+    structures, heavy = _medoid_inputs(structures, atoms, heavy_atoms_only)
+    atoms = np.asarray(atoms)
+    table, enant = _sums_symmetry(symmetry, prune_enantiomers, atoms, heavy, heavy_atoms_only)
+    N = structures.shape[0]
+    lab, n_groups = L.check_group_labels(labels, N)
+    if N == 0:
+        nan = np.full(n_groups, np.nan)
+        return RmsdMedoids(np.full(n_groups, -1, dtype=np.int64), np.zeros(n_groups, dtype=np.int64), nan, nan.copy(),
+                           np.zeros(0), np.zeros(0))
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
+        med, sizes, mean, radius, sums, ecc = ens.medoids_sym(lab, n_groups, symmetry=table, prune_enantiomers=enant)
+    return RmsdMedoids(med, sizes, mean, radius, sums.astype(np.float64) * Q32, ecc)
+
+
+def kmedoids_by_rmsd_sym(structures, atoms, n, init=None, max_iter=50, heavy_atoms_only=True, symmetry=None,
+                         prune_enantiomers=False):
+    """``kmedoids_by_rmsd`` under the symmetry-corrected distance of ``medoids_by_rmsd_sym``
+    (fc_ensemble_kmedoids_perm): the default start is the symmetry-aware ``select_diverse``, every conformer goes to
+    its nearest representative under that distance and every representative moves to the medoid under it.  With
+    neither keyword this is ``kmedoids_by_rmsd``.  Returns ``RmsdKMedoids``."""
+    structures, heavy = _medoid_inputs(structures, atoms, heavy_atoms_only)
+    atoms = np.asarray(atoms)
+    table, enant = _sums_symmetry(symmetry, prune_enantiomers, atoms, heavy, heavy_atoms_only)
+    N = structures.shape[0]
+    n = L.check_count("n", n)
+    max_iter = L.check_count("max_iter", max_iter, low=0)
+    if N == 0:
+        return RmsdKMedoids(np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0), 0.0, 0)
+    if n > N:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"n={n} representatives of N={N} conformers")
+    start = None if init is None else L.check_indices("init", init, N, distinct=True, count=n)
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
+        med, lab, dist, cost, n_iter = ens.kmedoids_sym(n, init=start, max_iter=max_iter, symmetry=table, prune_enantiomers=enant)
+    return RmsdKMedoids(med, lab, dist, cost * Q32, n_iter)
+
+
 RmsdClusters = namedtuple("RmsdClusters", ["labels", "representatives", "sizes"])
 
 
@@ -773,6 +831,61 @@ def silhouette_scan(structures, atoms, thresholds, method="butina", max_dev=None
                 out = ens.dbscan(max_rmsd, dev, min_samples)
             labels, sizes = out[0], out[2]  # (every clusterer: labels, representatives, sizes, ...)
             score = ens.silhouette(labels, max(len(sizes), 1))[6]
+            records.append(SilhouetteScanRecord(float(t), len(sizes), int((labels < 0).sum()), score))
+    return records
+
+
+def silhouette_by_rmsd_sym(structures, atoms, labels, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
+    """``silhouette_by_rmsd`` under the symmetry-corrected distance of ``medoids_by_rmsd_sym``
+    (fc_ensemble_silhouette_perm): the distance the labelling of ``cluster_by_rmsd(..., symmetry=)`` or
+    ``butina_by_rmsd(..., prune_enantiomers=True)`` was made under, so that a group of flipped or mirrored copies is
+    judged tight, not ångströms wide.  With neither keyword this is ``silhouette_by_rmsd``.  Returns ``RmsdSilhouette``."""
+    structures, heavy = _medoid_inputs(structures, atoms, heavy_atoms_only)
+    atoms = np.asarray(atoms)
+    table, enant = _sums_symmetry(symmetry, prune_enantiomers, atoms, heavy, heavy_atoms_only)
+    N = structures.shape[0]
+    lab, n_groups = L.check_group_labels(labels, N)
+    if N == 0:
+        return RmsdSilhouette(np.zeros(0), np.zeros(0), np.zeros(0), np.zeros(0, dtype=np.int32), np.full(n_groups, np.nan),
+                              np.zeros(n_groups, dtype=np.int64), float("nan"))
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
+        return RmsdSilhouette(*ens.silhouette_sym(lab, n_groups, symmetry=table, prune_enantiomers=enant))
+
+
+def silhouette_scan_sym(structures, atoms, thresholds, method="butina", max_dev=None, min_samples=5, heavy_atoms_only=True,
+                        symmetry=None, prune_enantiomers=False):
+    """``silhouette_scan`` where the clusterer AND the silhouette of every step work under the same symmetry-corrected
+    distance, with the ensemble uploaded once: ``symmetry=`` (a bond graph or a (K, A) table) or
+    ``prune_enantiomers=True`` is passed on to both.  The clusterers take one of the two, not both, so the combination
+    is refused here with their error.  With neither keyword this is ``silhouette_scan``.  Returns one
+    ``SilhouetteScanRecord`` per threshold."""
+    from firecode_amd import symmetry as S
+
+    if method not in ("butina", "components", "dbscan"):
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"method={method!r}: 'butina', 'components' or 'dbscan'")
+    structures, heavy = _medoid_inputs(structures, atoms, heavy_atoms_only)
+    atoms = np.asarray(atoms)
+    enant = L.check_flag("prune_enantiomers", prune_enantiomers)
+    S.refuse_with_enantiomers(S.resolve(symmetry, atoms, heavy_atoms_only), enant)
+    table, enant = _sums_symmetry(symmetry, enant, atoms, heavy, heavy_atoms_only)
+    min_samples = L.check_min_samples(min_samples)
+    ts = np.asarray(thresholds, dtype=np.float64)
+    if ts.ndim != 1:
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"thresholds must be a 1-D sequence of max_rmsd values, got {ts.shape}")
+    steps = [_thresholds(L.check_max_rmsd_cap(t), max_dev, 0.0) for t in ts]
+    if structures.shape[0] == 0:
+        return [SilhouetteScanRecord(float(t), 0, 0, float("nan")) for t in ts]
+    records = []
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
+        for t, (max_rmsd, dev, _) in zip(ts, steps):
+            if method == "butina":
+                out = ens.butina(max_rmsd, dev, prune_enantiomers=enant, symmetry=table)
+            elif method == "components":
+                out = ens.clusters(max_rmsd, dev, prune_enantiomers=enant, symmetry=table)
+            else:
+                out = ens.dbscan(max_rmsd, dev, min_samples, prune_enantiomers=enant, symmetry=table)
+            labels, sizes = out[0], out[2]  # (every clusterer: labels, representatives, sizes, ...)
+            score = ens.silhouette_sym(labels, max(len(sizes), 1), symmetry=table, prune_enantiomers=enant)[6]
             records.append(SilhouetteScanRecord(float(t), len(sizes), int((labels < 0).sum()), score))
     return records
 

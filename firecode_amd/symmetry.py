@@ -173,6 +173,23 @@ def knn_lds_check(n_perms, n_selected):
             f"LDS (limit {LDS_LIMIT}): at most {knn_max_selected(n_perms)} selected atoms")
 
 
+def medoid_lds_bytes(n_perms, n_selected):
+    """LDS of one workgroup of the symmetry-aware medoid sums and silhouettes (fc_ensemble_medoids_perm,
+    fc_ensemble_kmedoids_perm, fc_ensemble_silhouette_perm): the tile of the nearest-neighbour lists -- 16 row conformers
+    and the table -- and no static LDS on top."""
+    return knn_lds_bytes(n_perms, n_selected)
+
+
+def medoid_max_selected(n_perms):
+    """the largest number of selected atoms the symmetry-aware medoids and silhouettes take with ``n_perms`` permutations"""
+    return knn_max_selected(n_perms)
+
+
+def medoid_lds_check(n_perms, n_selected):
+    """FC_E_LIMIT, before any device use, where the library itself would refuse the sums for their LDS"""
+    knn_lds_check(n_perms, n_selected)
+
+
 def knn_table(symmetry, prune_enantiomers, atom_mask, n_atoms):
     """``symmetry=`` (a checked table over all atoms, or None) and the mirror flag of the nearest-neighbour lists -> the
     (K, A_sel) int32 table the library takes, or None when neither is set; the LDS limit checked on the way"""

@@ -191,9 +191,11 @@ def most_diverse_conformers(n, structures, seed=None, method="random", atoms=Non
 
     ``method="kmedoids"``: the n most REPRESENTATIVE structures instead -- k-medoids under the same RMSD, started from the
     ``method="rmsd"`` picks (``firecode_amd.pruner.kmedoids_by_rmsd``), in the order of the representatives; all of
-    them when there are at most n.  It has no symmetry- or mirror-aware form: the two keywords are an input error."""
-    if method not in ("random", "rmsd", "kmedoids"):
-        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"method={method!r}: 'random', 'rmsd' or 'kmedoids'")
+    them when there are at most n.  The two keywords are an input error with it; ``method="kmedoids_sym"`` is the
+    form that honours them (``firecode_amd.pruner.kmedoids_by_rmsd_sym``): k-medoids under the symmetry-corrected
+    distance, started from the symmetry-aware ``method="rmsd"`` picks."""
+    if method not in ("random", "rmsd", "kmedoids", "kmedoids_sym"):
+        raise L.FirecodeHipInputError(L.FC_E_INVALID, f"method={method!r}: 'random', 'rmsd', 'kmedoids' or 'kmedoids_sym'")
     enant = _diversity_keywords("method", method, symmetry, prune_enantiomers)
     if method == "kmedoids" and (symmetry is not None or enant):
         raise L.FirecodeHipInputError(
@@ -206,6 +208,18 @@ def most_diverse_conformers(n, structures, seed=None, method="random", atoms=Non
         X = L.f64(np.array(structures))
         sym = np.array(["C"] * X.shape[1]) if atoms is None else np.asarray(atoms)
         sel = kmedoids_by_rmsd(X, sym, min(L.check_count("n", n), len(X)), heavy_atoms_only=atoms is not None)
+        return list(X[sel.medoids])
+    if method == "kmedoids_sym":
+        from firecode_amd.pruner import kmedoids_by_rmsd_sym
+
+        from firecode_amd import symmetry as S
+
+        X = L.f64(np.array(structures))
+        table = S.resolve(symmetry, None if atoms is None else np.asarray(atoms), atoms is not None,
+                          n_atoms=X.shape[1] if X.ndim == 3 else None)
+        sym = np.array(["C"] * X.shape[1]) if atoms is None else np.asarray(atoms)
+        sel = kmedoids_by_rmsd_sym(X, sym, min(L.check_count("n", n), len(X)), heavy_atoms_only=atoms is not None,
+                                   symmetry=table, prune_enantiomers=enant)
         return list(X[sel.medoids])
     if method == "rmsd":
         from firecode_amd.pruner import select_diverse

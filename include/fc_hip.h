@@ -318,8 +318,8 @@ int fc_ensemble_knn_cross_perm(fc_ensemble *queries, fc_ensemble *refs, const in
  * k-medoids: cost 0, 0 iterations, nothing else written).  FC_E_LIMIT: N >= 2^31 - 256; and, once the ensemble's largest
  * G is known, a group too large for the 64-bit sum: (largest size) (ceil(sqrt(4 g_max / A)) + 1) 2^32 >= 2^63 (k-medoids
  * judges N, which no group exceeds) -- tens of millions of members at molecular coordinates.
- * Not offered: symmetry- and mirror-aware forms, a multi-GPU form, PAM's swap phase (between-group sums: the
- * silhouettes below).
+ * Symmetry- and mirror-aware forms: fc_ensemble_medoids_perm / fc_ensemble_kmedoids_perm, below.  Not offered: a
+ * multi-GPU form, PAM's swap phase (between-group sums: the silhouettes below).
  *
  * fc_ensemble_silhouette.  How good is a labelling: labels and n_groups as for fc_ensemble_medoids.
  * A conformer with a negative label is in no group: it is neither a row nor a column, and gets a = b = s = NaN and
@@ -343,8 +343,8 @@ int fc_ensemble_knn_cross_perm(fc_ensemble *queries, fc_ensemble *refs, const in
  * (n_groups), sizes_out (n_groups int64), *score_out; ms_kernel (or NULL): HIP-event time of the kernel pair (0 when no
  * device is used).  Refusals and limits as for fc_ensemble_medoids, in the same order (N = 0: every group empty, score
  * NaN); the 64-bit check is made on the number of LABELLED conformers -- a prefix runs over a whole row.
- * Not offered: symmetry- and mirror-aware forms, a multi-GPU form, the "simplified" silhouette against medoids, other
- * indices (Davies-Bouldin, Calinski-Harabasz). */
+ * Symmetry- and mirror-aware form: fc_ensemble_silhouette_perm, below.  Not offered: a multi-GPU form, the "simplified"
+ * silhouette against medoids, other indices (Davies-Bouldin, Calinski-Harabasz). */
 int fc_ensemble_silhouette(fc_ensemble *ens, const int32_t *labels /* N or NULL = one group */, int64_t n_groups,
                            double *s_out, double *a_out, double *b_out, int32_t *nearest_out, double *cluster_mean_out,
                            int64_t *sizes_out, double *score_out, double *ms_kernel /* or NULL */);
@@ -355,6 +355,51 @@ int fc_ensemble_medoids(fc_ensemble *ens, const int32_t *labels, int64_t n_group
 int fc_ensemble_kmedoids(fc_ensemble *ens, const int64_t *init /* n or NULL */, int64_t n, int64_t max_iter,
                          int64_t *medoids_out, int32_t *labels_out, double *dist_out, uint64_t *cost_q32_out,
                          int64_t *n_iter_out);
+/* ---- the symmetry- and mirror-aware forms of the three ----
+ * perms (K, A_sel), mirror: the table and the flag of fc_ensemble_knn_perm, with its checks.  The distance:
+ *
+ *   d_sym(i, j) = sqrt(min over p < K, h in H of ssq(p, h) / A_sel),   H = {+1}, or {+1, -1} when mirror != 0
+ *
+ * the value k_knn_tile_sym writes for row i and column j: ssq(p, h) the explicit rotated sum of squares of
+ * (X[i][perms[p]], h X[j]) under the rotation of its own covariance -- the permutation applied to the row side, h = -1 as
+ * -B, p + R q -- never the eigenvalue form.  Everything else is the contract of the plain twin with d replaced by d_sym:
+ *   fc_ensemble_medoids_perm: d_sym(i, j) is evaluated once per unordered pair, as (row i, column j) with i < j -- in the
+ *     order of the label-sorted conformers, which within a group is the ascending conformer index -- and serves both
+ *     partners; q, S, E, the medoid (the lowest index on ties), mean and radius as in fc_ensemble_medoids.
+ *   fc_ensemble_silhouette_perm: every ordered pair i != j; T, a, m, b, nearest (the lowest label on ties), s, negative
+ *     labels, singletons, fewer than two groups, cluster_mean and score as in fc_ensemble_silhouette.
+ *   fc_ensemble_kmedoids_perm: the loop of fc_ensemble_kmedoids where init = NULL stands for the picks of
+ *     fc_ensemble_select_diverse_perm(n_max = n, start = 0) under the same table and flag, the assignment is the k = 1
+ *     list of fc_ensemble_knn_cross_perm(ens, fc_ensemble_subset(ens, M_t)) (a representative: its own position and
+ *     distance 0, by index) and the move uses the S of fc_ensemble_medoids_perm; the same stopping rule on integer costs.
+ *     The table is uploaded once per call.
+ * The same bits: the sums are 64-bit integers and d_sym(i, j) is one value per (row, column) -- the minimum over the
+ * explicit sums that were formed; a (p, h) is skipped only where its eigenvalue form of A msd exceeds the pair's smallest
+ * explicit sum so far by more than A * 1e-6 for every counting lane of the wavefront, and a pair's first (p, h) is always
+ * explicit -- so every output is the same bits on every run, for every strip count (FC_MEDOID_STRIPS / FC_SILHOUETTE_STRIPS,
+ * the plain forms' knobs), with FC_MEDOID_SYM_FILTER=0 (every (p, h) explicit) and for any number of rows a wavefront
+ * puts through one atom loop; and d_sym here is bit for bit the d_sym fc_ensemble_knn_perm lists for the same (row,
+ * column).  K = 1 with mirror = 0 runs the plain twin's kernels, bit for bit.
+ * stats (2 values, or NULL; medoids and silhouette): (pair, p, h) whose eigenvalue was formed, and those taken through the
+ * explicit pass; 0 where no device is used and for K = 1 without the flag.
+ * Refused before any device use, in this order: the table (FC_E_INVALID / FC_E_LIMIT: K > FC_PERM_MAX), the LDS limit
+ * (FC_E_LIMIT: 16 x 24 A_sel bytes of rows and 2 K A_sel bytes of table, rounded up to 8, within 160 KiB -- A_sel <= 422 at
+ * K = 2, <= 413 at K = 6, <= 320 at K = 64; these kernels are staged only, there is no global-memory fallback), mirror
+ * outside {0, 1}, a NULL handle, an earlier epoch or an A_sel that is not the ensemble's (FC_E_INVALID); then the plain
+ * twin's own checks in its own order.  Not offered: sharded, multi-GPU and twin-workspace forms, a max-deviation or energy
+ * criterion. */
+int fc_ensemble_medoids_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
+                             const int32_t *labels, int64_t n_groups, int64_t *medoids_out, int64_t *sizes_out,
+                             double *mean_out, double *radius_out, uint64_t *sums_q32_out /* N or NULL */,
+                             double *ecc_out /* N or NULL */, double *ms_kernel /* or NULL */, int64_t *stats /* 2 or NULL */);
+int fc_ensemble_kmedoids_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
+                              const int64_t *init /* n or NULL */, int64_t n, int64_t max_iter, int64_t *medoids_out,
+                              int32_t *labels_out, double *dist_out, uint64_t *cost_q32_out, int64_t *n_iter_out);
+int fc_ensemble_silhouette_perm(fc_ensemble *ens, const int32_t *perms, int64_t K, int64_t A_sel, int mirror,
+                                const int32_t *labels /* N or NULL = one group */, int64_t n_groups, double *s_out,
+                                double *a_out, double *b_out, int32_t *nearest_out, double *cluster_mean_out,
+                                int64_t *sizes_out, double *score_out, double *ms_kernel /* or NULL */,
+                                int64_t *stats /* 2 or NULL */);
 /* a9: get_alignment_matrix(p, q) -- prism_pruner.rmsd; call site
  * hypermolecule_class.py:77.  M (3,3) row-major, applied as (M @ q.T).T */
 int fc_alignment_matrices(const double *p, const double *q, int64_t n_pairs, int64_t A,
