@@ -923,9 +923,9 @@ class DeviceEnsemble:
 
     def bench_rmsd_and_max_all(self, reps=1):
         """``reps`` complete all-pairs alignment passes, outputs resident ->
-        (mean kernel ms, total ms, stats [pairs, fix-up pairs, tiled])."""
+        (mean kernel ms, total ms, stats [pairs, fix-up pairs, tiled, general-form sub-tiles of the last pass])."""
         k, t = C.c_double(0), C.c_double(0)
-        stats = np.zeros(3, dtype=np.int64)
+        stats = np.zeros(4, dtype=np.int64)
         call("fc_bench_rmsd_and_max_all", self.handle, int(reps), C.byref(k), C.byref(t), pi(stats))
         return k.value, t.value, stats
 
@@ -936,7 +936,7 @@ class DeviceEnsemble:
         P = int(pi_.shape[0])
         r, m = np.empty(P), np.empty(P)
         k, t = C.c_double(0), C.c_double(0)
-        stats = np.zeros(3, dtype=np.int64)
+        stats = np.zeros(4, dtype=np.int64)
         call("fc_bench_rmsd_and_max_all_sampled", self.handle, int(reps), pi(pi_), pi(pj_), P, pf(r), pf(m),
              C.byref(k), C.byref(t), pi(stats))
         return k.value, t.value, stats, r, m

@@ -465,7 +465,8 @@ static int rmsd_and_max_all(fc_ensemble *ens, double *rmsd_out, double *maxdev_o
 // back on the library's stream (outputs: two dense (N, N) matrices that stay in HBM), one host wait.
 // ms_kernel_mean: HIP events around the dominant kernel (k_simbits_screen_mfma<., 2>) of every launch;
 // ms_total: first launch to the end of the last fix-up kernel.  stats[0] = pairs per pass,
-// stats[1] = pairs the last pass queued for the Jacobi fix-up, stats[2] = 1 when the tiled kernel ran.
+// stats[1] = pairs the last pass queued for the Jacobi fix-up, stats[2] = 1 when the tiled kernel ran, stats[3] = 16 x 16
+// sub-tiles of the last pass that took the general form of the rotation (the caller's array holds FOUR words).
 // sample_*: P elements (i, j) of the LAST pass's two output matrices, read back for the caller's checker
 static int bench_rmsd_and_max_all(fc_ensemble *ens, int64_t reps, double *ms_kernel_mean, double *ms_total,
                                   int64_t *stats, const int64_t *sample_i = nullptr, const int64_t *sample_j = nullptr,
@@ -513,6 +514,7 @@ static int bench_rmsd_and_max_all(fc_ensemble *ens, int64_t reps, double *ms_ker
     stats[0] = owned_pairs(N, 128, rank, world);  // pairs this rank computed: rows of its blocks of 128, columns right of the diagonal
     stats[1] = (int64_t)cnt[6];
     stats[2] = tiled ? 1 : 0;
+    stats[3] = (int64_t)cnt[kCntGeneralForm];  // 16 x 16 sub-tiles of the last pass that took the general form of the rotation
   }
   if (tiled && cnt[6] > (unsigned long long)ens->pairq_cap)
     return set_error(FC_E_LIMIT, "%llu degenerate pairs exceed the fix-up queue (%lld)", cnt[6], (long long)ens->pairq_cap);

@@ -339,6 +339,8 @@ constexpr unsigned long long kRefineLanesMin = 1ull << 17;
 // k_pair_buckets 131 us on 7.6e5 similar pairs, one wave-wide atomic instruction per 64 pairs)
 constexpr size_t kCounters = 64 + 20 * 16;
 constexpr int kCntLevel = 64, kCntLevelStride = 16;
+// [7]: 16 x 16 sub-tiles of a complete-alignment pass whose rotations took the general adjugate form (one add per item)
+constexpr int kCntGeneralForm = 7;
 
 // (global_block, local_block_count -- the snake order of the row blocks -- and the item tables: fc_items.h)
 
@@ -358,7 +360,12 @@ struct fc_ensemble {
   bool xsf_valid = false;
   fc::DevBuf Xt;               // row-tile-major copy of Xs for the atom pass of the complete alignments (fc_items.h; made on first use)
   bool xt_valid = false;
-  fc::DevBuf Xh;               // split-half copy of Xs for the f16-matrix-pipe screen (made on first use)
+  // the shared frame of the complete alignments (made on first use, invalid wherever Xt is): every conformer rotated once
+  // onto conformer 0 -- Xf in Xs layout, Gf its sums of squares, Xtf its row-tile-major copy.  Only the tiled
+  // complete-alignment kernel reads them (rmsd and maximum deviation do not depend on either conformer's frame).
+  fc::DevBuf Xf, Gf, Xtf;
+  bool frame_valid = false, xtf_valid = false;  // Xf and Gf | Xtf (made on the first call that reads the row tiles)
+  fc::DevBuf Xh;              // split-half copy of Xs for the f16-matrix-pipe screen (made on first use)
   bool xh_valid = false;
   double xh_scale = 0.0;       // the power of two Xh was made with
   double g_max = -1.0;         // largest G (host copy, found on first use): sizes the fp32 screen's band

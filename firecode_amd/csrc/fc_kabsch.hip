@@ -719,7 +719,10 @@ typedef double d4_t __attribute__((ext_vector_type(4)));
 // was declined.  EIG = false (the launcher's retry when the fix-up queue overflowed: an ensemble of near-duplicates): the sum.
 // ROWT (MODE 2): the atom pass reads its row conformer from Xt, the row-tile-major copy (fc_items.h), instead of three rows
 // of Xs per atom; the K loop's row operands stay on Xs.  Same arithmetic in the same order: the outputs are bit-identical.
-template <int NW, int MODE = 0, int TC = 64, bool EIG = false, bool ENANT = false, bool ROWT = false>
+// COL0 (MODE 2, on the ensemble's frame copy): the rotation from column 0 of the adjugate wherever a wave's pairs certify it
+// ("the shared frame"; general_only != 0: never -- the same kernel with the general form in every sub-tile,
+// which the tests compare bit for bit); without COL0 the epilogue is the straight-line general form.
+template <int NW, int MODE = 0, int TC = 64, bool EIG = false, bool ENANT = false, bool ROWT = false, bool COL0 = false>
 __global__ void __launch_bounds__(NW * 64, 2)
 k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ G, int64_t N,
                       int64_t Npad, int A, double A_thr2, int IB, int64_t rank, int64_t world,
@@ -727,9 +730,10 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
                       unsigned long long *__restrict__ counters, uint64_t *__restrict__ pairq,
                       unsigned long long Q, const uint64_t *__restrict__ item_table, unsigned long long n_items,
                       double *__restrict__ rmsd_out = nullptr, const unsigned long long *__restrict__ gate = nullptr,
-                      double *__restrict__ maxdev_out = nullptr, const double *__restrict__ Xt = nullptr) {
+                      double *__restrict__ maxdev_out = nullptr, const double *__restrict__ Xt = nullptr, int general_only = 0) {
   static_assert(!EIG || MODE == 2, "EIG: the complete alignments");
   static_assert(!ROWT || MODE == 2, "ROWT: the complete alignments");
+  static_assert(!COL0 || MODE == 2, "COL0: the complete alignments");
   static_assert(!ENANT || MODE == 0, "ENANT: the screen only");
   constexpr bool VALUES = MODE != 0;  // 1: rmsd values (Newton), 2: (rmsd, maxdev) by explicit difference
   // sub-tiles (16 columns) per unit: two share the row operands in the screens; the complete-alignment
@@ -857,6 +861,9 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
   // instead of in front of the next K loop.  pre_it = row tile those registers hold.
   double a0[3], a1[3], a2[3];
   int pre_it = -1;
+  int n_general = 0;  // MODE 2 (wave-uniform): sub-tiles of this wave whose rotations took the general form
+  (void)n_general;
+  (void)general_only;
   // first row of row tile it_ (MODE 2: under snake order the blocks of an item are not neighbours)
   const int tpb = IB >> 4;
   auto tile_row = [&](int it_) -> int64_t {
@@ -1026,28 +1033,85 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
           double msdA4[4] = {0.0, 0.0, 0.0, 0.0};  // EIG: (Gp + Gq) - 2 lambda
           {  // the four Newton iterations in one loop (independent chains side by side: 2.71 -> 2.66 ms per 10^4 x 10^4
              // against one pair after the other), -R straight from the adjugate column (no normalisation of q)
-            double B4[4][9], GG[4], Q44[4][4], nq4[4], lam4[4];
+            if constexpr (COL0) {
+              double B4[4][9], GG[4], lam4[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              GG[r] = Gp + ldsG[cs * 16 + 4 * kq + r];
+              for (int r = 0; r < 4; ++r) {
+                GG[r] = Gp + ldsG[cs * 16 + 4 * kq + r];
 #pragma unroll
-              for (int e = 0; e < 9; ++e) B4[r][e] = acc[t][e][r];
-            }
-            kabsch_quaternion_qcp_lean4(B4, GG, Q44, nq4, ok4, EIG ? lam4 : nullptr);
-            if constexpr (EIG) {
+                for (int e = 0; e < 9; ++e) B4[r][e] = acc[t][e][r];
+              }
+              QcpLeanPoly P4[4];
+              double dl4[4];
+              qcp_lean_eigenvalues4(B4, GG, P4, lam4, dl4);
+              bool conv4[4];  // (taken here: the last steps die in front of the rotations)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) conv4[r] = qcp_lean_converged(lam4[r], dl4[r]);
+              // The shared frame (the operands are the ensemble's frame copy, every conformer aligned
+              // onto conformer 0): the pair rotations are small there, column 0 of the adjugate is the one the general form
+              // would pick, and the wave takes it -- four cofactors, no pick -- for its pairs r when ONE ballot says that
+              // every lane's pair r inside the matrix certifies (qcp_lean_quaternion_col0).  Otherwise the general form for
+              // these 64 pairs: a certified pair has the same Q, nq and flag in both forms, so ok4, the fix-up queue and the
+              // outputs do not depend on the switch.  Pair by pair, each through to its -R: the covariance of pair r and its
+              // quaternion are dead behind the nine entries that replace them (one ballot per sub-tile with all four
+              // covariances held for a common fall-back, or the four -R behind the four quaternions, took 256 registers
+              // and scratch).
+              bool all_lean = true, try_col0 = general_only == 0;
               const double k_small = 2e-10 / (double)A;
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
-                msdA4[r] = GG[r] - 2.0 * lam4[r];
-                // too close for the difference (also NaN): a declined pair, the fix-up kernel's explicit sum decides
-                if (!(msdA4[r] > k_small * GG[r] * GG[r])) ok4[r] = false, msdA4[r] = 0.0;
+                double Qr[4], nqr;
+                // (outside the matrix: nothing of the pair is kept.  Behind a slot that did not certify the sub-tile's other
+                // slots take the general form unasked -- it counts as a general-form sub-tile either way, and a wave of
+                // unrelated pairs pays for one attempt per sub-tile, not four)
+                bool lean = false;
+                if (try_col0) {
+                  ok4[r] = qcp_lean_quaternion_col0(B4[r], P4[r].n2, lam4[r], conv4[r], Qr, nqr);
+                  lean = __builtin_amdgcn_ballot_w64(!(ok4[r] || i >= n32 || jb + r >= n32)) == 0ull;
+                  try_col0 = lean;
+                }
+                if (!lean) ok4[r] = qcp_lean_quaternion_raw(B4[r], P4[r].n2, lam4[r], conv4[r], Qr, nqr);
+                all_lean = all_lean && lean;
+                if constexpr (EIG) {
+                  msdA4[r] = GG[r] - 2.0 * lam4[r];
+                  // too close for the difference (also NaN): a declined pair, the fix-up kernel's explicit sum decides
+                  if (!(msdA4[r] > k_small * GG[r] * GG[r])) ok4[r] = false, msdA4[r] = 0.0;
+                }
+                // (NaN must not reach the stores: the fix-up overwrites what a declined pair leaves.  Column-0 form: every
+                // pair inside the matrix has a finite Q; one the eigenvalue form declined above keeps its rotation instead
+                // of the identity -- what it stores is finite and the fix-up overwrites it either way.  A lane OUTSIDE the
+                // matrix keeps whatever column 0 gave: for a zero padding conformer nq = 0, -R is inf / NaN and the lane's
+                // atom pass runs on NaN.  Nothing of such a lane is kept: row_in and j < n32 guard every store and the redo
+                // flag, and no value crosses lanes between here and there.)
+                if (!lean && !ok4[r]) Qr[0] = 1.0, Qr[1] = 0.0, Qr[2] = 0.0, Qr[3] = 0.0, nqr = 1.0;
+                neg_rotation_from_raw_quaternion(Qr, nqr, nR[r]);
               }
-            }
+              if (!all_lean) ++n_general;
+            } else {
+              double B4[4][9], GG[4], Q44[4][4], nq4[4], lam4[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              // (NaN must not reach the stores: the fix-up overwrites what a declined pair leaves)
-              if (!ok4[r]) Q44[r][0] = 1.0, Q44[r][1] = 0.0, Q44[r][2] = 0.0, Q44[r][3] = 0.0, nq4[r] = 1.0;
-              neg_rotation_from_raw_quaternion(Q44[r], nq4[r], nR[r]);
+              for (int r = 0; r < 4; ++r) {
+                GG[r] = Gp + ldsG[cs * 16 + 4 * kq + r];
+#pragma unroll
+                for (int e = 0; e < 9; ++e) B4[r][e] = acc[t][e][r];
+              }
+              kabsch_quaternion_qcp_lean4(B4, GG, Q44, nq4, ok4, EIG ? lam4 : nullptr);
+              ++n_general;
+              if constexpr (EIG) {
+                const double k_small = 2e-10 / (double)A;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                  msdA4[r] = GG[r] - 2.0 * lam4[r];
+                  // too close for the difference (also NaN): a declined pair, the fix-up kernel's explicit sum decides
+                  if (!(msdA4[r] > k_small * GG[r] * GG[r])) ok4[r] = false, msdA4[r] = 0.0;
+                }
+              }
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                // (NaN must not reach the stores: the fix-up overwrites what a declined pair leaves)
+                if (!ok4[r]) Q44[r][0] = 1.0, Q44[r][1] = 0.0, Q44[r][2] = 0.0, Q44[r][3] = 0.0, nq4[r] = 1.0;
+                neg_rotation_from_raw_quaternion(Q44[r], nq4[r], nR[r]);
+              }
             }
           }
           typedef double d2_t __attribute__((ext_vector_type(2)));
@@ -1312,11 +1376,19 @@ k_simbits_screen_mfma(const double *__restrict__ Xs, const double *__restrict__ 
   }
   // publish what the workgroup staged: one global atomic per queue (the screen's pairs: per wavefront)
   if constexpr (MODE == 0) flush_pairs_wave32(sq32_wave, n_staged32, (unsigned)i0, (unsigned)j0, pairq, Q, counters, lane);
+  // MODE 2: the general-form sub-tiles of the item, summed in LDS (the word queue's fill level has no other use here)
+  if constexpr (MODE == 2) {
+    if (lane == 0 && n_general != 0) atomicAdd(stageN + 1, (unsigned)n_general);
+  }
   __syncthreads();
 #ifdef FC_TIMELINE
   if (TL && tl && tid == 0) tl[(size_t)b * 4 + 2] = wall_clock64();
 #endif
   if (wv == 0) {
+    if constexpr (MODE == 2) {  // ... and ONE global add per item (kCntGeneralForm)
+      const unsigned n_gen = stageN[1];
+      if (lane == 0 && n_gen != 0) atomicAdd(&counters[kCntGeneralForm], (unsigned long long)n_gen);
+    }
     if constexpr (MODE != 0) {
       const uint64_t e = lane < kStagePairs ? stageQ[lane] : ~0ull;
       const bool valid = e != ~0ull;
@@ -3369,24 +3441,105 @@ static int make_row_tiles(fc_ensemble *e) {
   return FC_OK;
 }
 
+// The shared frame of the complete alignments: conformer n rotated onto conformer 0, once per ensemble.  One lane per
+// conformer (loads and stores coalesced along Npad; conformer 0's coordinates are wave-uniform): the covariance against
+// conformer 0, its rotation from kabsch_quaternion_qcp -- the identity where that declines (a collinear, planar or
+// one-point conformer: correctness never depends on the frame, only how many sub-tiles certify column 0) -- the rotated
+// conformer in Xs layout, and G of the ROTATED coordinates, summed over the atoms as k_prep sums it: the eigenvalue form's
+// (Gp + Gq) - 2 lambda must see the coordinates the covariance is made from.  Padding conformers and atom rows stay zero.
+__global__ void __launch_bounds__(64)
+k_frame(const double *__restrict__ Xs, int64_t N, int64_t Npad, int A, double *__restrict__ Xf, double *__restrict__ Gf) {
+  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= Npad) return;
+  const int A4 = (A + 3) & ~3;
+  for (int a = (n < N ? A : 0); a < A4; ++a) {
+    Xf[((int64_t)a * 3 + 0) * Npad + n] = 0.0;
+    Xf[((int64_t)a * 3 + 1) * Npad + n] = 0.0;
+    Xf[((int64_t)a * 3 + 2) * Npad + n] = 0.0;
+  }
+  if (n >= N) {
+    Gf[n] = 0.0;
+    return;
+  }
+  double B[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double g0 = 0.0, gn = 0.0;
+  for (int a = 0; a < A; ++a) {
+    const double *__restrict__ row = Xs + (int64_t)a * 3 * Npad;
+    const double px = row[0], py = row[Npad], pz = row[2 * Npad];  // conformer 0
+    const double qx = row[n], qy = row[Npad + n], qz = row[2 * Npad + n];
+    B[0] = fma(px, qx, B[0]); B[1] = fma(px, qy, B[1]); B[2] = fma(px, qz, B[2]);
+    B[3] = fma(py, qx, B[3]); B[4] = fma(py, qy, B[4]); B[5] = fma(py, qz, B[5]);
+    B[6] = fma(pz, qx, B[6]); B[7] = fma(pz, qy, B[7]); B[8] = fma(pz, qz, B[8]);
+    g0 += px * px + py * py + pz * pz;
+    gn += qx * qx + qy * qy + qz * qz;
+  }
+  double Q4[4], R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+  if (kabsch_quaternion_qcp(B, g0 + gn, Q4)) rotation_from_quaternion(Q4, R);
+  double g = 0.0;
+  for (int a = 0; a < A; ++a) {
+    const double *__restrict__ row = Xs + (int64_t)a * 3 * Npad;
+    double *__restrict__ out = Xf + (int64_t)a * 3 * Npad;
+    const double qx = row[n], qy = row[Npad + n], qz = row[2 * Npad + n];
+    const double x = R[0] * qx + R[1] * qy + R[2] * qz;
+    const double y = R[3] * qx + R[4] * qy + R[5] * qz;
+    const double z = R[6] * qx + R[7] * qy + R[8] * qz;
+    out[n] = x;
+    out[Npad + n] = y;
+    out[2 * Npad + n] = z;
+    g += x * x + y * y + z * z;
+  }
+  Gf[n] = g;
+}
+
+// e->Xf, Gf, Xtf: the frame copy, its sums of squares and its row-tile-major copy, unless the ensemble holds them already
+// (with_tiles: Xtf too -- made once, on the first call that reads it).  *made = false: a buffer could not be allocated and
+// the caller goes on without the frame (correctness never depends on it); launch errors are errors.
+static int make_frame(fc_ensemble *e, bool with_tiles, bool *made) {
+  *made = true;
+  if (e->frame_valid && (e->xtf_valid || !with_tiles)) return FC_OK;
+  const int64_t n_elems = row_tile_elems(e->Npad, e->A), n_alloc = n_elems + 96;
+  if (e->Xf.reserve((size_t)((e->A + 3) / 4 * 4) * 3 * e->Npad * sizeof(double)) != FC_OK ||
+      e->Gf.reserve((size_t)e->Npad * sizeof(double)) != FC_OK ||
+      (with_tiles && e->Xtf.reserve((size_t)n_alloc * sizeof(double)) != FC_OK)) {
+    e->frame_valid = e->xtf_valid = false;
+    *made = false;
+    return FC_OK;
+  }
+  if (!e->frame_valid) {
+    hipLaunchKernelGGL(k_frame, dim3((unsigned)ceil_div(e->Npad, 64)), dim3(64), 0, ctx().stream, e->Xs.as<double>(), e->N, e->Npad,
+                       (int)e->A, e->Xf.as<double>(), e->Gf.as<double>());
+    FC_TRY(check_launch("k_frame"));
+    e->frame_valid = true;
+  }
+  if (with_tiles && !e->xtf_valid) {
+    hipLaunchKernelGGL(k_row_tiles, dim3((unsigned)ceil_div(n_alloc, 256)), dim3(256), 0, ctx().stream, e->Xf.as<double>(), e->Npad,
+                       (int)e->A, n_elems, n_alloc, e->Xtf.as<double>());
+    FC_TRY(check_launch("k_row_tiles"));
+    e->xtf_valid = true;
+  }
+  return FC_OK;
+}
 // all-pairs RMSD values on the matrix pipe (world == 1 layout); rmsd_dev: (N, N), pre-zeroed.
 // maxdev_dev != nullptr: the complete alignment of every pair -- (rmsd, maxdev) from the explicit
 // rotated difference (MODE 2 of the kernel); pairs it could not rotate are redone by the fix-up.
 // one instantiation of the complete-alignment kernel: LDS attribute + launch
-template <int NW, int TC, bool EIG, bool ROWT>
+template <int NW, int TC, bool EIG, bool ROWT, bool COL0 = false>
 static int launch_complete_variant(fc_ensemble *e, dim3 grid, size_t lds_m, double A_small, int64_t rb, int64_t rank, int64_t world,
                                    unsigned long long *cnt, const uint64_t *item_table_dev, unsigned long long n_items,
-                                   double *rmsd_dev, double *maxdev_dev, uint64_t *timeline_dev) {
+                                   double *rmsd_dev, double *maxdev_dev, uint64_t *timeline_dev, bool frame, bool general_only) {
+  // frame: every operand from the ensemble's frame copy (make_frame); COL0: the column-0 form of the rotation there
+  const double *xs = frame ? e->Xf.as<double>() : e->Xs.as<double>(), *g = frame ? e->Gf.as<double>() : e->G.as<double>();
+  const double *xt = frame ? e->Xtf.as<double>() : e->Xt.as<double>();
   if (lds_m > 64 * 1024) {
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma<NW, 2, TC, EIG, false, ROWT>),
+    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(k_simbits_screen_mfma<NW, 2, TC, EIG, false, ROWT, COL0>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m);
     if (err != hipSuccess) return set_error(FC_E_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(err));
   }
-  hipLaunchKernelGGL((k_simbits_screen_mfma<NW, 2, TC, EIG, false, ROWT>), grid, dim3(NW * 64), lds_m, ctx().stream, e->Xs.as<double>(),
-                     e->G.as<double>(), e->N, e->Npad, (int)e->A, A_small, (int)rb, rank, world, timeline_dev, e->W, nullptr, cnt,
+  hipLaunchKernelGGL((k_simbits_screen_mfma<NW, 2, TC, EIG, false, ROWT, COL0>), grid, dim3(NW * 64), lds_m, ctx().stream, xs,
+                     g, e->N, e->Npad, (int)e->A, A_small, (int)rb, rank, world, timeline_dev, e->W, nullptr, cnt,
                      e->pairq.as<uint64_t>(), (unsigned long long)e->pairq_cap, item_table_dev, n_items, rmsd_dev, nullptr,
                      maxdev_dev,  // (bits: nullptr in the product build -- FC_TIMELINE builds pass their stamp buffer there)
-                     ROWT ? e->Xt.as<double>() : nullptr);
+                     ROWT ? xt : nullptr, general_only ? 1 : 0);
   return FC_OK;
 }
 
@@ -3468,13 +3621,22 @@ int launch_rmsd_values(fc_ensemble *e, double small_rmsd, double *rmsd_dev, doub
   // compare both forms bit for bit)
   const char *rt_env = getenv("FC_COMPLETE_ROW_TILES");
   const bool row_tiles = complete && !(rt_env && atoi(rt_env) == 0);
-  if (row_tiles) FC_TRY(make_row_tiles(e));
-#define FC_COMPLETE_ARGS e, grid, lds_m, A_small, rb, rank, world, cnt, item_table_dev, n_items, rmsd_dev, maxdev_dev, timeline_dev
+  // FC_COMPLETE_FRAME: 0 = the operands as the caller gave them, not the frame copy; FC_COMPLETE_COL0: 0 = the general form
+  // of the rotation on the frame copy too (both read per call: the tests compare the forms)
+  const char *fr_env = getenv("FC_COMPLETE_FRAME"), *c0_env = getenv("FC_COMPLETE_COL0");
+  bool frame = complete && !(fr_env && atoi(fr_env) == 0) && (!row_tiles || row_tiles_fit(e->Npad, e->A));
+  const bool general_only = c0_env && atoi(c0_env) == 0;
+  if (frame) FC_TRY(make_frame(e, row_tiles, &frame));  // (no memory for it: the operands as given)
+  if (!frame && row_tiles) FC_TRY(make_row_tiles(e));
+#define FC_COMPLETE_ARGS \
+  e, grid, lds_m, A_small, rb, rank, world, cnt, item_table_dev, n_items, rmsd_dev, maxdev_dev, timeline_dev, frame, general_only
+#define FC_LAUNCH_COMPLETE_IN(NW_, TC_, C0_)                                                                        \
+  (eig ? (row_tiles ? launch_complete_variant<NW_, TC_, true, true, C0_>(FC_COMPLETE_ARGS)                           \
+                    : launch_complete_variant<NW_, TC_, true, false, C0_>(FC_COMPLETE_ARGS))                         \
+       : (row_tiles ? launch_complete_variant<NW_, TC_, false, true, C0_>(FC_COMPLETE_ARGS)                          \
+                    : launch_complete_variant<NW_, TC_, false, false, C0_>(FC_COMPLETE_ARGS)))
 #define FC_LAUNCH_COMPLETE(NW_, TC_)                                                                                        \
-  FC_TRY((eig ? (row_tiles ? launch_complete_variant<NW_, TC_, true, true>(FC_COMPLETE_ARGS)                                  \
-                           : launch_complete_variant<NW_, TC_, true, false>(FC_COMPLETE_ARGS))                                \
-              : (row_tiles ? launch_complete_variant<NW_, TC_, false, true>(FC_COMPLETE_ARGS)                                 \
-                           : launch_complete_variant<NW_, TC_, false, false>(FC_COMPLETE_ARGS))))
+  FC_TRY((frame ? FC_LAUNCH_COMPLETE_IN(NW_, TC_, true) : FC_LAUNCH_COMPLETE_IN(NW_, TC_, false)))
   if (narrow && tc == 32) {
     FC_LAUNCH_COMPLETE(8, 32);
   } else if (narrow) {
@@ -3487,6 +3649,7 @@ int launch_rmsd_values(fc_ensemble *e, double small_rmsd, double *rmsd_dev, doub
     else FC_LAUNCH_VALUES(8, 1);
   }
 #undef FC_LAUNCH_COMPLETE
+#undef FC_LAUNCH_COMPLETE_IN
 #undef FC_COMPLETE_ARGS
 #undef FC_LAUNCH_VALUES
   FC_TRY(check_launch("k_simbits_screen_mfma<values>"));
@@ -3577,6 +3740,7 @@ int launch_prep_begin(fc_ensemble *e) {
   FC_HIP_TRY(hipMemsetAsync(gmax_bits, 0, sizeof(unsigned long long), ctx().stream));
   e->xsf_valid = false;
   e->xt_valid = false;
+  e->frame_valid = e->xtf_valid = false;
   e->xh_valid = false;
   e->g_max = -1.0;
   return FC_OK;
@@ -4113,7 +4277,7 @@ static int launch_fp64_screen(fc_ensemble *e, const ScreenPlan &p, int64_t n_lbl
   hipLaunchKernelGGL(fn, dim3((unsigned)it.n), dim3(threads), p.lds64, ctx().stream, e->Xs.as<double>(), e->G.as<double>(), e->N,
                      e->Npad, (int)e->A, A_thr2, (int)e->row_block, e->rank, e->world, e->bits.as<uint64_t>(), e->W,
                      e->cand.as<uint32_t>(), reinterpret_cast<unsigned long long *>(e->counters.p), e->pairq.as<uint64_t>(),
-                     (unsigned long long)e->pairq_cap, it.table, it.n, dbg, gate, nullptr, nullptr);
+                     (unsigned long long)e->pairq_cap, it.table, it.n, dbg, gate, nullptr, nullptr, 0);
   FC_TRY(check_launch("k_simbits_screen_mfma"));
 #ifdef FC_TIMELINE
   if (p.timeline) {

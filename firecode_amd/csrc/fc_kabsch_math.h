@@ -712,26 +712,51 @@ __host__ __device__ __forceinline__ bool qcp_lean_step(const QcpLeanPoly &P, dou
   x -= delta;
   return fabs(delta) > 1e-9 * fabs(x);
 }
-// (the adjugate column as it is, not normalised, and its squared length)
-__host__ __device__ __forceinline__ bool qcp_lean_quaternion_raw(const double (&B)[9], const QcpLeanPoly &P, double lam,
-                                                                 double delta, double (&Q)[4], double &nq_out) {
-#pragma clang fp contract(fast)
+// What column 0 of the adjugate of K - lambda I needs: K's entries outside row and column 0's diagonal, the six 2 x 2
+// minors L_ab of rows (2, 3) and the four cofactors a00 ... a03.  Every fused operation is said outright and nothing else
+// is contracted (contract(off)): the general form and the column-0 form below both start from THESE bits, whatever a
+// compiler would fuse around them in either context (with contract(fast) the two forms differed in the last place of a
+// cofactor in 2 % of the pairs of a host build with FMA: tools/qcp_col0_check.cpp).
+struct QcpAdjCol0 {
+  double m01, m02, m03, m11, m12, m13, m22, m23, m33;
+  double L01, L02, L03, L12, L13, L23;
+  double a00, a01, a02, a03;
+};
+__host__ __device__ __forceinline__ QcpAdjCol0 qcp_lean_adjugate_col0(const double (&B)[9], double lam) {
+#pragma clang fp contract(off)
   const double Sxx = B[0], Sxy = B[3], Sxz = B[6];
   const double Syx = B[1], Syy = B[4], Syz = B[7];
   const double Szx = B[2], Szy = B[5], Szz = B[8];
-  const bool converged = fabs(delta) <= 1e-9 * fabs(lam);  // false for NaN
-  const double m00 = (Sxx + Syy + Szz) - lam, m01 = Syz - Szy, m02 = Szx - Sxz, m03 = Sxy - Syx;
-  const double m11 = (Sxx - Syy - Szz) - lam, m12 = Sxy + Syx, m13 = Szx + Sxz;
-  const double m22 = (-Sxx + Syy - Szz) - lam, m23 = Syz + Szy;
-  const double m33 = (-Sxx - Syy + Szz) - lam;
-  const double L01 = m02 * m13 - m12 * m03, L02 = m02 * m23 - m22 * m03, L03 = m02 * m33 - m23 * m03;
-  const double L12 = m12 * m23 - m22 * m13, L13 = m12 * m33 - m23 * m13, L23 = m22 * m33 - m23 * m23;
+  QcpAdjCol0 h;
+  h.m01 = Syz - Szy, h.m02 = Szx - Sxz, h.m03 = Sxy - Syx;
+  h.m11 = (Sxx - Syy - Szz) - lam, h.m12 = Sxy + Syx, h.m13 = Szx + Sxz;
+  h.m22 = (-Sxx + Syy - Szz) - lam, h.m23 = Syz + Szy;
+  h.m33 = (-Sxx - Syy + Szz) - lam;
+  h.L01 = fma(h.m02, h.m13, -(h.m12 * h.m03)), h.L02 = fma(h.m02, h.m23, -(h.m22 * h.m03)), h.L03 = fma(h.m02, h.m33, -(h.m23 * h.m03));
+  h.L12 = fma(h.m12, h.m23, -(h.m22 * h.m13)), h.L13 = fma(h.m12, h.m33, -(h.m23 * h.m13)), h.L23 = fma(h.m22, h.m33, -(h.m23 * h.m23));
+  h.a00 = fma(h.m13, h.L12, fma(h.m11, h.L23, -(h.m12 * h.L13)));   // m11 L23 - m12 L13 + m13 L12
+  h.a01 = -fma(h.m13, h.L02, fma(h.m01, h.L23, -(h.m12 * h.L03)));  // -(m01 L23 - m12 L03 + m13 L02)
+  h.a02 = fma(h.m13, h.L01, fma(h.m01, h.L13, -(h.m11 * h.L03)));   // m01 L13 - m11 L03 + m13 L01
+  h.a03 = -fma(h.m12, h.L01, fma(h.m01, h.L12, -(h.m11 * h.L02)));  // -(m01 L12 - m11 L02 + m12 L01)
+  return h;
+}
+// (the adjugate column as it is, not normalised, and its squared length)
+// (converged: qcp_lean_converged of the last Newton step -- a caller with several pairs in flight takes it right behind
+// the loop and lets the steps die)
+__host__ __device__ __forceinline__ bool qcp_lean_converged(double lam, double delta) {
+  return fabs(delta) <= 1e-9 * fabs(lam);  // false for NaN
+}
+__host__ __device__ __forceinline__ bool qcp_lean_quaternion_raw(const double (&B)[9], double n2, double lam, bool converged,
+                                                                 double (&Q)[4], double &nq_out) {
+#pragma clang fp contract(fast)
+  const double Sxx = B[0], Syy = B[4], Szz = B[8];
+  const QcpAdjCol0 h = qcp_lean_adjugate_col0(B, lam);
+  const double m00 = (Sxx + Syy + Szz) - lam, m01 = h.m01, m02 = h.m02, m03 = h.m03;
+  const double m11 = h.m11, m12 = h.m12, m13 = h.m13, m22 = h.m22, m23 = h.m23, m33 = h.m33;
+  const double L01 = h.L01, L02 = h.L02, L03 = h.L03, L12 = h.L12, L13 = h.L13, L23 = h.L23;
   const double U01 = m00 * m11 - m01 * m01, U02 = m00 * m12 - m02 * m01, U03 = m00 * m13 - m03 * m01;
   const double U12 = m01 * m12 - m02 * m11, U13 = m01 * m13 - m03 * m11;
-  const double a00 = m11 * L23 - m12 * L13 + m13 * L12;
-  const double a01 = -(m01 * L23 - m12 * L03 + m13 * L02);
-  const double a02 = m01 * L13 - m11 * L03 + m13 * L01;
-  const double a03 = -(m01 * L12 - m11 * L02 + m12 * L01);
+  const double a00 = h.a00, a01 = h.a01, a02 = h.a02, a03 = h.a03;
   const double a11 = m00 * L23 - m02 * L03 + m03 * L02;
   const double a12 = -(m00 * L13 - m01 * L03 + m03 * L01);
   const double a13 = m00 * L12 - m01 * L02 + m02 * L01;
@@ -742,12 +767,39 @@ __host__ __device__ __forceinline__ bool qcp_lean_quaternion_raw(const double (&
   if (fabs(a11) > best) { best = fabs(a11); q0 = a01; q1 = a11; q2 = a12; q3 = a13; }
   if (fabs(a22) > best) { best = fabs(a22); q0 = a02; q1 = a12; q2 = a22; q3 = a23; }
   if (fabs(a33) > best) { best = fabs(a33); q0 = a03; q1 = a13; q2 = a23; q3 = a33; }
-  const double nq = q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3;
+  // (the fused chain said outright: qcp_lean_quaternion_col0 must get the same bits)
+  const double nq = fma(q3, q3, fma(q2, q2, fma(q0, q0, q1 * q1)));
   // best > 2e-3 (3 |B|_F)^3, squared: no square root
-  const bool simple = best * best > (2e-3 * 27.0) * (2e-3 * 27.0) * (P.n2 * P.n2) * P.n2;
+  const bool simple = best * best > (2e-3 * 27.0) * (2e-3 * 27.0) * (n2 * n2) * n2;
   Q[0] = q0; Q[1] = q1; Q[2] = q2; Q[3] = q3;
   nq_out = nq;
   return converged && simple && nq > 0.0;
+}
+__host__ __device__ __forceinline__ bool qcp_lean_quaternion_raw(const double (&B)[9], const QcpLeanPoly &P, double lam,
+                                                                 double delta, double (&Q)[4], double &nq_out) {
+  return qcp_lean_quaternion_raw(B, P.n2, lam, qcp_lean_converged(lam, delta), Q, nq_out);
+}
+// Column 0 of the same adjugate alone, for pairs whose rotation is known to be small (the complete alignments run on a
+// copy of the ensemble in which every conformer is aligned onto conformer 0 once: DESIGN.md 5.1, "the shared frame").
+// The adjugate of K - lambda I has rank one: every column is the eigenvector, a00^2 / nq = q0^2 for column 0, and at
+// q0^2 >= 0.6 the other diagonal entries are <= 0.4 of the trace, so the pick of qcp_lean_quaternion_raw takes column 0
+// too.  Minors and cofactors are the general form's own (qcp_lean_adjugate_col0): wherever this form certifies a pair,
+// Q, nq and the flag are the general form's, bit for bit (tools/qcp_col0_check.cpp).  Four cofactors instead of ten, no
+// U minors, no pick.  Returns "certified": converged && simple && nq > 0 && a00^2 >= 0.6 nq (false for NaN).
+__host__ __device__ __forceinline__ bool qcp_lean_quaternion_col0(const double (&B)[9], double n2, double lam, bool converged,
+                                                                  double (&Q)[4], double &nq_out) {
+#pragma clang fp contract(off)
+  const QcpAdjCol0 h = qcp_lean_adjugate_col0(B, lam);
+  const double q0 = h.a00, q1 = h.a01, q2 = h.a02, q3 = h.a03, best = fabs(h.a00);
+  const double nq = fma(q3, q3, fma(q2, q2, fma(q0, q0, q1 * q1)));
+  const bool simple = best * best > (2e-3 * 27.0) * (2e-3 * 27.0) * (n2 * n2) * n2;
+  Q[0] = q0; Q[1] = q1; Q[2] = q2; Q[3] = q3;
+  nq_out = nq;
+  return converged && simple && nq > 0.0 && best * best >= 0.6 * nq;
+}
+__host__ __device__ __forceinline__ bool qcp_lean_quaternion_col0(const double (&B)[9], const QcpLeanPoly &P, double lam,
+                                                                  double delta, double (&Q)[4], double &nq_out) {
+  return qcp_lean_quaternion_col0(B, P.n2, lam, qcp_lean_converged(lam, delta), Q, nq_out);
 }
 __host__ __device__ __forceinline__ bool qcp_lean_quaternion(const double (&B)[9], const QcpLeanPoly &P, double lam,
                                                              double delta, double (&Q)[4]) {
@@ -775,18 +827,14 @@ __host__ __device__ __forceinline__ bool kabsch_quaternion_qcp_lean(const double
   return qcp_lean_quaternion(B, P, x, delta, Q);
 }
 
-// four pairs of one lane: the Newton iterations of all four in one wave-uniform loop; the quaternions come back
-// NOT normalised with their squared lengths (neg_rotation_from_raw_quaternion divides once)
-// lam_out (optional): the converged eigenvalues -- sum |p - R q|^2 = (Gp + Gq) - 2 lambda for the optimal rotation
-__host__ __device__ __forceinline__ void kabsch_quaternion_qcp_lean4(const double (&B)[4][9], const double (&GpGq)[4],
-                                                                     double (&Q)[4][4], double (&nq)[4], bool (&ok)[4],
-                                                                     double *lam_out = nullptr) {
-  QcpLeanPoly P[4];
-  double x[4], delta[4] = {0.0, 0.0, 0.0, 0.0};
+// four pairs of one lane, first half: the polynomials and the Newton iterations of all four in one wave-uniform loop
+__host__ __device__ __forceinline__ void qcp_lean_eigenvalues4(const double (&B)[4][9], const double (&GpGq)[4],
+                                                               QcpLeanPoly (&P)[4], double (&x)[4], double (&delta)[4]) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     P[r] = qcp_lean_polynomial(B[r]);
     x[r] = 0.5 * GpGq[r];
+    delta[r] = 0.0;
   }
   for (int it = 0; it < 64; ++it) {
     bool moving = false;
@@ -798,6 +846,17 @@ __host__ __device__ __forceinline__ void kabsch_quaternion_qcp_lean4(const doubl
     if (!moving) break;
 #endif
   }
+}
+
+// four pairs of one lane: the Newton iterations of all four in one wave-uniform loop; the quaternions come back
+// NOT normalised with their squared lengths (neg_rotation_from_raw_quaternion divides once)
+// lam_out (optional): the converged eigenvalues -- sum |p - R q|^2 = (Gp + Gq) - 2 lambda for the optimal rotation
+__host__ __device__ __forceinline__ void kabsch_quaternion_qcp_lean4(const double (&B)[4][9], const double (&GpGq)[4],
+                                                                     double (&Q)[4][4], double (&nq)[4], bool (&ok)[4],
+                                                                     double *lam_out = nullptr) {
+  QcpLeanPoly P[4];
+  double x[4], delta[4];
+  qcp_lean_eigenvalues4(B, GpGq, P, x, delta);
 #pragma unroll
   for (int r = 0; r < 4; ++r) ok[r] = qcp_lean_quaternion_raw(B[r], P[r], x[r], delta[r], Q[r], nq[r]);
   if (lam_out != nullptr) {
