@@ -173,6 +173,7 @@ _SIGNATURES = {
     "fc_debug_screen_plan": [_i64, _i64, _i64, _i64, _f64, _f64, _i64, _p_i64],
     "fc_debug_mfma_f16_model": [_i64, _p_i64, _p_f64],
     "fc_debug_h2_covariance": [_ens, _i64, _i64, C.POINTER(C.c_float), _p_f64, _p_f64],
+    "fc_debug_kabsch_math": [C.c_int, _p_f64, _i64, _p_f64],
     "fc_comm_unique_id": [_p_u8],
     "fc_comm_init": [_i64, _i64, _p_u8],
     "fc_comm_destroy": [],

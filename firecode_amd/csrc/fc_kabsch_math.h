@@ -146,9 +146,16 @@ __host__ __device__ __forceinline__ double kabsch_rotation(const double (&B)[9],
 // ENANT (the enantiomer-aware prune): "may be similar in EITHER handedness".  Inverting one
 // structure through the origin turns B into -B: n2 and |cof B|_F^2 are even in B, det B changes sign, and P', P are
 // decreasing in det B (L > 0 where the test decides: `tiny`), so the OR of the two tests is this test at |det B|.
+// (kabsch_screen_values: the three values and what they are compared with, for the tests that check them against an
+// arbitrary-precision polynomial -- tests/test_kabsch_math_cpu.py; kabsch_may_be_below is its verdict)
+struct KabschScreenValues {
+  double P0, P1, P2;  // P, P'/4, P''/4 at L
+  double eps;         // the guard on P: 1e-12 s^4
+  bool tiny;
+};
 template <bool ENANT = false>
-__host__ __device__ __forceinline__ bool kabsch_may_be_below(const double (&B)[9], double GpGq,
-                                                     double A_thr2) {
+__host__ __device__ __forceinline__ KabschScreenValues kabsch_screen_values(const double (&B)[9], double GpGq,
+                                                                            double A_thr2) {
   // the screen has a 1e-6 A^2 margin and a 1e-12 relative guard: fused
   // multiply-adds are welcome here (the file is otherwise built contract=off)
 #pragma clang fp contract(fast)
@@ -180,7 +187,13 @@ __host__ __device__ __forceinline__ bool kabsch_may_be_below(const double (&B)[9
   const double P1 = u * L - 2.0 * detB;
   const double P0 = u * u - 4.0 * (e2 + 2.0 * L * detB);
   const double eps = 1e-12 * (s * s) * (s * s);
-  return tiny | (P2 < 0.0) | (P1 < 0.0) | !(P0 > eps);
+  return KabschScreenValues{P0, P1, P2, eps, tiny};
+}
+template <bool ENANT = false>
+__host__ __device__ __forceinline__ bool kabsch_may_be_below(const double (&B)[9], double GpGq,
+                                                     double A_thr2) {
+  const KabschScreenValues v = kabsch_screen_values<ENANT>(B, GpGq, A_thr2);
+  return v.tiny | (v.P2 < 0.0) | (v.P1 < 0.0) | !(v.P0 > v.eps);
 }
 
 
@@ -353,12 +366,22 @@ inline KabschF32Bounds kabsch_h2_bounds(int64_t KS2) {
           (float)(2.0 * (6.0 * db + 52.0 * u))};
 }
 
+// (the two constants of kabsch_lambda_is_settled, below; the first also says when kabsch_lambda_max reports a slope)
+constexpr double kLambdaSettledStep = 1e-12;
+constexpr double kLambdaSettledSlope = 1e-3;
+
 // Largest eigenvalue of the quaternion matrix by Newton's iteration on its
 // characteristic polynomial, started from the upper bound (Gp+Gq)/2 (monotone
 // convergence from above; Theobald's QCP).  rmsd^2 = (Gp + Gq - 2 lambda) / A.
 // Used for all-pairs RMSD *values*: no eigenvector, no rotation.  The caller
 // re-evaluates pairs with a tiny rmsd exactly (cancellation in Gp+Gq-2*lambda).
-// slope (may be NULL): P'(x) of the last step -- the product of the distances to the other three eigenvalues.  Where the
+// slope (may be NULL): P'(x) of the last step -- the product of the distances to the other three eigenvalues -- and 0 where
+// the iteration has not settled (its last step above kLambdaSettledStep |x|: the 64 steps ran out on the way): the value
+// is then no eigenvalue at all, and kabsch_lambda_is_sharp declines it as kabsch_lambda_is_settled does.  (A covariance
+// that vanishes against Gp + Gq -- all atoms of one structure in one point: B = 0, P = x^4 -- is approached by a factor
+// 3/4 per step only: 1e-8 (Gp + Gq) left after 64, at a slope that looks healthy; tests/test_kabsch_math_cpu.py.  A
+// simple root on a small slope may jitter by a few 1e-16 |x| for all 64 steps without meeting the stopping test: that
+// value is as good as any and keeps its slope.)  Where the
 // largest eigenvalue is (nearly) double -- a covariance of rank one: one atom, two atoms about their centroid, atoms on a
 // line -- P' vanishes with P, the iteration stalls where the rounding of P (a few u x^4) equals its quadratic, sqrt(u) x
 // away from the root ON EITHER SIDE of it (below the stall P / P' is rounding noise over a vanishing slope: a step can
@@ -393,7 +416,7 @@ __host__ __device__ __forceinline__ double kabsch_lambda_max(const double (&B)[9
     last = delta;
     if (fabs(delta) <= 4e-16 * fabs(x)) break;
   }
-  if (slope) *slope = den;
+  if (slope) *slope = fabs(last) <= kLambdaSettledStep * fabs(x) ? den : 0.0;
   if (step) *step = last;
   if (norm2) *norm2 = n2;
   return x;
@@ -416,8 +439,6 @@ __host__ __device__ __forceinline__ double kabsch_lambda_max(const double (&B)[9
 // that is 1.1e-11 x, and 1.1e-11 (Gp + Gq) on A msd.  (The slope is that of the iterate before the last step, 1e-12 x
 // away: P' moves by at most 1.2e-11 x^3 over that.)  Elsewhere the value is not to be used on this side: DESIGN.md
 // section 18 has what the iteration does there.  False for NaN.
-constexpr double kLambdaSettledStep = 1e-12;
-constexpr double kLambdaSettledSlope = 1e-3;
 __host__ __device__ __forceinline__ bool kabsch_lambda_is_settled(double lam, double slope, double step, double norm2) {
   return lam > 0.0 && fabs(step) <= kLambdaSettledStep * lam && 3.0 * (lam * lam) > norm2 &&
          slope >= kLambdaSettledSlope * (lam * lam * lam);

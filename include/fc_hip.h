@@ -1124,6 +1124,20 @@ int fc_debug_screen_plan(int64_t N, int64_t A, int64_t row_block, int64_t lean, 
 int fc_debug_mfma_f16_model(int64_t trials, int64_t *flags_out, double *worst_out);
 int fc_debug_h2_covariance(fc_ensemble *ens, int64_t ib, int64_t jb, float *B_out, double *scale_out,
                            double *entry_bound_out);
+/* The per-lane routines of csrc/fc_kabsch_math.h on the device, one lane per record, for the tests that hold them to
+ * an arbitrary-precision reference (tests/test_gpu_kabsch_math.py) -- no FIRECODE call maps to it.  `in` holds n records,
+ * `out` receives n records (float64 throughout); launches are whole wavefronts, padded with copies of the last record.
+ *   routine 0  the probe of csrc/fc_kabsch_math_probe.h: in 12 per record (B[9] row-major, Gp + Gq, A, A thr^2), out 94
+ *              (enum KabschProbeSlot): the Newton eigenvalues and their certificates, the fp64 screen and its three
+ *              values, the Jacobi rotation, the QCP rotations and quaternions in every form, flags included
+ *   routine 1  the fp32 screens: in 16 per record (B[9], s, A thr^2 / 2 -- values of fp32 --, a count, a kind, tiny_floor,
+ *              two unused), bounds = kabsch_f32_bounds(count) for kind 0, kabsch_h2_bounds(count) for kind 1; out 16:
+ *              for plain then ENANT the three-test verdict, the two-test verdict and its redo, the wave form's verdict
+ *              and redo bit of the lane (5 + 5), then the bounds p0, p1, p2 and three zeros
+ *   routine 2  in 1, out 2: fc_sqrt_nonneg(x), fc_rsqrt(x)
+ * FC_E_INVALID before any device use: NULL pointers, n outside 0..2^20, an unknown routine, a count outside 0..2^20 or a
+ * kind other than 0 / 1.  n = 0 needs no device. */
+int fc_debug_kabsch_math(int routine, const double *in, int64_t n, double *out);
 int fc_bench_prune_rmsd(fc_ensemble *ens, double max_rmsd, double max_dev, int64_t reps,
                         double *ms_simbits_kernel, double *ms_step, uint8_t *mask_out,
                         int64_t *stats);

@@ -101,6 +101,12 @@ def test_c_entry_points_reject_null_and_bad_sizes():
         L.call("fc_rototranslate", L.pf(out), 2, 5, None, None, L.pf(out))
     with pytest.raises(fc.FirecodeHipInputError):
         L.call("fc_prune_export_pairs_dev", None, None, 4)
+    with pytest.raises(fc.FirecodeHipInputError):
+        L.call("fc_debug_kabsch_math", 0, None, 1, L.pf(out))
+    with pytest.raises(fc.FirecodeHipInputError):
+        L.call("fc_debug_kabsch_math", 3, L.pf(out), 1, L.pf(out))
+    with pytest.raises(fc.FirecodeHipInputError):
+        L.call("fc_debug_kabsch_math", 2, L.pf(out), -1, L.pf(out))
 
 
 def test_prune_many_rejects_bad_lists():
