@@ -212,6 +212,8 @@ _SIGNATURES = {
                                   C.POINTER(C.c_int32), _p_f64, _p_u64, _p_i64],
     "fc_ensemble_silhouette_perm": [_ens, C.POINTER(C.c_int32), _i64, _i64, C.c_int, C.POINTER(C.c_int32), _i64, _p_f64, _p_f64,
                                     _p_f64, C.POINTER(C.c_int32), _p_f64, _p_i64, _p_f64, _p_f64, _p_i64],
+    "fc_ensemble_group_means": [_ens, C.POINTER(C.c_int32), _i64, _p_i64, _i64, C.c_double, _p_f64, _p_f64, _p_f64, _p_f64,
+                                _p_i64, _p_i64, _p_i64, _p_f64],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + ("fc_last_error",)
@@ -536,6 +538,34 @@ def check_group_labels(labels, n_conformers, n_groups=None):
     return np.ascontiguousarray(np.maximum(lab.astype(np.int64), -1), dtype=np.int32), n_groups
 
 
+def check_group_refs(refs, labels, n_groups, n_conformers):
+    """``refs`` of the group means: one conformer per group, a member of it (the entry of an empty group is not read),
+    against ``labels`` / ``n_groups`` as ``check_group_labels`` returned them, checked before any device use -> a
+    contiguous int64 array"""
+    idx = np.asarray(refs)
+    if idx.ndim != 1 or idx.shape[0] != n_groups or (idx.size and (idx.dtype == np.bool_ or not np.issubdtype(idx.dtype, np.integer))):
+        raise FirecodeHipInputError(FC_E_INVALID, f"refs must hold one integer per group ({n_groups}), got {idx.dtype} {idx.shape}")
+    idx = i64(idx)
+    lab = np.zeros(n_conformers, dtype=np.int32) if labels is None else labels
+    sizes = np.bincount(lab[lab >= 0], minlength=n_groups)
+    for g in np.flatnonzero(sizes):
+        r = int(idx[g])
+        if not 0 <= r < n_conformers:
+            raise FirecodeHipInputError(FC_E_INVALID, f"refs[{g}]={r} outside [0, {n_conformers})")
+        if lab[r] != g:
+            raise FirecodeHipInputError(FC_E_INVALID, f"refs[{g}]={r} is not a member of group {g}")
+    return idx
+
+
+def check_tol(name, value):
+    """A convergence tolerance: a real number >= 0, checked before any device use -> float"""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise FirecodeHipInputError(FC_E_INVALID, f"{name} must be a real number, got {value!r}")
+    if not float(value) >= 0.0:
+        raise FirecodeHipInputError(FC_E_INVALID, f"{name}={value!r} is negative or NaN")
+    return float(value)
+
+
 class DeviceEnsemble:
     """HBM-resident prepared ensemble (fc_ensemble)."""
 
@@ -819,6 +849,38 @@ class DeviceEnsemble:
         call("fc_ensemble_silhouette", self.handle, ptr(lab, C.c_int32), n_groups, pf(s), pf(a), pf(b), ptr(nearest, C.c_int32),
              pf(mean), pi(sizes), C.byref(score), C.byref(ms))
         out = (s, a, b, nearest, mean, sizes, score.value)
+        return out + (ms.value,) if want_ms else out
+
+    def group_means(self, labels=None, n_groups=None, refs=None, max_iter=50, tol=1e-9, want_rotations=True, want_ms=False):
+        """The mean structure of every group of conformers, its members superposed on it (generalized Procrustes per
+        group), the per-atom fluctuation about it and every member's RMSD to it (fc_ensemble_group_means; the contract,
+        the order of its sums included, is in include/fc_hip.h).  ``labels`` / ``n_groups`` as for ``medoids``;
+        ``refs`` (n_groups,): the member each group starts from (``None``: its lowest-index member, ``"medoids"``: the
+        medoids of ``medoids(labels, n_groups)`` on this same ensemble); at most ``max_iter`` turns, a group stops once
+        its mean moved by no more than ``tol`` (RMS over the selected atoms) -> ``(means (n_groups, A_sel, 3), rmsf
+        (n_groups, A_sel), distances (N,), closest (n_groups,) int64, sizes (n_groups,) int64, n_iter (n_groups,) int64,
+        rotations (N, 3, 3) or None)``.  An empty group has NaN mean and rmsf and closest -1; a conformer in no group NaN
+        distance and the identity.  ``want_ms=True`` appends the kernels' milliseconds."""
+        lab, n_groups = check_group_labels(labels, self.N, n_groups)
+        max_iter = check_count("max_iter", max_iter, low=0)
+        tol = check_tol("tol", tol)
+        if isinstance(refs, str):
+            if refs != "medoids":
+                raise FirecodeHipInputError(FC_E_INVALID, f"refs={refs!r}: an array, None or 'medoids'")
+            start = self.medoids(lab, n_groups)[0] if self.N else None
+        else:
+            start = None if refs is None else check_group_refs(refs, lab, n_groups, self.N)
+        mask = getattr(self, "_atom_mask", None)
+        a_sel = self.A_all if mask is None else int(np.count_nonzero(mask))
+        means, rmsf = np.full((n_groups, a_sel, 3), np.nan), np.full((n_groups, a_sel), np.nan)
+        dist = np.full(self.N, np.nan)
+        rot = np.tile(np.eye(3), (self.N, 1, 1)) if want_rotations else None
+        closest, sizes = np.full(n_groups, -1, dtype=np.int64), np.zeros(n_groups, dtype=np.int64)
+        n_iter = np.zeros(n_groups, dtype=np.int64)
+        ms = C.c_double(0)
+        call("fc_ensemble_group_means", self.handle, ptr(lab, C.c_int32), n_groups, pi(start), max_iter, tol, pf(means),
+             pf(rmsf), pf(dist), pf(rot), pi(closest), pi(sizes), pi(n_iter), C.byref(ms))
+        out = (means, rmsf, dist, closest, sizes, n_iter, rot)
         return out + (ms.value,) if want_ms else out
 
     def _sums_perm_args(self, symmetry, prune_enantiomers):

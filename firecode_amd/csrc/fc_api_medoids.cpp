@@ -12,15 +12,9 @@
 
 namespace fc {
 
-// the conformers by group: order = a stable sort of the labelled conformers by label, group c = order[offs[c] .. offs[c + 1])
-struct Grouping {
-  std::vector<int32_t> order;
-  std::vector<int64_t> offs;
-  int64_t largest = 0;
-};
-
-// labels (N, or nullptr: everything in group 0), already checked: label < n_groups, negative = in no group
-static void group_by_label(const int32_t *labels, int64_t N, int64_t n_groups, Grouping &g) {
+// (Grouping: fc_internal.h)  labels (N, or nullptr: everything in group 0), already checked: label < n_groups, negative =
+// in no group
+void group_by_label(const int32_t *labels, int64_t N, int64_t n_groups, Grouping &g) {
   g.offs.assign((size_t)n_groups + 1, 0);
   if (labels == nullptr) {
     g.offs[1] = N;
@@ -116,7 +110,7 @@ static void medoids_of(const Grouping &g, const std::vector<uint64_t> &S, const 
   }
 }
 
-static int labels_check(const int32_t *labels, int64_t N, int64_t n_groups) {
+int labels_check(const int32_t *labels, int64_t N, int64_t n_groups) {
   if (labels == nullptr) return FC_OK;
   for (int64_t i = 0; i < N; ++i)
     FC_REQUIRE(labels[i] < n_groups, "labels[%lld]=%d is not below n_groups=%lld", (long long)i, (int)labels[i], (long long)n_groups);

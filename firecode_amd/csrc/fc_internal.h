@@ -275,6 +275,37 @@ size_t silhouette_work_bytes(int64_t M, int S);
 int launch_silhouette(const fc_ensemble *e, const int32_t *seg_begin_dev, const int32_t *seg_end_dev, int S, uint8_t *work_dev,
                       bool timed, const SymTable *sym = nullptr);  // sym (may be NULL): under d_sym (k_silhouette_tile_sym)
 int warm_silhouette();
+// ---- fc_group_mean.hip -----------------------------------------------------------------------------------
+// the tables of a call, on the device, over the label-sorted ensemble (fc_api_group_mean.cpp builds them)
+struct GroupMeanPlan {
+  int64_t M = 0, n_groups = 0;          // positions of the sorted copy; group ids
+  const int32_t *grp_dev = nullptr;     // (M) the group of a position
+  const int32_t *init_dev = nullptr;    // (n_init, 2) group, position of its reference member: every non-empty group
+  int64_t n_init = 0;
+  const int32_t *chunks_dev = nullptr;  // (n_chunks, 3) begin, end, group: group_mean_chunk() positions of a segment each
+  int64_t n_chunks = 0;
+  const int32_t *active_dev = nullptr;  // (n_active, 4) group, first chunk, chunks, members: groups of two or more
+  int64_t n_active = 0;
+};
+// mean (n_groups, A, 3), rmsf (n_groups, A), frozen and n_iter (n_groups) are the caller's to size; the rest is sized
+// by group_means_run
+struct GroupMeanWork {
+  DevBuf mean, Gm, rmsf, frozen, n_iter, Y, part, d, R, words;
+};
+int64_t group_mean_stage_atoms();  // the mean is staged in LDS up to this many selected atoms
+int group_mean_chunk();
+bool group_mean_stage(int64_t A);
+int group_means_run(const fc_ensemble *e, const GroupMeanPlan &pl, GroupMeanWork &w, int64_t max_iter, double tol, bool timed);
+int warm_group_mean();
+// ---- fc_api_medoids.cpp ----------------------------------------------------------------------------------
+// the conformers by group: order = a stable sort of the labelled conformers by label, group c = order[offs[c] .. offs[c + 1])
+struct Grouping {
+  std::vector<int32_t> order;
+  std::vector<int64_t> offs;
+  int64_t largest = 0;
+};
+void group_by_label(const int32_t *labels, int64_t N, int64_t n_groups, Grouping &g);
+int labels_check(const int32_t *labels, int64_t N, int64_t n_groups);
 // ---- fc_tfd_ladder.hip -----------------------------------------------------------------------------------
 int tfd_ladder_device(const int64_t *fm_dev, const int64_t *fm_host, int64_t N, uint8_t *mask_out);
 int pyset_order_pairs_device(const int64_t *pairs_host, int64_t n, int64_t *order_out);

@@ -388,6 +388,7 @@ int fc_warmup(void) {
   FC_TRY(warm_knn());
   FC_TRY(warm_medoid());
   FC_TRY(warm_silhouette());
+  FC_TRY(warm_group_mean());
   FC_TRY(side_streams());  // the pipelines' streams and ordering events
   // the buffers a first large call would otherwise take from the runtime one by one (0.2 - 1 ms each): through the pool once
   {

@@ -218,6 +218,26 @@ class Ensemble:
                              f"representative {mean:.3f} A, {sel.n_iter} assignments, {perf_counter() - t0:.3f} s)")
         return sel
 
+    def mean_structures(self, labels=None, refs=None, max_iter=50, tol=1e-9, heavy_atoms_only=True, aligned=False):
+        """What each group looks like: its mean structure with the members superposed on it, the per-atom fluctuation
+        about that mean, every member's RMSD to it and the closest member (``firecode_amd.pruner.group_means_by_rmsd``).
+        ``labels``: the ``labels`` of a clusterer (negative: in no group); ``None``: the whole ensemble is one group;
+        ``refs``: where each group starts (``None``, indices or ``"medoids"``).  Returns the ``RmsdGroupMeans``; the
+        ensemble is not changed."""
+        from firecode_amd.pruner import group_means_by_rmsd
+
+        return group_means_by_rmsd(self.coords, self.atoms, labels=labels, refs=refs, max_iter=max_iter, tol=tol,
+                                   heavy_atoms_only=heavy_atoms_only, aligned=aligned)
+
+    def align_by_groups(self, labels, refs=None, max_iter=50, tol=1e-9, heavy_atoms_only=True):
+        """Superpose the members of every group on their group's mean structure: ``coords`` is replaced by the
+        ``aligned`` block of ``mean_structures`` (all atoms; every structure centred on its selected atoms, structures in
+        no group unrotated), so that ``to_xyz`` writes each cluster as one bundle.  Returns the ``RmsdGroupMeans``."""
+        res = self.mean_structures(labels=labels, refs=refs, max_iter=max_iter, tol=tol, heavy_atoms_only=heavy_atoms_only,
+                                   aligned=True)
+        self.coords = res.aligned
+        return res
+
     def nearest_neighbours(self, k, heavy_atoms_only=True, symmetry=None, prune_enantiomers=False):
         """The ``k`` nearest neighbours of every structure under the heavy-atom RMSD of the other RMSD stages
         (``firecode_amd.pruner.knn_by_rmsd``).  Returns the ``RmsdNeighbours``, whose ``k_distances(min_samples - 1)`` is

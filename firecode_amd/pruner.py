@@ -518,6 +518,56 @@ def kmedoids_by_rmsd_sym(structures, atoms, n, init=None, max_iter=50, heavy_ato
     return RmsdKMedoids(med, lab, dist, cost * Q32, n_iter)
 
 
+RmsdGroupMeans = namedtuple("RmsdGroupMeans", ["means", "rmsf", "distances", "closest", "sizes", "n_iter", "rotations", "aligned"])
+
+
+def group_means_by_rmsd(structures, atoms, labels=None, refs=None, max_iter=50, tol=1e-9, heavy_atoms_only=True,
+                        aligned=False):
+    """What each group looks like: its mean structure with the members superposed on it (generalized Procrustes per
+    group, under the heavy-atom Kabsch fit of ``prune_by_rmsd``), the per-atom fluctuation about that mean (RMSF), every
+    member's RMSD to it and the member closest to it -- on the GPU (fc_ensemble_group_means; the contract, the order of
+    its sums included, is written out in include/fc_hip.h).  ``labels`` as for ``medoids_by_rmsd`` (negative: in no
+    group; ``None``: one group).  ``refs``: the member each group's iteration starts from -- one index per group,
+    ``None`` (the lowest-index member) or ``"medoids"`` (the medoids, found on the same upload).  A group turns until
+    its mean moves by no more than ``tol`` A (RMS over the selected atoms), ``max_iter`` turns at most; ``max_iter=0``
+    leaves the reference member as the mean.
+
+    Returns ``RmsdGroupMeans(means, rmsf, distances, closest, sizes, n_iter, rotations, aligned)``: per group (largest
+    label + 1 of them) the mean (A_sel, 3) of the centred selected atoms, rmsf (A_sel,), the index of the closest
+    member, the member count and the turns taken; per conformer the RMSD to its group's mean and the rotation (3, 3)
+    that superposes it.  With ``aligned=True``, ``aligned`` is the whole (N, A, 3) block, hydrogens included, every
+    conformer moved rigidly by its rotation about the centroid of its selected atoms -- the members of a group lie
+    superposed on their mean, ready to write out; otherwise ``None``.  An empty group id has NaN mean and rmsf, size 0
+    and closest -1; a conformer in no group NaN distance, the identity, and comes back centred and unrotated."""
+    structures, heavy = _medoid_inputs(structures, atoms, heavy_atoms_only)
+    N = structures.shape[0]
+    lab, n_groups = L.check_group_labels(labels, N)
+    max_iter = L.check_count("max_iter", max_iter, low=0)
+    tol = L.check_tol("tol", tol)
+    want_aligned = L.check_flag("aligned", aligned)
+    if isinstance(refs, str):
+        if refs != "medoids":
+            raise L.FirecodeHipInputError(L.FC_E_INVALID, f"refs={refs!r}: an array, None or 'medoids'")
+    elif refs is not None:
+        refs = L.check_group_refs(refs, lab, n_groups, N)
+    if N == 0:
+        a_sel = int(np.count_nonzero(heavy))
+        return RmsdGroupMeans(np.full((n_groups, a_sel, 3), np.nan), np.full((n_groups, a_sel), np.nan), np.zeros(0),
+                              np.full(n_groups, -1, dtype=np.int64), np.zeros(n_groups, dtype=np.int64),
+                              np.zeros(n_groups, dtype=np.int64), np.zeros((0, 3, 3)),
+                              structures.copy() if want_aligned else None)
+    with L.DeviceEnsemble(structures, atom_mask=heavy, center=True) as ens:
+        means, rmsf, dist, closest, sizes, n_iter, rot = ens.group_means(lab, n_groups, refs=refs, max_iter=max_iter, tol=tol)
+    block = None
+    if want_aligned:
+        from firecode_amd.embeds import rototranslate
+
+        # R (x - c) = R x + (-R c), c the centroid of the selected atoms: one launch of the rototranslate kernel
+        c = structures[:, heavy].mean(axis=1)
+        block = rototranslate(structures, rot, -np.einsum("nij,nj->ni", rot, c))
+    return RmsdGroupMeans(means, rmsf, dist, closest, sizes, n_iter, rot, block)
+
+
 RmsdClusters = namedtuple("RmsdClusters", ["labels", "representatives", "sizes"])
 
 

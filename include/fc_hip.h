@@ -400,6 +400,54 @@ int fc_ensemble_silhouette_perm(fc_ensemble *ens, const int32_t *perms, int64_t 
                                 double *a_out, double *b_out, int32_t *nearest_out, double *cluster_mean_out,
                                 int64_t *sizes_out, double *score_out, double *ms_kernel /* or NULL */,
                                 int64_t *stats /* 2 or NULL */);
+/* ---- mean structures and per-atom fluctuations of groups: what a cluster looks like ----
+ * fc_ensemble_group_means.  X is the prepared ensemble: the atom selection applied, every conformer centred on its
+ * selected atoms -- create the handle with center = 1; an uncentred ensemble is taken as it is and its means are not
+ * centroids of anything.  labels and n_groups as for fc_ensemble_medoids (int32 per conformer, negative = in no group,
+ * NULL = one group, the same checks).  refs: (n_groups) one conformer per group, the member the iteration starts from (the
+ * medoid, say); the entry of an empty group is not read; NULL = the smallest-index member of each group.
+ * For every non-empty group g, members n in ascending conformer index:
+ *   M_g(0) = X[ref_g]
+ *   turn t = 0, 1, ... while t < max_iter and g is not frozen:
+ *       R_n = the Kabsch rotation that takes X[n] onto M_g(t): the rotation fc_ensemble_rmsd_pairs uses for the pair
+ *             (p = M_g, q = X[n]) -- covariance sum_a p_a q_a^T, Newton eigenvalue and adjugate, the Jacobi sweeps where the
+ *             eigenvalue is not clearly simple
+ *       M'  = (sum over n in g of R_n X[n]) / |g|          (no re-centring: rotations keep the centroid at 0)
+ *       c   = sqrt(sum_a |M'_a - M_g(t)_a|^2 / A_sel)
+ *       M_g(t+1) = M';  n_iter_g = t + 1;  if c <= tol: g is frozen
+ *   final pass, against M_g = M_g(n_iter_g):
+ *       R_n;  Y_n = R_n X[n];  d_n = sqrt(sum_a |Y_na - M_ga|^2 / A_sel)
+ *       rmsf_g[a] = sqrt(sum over n in g of |Y_na - M_ga|^2 / |g|)
+ *       closest_g = the member with the smallest d_n, the lowest index on ties
+ * A frozen group's mean is never touched again: a group's outputs are a function of its own members, ref_g, max_iter and
+ * tol alone -- not of what other groups of the call are still doing, and not of how often the host reads the device's "a
+ * group is still moving" word (it is read every few turns; FC_GROUP_MEAN_BATCH=<turns>).
+ * max_iter = 0: the mean is the reference member and d_n the plain RMSD to it.  A singleton: mean = itself, rmsf = 0,
+ * d = 0, R = identity, n_iter = 0, by definition.  An empty group id: NaN mean and rmsf, size 0, closest -1, n_iter 0.  A
+ * conformer in no group: d = NaN, R = identity.
+ * The order of the sums (part of the contract; double precision, no atomics, no integer quantisation -- a mean rounded to
+ * 2^-33 A would cost the 1e-10 the coordinates are held to).  A group's members in ascending conformer index are cut into
+ * chunks of 64, counted from the group's first member; the last chunk is filled up with +0.0.  A chunk's 64 values v[0..64)
+ * are added as a tree of neighbouring pairs: v[l] += v[l ^ 1], then ^ 2, ^ 4, ^ 8, ^ 16, ^ 32.  The chunk sums are added in
+ * ascending chunk order, starting from the first chunk's, and the total is DIVIDED by |g| (M') or divided by |g| and
+ * rooted (rmsf, whose values are (dx dx + dy dy) + dz dz per member and atom).  c: the squares of M' - M over the 3 A_sel
+ * coordinates r, 256 partial sums (r = k, k + 256, ... ascending), each 64 consecutive partials by the tree above, the
+ * four results added in order.  d_n: the atoms a = s, s + 8, ... per partial s < 8, dx dx + dy dy + dz dz added left to
+ * right, the eight partials by the tree; the covariance likewise, by fused multiply-adds.
+ * Hence the same bits on every run and for every launch shape: the mean staged in LDS or read from global memory
+ * (FC_GROUP_MEAN_STAGE=0; staged up to 2048 selected atoms, and only where a workgroup's 32 conformers share a group), any
+ * grid of the reduction kernels (FC_GROUP_MEAN_GRID=<workgroups>), any FC_GROUP_MEAN_BATCH.
+ * Outputs: means_out (n_groups, A_sel, 3), rmsf_out (n_groups, A_sel), dist_out (N), closest_out, sizes_out, n_iter_out
+ * (n_groups each), all required; rot_out (N, 9) row-major, applied as R x, or NULL; ms_kernel (or NULL): HIP-event time
+ * from the first launch to the last, the host's reads of the word included (0 when no device is used: nobody in a group).
+ * Refused with FC_E_INVALID before any device use, the message naming the argument: n_groups < 1; max_iter < 0; tol
+ * negative or NaN; a NULL ens or required output; labels[i] >= n_groups; for a non-empty group g a refs[g] outside [0, N)
+ * or not a member of g; an ensemble of an earlier context epoch.  N = 0 writes nothing.  FC_E_LIMIT: N >= 2^31 - 256.
+ * Not offered: symmetry- and mirror-aware forms, sharded, multi-GPU and twin-workspace forms, weights. */
+int fc_ensemble_group_means(fc_ensemble *ens, const int32_t *labels /* N or NULL = one group */, int64_t n_groups,
+                            const int64_t *refs /* n_groups or NULL */, int64_t max_iter, double tol, double *means_out,
+                            double *rmsf_out, double *dist_out, double *rot_out /* (N, 9) or NULL */, int64_t *closest_out,
+                            int64_t *sizes_out, int64_t *n_iter_out, double *ms_kernel /* or NULL */);
 /* a9: get_alignment_matrix(p, q) -- prism_pruner.rmsd; call site
  * hypermolecule_class.py:77.  M (3,3) row-major, applied as (M @ q.T).T */
 int fc_alignment_matrices(const double *p, const double *q, int64_t n_pairs, int64_t A,
